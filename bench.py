@@ -79,6 +79,9 @@ def parse_args():
     ap.add_argument("--independent-streams", action="store_true", help="do not fork-join the streams around every pass (A/B: 1 %% slower than the joined default)")
     ap.add_argument("--pad-kb", type=int, default=0, help="developer probe: allocate this many KiB of device memory before anything else (shifts the addresses of every later allocation: "
                                                          "placement sensitivity of the kernels, tools/placement_probe.sh)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="right after the main timed region, write what its last pass computed (the canvases a caller of ms_stitch receives, or the I420 slabs of the "
+                         "N>1 egress) as DIR/<name>.npy: per-frame row sums of every byte (float64) and a fixed, seeded sample of the bytes (float32), 64 MB at most")
     ap.add_argument("--streams", type=int, default=None,
                     help="contexts / HIP streams a step's frames are split over (default 3 x 32 frames: the small coarse-level kernels of one batch overlap the large kernels of another: +13 %% over one stream)")
     args = ap.parse_args()
@@ -170,6 +173,8 @@ def main():
     from benchlib import cpu_baseline as CB, dist_run, others, pmc, roofline as RL, shards
     from benchlib.regions import DTYPE, Opt, Workload
 
+    if args.dump_outputs and (args.view_shards > 1 or args.col_shards > 1):
+        sys.exit("bench.py: --dump-outputs covers the frame-parallel path only, not --view-shards / --col-shards")
     _pad = torch.empty(args.pad_kb * 1024, dtype=torch.uint8, device=dev) if args.pad_kb > 0 else None      # noqa: F841 (kept alive for the whole run)
     if args.view_shards > 1 or args.col_shards > 1:
         cfg = dict(synth.CONFIGS["cfg5" if args.config == "cfg5" else "cfg2"])

@@ -149,6 +149,8 @@ def run_regions(args, wl, rank, world, local_rank, share, dev):
     out = {"no_gather": None, "full_gather": None, "live_rate": None, "preamble": None}
     if not wl.gather:
         out["elapsed"], out["n_gathered"] = wl.timed_region(args.steps, args.warmup)
+        if args.dump_outputs and rank == 0:
+            wl.dump_outputs(args.dump_outputs)
         return out
     wd = Watchdog(args, wl, rank, world)
     wd.arm("preamble (torch.distributed all-gather of the ranks' devices)")
@@ -177,6 +179,8 @@ def run_regions(args, wl, rank, world, local_rank, share, dev):
     if args.gather_every <= 0:      # the live rate: about 30 batches per second and rank
         st["gather_every"] = max(1, int(round(out["no_gather"] / world / 30.0 / F)))
     out["elapsed"], out["n_gathered"] = wl.timed_region(args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:      # before the full-gather region below reuses the buffers
+        wl.dump_outputs(args.dump_outputs)
     main_every = st["gather_every"]
     wd.partial["value_main_region"] = round(world * F * passes * args.steps / out["elapsed"], 2)
     wd.partial["main_region_gathers_every"] = main_every

@@ -295,6 +295,32 @@ class Workload:
             el = float(t.item())
         return el, self.state["gathered"] - g0
 
+    # ---- --dump-outputs: what the timed path computed, for output-for-output comparison of two builds
+    DUMP_SAMPLES = 1 << 21      # sampled output bytes (float32 values + float64 flat indices: 24 MiB)
+
+    def dump_outputs(self, out_dir):
+        """What the last pass left in its buffers: the F output canvases (8UC3, out_h x out_w x 3 each), or the I420 slabs where the stitch writes those itself
+        (N>1 egress).  Written as <name>.npy: `rows` = float64 [F, rows] sums of every byte of each output row (covers all of it), `sample` = float32 values at
+        `sample_index` (float64 flat indices into the [F, ...] stack, drawn once from a fixed seed)."""
+        b = self.state["last_b"]
+        if self.direct_i420:
+            name, outs = "i420_slabs", [self.slabs[b][j] for j in range(self.F)]
+        else:
+            name, outs = "canvas", self.outs[b]
+        torch.cuda.synchronize()
+        per = outs[0].numel()
+        total = per * len(outs)
+        idx = np.sort(np.random.default_rng(20240607).choice(total, size=min(self.DUMP_SAMPLES, total), replace=False))
+        rows, sample = [], []
+        for j, t in enumerate(outs):
+            rows.append(t.reshape(t.shape[0], -1).sum(dim=1, dtype=torch.float64).cpu().numpy())
+            lo, hi = np.searchsorted(idx, [j * per, (j + 1) * per])
+            sample.append(t.reshape(-1)[torch.from_numpy(idx[lo:hi] - j * per).to(t.device)].float().cpu().numpy())
+        os.makedirs(out_dir, exist_ok=True)
+        np.save(os.path.join(out_dir, name + "_rows.npy"), np.stack(rows))
+        np.save(os.path.join(out_dir, name + "_sample.npy"), np.concatenate(sample).astype(np.float32))
+        np.save(os.path.join(out_dir, name + "_sample_index.npy"), idx.astype(np.float64))
+
     # ---- verification: frames of every batch of the LAST pass re-stitched one at a time on a one-frame context (live code path: other launch
     #      configuration, band tail one band finer) must equal what the batched, multi-stream passes left in the outputs
     def _live_context(self):

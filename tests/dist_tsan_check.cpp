@@ -1,6 +1,6 @@
 // dist_tsan_check.cpp -- ThreadSanitizer run of ms_dist's host transport, one thread per rank (how stitch_dist --share-gpu and stitch_app --gpus N
 // drive it).  Test infrastructure: compiled by tests/test_ms_dist.py::test_host_transport_under_tsan together with csrc/dist.cpp
-//   hipcc -fsanitize=thread -g -O1 tests/dist_tsan_check.cpp video-stitcher_amd/csrc/dist.cpp -L video-stitcher_amd -lmsstitch ...
+//   hipcc -fsanitize=thread -fno-gpu-sanitize -g -O1 tests/dist_tsan_check.cpp video-stitcher_amd/csrc/dist.cpp -L video-stitcher_amd -lmsstitch ...
 // (dist.cpp instrumented, the rest of the library as built).  Host-memory messages only: runs without a GPU.
 // What it exercises per iteration, on every rank: a group with TWO sends and TWO receives per peer (the per-channel posting order of round 4), a
 // broadcast from a rotating root, the frame gather into a rotating sink, a barrier, and the mesh exchange with an update every third iteration.

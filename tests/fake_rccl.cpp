@@ -1,12 +1,16 @@
 // fake_rccl.cpp -- TEST INFRASTRUCTURE ONLY: a loopback stand-in for librccl with RCCL's own prototypes (<rccl/rccl.h>), so that the RCCL branch of
 // csrc/dist.cpp (rccl_attach, ncclSend / ncclRecv inside ncclGroupStart / End, ncclBroadcast, ncclAllGather) runs with N > 1 ranks on a box with ONE
-// GPU -- the real library refuses two ranks on one device.  It proves call order, grouping, argument marshalling and stream / event ordering of the
-// callers; it says NOTHING about RCCL itself or about xGMI (tests/test_ms_dist_gpu.py keeps calling the N > 1 RCCL transport "unmeasured").
+// GPU -- the real library refuses two ranks on one device.  It proves call order, grouping, argument marshalling and the stream / event ordering of the
+// callers around a transfer (not the reuse of a send buffer, see below); it says NOTHING about RCCL itself or about xGMI (tests/test_ms_dist_gpu.py keeps calling the N > 1 RCCL transport "unmeasured").
 //
-// Semantics kept from NCCL: every call only ENQUEUES.  A transfer starts when the work enqueued before it on its stream has finished (a hipEvent the
-// proxy thread waits for) and the stream continues behind it only when the transfer has completed (a one-lane kernel on the stream spins on a word of
-// pinned host memory that the proxy thread advances) -- so a caller that forgets a stream / event dependency reads stale bytes here as it would with
-// the real library, and a caller that blocks the host where RCCL would not shows up as a deadlock.  The bytes themselves travel through a POSIX
+// Semantics kept from NCCL: a transfer starts when the work enqueued before it on its stream has finished (a hipEvent the proxy thread waits for), and
+// its result lands in the destination in the order of that stream: the proxy fills a pinned staging buffer, and the copy from there into the destination
+// is enqueued on the caller's stream (every stream of a group waits for the copies of all of them, as NCCL joins the streams of a group).  So a caller
+// that forgets a stream / event dependency on either side -- a producer the transfer must wait for, or a consumer that must wait for the transfer --
+// reads stale bytes here as it would with the real library.  What differs from NCCL: the call returns only when the proxy has moved the bytes into
+// staging (the calling thread waits; nothing waits ON the GPU -- a waiting kernel would share the process's few hardware queues with the kernels of the
+// other ranks of the same process, the very kernels it waits for), and a send buffer is free again when the call returns, so a caller that overwrites
+// a send buffer before its stream has passed the send goes unnoticed.  The bytes themselves travel through a POSIX
 // shared-memory mailbox (ranks = threads or processes), one single-slot channel per ordered rank pair, matched in posting order per channel.
 // Loaded through ms_dist_set_rccl_library(path); never on any default search path, never linked into the product.
 #include <hip/hip_runtime.h>
@@ -25,6 +29,7 @@
 #include <deque>
 #include <mutex>
 #include <thread>
+#include <utility>
 #include <vector>
 
 namespace {
@@ -67,21 +72,14 @@ struct Op {
     int peer;
     size_t done = 0;
     bool finished = false;
+    hipStream_t stream = nullptr;         // the caller's stream of this operation
+    unsigned char *stage = nullptr;       // RECV / COPY: pinned staging the proxy fills; copied into `buf` on `stream` once the batch is done
 };
 struct Batch {
     std::vector<Op> ops;
-    std::vector<hipEvent_t> ready;        // recorded on every stream of the batch before the wait kernel: the transfer starts behind them
+    std::vector<hipEvent_t> ready;        // recorded on every stream of the batch: the transfer starts behind them
     unsigned long long seq;
 };
-
-__global__ void k_fake_rccl_wait(const unsigned long long *flag, unsigned long long seq, unsigned *err)
-{
-    const unsigned long long t0 = wall_clock64();                      // 100 MHz
-    while (__hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) < seq) {
-        __builtin_amdgcn_s_sleep(64);
-        if (wall_clock64() - t0 > 100000000ull * (unsigned long long)TIMEOUT_S) { __hip_atomic_store(err, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); break; }
-    }
-}
 
 size_t dtype_size(ncclDataType_t t)
 {
@@ -102,10 +100,12 @@ struct ncclComm {
     size_t shm_len = 0;
     bool registered = false;
     hipStream_t priv = nullptr;
-    unsigned long long *flag = nullptr;   // pinned host: sequence number of the last completed batch
-    unsigned *err = nullptr;              // pinned host: set by a wait kernel that timed out
+    unsigned long long *flag = nullptr;   // sequence number of the last completed batch
     unsigned long long submitted = 0;
     std::mutex mu;
+    struct Stage { unsigned char *p; size_t cap; hipEvent_t done; bool busy; };
+    std::mutex stage_mu;
+    std::vector<Stage> stages;            // pinned staging buffers, reused once the copy out of them (`done`) has completed
     std::condition_variable cv;
     std::deque<Batch> queue;
     bool stop = false;
@@ -131,12 +131,12 @@ bool run_batch(ncclComm *c, Batch &b)
 {
     for (hipEvent_t e : b.ready) if (hipEventSynchronize(e) != hipSuccess) return false;      // (destroyed by worker_main)
     std::vector<Op> &ops = b.ops;
-    for (Op &o : ops) if (o.kind == COPY) { if (!copy_sync(c, o.buf, o.src, o.bytes, hipMemcpyDeviceToDevice)) return false; o.finished = true; }
+    for (Op &o : ops) if (o.kind == COPY) { if (!copy_sync(c, o.stage, o.src, o.bytes, hipMemcpyDeviceToHost)) return false; o.finished = true; }
     for (size_t i = 0; i < ops.size(); ++i) {                                  // a send to oneself pairs with the receive from oneself of the same batch
         if (ops[i].kind != SEND || ops[i].peer != c->rank || ops[i].finished) continue;
         for (size_t j = 0; j < ops.size(); ++j)
             if (ops[j].kind == RECV && ops[j].peer == c->rank && !ops[j].finished && ops[j].bytes == ops[i].bytes) {
-                if (!copy_sync(c, ops[j].buf, ops[i].buf, ops[i].bytes, hipMemcpyDeviceToDevice)) return false;
+                if (!copy_sync(c, ops[j].stage, ops[i].buf, ops[i].bytes, hipMemcpyDeviceToHost)) return false;
                 ops[i].finished = ops[j].finished = true;
                 break;
             }
@@ -164,7 +164,7 @@ bool run_batch(ncclComm *c, Batch &b)
                 if (h == t) { all = false; continue; }
                 const size_t n = (size_t)ch->len;
                 if (n > o.bytes - o.done) { fprintf(stderr, "fake_rccl: rank %d receives %zu bytes from %d, %zu posted\n", c->rank, n, o.peer, o.bytes - o.done); return false; }
-                if (!copy_sync(c, o.buf + o.done, ch->data, n, hipMemcpyHostToDevice)) return false;
+                if (n) memcpy(o.stage + o.done, ch->data, n);
                 ch->tail.store(t + 1, std::memory_order_release);
                 o.done += n;
             }
@@ -192,44 +192,142 @@ void worker_main(ncclComm *c)
         }
         if (!c->failed.load() && !run_batch(c, b)) c->failed.store(1);
         for (hipEvent_t e : b.ready) (void)hipEventDestroy(e);
-        __atomic_store_n(c->flag, b.seq, __ATOMIC_RELEASE);           // (also after a failure: the streams must not hang; the next call reports it)
+        {
+            std::lock_guard<std::mutex> lk(c->mu);
+            __atomic_store_n(c->flag, b.seq, __ATOMIC_RELEASE);       // (also after a failure: the caller must not hang; it reports it)
+        }
         c->cv.notify_all();
     }
 }
 
-// the calling thread's part: events on the streams, the batch to the proxy thread, one wait kernel per stream
-ncclResult_t submit(ncclComm *c, std::vector<Op> ops, const std::vector<hipStream_t> &streams)
+unsigned char *stage_get(ncclComm *c, size_t n)
 {
-    if (c->failed.load() || __atomic_load_n(c->err, __ATOMIC_ACQUIRE)) return ncclSystemError;
+    std::lock_guard<std::mutex> lk(c->stage_mu);
+    ncclComm::Stage *best = nullptr;
+    for (ncclComm::Stage &st : c->stages) {
+        if (st.busy && st.done && hipEventQuery(st.done) == hipSuccess) { (void)hipEventDestroy(st.done); st.done = nullptr; st.busy = false; }
+        if (!st.busy && st.cap >= n && (!best || st.cap < best->cap)) best = &st;
+    }
+    if (!best) {
+        unsigned char *p = nullptr;
+        if (hipHostMalloc((void **)&p, n, hipHostMallocDefault) != hipSuccess) return nullptr;
+        c->stages.push_back(ncclComm::Stage{p, n, nullptr, false});
+        best = &c->stages.back();
+    }
+    best->busy = true;
+    return best->p;
+}
+
+void stage_release(ncclComm *c, unsigned char *p, hipEvent_t done)      // done == nullptr: free at once (nothing was enqueued out of it)
+{
+    std::lock_guard<std::mutex> lk(c->stage_mu);
+    for (ncclComm::Stage &st : c->stages)
+        if (st.p == p) { st.done = done; st.busy = done != nullptr; return; }
+}
+
+// what the calling thread keeps of a batch it handed to the proxy: the copies out of staging it enqueues once the proxy is done
+struct Ticket {
+    ncclComm *comm;
+    unsigned long long seq;
+    std::vector<Op> outs;                 // RECV / COPY operations with a staging buffer
+    std::vector<hipStream_t> streams;     // the distinct streams of the batch
+};
+
+// the calling thread's part: events on the streams, staging for every destination, the batch to the proxy thread
+ncclResult_t enqueue(ncclComm *c, std::vector<Op> ops, Ticket *t)
+{
+    if (c->failed.load()) return ncclSystemError;
     int dev = 0;
     (void)hipGetDevice(&dev);
     if (dev != c->device) (void)hipSetDevice(c->device);
     Batch b;
-    b.ops = std::move(ops);
-    std::vector<hipStream_t> uniq;
-    for (hipStream_t s : streams) { bool seen = false; for (hipStream_t u : uniq) seen |= u == s; if (!seen) uniq.push_back(s); }
-    for (hipStream_t s : uniq) {
+    t->comm = c;
+    for (const Op &o : ops) { bool seen = false; for (hipStream_t u : t->streams) seen |= u == o.stream; if (!seen) t->streams.push_back(o.stream); }
+    ncclResult_t r = ncclSuccess;
+    for (Op &o : ops)
+        if ((o.kind == RECV || o.kind == COPY) && o.bytes) {
+            if (!(o.stage = stage_get(c, o.bytes))) { r = ncclUnhandledCudaError; break; }
+            t->outs.push_back(o);
+        }
+    for (hipStream_t s : t->streams) {
+        if (r != ncclSuccess) break;
         hipEvent_t e;
-        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess || hipEventRecord(e, s) != hipSuccess) return ncclUnhandledCudaError;
+        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess || hipEventRecord(e, s) != hipSuccess) { r = ncclUnhandledCudaError; break; }
         b.ready.push_back(e);
     }
+    if (dev != c->device) (void)hipSetDevice(dev);
+    if (r != ncclSuccess) {
+        for (hipEvent_t e : b.ready) (void)hipEventDestroy(e);
+        for (const Op &o : t->outs) stage_release(c, o.stage, nullptr);
+        t->outs.clear();
+        return r;
+    }
+    b.ops = std::move(ops);
     {
         std::lock_guard<std::mutex> lk(c->mu);
-        b.seq = ++c->submitted;
+        b.seq = t->seq = ++c->submitted;
         c->queue.push_back(std::move(b));
     }
-    const unsigned long long seq = c->submitted;
     c->cv.notify_all();
-    for (hipStream_t s : uniq) hipLaunchKernelGGL(k_fake_rccl_wait, dim3(1), dim3(1), 0, s, c->flag, seq, c->err);
+    return ncclSuccess;
+}
+
+// blocks until the proxy has finished the batch, then enqueues the copies out of staging on the operations' streams and joins the streams of the batch
+ncclResult_t finish(const Ticket &t)
+{
+    ncclComm *c = t.comm;
+    {
+        std::unique_lock<std::mutex> lk(c->mu);
+        c->cv.wait(lk, [&] { return __atomic_load_n(c->flag, __ATOMIC_ACQUIRE) >= t.seq; });
+    }
+    const bool ok = !c->failed.load();
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev != c->device) (void)hipSetDevice(c->device);
+    bool hip_ok = true;
+    for (const Op &o : t.outs) {
+        hipEvent_t done = nullptr;
+        if (!ok) { stage_release(c, o.stage, nullptr); continue; }
+        if (hipMemcpyAsync(o.buf, o.stage, o.bytes, hipMemcpyHostToDevice, o.stream) != hipSuccess) { hip_ok = false; stage_release(c, o.stage, nullptr); continue; }
+        if (hipEventCreateWithFlags(&done, hipEventDisableTiming) != hipSuccess || hipEventRecord(done, o.stream) != hipSuccess) {
+            hip_ok = false;                                            // (no event to reuse the staging behind: wait for the copy here)
+            (void)hipStreamSynchronize(o.stream);
+            if (done) (void)hipEventDestroy(done);
+            done = nullptr;
+        }
+        stage_release(c, o.stage, done);
+    }
+    if (ok && t.streams.size() > 1) {                                  // NCCL joins the streams of a group: each continues behind the operations of all of them
+        std::vector<hipEvent_t> evs;
+        for (hipStream_t s : t.streams) {
+            hipEvent_t e;
+            if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess || hipEventRecord(e, s) != hipSuccess) { hip_ok = false; break; }
+            evs.push_back(e);
+        }
+        if (hip_ok)
+            for (size_t i = 0; i < t.streams.size(); ++i)
+                for (size_t j = 0; j < evs.size(); ++j)
+                    if (i != j && hipStreamWaitEvent(t.streams[i], evs[j], 0) != hipSuccess) hip_ok = false;
+        for (hipEvent_t e : evs) (void)hipEventDestroy(e);
+    }
     if (dev != c->device) (void)hipSetDevice(dev);
-    return hipGetLastError() == hipSuccess ? ncclSuccess : ncclUnhandledCudaError;
+    return !ok ? ncclSystemError : hip_ok ? ncclSuccess : ncclUnhandledCudaError;
+}
+
+ncclResult_t submit(ncclComm *c, std::vector<Op> ops)
+{
+    Ticket t;
+    const ncclResult_t r = enqueue(c, std::move(ops), &t);
+    return r != ncclSuccess ? r : finish(t);
 }
 
 ncclResult_t post(ncclComm *c, hipStream_t s, const std::vector<Op> &ops)
 {
     if (!c) return ncclInvalidArgument;
-    if (g_depth > 0) { for (const Op &o : ops) g_pending.push_back(Pending{c, s, o}); return ncclSuccess; }
-    return submit(c, ops, std::vector<hipStream_t>(1, s));
+    std::vector<Op> mine(ops);
+    for (Op &o : mine) o.stream = s;
+    if (g_depth > 0) { for (const Op &o : mine) g_pending.push_back(Pending{c, s, o}); return ncclSuccess; }
+    return submit(c, std::move(mine));
 }
 
 void shm_name(const ncclUniqueId &id, char out[48])
@@ -302,12 +400,8 @@ FR_API ncclResult_t ncclCommInitRank(ncclComm_t *out, int nranks, ncclUniqueId i
     if (rank == 0) shm_unlink(name);                                  // every rank has mapped it: nothing stays in /dev/shm
     c->registered = hipHostRegister(p, len, hipHostRegisterDefault) == hipSuccess;       // (pageable staging works too, only slower)
     if (!c->registered) (void)hipGetLastError();
-    bool ok = hipStreamCreateWithFlags(&c->priv, hipStreamNonBlocking) == hipSuccess;    // non-blocking: a wait kernel on the NULL stream must not hold the proxy's copies
-    ok = ok && hipHostMalloc((void **)&c->flag, 64, hipHostMallocDefault) == hipSuccess;
-    if (!ok) { delete c; return ncclUnhandledCudaError; }
-    c->flag[0] = 0;
-    c->err = reinterpret_cast<unsigned *>(c->flag + 4);
-    *c->err = 0;
+    if (hipStreamCreateWithFlags(&c->priv, hipStreamNonBlocking) != hipSuccess) { delete c; return ncclUnhandledCudaError; }    // (not ordered behind the NULL stream)
+    c->flag = new unsigned long long(0);
     c->worker = std::thread(worker_main, c);
     *out = c;
     return ncclSuccess;
@@ -323,9 +417,12 @@ FR_API ncclResult_t ncclCommDestroy(ncclComm_t c)
     }
     c->cv.notify_all();
     if (c->worker.joinable()) c->worker.join();
-    (void)hipDeviceSynchronize();                                      // the wait kernels of the last batches have left the streams
+    for (ncclComm::Stage &st : c->stages) {
+        if (st.done) { (void)hipEventSynchronize(st.done); (void)hipEventDestroy(st.done); }
+        (void)hipHostFree(st.p);
+    }
     if (c->priv) (void)hipStreamDestroy(c->priv);
-    if (c->flag) (void)hipHostFree(c->flag);
+    delete c->flag;
     if (c->shm) { if (c->registered) (void)hipHostUnregister(c->shm); munmap(c->shm, c->shm_len); }
     delete c;
     return ncclSuccess;
@@ -387,13 +484,19 @@ FR_API ncclResult_t ncclGroupEnd()
     pend.swap(g_pending);
     ncclResult_t res = ncclSuccess;
     std::vector<bool> taken(pend.size(), false);
+    std::vector<Ticket> batches;
     for (size_t i = 0; i < pend.size(); ++i) {                         // one batch per communicator, operations in posting order
         if (taken[i]) continue;
         std::vector<Op> ops;
-        std::vector<hipStream_t> streams;
         for (size_t j = i; j < pend.size(); ++j)
-            if (!taken[j] && pend[j].comm == pend[i].comm) { taken[j] = true; ops.push_back(pend[j].op); streams.push_back(pend[j].stream); }
-        const ncclResult_t r = submit(pend[i].comm, std::move(ops), streams);
+            if (!taken[j] && pend[j].comm == pend[i].comm) { taken[j] = true; ops.push_back(pend[j].op); }
+        Ticket t;
+        const ncclResult_t r = enqueue(pend[i].comm, std::move(ops), &t);
+        if (r != ncclSuccess) res = r;
+        else batches.push_back(std::move(t));
+    }
+    for (const Ticket &b : batches) {                                  // every communicator's batch is with its proxy before the caller waits for any of them
+        const ncclResult_t r = finish(b);
         if (r != ncclSuccess) res = r;
     }
     return res;

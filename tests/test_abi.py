@@ -88,12 +88,32 @@ def test_ms_image_layout_matches_the_references_ptrstepsz():
     import subprocess
     inc = "/root/reference/sources/modules/core/include"
     if not os.path.isfile(os.path.join(inc, "opencv2", "core", "cuda_types.hpp")):
-        pytest.skip("the reference is not on this machine")
+        _ms_image_layout_matches_the_stored_ptrstepsz_layout()
+        return
     exe = os.path.join(ROOT, "video-stitcher_amd", "build", "abi_layout_check")
     os.makedirs(os.path.dirname(exe), exist_ok=True)
     subprocess.check_call(["g++", "-std=c++11", "-I" + inc, os.path.join(ROOT, "video-stitcher_amd", "shim", "abi_layout_check.cpp"), "-o", exe])
     out = subprocess.run([exe], capture_output=True, text=True)
     assert out.returncode == 0 and "layout ok" in out.stdout, out.stdout
+
+
+def _ms_image_layout_matches_the_stored_ptrstepsz_layout():
+    """Where the reference is not present: the offsets its PtrStepSz<uchar> has (tests/golden/ptrstepsz_layout.json, printed by shim/abi_layout_check.cpp) against
+    ms_image as include/ms_stitch.h declares it, compiled here."""
+    import json
+    import subprocess
+    import tempfile
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "ptrstepsz_layout.json")))
+    src = ('#include <cstddef>\n#include <cstdio>\n#include "ms_stitch.h"\nint main() { ms_image m; std::printf("%zu %zu %zu %zu %zu %zu %zu\\n", offsetof(ms_image, data), '
+           'offsetof(ms_image, step), offsetof(ms_image, cols), offsetof(ms_image, rows), offsetof(ms_image, type), sizeof(m.step), sizeof(m.cols)); return 0; }\n')
+    with tempfile.TemporaryDirectory() as d:
+        with open(os.path.join(d, "layout.cpp"), "w") as f:
+            f.write(src)
+        subprocess.check_call(["g++", "-std=c++11", "-I" + os.path.join(ROOT, "include"), os.path.join(d, "layout.cpp"), "-o", os.path.join(d, "layout")])
+        data, step, cols, rows, typ, sz_step, sz_cols = map(int, subprocess.check_output([os.path.join(d, "layout")], text=True).split())
+    assert (data, step, cols, rows) == (want["data"], want["step"], want["cols"], want["rows"])
+    assert sz_step == want["sizeof_step"] and sz_cols == want["sizeof_cols"] == 4
+    assert want["size"] <= typ + 4 and typ >= rows + 4          # PtrStepSz<T> is a prefix of ms_image; `type` follows `rows`
 
 
 def test_config_struct_size_is_checked(ms):

@@ -156,7 +156,7 @@ def test_plain_invocation_spawns_ranks():
 
 def _fake_env(**kw):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    env.update(MS_BENCH_SHARE_GPU="1", MS_BENCH_RCCL_LIB=FAKE_RCCL, GPU_MAX_HW_QUEUES="16", **kw)
+    env.update(MS_BENCH_SHARE_GPU="1", MS_BENCH_RCCL_LIB=FAKE_RCCL, **kw)
     return env
 
 
@@ -244,3 +244,26 @@ def test_column_sharded_ranks_exchange_slabs_and_match_the_unsharded_frame():
     d = last_json(p.stdout)
     assert d["n_gpus"] == 2 and d["equals_unsharded"] is True and d["value"] > 0
     assert ("RCCL" in d["config"]["workload"]) == two
+
+
+def test_dump_outputs_are_the_timed_paths_last_pass_and_repeat(tmp_path):
+    """--dump-outputs: after the main timed region, the canvases of its last pass as <name>.npy in float32 / float64, 64 MB at most, and the same files from two
+    runs with the same arguments (the inputs are synthetic and seeded: two builds compare output for output).  The row sums cover every byte of every canvas."""
+    import numpy as np
+    common = ["--steps", "2", "--warmup", "1", "--passes", "2", "--no-others", "--no-cpu-baseline", "--no-pcie", "--no-pmc", "--no-live", "--no-verify", "--no-distinct"]
+    dirs = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        p = subprocess.run([sys.executable, "bench.py"] + common + ["--dump-outputs", str(d)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        assert last_json(p.stdout)["steps"] == 2
+        dirs.append(d)
+    names = sorted(os.listdir(dirs[0]))
+    assert names == ["canvas_rows.npy", "canvas_sample.npy", "canvas_sample_index.npy"] and sorted(os.listdir(dirs[1])) == names
+    assert sum(os.path.getsize(dirs[0] / n) for n in names) <= 64 << 20
+    a = {n: np.load(dirs[0] / n) for n in names}
+    assert a["canvas_rows.npy"].dtype == np.float64 and a["canvas_sample.npy"].dtype == np.float32 and a["canvas_sample_index.npy"].dtype == np.float64
+    assert a["canvas_rows.npy"].shape == (96, 1920) and a["canvas_sample.npy"].shape == a["canvas_sample_index.npy"].shape
+    assert a["canvas_rows.npy"].sum() > 0 and 0 <= a["canvas_sample.npy"].min() and a["canvas_sample.npy"].max() <= 255
+    for n in names:
+        assert np.array_equal(a[n], np.load(dirs[1] / n)), n

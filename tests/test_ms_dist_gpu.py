@@ -6,6 +6,7 @@ communicator initialised and its all-gather executed on every box."""
 import json
 import os
 import subprocess
+import time
 
 import numpy as np
 import pytest
@@ -228,10 +229,12 @@ def fake(n):
     return ["--gpus", n, "--share-gpu", "--transport", "rccl", "--rccl-lib", FAKE_RCCL]
 
 
-# The loopback library holds a stream with a one-lane kernel that waits for the transfer (as an RCCL kernel waits for its peer).  HIP multiplexes the streams of a
-# process over 4 hardware queues by default; with every rank of stitch_dist in ONE process on ONE device, a rank's waiting kernel would then sit in front of the
-# very kernels of another rank that it waits for -- a deadlock that separate GPUs cannot have.  Give every stream of the test process its own hardware queue.
-FAKE_ENV = dict(os.environ, GPU_MAX_HW_QUEUES="32")
+# The loopback library waits for a transfer on the calling thread, not with a kernel on the stream: HIP multiplexes the streams of a process over a few
+# hardware queues, and with every rank of stitch_dist in ONE process on ONE device a rank's waiting kernel would sit in front of the very kernels of
+# another rank that it waits for -- a deadlock that separate GPUs cannot have.  So the runs need no queue settings of their own.  The received bytes still
+# reach their buffer in the order of the caller's stream (a copy out of pinned staging, enqueued there): a consumer that skips the dependency reads stale
+# bytes (test_rccl_consumer_that_skips_the_dependency_reads_stale_bytes).  Not covered: a send buffer reused before its stream has passed the send.
+FAKE_ENV = dict(os.environ)
 
 
 def _is_fake_rccl(res, ranks):
@@ -258,9 +261,10 @@ def test_rccl_branch_column_shards_recalibration_and_table_blob_over_the_loopbac
     for extra in ([], ["--col-shards", 2]):
         res = run(*fake(4), *extra, "--frames", 32, "--batch", 4 if extra else 2, "--recalib-every", 8, "--mesh", "9x11", env=FAKE_ENV)
         assert _is_fake_rccl(res, 4) and res["recalibrations_applied"] == cp["recalibrations_applied"] == 3 and res["checksum_all"] == cp["checksum_all"], extra
-    # (--tables-from-rank0 is not run this way: rank 0 calibrates -- hipDeviceSynchronize inside -- while the other rank THREADS of the same process already hold their
-    #  streams in the loopback library's waiting kernels for the blob: a deadlock of ranks that share one device and one process, impossible with a GPU per rank.  The
-    #  large staged host broadcast is covered between PROCESSES below, the blob itself over the host transport above.)
+    # the table blob from rank 0 (rank 0 calibrates -- hipDeviceSynchronize inside -- while the other rank threads wait for the blob in ncclBroadcast: on the host, so
+    # nothing of theirs holds the device)
+    res = run(*fake(2), "--frames", 16, "--batch", 4, "--tables-from-rank0", env=FAKE_ENV)
+    assert _is_fake_rccl(res, 2) and res["checksum_all"] == one["checksum_all"]
 
 
 def _exchange_rccl(rank, world, idb, fake_lib, q):
@@ -357,6 +361,82 @@ def test_rccl_branch_between_processes_over_the_loopback_library(cuda, world):
     for p in procs:
         p.join(timeout=60)
     assert got == {r: "ok" for r in range(world)}, got
+
+
+def _stale_consumer_rccl(rank, idb, fake_lib, go, q):
+    """rank 1 receives 64 MiB from rank 0 on stream `cs`.  While its thread waits in ncclRecv (the proxy is done only once rank 0 sends), a second thread enqueues
+    about a second of matmuls on `cs` and only then lets rank 0 send: the copy into the destination lands on `cs` behind that work.  A consumer on another stream
+    that skips the dependency runs at once and must see the old bytes; the one that waits for `cs` must see the new ones."""
+    try:
+        import threading
+        import msdist
+        msdist.set_rccl_library(fake_lib)
+        torch.cuda.set_device(0)
+        dev = torch.device("cuda:0")
+        n = 64 << 20
+        d = msdist.Dist(rank, 2, idb, device=0)
+        try:
+            if rank == 0:
+                out = torch.full((n,), 7, dtype=torch.uint8, device=dev)
+                torch.cuda.synchronize()
+                assert go.wait(120)
+                d.send(out, 1)
+                torch.cuda.synchronize()
+                q.put((rank, "ok"))
+                return
+            got = torch.zeros(n, dtype=torch.uint8, device=dev)
+            x = torch.randn(8192, 8192, device=dev)
+            cs = torch.cuda.Stream(device=dev)
+            side = torch.cuda.Stream(device=dev, priority=-1)      # (another priority level: never behind `cs` in a shared hardware queue)
+            torch.cuda.synchronize()
+
+            def hold_cs():
+                time.sleep(1.0)                                    # the main thread is inside ncclRecv by now: its ready event precedes what follows
+                with torch.cuda.stream(cs):
+                    for _ in range(100):
+                        torch.mm(x, x)
+                go.set()
+            t = threading.Thread(target=hold_cs)
+            t.start()
+            with torch.cuda.stream(cs):
+                d.recv(got, 0)
+            t.join()
+            with torch.cuda.stream(side):                          # the defect: no wait for `cs`
+                early = int(got.sum(dtype=torch.int64))
+            busy = not cs.query()
+            side.wait_stream(cs)
+            with torch.cuda.stream(side):                          # the correct consumer
+                late = int(got.sum(dtype=torch.int64))
+            q.put((rank, "ok" if (early == 0 and late == 7 * n) else "early %d late %d (of %d) cs busy after the early read: %s" % (early, late, 7 * n, busy)))
+        finally:
+            d.close()
+    except Exception as e:      # noqa: BLE001
+        import traceback
+        q.put((rank, traceback.format_exc()[-1500:] or repr(e)))
+
+
+def test_rccl_consumer_that_skips_the_dependency_reads_stale_bytes(cuda):
+    """The loopback library keeps the post-transfer side of NCCL's stream semantics: what ncclRecv delivers reaches the destination in the order of the caller's
+    stream, so a consumer on another stream that does not wait for it reads the bytes that were there before -- the defect the checksum tests of this file would
+    then catch -- and one that waits reads the received bytes."""
+    import msdist
+    import torch.multiprocessing as mp
+    assert os.path.isfile(FAKE_RCCL)
+    ctx = mp.get_context("spawn")
+    q0 = ctx.Queue()
+    idp = ctx.Process(target=_make_fake_id, args=(2, FAKE_RCCL, q0))
+    idp.start()
+    idb = q0.get(timeout=120)
+    idp.join(timeout=60)
+    assert isinstance(idb, bytes) and msdist.id_transport(idb) == msdist.RCCL, idb
+    q, go = ctx.Queue(), ctx.Event()
+    procs = [ctx.Process(target=_stale_consumer_rccl, args=(r, idb, FAKE_RCCL, go, q)) for r in range(2)]
+    for p in procs:
+        p.start()
+    got = dict(q.get(timeout=300) for _ in range(2))
+    for p in procs:
+        p.join(timeout=60)
+    assert got == {0: "ok", 1: "ok"}, got
 
 
 def _make_fake_id(world, fake_lib, q):

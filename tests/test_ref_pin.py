@@ -11,6 +11,84 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = os.path.join(ROOT, "oracle", "_ref", "libref_pin.so")
 
 
+GOLDEN = os.path.join(ROOT, "tests", "golden", "ref_pin_small.npz")
+
+
+class _Fn:
+    """a Python callable that, like a ctypes function, takes restype / argtypes"""
+
+    def __init__(self, f):
+        self.f = f
+
+    def __call__(self, *a):
+        return self.f(*a)
+
+
+class GoldenPin:
+    """Stand-in for oracle/_ref/libref_pin.so where the reference is not present: the same entry points, answered from what the harness returned on a fixed,
+    structured sample of inputs (tests/golden/ref_pin_small.npz, tests/golden/make_ref_pin_golden.py).  The sweeps cover that sample instead of every pattern."""
+
+    def __init__(self, path):
+        import numpy as np
+        self.np = np
+        g = self.g = dict(np.load(path))
+        self.f64_sample = g["f64"]
+        keys = np.concatenate([g["f64"], g["f64_special"]]).view(np.uint64)
+        self.f64_keys, order = np.unique(keys, return_index=True)
+        self.f64_vals = {w: np.concatenate([g["f64_out"][w], g["f64_special_out"][w - 2] if w in (2, 3) else np.zeros(g["f64_special"].size, np.int32)])[order]
+                         for w in range(6)}
+        self.const = dict(zip(g["const_ids"].tolist(), g["const_vals"].tolist()))
+        self.app_ints = dict(zip(g["int_names"].tolist(), g["int_vals"].tolist()))
+        self.app_doubles = dict(zip(g["double_names"].tolist(), g["double_vals"].tolist()))
+        for name in ("ref_pin_sweep_f32", "ref_pin_sweep_i32", "ref_pin_sweep_ceil_floor_f32", "ref_pin_eval_f64", "ref_pin_const", "ref_pin_app_int", "ref_pin_app_double"):
+            setattr(self, name, _Fn(getattr(self, "_" + name)))
+
+    def _ref_pin_sweep_f32(self, which, fp, first, count, limit, skip_nan, first_bad):
+        np = self.np
+        f = C.CFUNCTYPE(C.c_int, C.c_float)(fp.value)
+        bits = self.g["f32_bits"]
+        v = bits.view(np.float32)
+        sel = ((bits.astype(np.int64) - int(first)) % (1 << 32) < int(count)) & np.where(np.isnan(v), not skip_nan, (v > -limit) & (v < limit))
+        bad = [int(b) for b, x, r in zip(bits[sel], v[sel], self.g["f32_out"][which][sel]) if f(float(x)) != r]
+        first_bad._obj.value = min(bad) if bad else 0
+        return len(bad)
+
+    def _ref_pin_sweep_i32(self, which, fp, first, count):
+        np = self.np
+        f = C.CFUNCTYPE(C.c_int, C.c_int)(fp.value)
+        x = self.g["i32"]
+        sel = (x.astype(np.int64) >= first) & (x.astype(np.int64) < first + count)
+        return sum(f(int(a)) != r for a, r in zip(x[sel], self.g["i32_out"][which][sel]))
+
+    def _ref_pin_sweep_ceil_floor_f32(self):
+        np = self.np
+        v = self.g["f32_bits"].view(np.float32)
+        sel = (v > -2147483000.0) & (v < 2147483000.0)
+        return int(np.sum(self.g["f32_out"][4][sel] != np.ceil(v[sel]).astype(np.int32)) + np.sum(self.g["f32_out"][3][sel] != np.floor(v[sel]).astype(np.int32)))
+
+    def _ref_pin_eval_f64(self, which, xp, op, n):
+        np = self.np
+        x = np.ctypeslib.as_array((C.c_double * n).from_address(xp)).view(np.uint64)
+        i = np.minimum(np.searchsorted(self.f64_keys, x), self.f64_keys.size - 1)
+        assert np.array_equal(self.f64_keys[i], x), "the golden stand-in knows the reference's values on its stored sample only"
+        np.ctypeslib.as_array((C.c_int * n).from_address(op))[:] = self.f64_vals[which][i]
+
+    def _ref_pin_const(self, which):
+        return self.const.get(which, -1)
+
+    def _ref_pin_app_int(self, name, out):
+        if name.decode() not in self.app_ints:
+            return 0
+        out._obj.value = self.app_ints[name.decode()]
+        return 1
+
+    def _ref_pin_app_double(self, name, out):
+        if name.decode() not in self.app_doubles:
+            return 0
+        out._obj.value = self.app_doubles[name.decode()]
+        return 1
+
+
 @pytest.fixture(scope="module")
 def pin(oracle):
     if not os.path.exists(REF):
@@ -18,7 +96,7 @@ def pin(oracle):
             import subprocess
             subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "ref"])
         else:
-            pytest.skip("oracle/_ref/libref_pin.so not built (needs /root/reference)")
+            return GoldenPin(GOLDEN), oracle.lib()
     ref = C.CDLL(REF)
     ref.ref_pin_sweep_f32.restype = C.c_longlong
     ref.ref_pin_sweep_f32.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_ulonglong, C.c_float, C.c_int, C.POINTER(C.c_uint32)]
@@ -123,6 +201,7 @@ def test_double_precision_rounding_helpers(pin6):
     ties = np.arange(-200000, 200000, dtype=np.float64) + 0.5
     sizes = np.arange(1, 8193, dtype=np.float64)[:, None] * np.sqrt(np.array([0.6, 0.01, 1.4, 2.2]) * 1e6 / (1920.0 * 1080.0))[None, :]
     v = np.ascontiguousarray(np.concatenate([v, ties, sizes.ravel(), rng.uniform(-70000, 70000, 500000)]))
+    v = getattr(pin6, "f64_sample", v)      # (the golden stand-in knows the reference's values on its stored sample of the same kinds only)
     out = np.empty(v.size, np.int32)
 
     def ref(which, x=v, o=out):
