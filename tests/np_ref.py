@@ -1,6 +1,7 @@
 """Independent numpy restatements of the reference kernels, used ONLY to cross-check the C oracle
-(tests/test_oracle_crosscheck.py).  Deliberately written differently from oracle/*.c: vectorised, integer
-arithmetic for the 16S pyramids (the CUDA fp32 sums are exact dyadics), float64 emulation of fmaf for the taps."""
+(tests/test_oracle_crosscheck.py, tests/test_np_ref_crosscheck.py) and the device (tests/test_prims_vs_numpy_gpu.py).  Deliberately written
+differently from oracle/*.c: vectorised, integer arithmetic for the 16S pyramids (the CUDA fp32 sums are exact dyadics), an exactly rounded
+fp32 fma (fmaf32) for the fused chains, definitions instead of algorithms where the reference's result is defined by them (distance transform)."""
 import numpy as np
 
 
@@ -59,8 +60,8 @@ def pyr_up_16s(src):
 
 
 def remap_linear(src, mx, my):
-    """filters.hpp:90-114 + border_interpolate.hpp:698-717; fmaf emulated in float64 (products of two fp32 are exact
-    in fp64; the final rounding to fp32 can double-round in rare cases -> compare with tolerance 1)."""
+    """filters.hpp:90-114 (`out = out + src_reg * w` in tap order, contracted to fma by nvcc) + border_interpolate.hpp:698-717 (taps outside
+    the image read 0); the fma chain through fmaf32, so the result is exact."""
     h, w = src.shape[:2]
     x1 = np.floor(mx).astype(np.int64); y1 = np.floor(my).astype(np.int64)
     x2, y2 = x1 + 1, y1 + 1
@@ -71,10 +72,9 @@ def remap_linear(src, mx, my):
     out = np.zeros(mx.shape + (3,), np.float32)
     for (yy, xx), wt in zip(taps, wts):
         inb = (xx >= 0) & (xx < w) & (yy >= 0) & (yy < h)
-        v = np.where(inb[..., None], src[np.clip(yy, 0, h - 1), np.clip(xx, 0, w - 1)], 0).astype(np.float64)
-        out = (v * wt[..., None].astype(np.float64) + out.astype(np.float64)).astype(np.float32)
-    r = np.rint(out)
-    return np.clip(np.nan_to_num(r, nan=0.0), 0, 255).astype(np.uint8)
+        v = np.where(inb[..., None], src[np.clip(yy, 0, h - 1), np.clip(xx, 0, w - 1)], 0).astype(np.float32)
+        out = fmaf32(v, wt.astype(np.float32)[..., None], out)
+    return sat_u8(out)
 
 
 def add_src_weight(src, w, dst, dst_w):
@@ -181,3 +181,324 @@ def cv_pyr_down_32f(src):
     nvec = (len(ox) // 8) * 8
     out = np.where(np.arange(len(ox))[None, :] < nvec, vec, tail).astype(f)
     return (out * f(1.0 / 256)).astype(f)
+
+
+# ---- the remaining oracle kernels (CUDA flavour unless said otherwise), stated from the reference sources the oracle cites ------------------
+F32 = np.float32
+
+
+def fmaf32(a, b, c):
+    """Correctly rounded fp32 fused multiply-add, elementwise.  a*b of two fp32 values is exact in fp64; s = p + c and its TwoSum error e
+    give the exact sum s + e; rounding s to odd (step one ulp toward e when e != 0 and s has an even mantissa) keeps 53 - 24 > 2 guard bits,
+    so the final cast to fp32 rounds once, correctly."""
+    a, b, c = (np.asarray(v, F32).astype(np.float64) for v in (a, b, c))
+    a, b, c = np.broadcast_arrays(a, b, c)
+    with np.errstate(invalid="ignore", over="ignore"):
+        p = a * b
+        s = p + c
+        bb = s - p
+        e = (p - (s - bb)) + (c - bb)
+        fix = np.isfinite(s) & np.isfinite(e) & (e != 0) & ((s.view(np.int64) & 1) == 0)
+        s = np.where(fix, np.nextafter(s, np.where(e > 0, np.inf, -np.inf)), s)
+        return s.astype(F32)
+
+
+def sat_u8(v):
+    """saturate_cast<uchar>(float) (cuda/saturate_cast.hpp): round to nearest even, clamp, NaN -> 0."""
+    v = np.asarray(v, F32)
+    with np.errstate(invalid="ignore"):
+        return np.clip(np.nan_to_num(np.rint(v), nan=0.0, posinf=255.0, neginf=0.0), 0, 255).astype(np.uint8)
+
+
+def f2i_rz(v):
+    """__float2int_rz: toward zero, saturating to int32, NaN -> 0."""
+    v = np.asarray(v, np.float64)
+    with np.errstate(invalid="ignore"):
+        return np.clip(np.nan_to_num(np.trunc(v), nan=0.0), -2.0 ** 31, 2.0 ** 31 - 1).astype(np.int64)
+
+
+def pyr_down_32f(src):
+    """pyr_down.cu:55-174 instantiated for float (the weight pyramids, blenders.cpp:420-423): per source column the vertical chain
+    sum = 0.0625 r[-2]; sum = sum + 0.25 r[-1]; ... (contracted to fma), then the same chain horizontally over the column sums;
+    BORDER_REFLECT_101 on both axes, ((h + 1) / 2, (w + 1) / 2) outputs, every second row and column."""
+    h, w = src.shape
+    s = np.asarray(src, F32)
+    k = [F32(0.0625), F32(0.25), F32(0.375), F32(0.25), F32(0.0625)]
+    oy, ox = np.arange((h + 1) // 2) * 2, np.arange((w + 1) // 2) * 2
+
+    def chain(taps):
+        acc = (k[0] * taps[0]).astype(F32)
+        for c, t in zip(k[1:], taps[1:]):
+            acc = fmaf32(c, t, acc)
+        return acc
+    vert = chain([s[r101(oy + a - 2, h)] for a in range(5)])                 # (dh, w): the column sums of the rows the outputs use
+    return chain([vert[:, r101(ox + b - 2, w)] for b in range(5)])
+
+
+def resize_linear_8u(src, dsize=None, fx=0.0, fy=0.0):
+    """cuda::resize INTER_LINEAR.  Host (resize.cpp): dsize = saturate_cast<int>(cols * fx) when not given, else fx = dsize.width / cols;
+    dsize == src.size() is a copy; the kernel gets float(1 / fx).  Kernel resize.cu:71-106: src_x = dst_x * fx (fp32), x1 = floor, x2 = x1 + 1,
+    reads of x2 / y2 clamped to the last column / row (the weights keep the unclamped x2, y2), out = out + src * w in tap order, saturate_cast."""
+    rows, cols = src.shape[:2]
+    if dsize is None:
+        dsize = (int(np.rint(cols * fx)), int(np.rint(rows * fy)))
+    else:
+        fx, fy = dsize[0] / cols, dsize[1] / rows
+    if (dsize[1], dsize[0]) == (rows, cols):
+        return np.array(src, copy=True)
+    ifx, ify = F32(1.0 / fx), F32(1.0 / fy)
+    img = src[..., None] if src.ndim == 2 else src
+    sx = (np.arange(dsize[0]).astype(F32) * ifx).astype(F32)
+    sy = (np.arange(dsize[1]).astype(F32) * ify).astype(F32)
+    x1, y1 = np.floor(sx).astype(np.int64), np.floor(sy).astype(np.int64)
+    x2, y2 = x1 + 1, y1 + 1
+    x2r, y2r = np.minimum(x2, cols - 1), np.minimum(y2, rows - 1)
+    wx1, wx2 = (x2.astype(F32) - sx)[None, :], (sx - x1.astype(F32))[None, :]
+    wy1, wy2 = (y2.astype(F32) - sy)[:, None], (sy - y1.astype(F32))[:, None]
+    out = np.zeros((dsize[1], dsize[0], img.shape[2]), F32)
+    for ry, rx, wt in ((y1, x1, wx1 * wy1), (y1, x2r, wx2 * wy1), (y2r, x1, wx1 * wy2), (y2r, x2r, wx2 * wy2)):
+        out = fmaf32(img[ry][:, rx].astype(F32), wt.astype(F32)[..., None], out)
+    out = sat_u8(out)
+    return out[..., 0] if src.ndim == 2 else out
+
+
+# ITU-R BT.601 fixed point of OpenCV's YUV <-> RGB invokers (imgproc color.cpp, ITUR_BT_601_*: coefficient * 2^20, rounded)
+_SH = 20
+_CY, _CUB, _CUG, _CVG, _CVR = 1220542, 2116026, -409993, -852492, 1673527
+_CRY, _CGY, _CBY, _CRU, _CGU, _CBU, _CGV, _CBV = 269484, 528482, 102760, -155188, -305135, 460324, -385875, -74448
+
+
+def nv12_to_bgr(src):
+    """YUV420sp2RGB888Invoker<bIdx 0, uIdx 0>: Y plane (h rows) then h/2 rows of interleaved U, V shared by a 2x2 block;
+    Y' = max(0, Y - 16) * CY; B = (Y' + CUB u + 2^19) >> 20, G = (Y' + CVG v + CUG u + 2^19) >> 20, R = (Y' + CVR v + 2^19) >> 20, saturated."""
+    h = src.shape[0] * 2 // 3
+    Y = src[:h].astype(np.int64)
+    uv = src[h:].astype(np.int64)
+    u = np.repeat(np.repeat(uv[:, 0::2], 2, axis=0), 2, axis=1)[:h] - 128
+    v = np.repeat(np.repeat(uv[:, 1::2], 2, axis=0), 2, axis=1)[:h] - 128
+    yy = np.maximum(Y - 16, 0) * _CY
+    half = 1 << (_SH - 1)
+    b = (yy + half + _CUB * u) >> _SH
+    g = (yy + half + _CVG * v + _CUG * u) >> _SH
+    r = (yy + half + _CVR * v) >> _SH
+    return np.clip(np.stack([b, g, r], -1), 0, 255).astype(np.uint8)
+
+
+def bgr_to_i420(src):
+    """RGB888toYUV420pInvoker (planar, U before V): Y = (CRY r + CGY g + CBY b + 2^19 + 16 * 2^20) >> 20 per pixel; U, V from the TOP-LEFT pixel
+    of each 2x2 block: U = (CRU r + CGU g + CBU b + 2^19 + 128 * 2^20) >> 20, V = (CBU r + CGV g + CBV b + ...) >> 20 (CRV = CBU); saturated.
+    Output (h * 3 / 2, w): Y, then U (h/2 x w/2) and V (h/2 x w/2) back to back."""
+    h, w = src.shape[:2]
+    s = src.astype(np.int64)
+    b, g, r = s[..., 0], s[..., 1], s[..., 2]
+    half = 1 << (_SH - 1)
+    Y = (_CRY * r + _CGY * g + _CBY * b + half + (16 << _SH)) >> _SH
+    tl = (slice(0, h - h % 2, 2), slice(0, w - w % 2, 2))
+    U = (_CRU * r[tl] + _CGU * g[tl] + _CBU * b[tl] + half + (128 << _SH)) >> _SH
+    V = (_CBU * r[tl] + _CGV * g[tl] + _CBV * b[tl] + half + (128 << _SH)) >> _SH
+    out = np.zeros((h * 3 // 2, w), np.uint8)
+    out[:h] = np.clip(Y, 0, 255)
+    chroma = np.concatenate([np.clip(U, 0, 255).ravel(), np.clip(V, 0, 255).ravel()]).astype(np.uint8)
+    out.reshape(-1)[h * w:h * w + chroma.size] = chroma
+    return out
+
+
+# BT.601 in float64 from its definition (Kr = 0.299, Kb = 0.114; studio range: Y' 16..235 over 219 steps, chroma 128 +- 112 over 224)
+_KR, _KB = 0.299, 0.114
+_KG = 1.0 - _KR - _KB
+
+
+def bt601_yuv_to_bgr_f64(Y, U, V):
+    """R, G, B in 0..255 (float64, unrounded) of studio-range Y'CbCr; Y' below 16 is clamped to 16 (the footroom convention of the invoker)."""
+    y = np.maximum(np.asarray(Y, np.float64) - 16.0, 0.0) * (255.0 / 219.0)
+    cb = (np.asarray(U, np.float64) - 128.0) * (255.0 / 224.0)
+    cr = (np.asarray(V, np.float64) - 128.0) * (255.0 / 224.0)
+    r = y + 2.0 * (1.0 - _KR) * cr
+    b = y + 2.0 * (1.0 - _KB) * cb
+    g = (y - _KR * r - _KB * b) / _KG
+    return np.stack([b, g, r], -1)
+
+
+def bt601_bgr_to_yuv_f64(bgr):
+    """(Y', Cb, Cr) float64, unrounded, of 8-bit full-range B, G, R."""
+    s = np.asarray(bgr, np.float64)
+    b, g, r = s[..., 0], s[..., 1], s[..., 2]
+    yn = _KR * r + _KG * g + _KB * b
+    return 16.0 + yn * (219.0 / 255.0), 128.0 + (b - yn) / (2.0 * (1.0 - _KB)) * (224.0 / 255.0), 128.0 + (r - yn) / (2.0 * (1.0 - _KR)) * (224.0 / 255.0)
+
+
+def _cell(x, n, t):
+    """custom_resize's cell index (APP/resize.cu:14-15, integer division) and fp32 fraction ((float)x * (n - 1) / t - index)."""
+    i = (x * (n - 1)) // t
+    q = ((x.astype(F32) * F32(n - 1)).astype(F32) / F32(t)).astype(F32)
+    return i, (q - i.astype(F32)).astype(F32)
+
+
+def custom_resize_32f(src, tx, ty):
+    """APP/resize.cu:9-27: out = (1-uu)(1-vv) in[top][left] + uu(1-vv) in[top][left+1] + (1-uu)vv in[top+1][left] + uu vv in[top+1][left+1],
+    left to right with the three additions contracted to fma; NaN in a tap propagates.  Needs rows, cols >= 2."""
+    src = np.asarray(src, F32)
+    rows, cols = src.shape
+    left, uu = _cell(np.arange(tx), cols, tx)
+    top, vv = _cell(np.arange(ty), rows, ty)
+    U, V = uu[None, :], vv[:, None]
+    one = F32(1)
+    a, b, c, d = (one - U) * (one - V), U * (one - V), (one - U) * V, U * V
+    T, L = top[:, None], left[None, :]
+    with np.errstate(invalid="ignore"):
+        r = (a * src[T, L]).astype(F32)
+        r = fmaf32(b, src[T, L + 1], r)
+        r = fmaf32(c, src[T + 1, L], r)
+        return fmaf32(d, src[T + 1, L + 1], r)
+
+
+def convert_mesh_to_map(mesh_x, mesh_y, width, height):
+    """MeshWarper::convertMeshesToMap for one view (APP/meshwarper.cpp:823-886): the vertex mesh resized to the view (custom_resize), each
+    pixel (x, y) dropped into the half-resolution cell ((int)mx / 2, (int)my / 2) (C truncation, so (-2, 0) lands in cell 0), every cell's
+    mean of the x and y that landed there (0 / 0 = NaN for an empty cell), resized back to width x height."""
+    bx, by = custom_resize_32f(mesh_x, width, height), custom_resize_32f(mesh_y, width, height)
+    hw, hh = width // 2, height // 2
+    with np.errstate(invalid="ignore"):
+        ok = (bx > -2.0 ** 31) & (bx < 2.0 ** 31) & (by > -2.0 ** 31) & (by < 2.0 ** 31)
+    ix = np.where(ok, np.trunc(np.where(ok, bx, 0)), 0).astype(np.int64)
+    iy = np.where(ok, np.trunc(np.where(ok, by, 0)), 0).astype(np.int64)
+    cx, cy = np.sign(ix) * (np.abs(ix) // 2), np.sign(iy) * (np.abs(iy) // 2)
+    ok &= (cx >= 0) & (cy >= 0) & (cx < hw) & (cy < hh)
+    yy, xx = np.mgrid[0:height, 0:width]
+    sx, sy, cnt = (np.zeros((hh, hw)) for _ in range(3))       # integer sums, exact in fp64 (and in the fp32 of the reference while < 2^24)
+    np.add.at(sx, (cy[ok], cx[ok]), xx[ok]); np.add.at(sy, (cy[ok], cx[ok]), yy[ok]); np.add.at(cnt, (cy[ok], cx[ok]), 1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mx, my = (sx.astype(F32) / cnt.astype(F32)).astype(F32), (sy.astype(F32) / cnt.astype(F32)).astype(F32)
+    return custom_resize_32f(mx, width, height), custom_resize_32f(my, width, height)
+
+
+def remap_nearest_8uc1(src, mx, my):
+    """PointFilter (filters.hpp:58-77): src(__float2int_rz(y), __float2int_rz(x)); BrdConstant(0) outside."""
+    h, w = src.shape
+    xi, yi = f2i_rz(mx), f2i_rz(my)
+    inb = (xi >= 0) & (xi < w) & (yi >= 0) & (yi < h)
+    return np.where(inb, src[np.clip(yi, 0, h - 1), np.clip(xi, 0, w - 1)], 0).astype(np.uint8)
+
+
+def convert_scale_8u(src, alpha):
+    """Convertor<uchar, uchar, float> (gpu_mat.cu): saturate_cast<uchar>(float(alpha) * src + 0)."""
+    return sat_u8(F32(alpha) * np.asarray(src).astype(F32))
+
+
+def convert_8u_32f_scale(src, alpha):
+    """Convertor<uchar, float, float>: float(alpha) * src (the + 0 of beta is exact)."""
+    return (F32(alpha) * np.asarray(src).astype(F32)).astype(F32)
+
+
+def convert_16s_8u(src):
+    """saturate_cast<uchar>(short)."""
+    return np.clip(src, 0, 255).astype(np.uint8)
+
+
+def copy_make_border_const_32f(src, top, bottom, left, right):
+    """copyMakeBorder BORDER_CONSTANT(0) on 32FC1."""
+    return np.pad(np.asarray(src, F32), ((top, bottom), (left, right)), mode="constant", constant_values=0)
+
+
+def dilate3x3_8u(src):
+    """3x3 maximum, the border replicated (a max filter's identity for the frame)."""
+    h, w = src.shape
+    p = np.pad(src, 1, mode="edge")
+    return np.max(np.stack([p[dy:dy + h, dx:dx + w] for dy in range(3) for dx in range(3)]), axis=0)
+
+
+def _wrap16(v):
+    return ((np.asarray(v, np.int64) + 32768) % 65536 - 32768).astype(np.int16)
+
+
+def add_src_weight_16s(src, w, dst, dst_w):
+    """addSrcWeightKernel16S (multiband_blend.cu:10-24): dst += short((v * w) >> 8) (int product, arithmetic shift = floor), dst_w += w; short wraps."""
+    ww = w.astype(np.int64)
+    dst[...] = _wrap16(dst.astype(np.int64) + _wrap16((src.astype(np.int64) * ww[..., None]) >> 8))
+    dst_w[...] = _wrap16(dst_w.astype(np.int64) + ww)
+
+
+def normalize_16s(w, src):
+    """normalizeUsingWeightKernel16S (multiband_blend.cu:62-74): short((v << 8) / w), C division (toward zero).  w == 0 is undefined there."""
+    num = src.astype(np.int64) * 256
+    den = np.broadcast_to(w.astype(np.int64)[..., None], num.shape)
+    assert (den != 0).all(), "w == 0: undefined in the reference"
+    q = np.abs(num) // np.abs(den) * np.sign(num) * np.sign(den)
+    src[...] = _wrap16(q)
+
+
+def distance_transform_l1(src):
+    """cv::distanceTransform(DIST_L1): for every pixel, the taxicab distance |dx| + |dy| to the nearest zero pixel of the image (pixels outside
+    the image are not zeros).  An image without a zero pixel: +inf everywhere (the reference holds a large sentinel there)."""
+    src = np.asarray(src)
+    h, w = src.shape
+    zy, zx = np.nonzero(src == 0)
+    if zy.size == 0:
+        return np.full((h, w), np.inf, F32)
+    py, px = np.mgrid[0:h, 0:w]
+    py, px = py.ravel(), px.ravel()
+    out = np.empty(h * w, np.int64)
+    step = max(1, 4_000_000 // zy.size)
+    for i in range(0, h * w, step):
+        out[i:i + step] = (np.abs(py[i:i + step, None] - zy[None, :]) + np.abs(px[i:i + step, None] - zx[None, :])).min(axis=1)
+    return out.reshape(h, w).astype(F32)
+
+
+def voronoi_seams(corners, masks):
+    """VoronoiSeamFinder (seam_finders.cpp:71-83, 111-160), masks edited in place: for every overlapping pair (i < j, in order), over the
+    overlap grown by a 10-px gap (outside a view: 0), each view's 'unique' pixels (its mask minus the collision of the two) and the taxicab
+    distance of every pixel to them; a pixel of the overlap strictly nearer to view i's unique pixels is cleared from view j, every other one
+    from view i."""
+    gap = 10
+    n = len(masks)
+    for i in range(n - 1):
+        for j in range(i + 1, n):
+            (x1, y1), (x2, y2) = corners[i], corners[j]
+            (h1, w1), (h2, w2) = masks[i].shape, masks[j].shape
+            tlx, tly = max(x1, x2), max(y1, y2)
+            brx, bry = min(x1 + w1, x2 + w2), min(y1 + h1, y2 + h2)
+            if not (tlx < brx and tly < bry):
+                continue
+            ys, xs = np.arange(tly - gap, bry + gap), np.arange(tlx - gap, brx + gap)
+
+            def cut(m, cx, cy):
+                yy, xx = ys - cy, xs - cx
+                okr, okc = (yy >= 0) & (yy < m.shape[0]), (xx >= 0) & (xx < m.shape[1])
+                sub = m[np.clip(yy, 0, m.shape[0] - 1)][:, np.clip(xx, 0, m.shape[1] - 1)]
+                return np.where(okr[:, None] & okc[None, :], sub, 0)
+            s1, s2 = cut(masks[i], x1, y1), cut(masks[j], x2, y2)
+            both = (s1 != 0) & (s2 != 0)
+            d1 = distance_transform_l1(np.where(both, 0, s1) == 0)
+            d2 = distance_transform_l1(np.where(both, 0, s2) == 0)
+            seam = (d1 < d2)[gap:-gap, gap:-gap]
+            v2 = masks[j][tly - y2:bry - y2, tlx - x2:brx - x2]
+            v1 = masks[i][tly - y1:bry - y1, tlx - x1:brx - x1]
+            v2[seam] = 0
+            v1[~seam] = 0
+    return masks
+
+
+def warp_maps_f64(proj, tl_u, tl_v, rows, cols, k_rinv, scale, t=(0, 0, 0)):
+    """The backward maps of buildWarpMapsKernel (build_warp_maps.cu:67-152) in float64, from the same fp32 k_rinv, scale and t: the TRUE map
+    the fp32 kernel approximates.  proj 0 plane, 1 cylindrical, 2 spherical (the ms_stitch.h / ORC_PROJ_* codes).  Returns (x, y, z) -- z is
+    the denominator, whose sign decides the reference's (-1, -1) for points behind the camera (cylindrical, spherical; the plane divides)."""
+    k = np.asarray(k_rinv, F32).astype(np.float64).reshape(9)
+    sc = float(F32(scale))
+    tt = np.asarray(t, F32).astype(np.float64)
+    u = (tl_u + np.arange(cols, dtype=np.float64))[None, :] / sc
+    v = (tl_v + np.arange(rows, dtype=np.float64))[:, None] / sc
+    if proj == 0:
+        x_, y_, z_ = u - tt[0], v - tt[1], 1.0 - tt[2]
+    elif proj == 1:
+        x_, y_, z_ = np.sin(u), v, np.cos(u)
+    else:
+        x_, y_, z_ = np.sin(v) * np.sin(u), -np.cos(v), np.sin(v) * np.cos(u)
+    x_, y_, z_ = np.broadcast_arrays(x_, y_, z_)
+    x = k[0] * x_ + k[1] * y_ + k[2] * z_
+    y = k[3] * x_ + k[4] * y_ + k[5] * z_
+    z = k[6] * x_ + k[7] * y_ + k[8] * z_
+    with np.errstate(divide="ignore", invalid="ignore"):
+        x, y = x / z, y / z
+    if proj != 0:
+        x, y = np.where(z > 0, x, -1.0), np.where(z > 0, y, -1.0)
+    return x, y, z
