@@ -361,20 +361,32 @@ def test_cpw_stage1_short_list_and_fallback(ms, cuda, oracle, amp):
     comp.close()
 
 
-@pytest.mark.parametrize("rig", ["cfg2", "mini4"])
-def test_lds_staged_warp_equals_direct(ms, cuda, rig):
+@pytest.mark.parametrize("rig,nf", [pytest.param("cfg2", 1, id="cfg2"), pytest.param("mini4", 1, id="mini4"), pytest.param("mini4", 49, id="mini4-49frames")])
+def test_lds_staged_warp_equals_direct(ms, cuda, rig, nf):
     """Opt-in variant of the warp kernel that stages each tile's source bounding box through LDS (16-byte chunk copy,
-    v_alignbyte extraction): same pixels as the default direct-gather path."""
+    v_alignbyte extraction): same pixels as the default direct-gather path.  49 frames of mini4: a full chunk of 48 (192 / 4 views) in 16-byte
+    aligned tensors, then a one-frame chunk whose views start 4 bytes into their buffers -- the tail fails the staged form's 16-byte check and
+    runs the direct form; ms_get_stitch_kernels reports the first chunk's form, and every frame equals the same frame stitched alone."""
     outs = []
     for lds in (False, True):
-        comp, cfg, gains = make_rig(ms, rig, lds_stage=lds)
+        comp, cfg, gains = make_rig(ms, rig, max_frames=nf, lds_stage=lds)
         pg = comp.pano_geom()
-        out16 = torch.zeros((pg.dst_roi_final.height, pg.dst_roi_final.width, 3), dtype=torch.int16, device=cuda)
-        comp.stitch([[to_dev(synth.frame(cfg["w"], cfg["h"], i, 4)) for i in range(cfg["n"])]], out16s=[out16])
+        shape = (pg.dst_roi_final.height, pg.dst_roi_final.width, 3)
+        frames = [[to_dev(synth.frame(cfg["w"], cfg["h"], i, 4 + t)) for i in range(cfg["n"])] for t in range(nf)]
+        if nf > 1:
+            frames[-1] = [_laid_out(synth.frame(cfg["w"], cfg["h"], i, 4 + nf - 1), 0, 4) for i in range(cfg["n"])]
+        batch = [torch.zeros(shape, dtype=torch.int16, device=cuda) for _ in range(nf)]
+        comp.stitch(frames, out16s=batch)
         torch.cuda.synchronize()
-        outs.append(out16)
+        if lds:
+            assert comp.stitch_kernels()[0] == "lds_staged", comp.stitch_kernels()
+            for t in range(nf if nf > 1 else 0):
+                single = torch.zeros(shape, dtype=torch.int16, device=cuda)
+                comp.stitch([frames[t]], out16s=[single])
+                assert torch.equal(single, batch[t]), t
+        outs.append(batch)
         comp.close()
-    assert torch.equal(outs[0], outs[1])
+    assert all(torch.equal(a, b) for a, b in zip(*outs))
 
 
 @pytest.mark.parametrize("rig,shards", [("mini6", 2), ("mini6", 3), ("cfg2", 2), ("cfg5", 2)])       # cfg5 = BASELINE configs[4]: 12 x 4K, views 6 + 6

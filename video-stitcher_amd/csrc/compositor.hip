@@ -2090,7 +2090,7 @@ int ms_create(const ms_config *cfg, ms_ctx **out)
     MS_CHECK(cfg->warp_scale > 0.f, "ms_create: warp_scale must be positive");
     MS_CHECK(cfg->num_bands >= 0 && cfg->num_bands < MAX_LEVELS, "ms_create: num_bands %d not in [0,%d)", cfg->num_bands, MAX_LEVELS);
     const int F = cfg->max_frames > 0 ? cfg->max_frames : 1;
-    MS_CHECK(F <= MAX_FRAMES && cfg->num_views <= MAX_SRC, "ms_create: max_frames %d exceeds the per-call limit %d", F, MAX_FRAMES);
+    MS_CHECK(F <= MAX_FRAMES, "ms_create: max_frames %d exceeds the per-call limit %d", F, MAX_FRAMES);
     ms_ctx *c = new (std::nothrow) ms_ctx();
     if (!c) return fail(MS_ERR_NOMEM, "ms_create: out of host memory");
     c->cfg = *cfg;
@@ -3055,363 +3055,386 @@ int ms_get_mesh_displacement(ms_ctx *c, int view, float *out_px)
     return MS_OK;
 }
 
+}  // extern "C" (templates below)
+
 // ---- the per-frame path --------------------------------------------------------------------------
-// launch a kernel whose LAST template argument is the projection, with the context's projection.
-// TARGS = the leading template arguments in parentheses, with a trailing comma, e.g. (true, false,) or ()
-#define MS_UNPAREN(...) __VA_ARGS__
-#define MS_PROJ_LAUNCH(K, TARGS, CFG, ...)                                                                                   \
-    do {                                                                                                                    \
-        if (c->cfg.projection == MS_PROJ_SPHERICAL) K<MS_UNPAREN TARGS MS_PROJ_SPHERICAL><<<MS_UNPAREN CFG>>>(__VA_ARGS__);         \
-        else if (c->cfg.projection == MS_PROJ_CYLINDRICAL) K<MS_UNPAREN TARGS MS_PROJ_CYLINDRICAL><<<MS_UNPAREN CFG>>>(__VA_ARGS__); \
-        else K<MS_UNPAREN TARGS MS_PROJ_PLANE><<<MS_UNPAREN CFG>>>(__VA_ARGS__);                                                    \
-    } while (0)
+// stitch_impl: check the call, hand the mesh / mask tables over, then enqueue the warps, the reduce chain and the band chain.  The kernel a launch runs is
+// chosen once (stage1_form / warp_form); the launch switches on that choice, and ms_get_stitch_kernels reports the same value.
 
-// k_stage1_t<PROJ, AL>: the projection comes first there
-#define MS_PROJ_AL_LAUNCH(K, AL, NF, CFG, ...)                                                                              \
-    do {                                                                                                                    \
-        if (c->cfg.projection == MS_PROJ_SPHERICAL) K<MS_PROJ_SPHERICAL, AL, NF><<<MS_UNPAREN CFG>>>(__VA_ARGS__);           \
-        else if (c->cfg.projection == MS_PROJ_CYLINDRICAL) K<MS_PROJ_CYLINDRICAL, AL, NF><<<MS_UNPAREN CFG>>>(__VA_ARGS__);  \
-        else K<MS_PROJ_PLANE, AL, NF><<<MS_UNPAREN CFG>>>(__VA_ARGS__);                                                      \
-    } while (0)
-
-// k_warp_s<CPW, PROJ, NF>: NF frames per lane, or 1 for a one-frame call
-#define MS_WARP_S_LAUNCH(CPW_, NF_, LDS_, ...)                                                                                                  \
-    do {                                                                                                                                        \
-        const dim3 b_(WARP_BX, WARP_WY);                                                                                                        \
-        if (F == 1) { const dim3 g_(c->n_warp_tiles, WARP_BY / WARP_WY, 1);                                                                     \
-            if (c->cfg.projection == MS_PROJ_SPHERICAL) k_warp_s<CPW_, MS_PROJ_SPHERICAL, 1><<<g_, b_, LDS_, st>>>(__VA_ARGS__);                 \
-            else if (c->cfg.projection == MS_PROJ_CYLINDRICAL) k_warp_s<CPW_, MS_PROJ_CYLINDRICAL, 1><<<g_, b_, LDS_, st>>>(__VA_ARGS__);        \
-            else k_warp_s<CPW_, MS_PROJ_PLANE, 1><<<g_, b_, LDS_, st>>>(__VA_ARGS__);                                                            \
-        } else { const dim3 g_(c->n_warp_tiles, WARP_BY / WARP_WY, div_up(F, NF_));                                                             \
-            if (c->cfg.projection == MS_PROJ_SPHERICAL) k_warp_s<CPW_, MS_PROJ_SPHERICAL, NF_><<<g_, b_, LDS_, st>>>(__VA_ARGS__);               \
-            else if (c->cfg.projection == MS_PROJ_CYLINDRICAL) k_warp_s<CPW_, MS_PROJ_CYLINDRICAL, NF_><<<g_, b_, LDS_, st>>>(__VA_ARGS__);      \
-            else k_warp_s<CPW_, MS_PROJ_PLANE, NF_><<<g_, b_, LDS_, st>>>(__VA_ARGS__);                                                          \
-        }                                                                                                                                       \
-    } while (0)
-
-static int stitch_impl(ms_ctx *c, int n_frames, const ms_image *views, ms_image *out8u, ms_image *out16s, hipStream_t st,
-                       int cap, const char **names, float *ms_out, int *n_rec, ShardArgs S = ShardArgs{}, ms_image *out_i420 = nullptr, bool nv12 = false)
+// with_value<V0, V1, ..>(v, f) calls f(std::integral_constant<decltype(Vi), Vi>{}) for the first Vi equal to v, the LAST one where none is: a runtime value
+// as a kernel's template argument.  Every branch inlines to its own plain launch.
+template <auto V0, auto... Vs, class T, class Fn>
+static inline void with_value(T v, Fn &&f)
 {
-    if (!c) return fail(MS_ERR_INVALID, "null context");
-    std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);      // a synchronous table rebuild on another thread (ms_update_mask without a margin) waits for this enqueue, and vice versa
+    if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<decltype(V0), V0>{});
+    else if (v == V0) f(std::integral_constant<decltype(V0), V0>{});
+    else with_value<Vs...>(v, f);
+}
+template <class Fn>
+static inline void with_proj(const ms_ctx *c, Fn &&f) { with_value<(int)MS_PROJ_SPHERICAL, (int)MS_PROJ_CYLINDRICAL, (int)MS_PROJ_PLANE>(c->cfg.projection, f); }
+
+// one ms_stitch* call: what check_call establishes before anything is enqueued, and what the enqueue stages share
+struct StitchCall {
+    int F_call;                       // frames of the call (the launches that read the callers' frames take them in chunks: for_each_chunk)
+    hipStream_t st;
+    ShardArgs S;
+    bool nv12, nv_al, cpw, src_shared, src_steps_equal, int_only;
+    SrcAll src; OutTable out; PanoDesc P; const ViewDesc *vt; MeshTable mesh; DispTable disp;
+    int cap, rec; const char **names; std::vector<hipEvent_t> ev;      // ms_stitch_timed: an event after every launch group (mark), the region names beside them
+};
+
+// the form of a source-reading launch: MS_WARP_KERNEL_*, frames per lane, aligned taps, dynamic LDS bytes
+struct KernelForm { int kernel, nf; bool al; size_t lds; };
+
+// one chunk of a call's frames, as the source-reading launches take it: its own source table, the per-frame buffers offset by its first frame
+struct Chunk { int f0, nf; SrcTable src; uint8_t *stage, *g0; };
+
+static int check_call(ms_ctx *c, StitchCall &k, const ms_image *views, const ms_image *out8u, const ms_image *out16s, const ms_image *out_i420)
+{
     if (!c->blender_ready) return fail(MS_ERR_STATE, "ms_stitch: call ms_build_maps / masks / ms_init_blender first");
-    MS_CHECK(n_frames >= 1 && n_frames <= c->cfg.max_frames, "ms_stitch: n_frames %d not in [1,%d]", n_frames, c->cfg.max_frames);
-    const int N = c->N, nb = c->pano.nb, F = n_frames;
+    MS_CHECK(k.F_call >= 1 && k.F_call <= c->cfg.max_frames, "ms_stitch: n_frames %d not in [1,%d]", k.F_call, c->cfg.max_frames);
+    const int N = c->N, F = k.F_call;
+    ShardArgs &S = k.S;
+    const PanoDesc &P = c->pano;
     const bool sharded = c->own_mask != ((N >= 32) ? 0xffffffffu : ((1u << N) - 1u));
     if (S.mode == 0 && sharded) return fail(MS_ERR_STATE, "ms_stitch: this context owns a view shard; use ms_stitch_partial / ms_stitch_finish");
     S.own_mask = c->own_mask;
     S.pstride = c->pacc_stride;
     MS_CHECK(S.mode == 2 || views != nullptr, "ms_stitch: null views");
-    PanoDesc P = c->pano;              // (the pointers of the active copy of the tables are filled in under the lock below)
-    // Frames per call: up to MAX_FRAMES (64 since round 6).  The kernels that read the callers' frames take their pointers in a by-value table of MAX_SRC entries (a kernel's
-    // arguments are limited to 4 KiB): those launches -- the projection warp, the first CPW remap, the mesh remap -- go out in chunks of f_chunk = MAX_SRC / views frames (32 for six
-    // views, 16 for twelve), each chunk with its own table and the per-frame buffers offset by its first frame; they are the frame's large, bandwidth-bound launches and lose
-    // nothing by it.  Every other kernel of the call (the reduce chain, the tails, the band chain: latency-bound launches whose fixed cost a longer batch amortises) covers all frames.
-    const int F_all = F, f_chunk = std::min(F, std::max(1, MAX_SRC / N));
-    SrcAll src{};
-    auto src_chunk = [&](int f0, int nf) { SrcTable t{}; for (int i = 0; i < nf * N; ++i) { t.p[i] = src.p[f0 * N + i]; t.step[i] = src.step[f0 * N + i]; } return t; };
     for (int i = 0; i < F * N && S.mode != 2; ++i) {
         if (!((c->own_mask >> (i % N)) & 1u)) continue;       // another shard's view: not read
         if (!((c->needed_mask >> (i % N)) & 1u)) continue;    // column sharding: no pixel of this view reaches the window
-        if (nv12)
+        if (k.nv12)
             MS_CHECK(views[i].data && views[i].type == MS_8UC1 && views[i].rows == c->cfg.src_height * 3 / 2 && views[i].cols == c->cfg.src_width && views[i].step == views[i % N].step,
                      "ms_stitch_nv12: view %d must be the NV12 planes of a %dx%d frame (8UC1, %d rows), every frame of a view with the same step", i, c->cfg.src_width, c->cfg.src_height, c->cfg.src_height * 3 / 2);
         else
         MS_CHECK(views[i].data && views[i].type == MS_8UC3 && views[i].rows == c->cfg.src_height && views[i].cols == c->cfg.src_width,
                  "ms_stitch: view %d must be 8UC3 %dx%d", i, c->cfg.src_width, c->cfg.src_height);
-        src.p[i] = (const uint8_t *)views[i].data;
-        src.step[i] = (unsigned)views[i].step;
+        k.src.p[i] = (const uint8_t *)views[i].data;
+        k.src.step[i] = (unsigned)views[i].step;
     }
     if (sharded && S.mode == 1)      // the full-grid fallback kernels touch every view slot: give the unowned ones a valid (ignored) source
         for (int f = 0; f < F; ++f) {
             int owned = 0;
             while (!((c->own_mask >> owned) & 1u)) ++owned;
             for (int v = 0; v < N; ++v)
-                if (!((c->own_mask >> v) & 1u)) { src.p[f * N + v] = src.p[f * N + owned]; src.step[f * N + v] = src.step[f * N + owned]; }
+                if (!((c->own_mask >> v) & 1u)) { k.src.p[f * N + v] = k.src.p[f * N + owned]; k.src.step[f * N + v] = k.src.step[f * N + owned]; }
         }
-    OutTable out{};
     for (int f = 0; f < F; ++f) {
         if (out8u && out8u[f].data) {
             MS_CHECK(out8u[f].type == MS_8UC3 && out8u[f].rows == P.out_h && out8u[f].cols == P.out_w,
                      "ms_stitch: out8u[%d] must be 8UC3 %dx%d", f, P.out_w, P.out_h);
-            out.p8[f] = (uint8_t *)out8u[f].data; out.step8[f] = (unsigned)out8u[f].step;
+            k.out.p8[f] = (uint8_t *)out8u[f].data; k.out.step8[f] = (unsigned)out8u[f].step;
         }
         if (out16s && out16s[f].data) {
             MS_CHECK(out16s[f].type == MS_16SC3 && out16s[f].rows == P.fh && out16s[f].cols == P.fw,
                      "ms_stitch: out16s[%d] must be 16SC3 %dx%d", f, P.fw, P.fh);
-            out.p16[f] = (int16_t *)out16s[f].data; out.step16[f] = (unsigned)out16s[f].step;
+            k.out.p16[f] = (int16_t *)out16s[f].data; k.out.step16[f] = (unsigned)out16s[f].step;
         }
         if (out_i420 && out_i420[f].data) {
             MS_CHECK(out_i420[f].type == MS_8UC1 && out_i420[f].cols == P.out_w && out_i420[f].rows == P.i_rows * 3 / 2 && out_i420[f].step == (size_t)P.out_w,
                      "ms_stitch_i420: out[%d] must be a contiguous 8UC1 image of %d x %d (I420 of canvas rows %d..%d)", f, P.out_w, P.i_rows * 3 / 2, P.i_y0, P.i_y0 + P.i_rows - 1);
-            out.pi[f] = (uint8_t *)out_i420[f].data;
+            k.out.pi[f] = (uint8_t *)out_i420[f].data;
         }
     }
     if (out_i420) {
         if (!(P.nb >= 1 && c->blend_vec[0] && c->cfg.debug_simple_kernels == 0 && S.mode == 0 && (P.out_w & 1) == 0 && P.i_rows > 0))
             return fail(MS_ERR_UNSUPPORTED, "ms_stitch_i420: needs the tiled level-0 band kernel (>= 1 band, pano width a multiple of 8, no view sharding) and an even canvas width");
     }
-    if (nv12 && !(c->warp_tiled && c->cfg.debug_simple_kernels == 0 && c->cfg.cpu_flavour_remap == 0 && S.mode == 0 &&
-                  (c->cfg.src_width & 1) == 0 && (c->cfg.src_height & 1) == 0 && c->cfg.src_width >= 4))
+    if (k.nv12 && !(c->warp_tiled && c->cfg.debug_simple_kernels == 0 && c->cfg.cpu_flavour_remap == 0 && S.mode == 0 &&
+                    (c->cfg.src_width & 1) == 0 && (c->cfg.src_height & 1) == 0 && c->cfg.src_width >= 4))
         return fail(MS_ERR_UNSUPPORTED, "ms_stitch_nv12: the NV12-sampling kernels cover the tiled projection warp / CPW stage 1 of even-sized frames, unsharded; convert with ms_nv12_to_bgr_batch otherwise");
+    if (P.nb == 0 && S.mode != 0) return fail(MS_ERR_UNSUPPORTED, "view sharding needs num_bands >= 1");
+    k.cpw = c->cfg.enable_cpw != 0;
+    if (k.cpw) MS_CHECK((c->stage_stride & 3) == 0, "internal: stage image stride %lld not a multiple of 4", c->stage_stride);
+
     // aligned 8-byte windows where every plane, step and the width are multiples of 4 (cameras' frames in ordinary buffers are); the unaligned 2- / 4-byte reads otherwise
-    bool nv_al = nv12 && (c->cfg.src_width & 3) == 0 && c->cfg.src_width >= 8 && dev_knob("MS_NV12_ALIGNED", 1) != 0;
-    for (int i = 0; i < F * N && nv_al; ++i) if (src.p[i]) nv_al = (((uintptr_t)src.p[i] | src.step[i]) & 3) == 0;
-    MeshTable mesh{};
-    const bool cpw = c->cfg.enable_cpw != 0;
-    DispTable disp{};
-    { const float lim = (float)CPW_DMAX; memcpy(&disp.limit_bits, &lim, 4); }
-    // CPW: mesh_mu is held from here to the hipEventRecord(last_stitch) at the end of the enqueue (RAII): a mesh update that starts meanwhile
-    // sees this stitch in last_stitch before it may touch the buffer this stitch reads.  Only enqueues happen under the lock.
-    std::unique_lock<std::mutex> mesh_lk(c->mesh_mu, std::defer_lock);
-    if (cpw) {
-        mesh_lk.lock();
+    k.nv_al = k.nv12 && (c->cfg.src_width & 3) == 0 && c->cfg.src_width >= 8 && dev_knob("MS_NV12_ALIGNED", 1) != 0;
+    for (int i = 0; i < F * N && k.nv_al; ++i) if (k.src.p[i]) k.nv_al = (((uintptr_t)k.src.p[i] | k.src.step[i]) & 3) == 0;
+    // k_warp_s / the shared form of k_stage1_t: every frame of a view with the same row step and the same address modulo 4 (then a pixel's aligned tap offset is one
+    // 32-bit value for all frames of a lane).  True for any sane caller (frames of one camera in buffers of one shape); checked, not assumed.
+    static const bool warp_shared_knob = dev_knob("MS_WARP_SHARED", 1) != 0;
+    k.src_shared = warp_shared_knob && S.mode != 2;
+    for (int i = N; i < F * N && k.src_shared; ++i)
+        if (k.src.p[i]) k.src_shared = k.src.p[i % N] && k.src.step[i] == k.src.step[i % N] && (((uintptr_t)k.src.p[i] ^ (uintptr_t)k.src.p[i % N]) & 3) == 0;
+    k.src_steps_equal = warp_shared_knob && S.mode != 2;
+    for (int i = N; i < F * N && k.src_steps_equal; ++i)
+        if (k.src.p[i]) k.src_steps_equal = k.src.p[i % N] && k.src.step[i] == k.src.step[i % N];
+    return MS_OK;
+}
+
+// CPW meshes and the active copy of the mask-dependent tables; the caller holds mesh_mu with CPW (see stitch_impl)
+static int hand_over_tables(ms_ctx *c, StitchCall &k)
+{
+    const int N = c->N, nb = c->pano.nb;
+    k.P = c->pano;
+    k.vt = (const ViewDesc *)c->view_tab.p;
+    { const float lim = (float)CPW_DMAX; memcpy(&k.disp.limit_bits, &lim, 4); }
+    if (k.cpw) {
+        for (int v = 0; v < N; ++v)
+            if (!c->mesh_set[v]) return fail(MS_ERR_STATE, "ms_stitch: enable_cpw is set but view %d has no mesh", v);
         hipEvent_t mesh_waited = nullptr;
         for (int v = 0; v < N; ++v) {
-            if (!c->mesh_set[v]) return fail(MS_ERR_STATE, "ms_stitch: enable_cpw is set but view %d has no mesh", v);
-            disp.p[v] = (const unsigned *)c->disp_dev.p + 2 * v + c->mesh_active[v];
+            k.disp.p[v] = (const unsigned *)c->disp_dev.p + 2 * v + c->mesh_active[v];
             if (c->mesh_wait[v]) {
                 hipEvent_t e = mesh_ready_event(c, v);
-                if (e != mesh_waited) { MS_HIP(hipStreamWaitEvent(st, e, 0)); mesh_waited = e; }      // (the views of one ms_set_meshes call share their event: one wait)
+                if (e != mesh_waited) { MS_HIP(hipStreamWaitEvent(k.st, e, 0)); mesh_waited = e; }      // (the views of one ms_set_meshes call share their event: one wait)
                 c->mesh_wait[v] = false;
             }
             ms_image mx = mesh_image(c, c->mesh_active[v], v, 0), my = mesh_image(c, c->mesh_active[v], v, 1);
-            mesh.x[v] = (const float *)mx.data; mesh.y[v] = (const float *)my.data; mesh.pitch[v] = c->map_pitch[v];
+            k.mesh.x[v] = (const float *)mx.data; k.mesh.y[v] = (const float *)my.data; k.mesh.pitch[v] = c->map_pitch[v];
         }
     }
     // which copy of the mask-dependent tables (enqueue-only ms_update_mask; same lock, same hand-over as the meshes)
-    const ViewDesc *vt = (const ViewDesc *)c->view_tab.p;
-    if (cpw && c->cfg.update_mask_margin > 0) {
-        if (c->tab_wait) MS_HIP(hipStreamWaitEvent(st, c->tab_ready, 0));
+    if (k.cpw && c->cfg.update_mask_margin > 0) {
+        if (c->tab_wait) MS_HIP(hipStreamWaitEvent(k.st, c->tab_ready, 0));
         if (c->tab_active == 1) {
-            vt = (const ViewDesc *)c->alt.view_tab.p;
-            for (int l = 0; l <= nb; ++l) P.den[l] = c->alt.pano.den[l];
-            for (int l = 0; l < nb; ++l) P.pure[l] = c->alt.pano.pure[l];
-            P.mask = c->alt.pano.mask;
+            k.vt = (const ViewDesc *)c->alt.view_tab.p;
+            for (int l = 0; l <= nb; ++l) k.P.den[l] = c->alt.pano.den[l];
+            for (int l = 0; l < nb; ++l) k.P.pure[l] = c->alt.pano.pure[l];
+            k.P.mask = c->alt.pano.mask;
         }
     }
+    k.int_only = c->l0_integer_only.load() && k.P.pure[0] != nullptr;      // (an enqueue-only mask update clears it before it publishes its tables under mesh_mu: a stale `true` can only meet the old tables)
+    return MS_OK;
+}
 
+static int mark(StitchCall &k, const char *name)
+{
+    if (!k.names) return MS_OK;
+    hipEvent_t e;
+    MS_HIP(hipEventCreate(&e));
+    MS_HIP(hipEventRecord(e, k.st));
+    k.ev.push_back(e);
+    if (name && k.rec < k.cap) k.names[k.rec++] = name;
+    return MS_OK;
+}
+
+// ms_stitch_timed: wait for the call, the time between consecutive marks per region
+static int read_marks(StitchCall &k, float *ms_out, int *n_rec)
+{
+    MS_HIP(hipEventSynchronize(k.ev.back()));
+    for (size_t i = 1; i < k.ev.size() && (int)i - 1 < k.cap; ++i) {
+        float t = 0.f;
+        MS_HIP(hipEventElapsedTime(&t, k.ev[i - 1], k.ev[i]));
+        ms_out[i - 1] = t;
+    }
+    for (auto e : k.ev) (void)hipEventDestroy(e);
+    if (n_rec) *n_rec = k.rec;
+    return MS_OK;
+}
+
+// Frames per call: up to MAX_FRAMES (64 since round 6).  The kernels that read the callers' frames take their pointers in a by-value table of MAX_SRC entries (a kernel's
+// arguments are limited to 4 KiB): those launches -- the projection warp, the first CPW remap, the mesh remap -- go out in chunks of MAX_SRC / views frames (32 for six
+// views, 16 for twelve), each chunk with its own table and the per-frame buffers offset by its first frame; they are the frame's large, bandwidth-bound launches and lose
+// nothing by it.  Every other kernel of the call (the reduce chain, the tails, the band chain: latency-bound launches whose fixed cost a longer batch amortises) covers all frames.
+template <class Fn>
+static void for_each_chunk(const ms_ctx *c, const StitchCall &k, Fn &&launch)
+{
+    const int N = c->N, f_chunk = MAX_SRC / N;
+    for (int f0 = 0; f0 < k.F_call; f0 += f_chunk) {
+        Chunk ch{f0, std::min(f_chunk, k.F_call - f0), {}, (uint8_t *)c->stage.p + (size_t)f0 * c->stage_stride, (uint8_t *)c->g0.p + (size_t)f0 * c->g0_stride};
+        for (int i = 0; i < ch.nf * N; ++i) { ch.src.p[i] = k.src.p[f0 * N + i]; ch.src.step[i] = k.src.step[f0 * N + i]; }
+        launch(ch);
+    }
+}
+
+// the first CPW remap (the callers' frames -> the context's stage images) of a chunk of nf frames
+static KernelForm stage1_form(const ms_ctx *c, const StitchCall &k, int nf)
+{
+    if (k.nv12) return {MS_WARP_KERNEL_NV12, nf == 1 ? 1 : 2, k.nv_al, 0};      // CPW stage 1 straight from the cameras' NV12 planes (k_stage1_nv12)
+    if (c->cfg.debug_simple_kernels != 0) return {MS_WARP_KERNEL_SIMPLE, 1, false, 0};
+    // frames per lane of the first CPW remap: three where the source is sampled about 1 : 1 (VALU-bound), two otherwise (see k_stage1_t)
+    static const int s1_env = dev_knob("MS_S1_NF", 0);
+    // (round 5: the shared-offset form takes three wherever it runs -- config 3's first remap 406 -> 387-392 us per 32 frames, 385 -> 364 per 30; the per-frame form keeps the minification rule)
+    const int s1_nf = s1_env == 2 || s1_env == 3 ? s1_env : ((c->warp_aligned && k.src_shared) || (c->warp_minification > 0 && c->warp_minification < 1.5)) ? 3 : 2;
+    static const int s1_lds = dev_knob("MS_S1_LDS", 0);      // occupancy A/B knob (dynamic LDS nobody touches)
+    if (c->warp_aligned && k.src_shared) return {MS_WARP_KERNEL_SHARED_ALIGNED, s1_nf, true, (size_t)s1_lds};
+    return {c->warp_aligned ? MS_WARP_KERNEL_PER_FRAME_ALIGNED : MS_WARP_KERNEL_PER_FRAME_UNALIGNED, s1_nf, c->warp_aligned, (size_t)s1_lds};
+}
+
+static void launch_stage1(const ms_ctx *c, const StitchCall &k, const Chunk &ch, const KernelForm &f)
+{
+    const WarpTile *tiles = (const WarpTile *)c->stage1_tiles.p;
+    const int N = c->N, H = c->cfg.src_height, W = c->cfg.src_width;
+    const dim3 g(c->n_stage1_tiles, 1, div_up(ch.nf, f.nf)), b(WARP_BX, S1_BY);
+    switch (f.kernel) {
+    case MS_WARP_KERNEL_NV12:
+        with_proj(c, [&](auto P) { with_value<1, 2>(f.nf, [&](auto NF) { with_value<true, false>(f.al, [&](auto AL) {
+            k_stage1_nv12<P, NF, AL><<<g, dim3(WARP_BX, S1_BY_NV), 0, k.st>>>(tiles, k.vt, N, ch.src, H, W, ch.stage, c->stage_stride, k.disp, ch.nf);
+        }); }); });
+        break;
+    case MS_WARP_KERNEL_SHARED_ALIGNED:
+        with_proj(c, [&](auto P) { with_value<3, 2>(f.nf, [&](auto NF) {
+            k_stage1_s<P, NF><<<g, b, f.lds, k.st>>>(tiles, k.vt, N, ch.src, H, W, ch.stage, c->stage_stride, k.disp, ch.nf);
+        }); });
+        break;
+    case MS_WARP_KERNEL_PER_FRAME_ALIGNED:
+    case MS_WARP_KERNEL_PER_FRAME_UNALIGNED:
+        with_proj(c, [&](auto P) { with_value<true, false>(f.al, [&](auto AL) { with_value<3, 2>(f.nf, [&](auto NF) {
+            k_stage1_t<P, AL, NF><<<g, b, f.lds, k.st>>>(tiles, k.vt, N, ch.src, H, W, ch.stage, c->stage_stride, k.disp, ch.nf);
+        }); }); });
+        break;
+    default:      // MS_WARP_KERNEL_SIMPLE
+        k_remap_gain<<<dim3(div_up(c->max_aw, 64), div_up(c->max_ah, 4), ch.nf * N), dim3(64, 4), 0, k.st>>>(k.vt, N, ch.src, H, W, ch.stage, c->stage_stride);
+    }
+}
+
+// the projection warp (no CPW) or the mesh remap (CPW: stage images -> level 0) of a chunk
+static KernelForm warp_form(const ms_ctx *c, const StitchCall &k, const Chunk &ch)
+{
+    if (!c->warp_tiled || c->cfg.debug_simple_kernels != 0) return {MS_WARP_KERNEL_SIMPLE, 1, false, 0};
     // Occupancy of the warp kernels, set through dynamic LDS nobody touches (bytes per 128-lane workgroup; 160 KiB per CU).  The aligned-read projection warp needs 85 VGPRs
     // (5 waves per SIMD) since its tap addresses became SGPR base + 32-bit offset, and runs 3.7 % FASTER at 4 waves (20 000 bytes -> 8 workgroups per CU): fewer waves
     // thrash the vector cache less (same-box sweep, us per 16 frames: 5 waves 215, 4 waves 207, 3 waves 214; profiles/r03_resize_ab.txt).  The unaligned variant
     // (config 5, 61 VGPRs) and the mesh remap (98 VGPRs = 4 waves anyway) are best left alone.  MS_WARP_LDS=<bytes> overrides all three (A/B).
     static const int warp_lds_env = dev_knob("MS_WARP_LDS", -1);
-    const size_t warp_lds = warp_lds_env >= 0 ? (size_t)warp_lds_env : 0, warp_lds_al = warp_lds_env >= 0 ? (size_t)warp_lds_env : (F <= 2 ? 0 : 20000);      // (one or two frames per call: the chip is not full, every wave that fits helps -- 92.5 -> 91.2 us per frame)
-    // k_warp_s / the shared form of k_stage1_t: every frame of a view with the same row step and the same address modulo 4 (then a pixel's aligned tap offset is one
-    // 32-bit value for all frames of a lane).  True for any sane caller (frames of one camera in buffers of one shape); checked, not assumed.
-    static const bool warp_shared_knob = dev_knob("MS_WARP_SHARED", 1) != 0;
-    c->last_warp_kernel = MS_WARP_KERNEL_SIMPLE; c->last_stage1_kernel = MS_WARP_KERNEL_NONE;      // (overwritten below by whichever tile kernel is launched)
-    bool src_shared = warp_shared_knob && S.mode != 2;
-    for (int i = N; i < F * N && src_shared; ++i)
-        if (src.p[i]) src_shared = src.p[i % N] && src.step[i] == src.step[i % N] && (((uintptr_t)src.p[i] ^ (uintptr_t)src.p[i % N]) & 3) == 0;
-    bool src_steps_equal = warp_shared_knob && S.mode != 2;
-    for (int i = N; i < F * N && src_steps_equal; ++i)
-        if (src.p[i]) src_steps_equal = src.p[i % N] && src.step[i] == src.step[i % N];
-    const bool int_only = c->l0_integer_only.load() && P.pure[0] != nullptr;      // (an enqueue-only mask update clears it before it publishes its tables under mesh_mu: a stale `true` can only meet the old tables)
+    const size_t warp_lds = warp_lds_env >= 0 ? (size_t)warp_lds_env : 0, warp_lds_al = warp_lds_env >= 0 ? (size_t)warp_lds_env : (k.F_call <= 2 ? 0 : 20000);      // (one or two frames per call: the chip is not full, every wave that fits helps -- 92.5 -> 91.2 us per frame)
+    // the stage images of a view have the same pitch and the same address modulo 4 in every frame BY CONSTRUCTION (stage_stride is a multiple of 256): the mesh remap
+    // always takes the shared-offset form (its unshared twin was unreachable in the shipped library and untested, VERDICT r04, and is gone)
+    if (k.cpw) return {MS_WARP_KERNEL_SHARED_ALIGNED, ch.nf == 1 ? 1 : warp_nf(true), true, warp_lds};
+    if (k.nv12) return {MS_WARP_KERNEL_NV12, ch.nf == 1 ? 1 : 2, k.nv_al, 0};      // the cameras' NV12 planes sampled directly (k_warp_nv12): no BGR image in between
+    // opt-in (ms_config.warp_lds_stage = 1; MS_WARP_ASYNC=1 in a dev-knob build): source tiles staged in LDS by asynchronous LDS-DMA, persistent waves (k_warp_a) -- bit-identical,
+    // measured slower than the direct gathers on config 2 (353 vs 242 us per 16 frames: at its 1.6-2.1 x minification only 54 % of the tiles' source
+    // boxes fit a staging buffer and 10 waves per CU cannot hide what 20 do; profiles/r02_warp_probes.txt)
+    static const bool env_on = dev_knob("MS_WARP_ASYNC", 0) != 0;
+    bool staged = c->warp_lds_tiles > 0 && (c->cfg.warp_lds_stage == 1 || (env_on && c->cfg.warp_lds_stage != 2));
+    for (int i = 0; i < ch.nf * c->N; ++i) staged = staged && ((uintptr_t)ch.src.p[i] & 15) == 0;   // chunk copies start on 16-byte lines of the buffer
+    if (staged) return {MS_WARP_KERNEL_LDS_STAGED, 1, false, 2 * WA_BUF_BYTES};
+    // (with shared offsets the aligned form wins at every minification measured: config 5 -- 2.7 x, k_warp_t's unaligned territory -- 757 -> 730 / 738 -> 699 us per 16 frames;
+    //  the minification rule of build_plan still picks between k_warp_t's two forms when the frames do not share step and alignment)
+    static const int force_al = dev_knob("MS_WARP_ALIGNED", -1);
+    if ((c->warp_aligned || force_al != 0) && k.src_shared) return {MS_WARP_KERNEL_SHARED_ALIGNED, ch.nf == 1 ? 1 : WARP_NF_S, true, warp_lds_al};
+    if (c->warp_aligned) return {MS_WARP_KERNEL_PER_FRAME_ALIGNED, WARP_NF, true, warp_lds_al};
+    // the unaligned-read form with shared offsets (config 5): only the row step has to agree
+    if (k.src_steps_equal && ch.nf > 1 && dev_knob("MS_WARP_SHARED_U", 1)) return {MS_WARP_KERNEL_SHARED_UNALIGNED, WARP_NF, false, warp_lds};
+    return {MS_WARP_KERNEL_PER_FRAME_UNALIGNED, WARP_NF, false, warp_lds};
+}
 
-    // one context has ONE set of per-batch intermediates: calls on a different stream than the previous one are ordered behind it on the GPU
-    // (the reference makes a fresh cuda::Stream per stitch_online call, timed.cpp:64, and relies on the NULL stream for ordering)
-    if (c->last_stream_set && c->last_stream != st && c->stitch_pending) MS_HIP(hipStreamWaitEvent(st, c->last_stitch, 0));
-    c->last_stream = st; c->last_stream_set = true;
+static void launch_warp(const ms_ctx *c, const StitchCall &k, const Chunk &ch, const KernelForm &f)
+{
+    const WarpTile *tiles = (const WarpTile *)c->warp_tiles.p;
+    const float2 *tabs = (const float2 *)c->tabs.p;
+    const int N = c->N, H = c->cfg.src_height, W = c->cfg.src_width;
+    const dim3 g(c->n_warp_tiles, WARP_BY / WARP_WY, div_up(ch.nf, f.nf)), b(WARP_BX, WARP_WY);
+    switch (f.kernel) {
+    case MS_WARP_KERNEL_SHARED_ALIGNED:
+        if (k.cpw)
+            with_proj(c, [&](auto P) { with_value<warp_nf(true), 1>(f.nf, [&](auto NF) {
+                k_warp_s<true, P, NF><<<g, b, f.lds, k.st>>>(tiles, k.vt, N, ch.src, H, W, k.mesh, ch.stage, c->stage_stride, ch.g0, c->g0_stride, tabs, ch.nf);
+            }); });
+        else
+            with_proj(c, [&](auto P) { with_value<WARP_NF_S, 1>(f.nf, [&](auto NF) {
+                k_warp_s<false, P, NF><<<g, b, f.lds, k.st>>>(tiles, k.vt, N, ch.src, H, W, k.mesh, nullptr, 0, ch.g0, c->g0_stride, tabs, ch.nf);
+            }); });
+        break;
+    case MS_WARP_KERNEL_SHARED_UNALIGNED:
+        with_proj(c, [&](auto P) {
+            k_warp_s<false, P, WARP_NF, false><<<g, b, f.lds, k.st>>>(tiles, k.vt, N, ch.src, H, W, k.mesh, nullptr, 0, ch.g0, c->g0_stride, tabs, ch.nf);
+        });
+        break;
+    case MS_WARP_KERNEL_PER_FRAME_ALIGNED:
+    case MS_WARP_KERNEL_PER_FRAME_UNALIGNED:
+        with_proj(c, [&](auto P) { with_value<true, false>(f.al, [&](auto AL) {
+            k_warp_t<false, AL, P><<<g, b, f.lds, k.st>>>(tiles, k.vt, N, ch.src, H, W, k.mesh, nullptr, 0, ch.g0, c->g0_stride, tabs, ch.nf);
+        }); });
+        break;
+    case MS_WARP_KERNEL_NV12:
+        with_proj(c, [&](auto P) { with_value<1, 2>(f.nf, [&](auto NF) { with_value<true, false>(f.al, [&](auto AL) {
+            k_warp_nv12<P, NF, AL><<<g, b, 0, k.st>>>(tiles, k.vt, N, ch.src, H, W, ch.g0, c->g0_stride, tabs, ch.nf);
+        }); }); });
+        break;
+    case MS_WARP_KERNEL_LDS_STAGED: {
+        const long long items = (long long)c->n_warp_tiles * ch.nf;
+        const int grid = (int)std::min<long long>(items, (long long)c->n_cus * (160 * 1024 / (2 * WA_BUF_BYTES)));
+        with_proj(c, [&](auto P) {
+            k_warp_a<P><<<dim3(grid), dim3(64), f.lds, k.st>>>(tiles, c->n_warp_tiles, k.vt, N, ch.src, H, W, ch.g0, c->g0_stride, tabs, ch.nf);
+        });
+        break;
+    }
+    default: {      // MS_WARP_KERNEL_SIMPLE
+        const dim3 gs(div_up(c->max_pw, 64), div_up(c->max_ph, 4), ch.nf * N), bs(64, 4);
+        if (k.cpw) k_warp<true><<<gs, bs, 0, k.st>>>(k.vt, N, ch.src, H, W, k.mesh, ch.stage, c->stage_stride, ch.g0, c->g0_stride);
+        else if (c->cfg.cpu_flavour_remap != 0) k_warp<false, true><<<gs, bs, 0, k.st>>>(k.vt, N, ch.src, H, W, k.mesh, nullptr, 0, ch.g0, c->g0_stride);
+        else k_warp<false><<<gs, bs, 0, k.st>>>(k.vt, N, ch.src, H, W, k.mesh, nullptr, 0, ch.g0, c->g0_stride);
+    }
+    }
+}
 
+// the launches that read the callers' frames, chunk by chunk; ms_get_stitch_kernels reports the form of the first (full) chunk
+static int enqueue_warps(ms_ctx *c, StitchCall &k)
+{
+    if (k.cpw) {
+        for_each_chunk(c, k, [&](const Chunk &ch) {
+            const KernelForm f = stage1_form(c, k, ch.nf);
+            if (ch.f0 == 0) c->last_stage1_kernel = f.kernel;
+            launch_stage1(c, k, ch, f);
+        });
+        MS_LAUNCH_CHECK();
+        if (int e = mark(k, "k_remap_gain")) return e;
+    }
+    for_each_chunk(c, k, [&](const Chunk &ch) {
+        const KernelForm f = warp_form(c, k, ch);
+        if (ch.f0 == 0) c->last_warp_kernel = f.kernel;
+        launch_warp(c, k, ch, f);
+    });
+    MS_LAUNCH_CHECK();
+    return mark(k, "k_warp");
+}
+
+// level 0 -> the Gaussian pyramid of every view, all frames per launch
+static int enqueue_reduce(ms_ctx *c, StitchCall &k)
+{
+    static const char *down_names[MAX_LEVELS] = {"k_down_l0", "k_down_l1", "k_down_l2", "k_down_l3", "k_down_l4", "k_down_l5", "k_down_l6", "k_down_l7"};
+    const int N = c->N, nb = c->pano.nb, F = k.F_call;
+    const ViewDesc *vt = k.vt;
     const uint8_t *g0 = (const uint8_t *)c->g0.p;
     uint8_t *gl = (uint8_t *)c->gl.p;
-    int16_t *cl = (int16_t *)c->cl.p;
     const dim3 blk(64, 4);
-
-    std::vector<hipEvent_t> ev;
-    int rec = 0;
-    auto mark = [&](const char *name) -> int {
-        if (!names) return MS_OK;
-        hipEvent_t e;
-        MS_HIP(hipEventCreate(&e));
-        MS_HIP(hipEventRecord(e, st));
-        ev.push_back(e);
-        if (name && rec < cap) names[rec++] = name;
-        return MS_OK;
-    };
-    if (int e = mark(nullptr)) return e;
-
-    static const char *down_names[MAX_LEVELS] = {"k_down_l0", "k_down_l1", "k_down_l2", "k_down_l3", "k_down_l4", "k_down_l5", "k_down_l6", "k_down_l7"};
-    static const char *blend_names[MAX_LEVELS] = {"k_blend_l0", "k_blend_l1", "k_blend_l2", "k_blend_l3", "k_blend_l4", "k_blend_l5", "k_blend_l6", "k_blend_l7"};
-    if (S.mode != 2) {       // (finish mode starts from the partial sums: no warp, no pyramids)
-    if (cpw) {
-        for (int fc0 = 0; fc0 < F_all; fc0 += f_chunk) {      // (source-table chunks: see f_chunk above)
-            const int F = std::min(f_chunk, F_all - fc0);
-            const SrcTable src = src_chunk(fc0, F);
-            uint8_t *const stage_w = (uint8_t *)c->stage.p + (size_t)fc0 * c->stage_stride, *const g0_w = (uint8_t *)c->g0.p + (size_t)fc0 * c->g0_stride;
-            (void)stage_w; (void)g0_w;
-        if (nv12) {        // CPW stage 1 straight from the cameras' NV12 planes (k_stage1_nv12)
-            const dim3 b_(WARP_BX, S1_BY_NV);
-#define MS_S1NV_LAUNCH(NF_, ALN_)                                                                                                                                     \
-    do {                                                                                                                                                              \
-        const dim3 g_(c->n_stage1_tiles, 1, div_up(F, NF_));                                                                                                          \
-        if (c->cfg.projection == MS_PROJ_SPHERICAL) k_stage1_nv12<MS_PROJ_SPHERICAL, NF_, ALN_><<<g_, b_, 0, st>>>((const WarpTile *)c->stage1_tiles.p, vt, N, src, c->cfg.src_height, c->cfg.src_width, stage_w, c->stage_stride, disp, F); \
-        else if (c->cfg.projection == MS_PROJ_CYLINDRICAL) k_stage1_nv12<MS_PROJ_CYLINDRICAL, NF_, ALN_><<<g_, b_, 0, st>>>((const WarpTile *)c->stage1_tiles.p, vt, N, src, c->cfg.src_height, c->cfg.src_width, stage_w, c->stage_stride, disp, F); \
-        else k_stage1_nv12<MS_PROJ_PLANE, NF_, ALN_><<<g_, b_, 0, st>>>((const WarpTile *)c->stage1_tiles.p, vt, N, src, c->cfg.src_height, c->cfg.src_width, stage_w, c->stage_stride, disp, F); \
-    } while (0)
-            c->last_stage1_kernel = MS_WARP_KERNEL_NV12;
-            if (nv_al) { if (F == 1) MS_S1NV_LAUNCH(1, true); else MS_S1NV_LAUNCH(2, true); }
-            else { if (F == 1) MS_S1NV_LAUNCH(1, false); else MS_S1NV_LAUNCH(2, false); }
-#undef MS_S1NV_LAUNCH
-        } else
-        if (c->cfg.debug_simple_kernels == 0)
-        {
-            // frames per lane of the first CPW remap: three where the source is sampled about 1 : 1 (VALU-bound), two otherwise (see k_stage1_t)
-            static const int s1_env = dev_knob("MS_S1_NF", 0);
-            // (round 5: the shared-offset form takes three wherever it runs -- config 3's first remap 406 -> 387-392 us per 32 frames, 385 -> 364 per 30; the per-frame form keeps the minification rule)
-            const int s1_nf = s1_env == 2 || s1_env == 3 ? s1_env : ((c->warp_aligned && src_shared) || (c->warp_minification > 0 && c->warp_minification < 1.5)) ? 3 : 2;
-            static const int s1_lds = dev_knob("MS_S1_LDS", 0);      // occupancy A/B knob (dynamic LDS nobody touches)
-#define MS_S1_LAUNCH(AL, NF) MS_PROJ_AL_LAUNCH(k_stage1_t, AL, NF, (dim3(c->n_stage1_tiles, 1, div_up(F, NF)), dim3(WARP_BX, S1_BY), s1_lds, st), \
-                    (const WarpTile *)c->stage1_tiles.p, vt, N, src, c->cfg.src_height, c->cfg.src_width, stage_w, c->stage_stride, disp, F)
-#define MS_S1S_LAUNCH(NF)                                                                                                                                     \
-    do {                                                                                                                                                      \
-        const dim3 g_(c->n_stage1_tiles, 1, div_up(F, NF)), b_(WARP_BX, S1_BY);                                                                               \
-        if (c->cfg.projection == MS_PROJ_SPHERICAL) k_stage1_s<MS_PROJ_SPHERICAL, NF><<<g_, b_, s1_lds, st>>>((const WarpTile *)c->stage1_tiles.p, vt, N, src, c->cfg.src_height, c->cfg.src_width, stage_w, c->stage_stride, disp, F); \
-        else if (c->cfg.projection == MS_PROJ_CYLINDRICAL) k_stage1_s<MS_PROJ_CYLINDRICAL, NF><<<g_, b_, s1_lds, st>>>((const WarpTile *)c->stage1_tiles.p, vt, N, src, c->cfg.src_height, c->cfg.src_width, stage_w, c->stage_stride, disp, F); \
-        else k_stage1_s<MS_PROJ_PLANE, NF><<<g_, b_, s1_lds, st>>>((const WarpTile *)c->stage1_tiles.p, vt, N, src, c->cfg.src_height, c->cfg.src_width, stage_w, c->stage_stride, disp, F); \
-    } while (0)
-            if (c->warp_aligned && src_shared) { c->last_stage1_kernel = MS_WARP_KERNEL_SHARED_ALIGNED; if (s1_nf == 3) MS_S1S_LAUNCH(3); else MS_S1S_LAUNCH(2); }
-            else if (c->warp_aligned) { c->last_stage1_kernel = MS_WARP_KERNEL_PER_FRAME_ALIGNED; if (s1_nf == 3) MS_S1_LAUNCH(true, 3); else MS_S1_LAUNCH(true, 2); }
-            else { c->last_stage1_kernel = MS_WARP_KERNEL_PER_FRAME_UNALIGNED; if (s1_nf == 3) MS_S1_LAUNCH(false, 3); else MS_S1_LAUNCH(false, 2); }
-#undef MS_S1_LAUNCH
-#undef MS_S1S_LAUNCH
-        }
-        else {
-            c->last_stage1_kernel = MS_WARP_KERNEL_SIMPLE;
-            k_remap_gain<<<dim3(div_up(c->max_aw, 64), div_up(c->max_ah, 4), F * N), blk, 0, st>>>(
-                vt, N, src, c->cfg.src_height, c->cfg.src_width, stage_w, c->stage_stride);
-        }
-        }
-        MS_LAUNCH_CHECK();
-        if (int e = mark("k_remap_gain")) return e;
-        for (int fc0 = 0; fc0 < F_all; fc0 += f_chunk) {      // (source-table chunks: see f_chunk above)
-            const int F = std::min(f_chunk, F_all - fc0);
-            const SrcTable src = src_chunk(fc0, F);
-            uint8_t *const stage_w = (uint8_t *)c->stage.p + (size_t)fc0 * c->stage_stride, *const g0_w = (uint8_t *)c->g0.p + (size_t)fc0 * c->g0_stride;
-            (void)stage_w; (void)g0_w;
-        // the stage images of a view have the same pitch and the same address modulo 4 in every frame BY CONSTRUCTION (stage_stride is a multiple of 256): the mesh remap
-        // always takes the shared-offset form.  Its unshared twin (k_warp_t<CPW>) was unreachable in the shipped library and untested: dev-knob builds only.
-        if (c->warp_tiled && c->cfg.debug_simple_kernels == 0 && warp_shared_knob) {
-            MS_CHECK((c->stage_stride & 3) == 0, "internal: stage image stride %lld not a multiple of 4", c->stage_stride);
-            c->last_warp_kernel = MS_WARP_KERNEL_SHARED_ALIGNED;
-            MS_WARP_S_LAUNCH(true, warp_nf(true), warp_lds, (const WarpTile *)c->warp_tiles.p, vt, N, src, c->cfg.src_height, c->cfg.src_width, mesh, (const uint8_t *)stage_w, c->stage_stride, g0_w, c->g0_stride, (const float2 *)c->tabs.p, F);
-        }
-#ifdef MS_DEV_KNOBS
-        else if (c->warp_tiled && c->cfg.debug_simple_kernels == 0) {
-            c->last_warp_kernel = MS_WARP_KERNEL_PER_FRAME_ALIGNED;
-            MS_PROJ_LAUNCH(k_warp_t, (true, true,), (dim3(c->n_warp_tiles, WARP_BY / WARP_WY, div_up(F, warp_nf(true))), dim3(WARP_BX, WARP_WY), warp_lds, st), (const WarpTile *)c->warp_tiles.p, vt, N, src, c->cfg.src_height, c->cfg.src_width, mesh, (const uint8_t *)stage_w, c->stage_stride, g0_w, c->g0_stride, (const float2 *)c->tabs.p, F);
-        }
-#endif
-        else
-            k_warp<true><<<dim3(div_up(c->max_pw, 64), div_up(c->max_ph, 4), F * N), blk, 0, st>>>(
-                vt, N, src, c->cfg.src_height, c->cfg.src_width, mesh, (const uint8_t *)stage_w, c->stage_stride, g0_w, c->g0_stride);
-        }
-    } else {
-        for (int fc0 = 0; fc0 < F_all; fc0 += f_chunk) {      // (source-table chunks: see f_chunk above)
-            const int F = std::min(f_chunk, F_all - fc0);
-            const SrcTable src = src_chunk(fc0, F);
-            uint8_t *const stage_w = (uint8_t *)c->stage.p + (size_t)fc0 * c->stage_stride, *const g0_w = (uint8_t *)c->g0.p + (size_t)fc0 * c->g0_stride;
-            (void)stage_w; (void)g0_w;
-        if (c->warp_tiled && c->cfg.debug_simple_kernels == 0) {
-        // opt-in (ms_config.warp_lds_stage = 1; MS_WARP_ASYNC=1 in a dev-knob build): source tiles staged in LDS by asynchronous LDS-DMA, persistent waves (k_warp_a) -- bit-identical,
-        // measured slower than the direct gathers on config 2 (353 vs 242 us per 16 frames: at its 1.6-2.1 x minification only 54 % of the tiles' source
-        // boxes fit a staging buffer and 10 waves per CU cannot hide what 20 do; profiles/r02_warp_probes.txt)
-        static const bool env_on = dev_knob("MS_WARP_ASYNC", 0) != 0;
-        bool staged = c->warp_lds_tiles > 0 && (c->cfg.warp_lds_stage == 1 || (env_on && c->cfg.warp_lds_stage != 2));
-        for (int i = 0; i < F * N; ++i) staged = staged && ((uintptr_t)src.p[i] & 15) == 0;   // chunk copies start on 16-byte lines of the buffer
-        if (nv12) {        // the cameras' NV12 planes sampled directly (k_warp_nv12): no BGR image in between
-            const dim3 b_(WARP_BX, WARP_WY);
-#define MS_NV12_LAUNCH(NF_, ALN_)                                                                                                                                     \
-    do {                                                                                                                                                              \
-        const dim3 g_(c->n_warp_tiles, WARP_BY / WARP_WY, div_up(F, NF_));                                                                                            \
-        if (c->cfg.projection == MS_PROJ_SPHERICAL) k_warp_nv12<MS_PROJ_SPHERICAL, NF_, ALN_><<<g_, b_, 0, st>>>((const WarpTile *)c->warp_tiles.p, vt, N, src, c->cfg.src_height, c->cfg.src_width, g0_w, c->g0_stride, (const float2 *)c->tabs.p, F); \
-        else if (c->cfg.projection == MS_PROJ_CYLINDRICAL) k_warp_nv12<MS_PROJ_CYLINDRICAL, NF_, ALN_><<<g_, b_, 0, st>>>((const WarpTile *)c->warp_tiles.p, vt, N, src, c->cfg.src_height, c->cfg.src_width, g0_w, c->g0_stride, (const float2 *)c->tabs.p, F); \
-        else k_warp_nv12<MS_PROJ_PLANE, NF_, ALN_><<<g_, b_, 0, st>>>((const WarpTile *)c->warp_tiles.p, vt, N, src, c->cfg.src_height, c->cfg.src_width, g0_w, c->g0_stride, (const float2 *)c->tabs.p, F); \
-    } while (0)
-            c->last_warp_kernel = MS_WARP_KERNEL_NV12;
-            if (nv_al) { if (F == 1) MS_NV12_LAUNCH(1, true); else MS_NV12_LAUNCH(2, true); }
-            else { if (F == 1) MS_NV12_LAUNCH(1, false); else MS_NV12_LAUNCH(2, false); }
-#undef MS_NV12_LAUNCH
-        } else if (staged) {
-            c->last_warp_kernel = MS_WARP_KERNEL_LDS_STAGED;
-            const long long items = (long long)c->n_warp_tiles * F;
-            const int grid = (int)std::min<long long>(items, (long long)c->n_cus * (160 * 1024 / (2 * WA_BUF_BYTES)));
-            MS_PROJ_LAUNCH(k_warp_a, (), (dim3(grid), dim3(64), 2 * WA_BUF_BYTES, st), (const WarpTile *)c->warp_tiles.p, c->n_warp_tiles, vt, N, src, c->cfg.src_height, c->cfg.src_width, g0_w, c->g0_stride, (const float2 *)c->tabs.p, F);
-        } else
-        {
-            // (with shared offsets the aligned form wins at every minification measured: config 5 -- 2.7 x, k_warp_t's unaligned territory -- 757 -> 730 / 738 -> 699 us per 16 frames;
-            //  the minification rule of build_plan still picks between k_warp_t's two forms when the frames do not share step and alignment)
-            static const int force_al = dev_knob("MS_WARP_ALIGNED", -1);
-            c->last_warp_kernel = ((c->warp_aligned || force_al != 0) && src_shared) ? MS_WARP_KERNEL_SHARED_ALIGNED : c->warp_aligned ? MS_WARP_KERNEL_PER_FRAME_ALIGNED
-                                  : (src_steps_equal && F > 1 && dev_knob("MS_WARP_SHARED_U", 1)) ? MS_WARP_KERNEL_SHARED_UNALIGNED : MS_WARP_KERNEL_PER_FRAME_UNALIGNED;
-            if ((c->warp_aligned || force_al != 0) && src_shared)
-                MS_WARP_S_LAUNCH(false, WARP_NF_S, warp_lds_al, (const WarpTile *)c->warp_tiles.p, vt, N, src, c->cfg.src_height, c->cfg.src_width, mesh, nullptr, 0, g0_w, c->g0_stride, (const float2 *)c->tabs.p, F);
-            else if (c->warp_aligned)
-                MS_PROJ_LAUNCH(k_warp_t, (false, true,), (dim3(c->n_warp_tiles, WARP_BY / WARP_WY, div_up(F, WARP_NF)), dim3(WARP_BX, WARP_WY), warp_lds_al, st), (const WarpTile *)c->warp_tiles.p, vt, N, src, c->cfg.src_height, c->cfg.src_width, mesh, nullptr, 0, g0_w, c->g0_stride, (const float2 *)c->tabs.p, F);
-            else if (src_steps_equal && F > 1 && dev_knob("MS_WARP_SHARED_U", 1)) {      // the unaligned-read form with shared offsets (config 5): only the row step has to agree
-                const dim3 g_(c->n_warp_tiles, WARP_BY / WARP_WY, div_up(F, WARP_NF)), b_(WARP_BX, WARP_WY);
-                if (c->cfg.projection == MS_PROJ_SPHERICAL) k_warp_s<false, MS_PROJ_SPHERICAL, WARP_NF, false><<<g_, b_, warp_lds, st>>>((const WarpTile *)c->warp_tiles.p, vt, N, src, c->cfg.src_height, c->cfg.src_width, mesh, nullptr, 0, g0_w, c->g0_stride, (const float2 *)c->tabs.p, F);
-                else if (c->cfg.projection == MS_PROJ_CYLINDRICAL) k_warp_s<false, MS_PROJ_CYLINDRICAL, WARP_NF, false><<<g_, b_, warp_lds, st>>>((const WarpTile *)c->warp_tiles.p, vt, N, src, c->cfg.src_height, c->cfg.src_width, mesh, nullptr, 0, g0_w, c->g0_stride, (const float2 *)c->tabs.p, F);
-                else k_warp_s<false, MS_PROJ_PLANE, WARP_NF, false><<<g_, b_, warp_lds, st>>>((const WarpTile *)c->warp_tiles.p, vt, N, src, c->cfg.src_height, c->cfg.src_width, mesh, nullptr, 0, g0_w, c->g0_stride, (const float2 *)c->tabs.p, F);
-            } else
-                MS_PROJ_LAUNCH(k_warp_t, (false, false,), (dim3(c->n_warp_tiles, WARP_BY / WARP_WY, div_up(F, WARP_NF)), dim3(WARP_BX, WARP_WY), warp_lds, st), (const WarpTile *)c->warp_tiles.p, vt, N, src, c->cfg.src_height, c->cfg.src_width, mesh, nullptr, 0, g0_w, c->g0_stride, (const float2 *)c->tabs.p, F);
-        }
-    } else if (c->cfg.cpu_flavour_remap != 0) {
-        k_warp<false, true><<<dim3(div_up(c->max_pw, 64), div_up(c->max_ph, 4), F * N), blk, 0, st>>>(
-            vt, N, src, c->cfg.src_height, c->cfg.src_width, mesh, nullptr, 0, g0_w, c->g0_stride);
-    } else {
-        k_warp<false><<<dim3(div_up(c->max_pw, 64), div_up(c->max_ph, 4), F * N), blk, 0, st>>>(
-            vt, N, src, c->cfg.src_height, c->cfg.src_width, mesh, nullptr, 0, g0_w, c->g0_stride);
-    }
-        }
-    }
-    MS_LAUNCH_CHECK();
-    if (int e = mark("k_warp")) return e;
-
     static const int tail_sw_knob = dev_knob("MS_TAIL_SW", 0);      // A/B: force the strip width of the reduce tail (16 = the round-4 form)
     const bool dt_wide = F > 2 && tail_sw_knob != TAIL_STRIP;
     const int dt_l0 = c->tail_l0, dt_lds = dt_wide ? c->tail_lds_b : c->tail_lds, dt_strips = dt_wide ? c->tail_strips_b : c->tail_strips, dt_sw = dt_wide ? c->tail_sw_b : TAIL_STRIP;     // (starting the reduce tail a level finer was measured slower even for one frame)
     for (int l = 0; l < nb; ++l) {
         if (l == dt_l0 && c->cfg.debug_simple_kernels == 0) {
-            k_down_tail<<<dim3(F * N * 3 * dt_strips), (F <= 2 || dt_sw > TAIL_STRIP) ? dim3(64, 16) : blk, dt_lds, st>>>(vt, N, l, nb, dt_strips, dt_sw, gl, c->gl_stride, c->own_mask & c->needed_mask);
+            k_down_tail<<<dim3(F * N * 3 * dt_strips), (F <= 2 || dt_sw > TAIL_STRIP) ? dim3(64, 16) : blk, dt_lds, k.st>>>(vt, N, l, nb, dt_strips, dt_sw, gl, c->gl_stride, c->own_mask & c->needed_mask);
             MS_LAUNCH_CHECK();
-            if (int e = mark("k_down_tail")) return e;
-            break;
+            return mark(k, "k_down_tail");
         }
         const int ow = (std::max(c->max_pw >> l, 1) + 1) / 2, oh = (std::max(c->max_ph >> l, 1) + 1) / 2;
         if (c->down_vec[l] && c->cfg.debug_simple_kernels == 0) {   // level-l widths are multiples of 8: tile list, DOWN_ROWS (4) rows x 4 cols per lane
             const dim3 g(c->n_down_tiles[l], 3, F), b(32, 8);
             static const int down_lds = dev_knob("MS_DOWN_LDS", 0);      // occupancy A/B knob (dynamic LDS nobody touches)
-            if (l == 0) k_down_t<true><<<g, b, down_lds, st>>>((const DownTile *)c->down_tiles[l].p, vt, l, g0, c->g0_stride, gl, c->gl_stride);
-            else        k_down_t<false><<<g, b, 0, st>>>((const DownTile *)c->down_tiles[l].p, vt, l, gl, c->gl_stride, gl, c->gl_stride);
+            if (l == 0) k_down_t<true><<<g, b, down_lds, k.st>>>((const DownTile *)c->down_tiles[l].p, vt, l, g0, c->g0_stride, gl, c->gl_stride);
+            else        k_down_t<false><<<g, b, 0, k.st>>>((const DownTile *)c->down_tiles[l].p, vt, l, gl, c->gl_stride, gl, c->gl_stride);
         } else {
             const dim3 g(div_up(ow, 64), div_up(oh, 4), F * N * 3);
-            if (l == 0) k_down<<<g, blk, 0, st>>>(vt, N, l, g0, c->g0_stride, gl, c->gl_stride);
-            else        k_down<<<g, blk, 0, st>>>(vt, N, l, gl, c->gl_stride, gl, c->gl_stride);
+            if (l == 0) k_down<<<g, blk, 0, k.st>>>(vt, N, l, g0, c->g0_stride, gl, c->gl_stride);
+            else        k_down<<<g, blk, 0, k.st>>>(vt, N, l, gl, c->gl_stride, gl, c->gl_stride);
         }
         MS_LAUNCH_CHECK();
-        if (int e = mark(down_names[l])) return e;
+        if (int e = mark(k, down_names[l])) return e;
     }
-    }   // S.mode != 2
+    return MS_OK;
+}
+
+// the band chain: normalise, collapse and write the outputs (all frames per launch); single band without a pyramid
+static int enqueue_bands(ms_ctx *c, StitchCall &k)
+{
+    static const char *blend_names[MAX_LEVELS] = {"k_blend_l0", "k_blend_l1", "k_blend_l2", "k_blend_l3", "k_blend_l4", "k_blend_l5", "k_blend_l6", "k_blend_l7"};
+    const int nb = c->pano.nb, F = k.F_call;
+    const ViewDesc *vt = k.vt;
+    const PanoDesc &P = k.P;
+    const ShardArgs &S = k.S;
+    const hipStream_t st = k.st;
+    const uint8_t *g0 = (const uint8_t *)c->g0.p;
+    uint8_t *gl = (uint8_t *)c->gl.p;
+    int16_t *cl = (int16_t *)c->cl.p;
+    const dim3 blk(64, 4);
     if (nb == 0) {       // single band (FeatherBlender weights or plain mask weights): no pyramid, one pass over the pano
-        if (S.mode != 0) return fail(MS_ERR_UNSUPPORTED, "view sharding needs num_bands >= 1");
-        k_single_band<<<dim3(div_up(P.fw, 64), div_up(P.fh, 4), F), blk, 0, st>>>(vt, P, g0, c->g0_stride, out);
+        k_single_band<<<dim3(div_up(P.fw, 64), div_up(P.fh, 4), F), blk, 0, st>>>(vt, P, g0, c->g0_stride, k.out);
         MS_LAUNCH_CHECK();
-        if (int e = mark("k_single_band")) return e;
-    } else {
-#define MS_MODE_LAUNCH(K, G, B, ...)                                     \
-    do {                                                                \
-        if (S.mode == 0) K<0><<<G, B, 0, st>>>(__VA_ARGS__);            \
-        else if (S.mode == 1) K<1><<<G, B, 0, st>>>(__VA_ARGS__);       \
-        else K<2><<<G, B, 0, st>>>(__VA_ARGS__);                        \
-    } while (0)
-#define MS_MODE_LAUNCH2(K, L0, G, B, ...)                               \
-    do {                                                                \
-        if (S.mode == 0) K<L0, 0><<<G, B, 0, st>>>(__VA_ARGS__);        \
-        else if (S.mode == 1) K<L0, 1><<<G, B, 0, st>>>(__VA_ARGS__);   \
-        else K<L0, 2><<<G, B, 0, st>>>(__VA_ARGS__);                    \
-    } while (0)
+        return mark(k, "k_single_band");
+    }
     int l_first = nb - 1;
     static const bool bt2_off = dev_knob("MS_LIVE_TAIL", 1) == 0;
     const bool bt2 = F <= 2 && c->btail2_t >= 0 && !bt2_off;      // live mode (1-2 frames per call): launches dominate, the band tail starts one band finer
@@ -3428,12 +3451,14 @@ static int stitch_impl(ms_ctx *c, int n_frames, const ms_image *views, ms_image 
         if (F <= 2) k_blend_tail<true><<<dim3(s1 - s0, 3, F), bt_blk, bt_lds, st>>>(vt, P, bt_t, gl, c->gl_stride, cl, c->cl_stride, s0, bt_w);
         else        k_blend_tail<false><<<dim3(s1 - s0, 3, F), bt_blk, bt_lds, st>>>(vt, P, bt_t, gl, c->gl_stride, cl, c->cl_stride, s0, bt_w);
         MS_LAUNCH_CHECK();
-        if (int e = mark("k_blend_tail")) return e;
+        if (int e = mark(k, "k_blend_tail")) return e;
         l_first = bt_t - 1;
     } else {
-        MS_MODE_LAUNCH(k_blend_top, dim3(div_up(P.qw[nb], 64), div_up(P.qh[nb], 4), F), blk, vt, P, g0, c->g0_stride, gl, c->gl_stride, cl, c->cl_stride, S);
+        with_value<0, 1, 2>(S.mode, [&](auto M) {
+            k_blend_top<M><<<dim3(div_up(P.qw[nb], 64), div_up(P.qh[nb], 4), F), blk, 0, st>>>(vt, P, g0, c->g0_stride, gl, c->gl_stride, cl, c->cl_stride, S);
+        });
         MS_LAUNCH_CHECK();
-        if (int e = mark(blend_names[nb])) return e;
+        if (int e = mark(k, blend_names[nb])) return e;
     }
     for (int l = l_first; l >= 0; --l) {
         if (c->blend_vec[l] && c->cfg.debug_simple_kernels == 0) {
@@ -3441,33 +3466,57 @@ static int stitch_impl(ms_ctx *c, int n_frames, const ms_image *views, ms_image 
             static const bool no_cls = dev_knob("MS_BLEND_CLS", 1) == 0;      // MS_BLEND_CLS=0: always the all-classes build (A/B)
             // level 0 without general cells (the usual case: binary Voronoi seam masks): the build that has no general path -- 88 instead of 120 VGPRs, 5 waves per SIMD
             static const int blend_lds = dev_knob("MS_BLEND_LDS", 0);      // occupancy A/B knob
-            if (l == 0 && S.mode == 0 && int_only && !no_cls) k_blend8<true, 0, 1><<<g, b, blend_lds, st>>>((const BlendTile *)c->blend_tiles[l].p, vt, P, l, g0, c->g0_stride, gl, c->gl_stride, cl, c->cl_stride, out, S);
-            else if (l == 0) MS_MODE_LAUNCH2(k_blend8, true, g, b, (const BlendTile *)c->blend_tiles[l].p, vt, P, l, g0, c->g0_stride, gl, c->gl_stride, cl, c->cl_stride, out, S);
-            else        MS_MODE_LAUNCH2(k_blend8, false, g, b, (const BlendTile *)c->blend_tiles[l].p, vt, P, l, g0, c->g0_stride, gl, c->gl_stride, cl, c->cl_stride, out, S);
+            const BlendTile *tiles = (const BlendTile *)c->blend_tiles[l].p;
+            if (l == 0 && S.mode == 0 && k.int_only && !no_cls) k_blend8<true, 0, 1><<<g, b, blend_lds, st>>>(tiles, vt, P, l, g0, c->g0_stride, gl, c->gl_stride, cl, c->cl_stride, k.out, S);
+            else
+                with_value<true, false>(l == 0, [&](auto L0) { with_value<0, 1, 2>(S.mode, [&](auto M) {
+                    k_blend8<L0, M><<<g, b, 0, st>>>(tiles, vt, P, l, g0, c->g0_stride, gl, c->gl_stride, cl, c->cl_stride, k.out, S);
+                }); });
         } else {
             const dim3 g(div_up(P.qw[l] / 2, 64), div_up(P.qh[l] / 2, 4), F);
-            if (l == 0) MS_MODE_LAUNCH2(k_blend, true, g, blk, vt, P, l, g0, c->g0_stride, gl, c->gl_stride, cl, c->cl_stride, out, S);
-            else        MS_MODE_LAUNCH2(k_blend, false, g, blk, vt, P, l, g0, c->g0_stride, gl, c->gl_stride, cl, c->cl_stride, out, S);
+            with_value<true, false>(l == 0, [&](auto L0) { with_value<0, 1, 2>(S.mode, [&](auto M) {
+                k_blend<L0, M><<<g, blk, 0, st>>>(vt, P, l, g0, c->g0_stride, gl, c->gl_stride, cl, c->cl_stride, k.out, S);
+            }); });
         }
         MS_LAUNCH_CHECK();
-        if (int e = mark(blend_names[l])) return e;
-    }
-    }   // nb > 0
-    MS_HIP(hipEventRecord(c->last_stitch, st));
-    c->stitch_pending = true;
-
-    if (names) {
-        MS_HIP(hipEventSynchronize(ev.back()));
-        for (size_t i = 1; i < ev.size() && (int)i - 1 < cap; ++i) {
-            float t = 0.f;
-            MS_HIP(hipEventElapsedTime(&t, ev[i - 1], ev[i]));
-            ms_out[i - 1] = t;
-        }
-        for (auto e : ev) (void)hipEventDestroy(e);
-        if (n_rec) *n_rec = rec;
+        if (int e = mark(k, blend_names[l])) return e;
     }
     return MS_OK;
 }
+
+static int stitch_impl(ms_ctx *c, int n_frames, const ms_image *views, ms_image *out8u, ms_image *out16s, hipStream_t st,
+                       int cap, const char **names, float *ms_out, int *n_rec, ShardArgs S = ShardArgs{}, ms_image *out_i420 = nullptr, bool nv12 = false)
+{
+    if (!c) return fail(MS_ERR_INVALID, "null context");
+    std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);      // a synchronous table rebuild on another thread (ms_update_mask without a margin) waits for this enqueue, and vice versa
+    StitchCall k{};
+    k.F_call = n_frames; k.st = st; k.S = S; k.nv12 = nv12;
+    k.cap = cap; k.names = names;
+    if (int e = check_call(c, k, views, out8u, out16s, out_i420)) return e;
+    // CPW: mesh_mu is held from here to the hipEventRecord(last_stitch) at the end of the enqueue (RAII): a mesh update that starts meanwhile
+    // sees this stitch in last_stitch before it may touch the buffer this stitch reads.  Only enqueues happen under the lock.
+    std::unique_lock<std::mutex> mesh_lk(c->mesh_mu, std::defer_lock);
+    if (k.cpw) mesh_lk.lock();
+    if (int e = hand_over_tables(c, k)) return e;
+    c->last_warp_kernel = MS_WARP_KERNEL_SIMPLE; c->last_stage1_kernel = MS_WARP_KERNEL_NONE;      // (overwritten by enqueue_warps with the form it launches)
+
+    // one context has ONE set of per-batch intermediates: calls on a different stream than the previous one are ordered behind it on the GPU
+    // (the reference makes a fresh cuda::Stream per stitch_online call, timed.cpp:64, and relies on the NULL stream for ordering)
+    if (c->last_stream_set && c->last_stream != st && c->stitch_pending) MS_HIP(hipStreamWaitEvent(st, c->last_stitch, 0));
+    c->last_stream = st; c->last_stream_set = true;
+
+    if (int e = mark(k, nullptr)) return e;
+    if (k.S.mode != 2) {       // (finish mode starts from the partial sums: no warp, no pyramids)
+        if (int e = enqueue_warps(c, k)) return e;
+        if (int e = enqueue_reduce(c, k)) return e;
+    }
+    if (int e = enqueue_bands(c, k)) return e;
+    MS_HIP(hipEventRecord(c->last_stitch, st));
+    c->stitch_pending = true;
+    return names ? read_marks(k, ms_out, n_rec) : MS_OK;
+}
+
+extern "C" {
 
 int ms_stitch(ms_ctx *c, int n_frames, const ms_image *views, ms_image *out8u, ms_image *out16s, ms_stream stream)
 {

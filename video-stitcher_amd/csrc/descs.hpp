@@ -6,8 +6,9 @@ namespace ms {
 
 constexpr int MAX_LEVELS = 8;     // num_bands <= 7
 constexpr int MAX_VIEWS = 16;
-constexpr int MAX_SRC = 192;      // frames * views of ONE by-value source table (a launch of the kernels that read the callers' frames: stitch_impl sends them out in chunks)
+constexpr int MAX_SRC = 192;      // frames * views of ONE by-value source table (a launch of the kernels that read the callers' frames: the per-frame path sends them out in chunks)
 constexpr int MAX_FRAMES = 64;    // frames per ms_stitch call
+static_assert(MAX_SRC >= MAX_VIEWS, "a source table holds at least one frame of every view");
 
 struct LevelDesc {
     int w, h, pitch;              // level size; pitch in elements
