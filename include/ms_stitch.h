@@ -323,8 +323,33 @@ MS_API int ms_get_mesh_displacement(ms_ctx *ctx, int view, float *out_px);
  * With ms_config.update_mask_margin > 0 the call is asynchronous like ms_set_mesh: it enqueues the re-warp, the view's weight pyramid, the weight
  * sums, the result mask and the owner maps into the inactive copy of the tables on `stream` and swaps; the next ms_stitch waits for it on the GPU.
  * Safe from the recalibration thread while another thread stitches (timed.cpp:598-605 calls it right after the mesh swap).
- * ms_get_mask keeps returning the original mask; ms_set_mask / ms_build_masks / ms_calibrate_seam drop the re-warped one. */
+ * ms_get_mask keeps returning the original mask; ms_set_mask / ms_build_masks / ms_calibrate_seam drop the re-warped one.
+ * MS_ERR_STATE while views are left out (ms_set_active_views): make every view active first. */
 MS_API int ms_update_mask(ms_ctx *ctx, int view, ms_stream stream);
+
+/* Camera dropout.  Bit v set = view v is composited.  The views left out are treated exactly as MultiBandBlender treats a view whose feed_online
+ * was not called for the frame (blenders.cpp:700-749, 758-832): they add nothing to the band sums or the weight sums; pixels covered only by them
+ * come out 0 with result mask 0.  Panorama ROI, canvas placement and output sizes do not change.
+ *   - Takes effect at the next ms_stitch / ms_stitch_nv12 / ms_stitch_i420 / ms_blend issued after the call returns, for every frame of that call.
+ *     The set is per call, not per frame: a caller that sees a camera drop out in the middle of a batch splits the batch there.
+ *   - Enqueue-only: the table rebuild runs on `stream`, and the next stitch waits for it on the GPU.  The call never waits for GPU work; it waits
+ *     only for a stitch being enqueued on another thread, or a table rebuild (ms_init_blender, synchronous ms_update_mask), to finish.  Safe from
+ *     another thread while one thread stitches (same contract as ms_set_mesh).
+ *   - The views left out are never read: their ms_image may be all-zero.  ms_blend needs only the active views fed (feeds of the others are ignored),
+ *     ms_get_needed_views returns needed & active, ms_get_result_mask the active set's mask.
+ *   - All views = the original tables again (bit-identical, no rebuild).  The full-set tables are never overwritten.  ms_init_blender, ms_load_tables
+ *     and everything else that rebuilds the tables start with all views active; ms_save_tables saves the full-set tables (the set is run-time state).
+ *     ms_set_mesh* and ms_set_gain stay allowed for every view: a mesh set on an inactive view is used once it is active again, and a gain applies to
+ *     the full set and to every cached subset.
+ *   - A subset's tables (made on the device: weight sums, result mask and owner maps of the active views, work lists without the others) are cached
+ *     for the last num_views + 1 subsets, so a camera that goes away and comes back costs a pointer swap after the first time.  Memory per cached set:
+ *     4 bytes per pixel of every pano level (the weight sums: about 5.3 bytes per pano-ROI pixel), 1 byte per pano-ROI pixel
+ *     (the result mask), 1 byte per 64 x 16 cell per band (owner maps), the work lists (24 bytes per warp tile, 8 per pyramid / band tile), plus once per
+ *     context zeros as large as the largest view's level-0 weights.
+ * MS_ERR_INVALID: mask 0 or a bit >= num_views.  MS_ERR_STATE: before ms_init_blender.  MS_ERR_UNSUPPORTED: view-sharded contexts and FeatherBlender
+ * contexts (ms_init_feather).  Column-sharded contexts are supported. */
+MS_API int ms_set_active_views(ms_ctx *ctx, unsigned mask, ms_stream stream);
+MS_API int ms_get_active_views(const ms_ctx *ctx, unsigned *mask);
 
 /* MeshWarper::convertMeshesToMap for one view (APP/meshwarper.cpp:823-886): N x M vertex mesh (HOST fp32,
  * forward positions in view-ROI pixels) -> dense backward maps x_mesh/y_mesh, double-buffered; takes
@@ -365,7 +390,8 @@ MS_API int ms_stitch_partial(ms_ctx *ctx, int n_frames, const ms_image *views, v
 MS_API int ms_stitch_finish(ms_ctx *ctx, int n_frames, const void *const *partials, int n_partials,
                             ms_image *out8u, ms_image *out16s, ms_stream stream);
 
-/* gpu_dst_mask_ (blenders.cpp:803): frame-invariant; 8UC1 pano-ROI sized DEVICE image owned by ctx. */
+/* gpu_dst_mask_ (blenders.cpp:803): frame-invariant; 8UC1 pano-ROI sized DEVICE image owned by ctx.  While views are left out (ms_set_active_views) it is
+ * the active set's mask, held by that set's cached tables: valid until the next ms_set_active_views or table rebuild (ms_init_blender, ms_update_mask). */
 MS_API int ms_get_result_mask(ms_ctx *ctx, ms_image *mask);
 
 /* Calibration tables as a blob (the reference re-runs stitch_calib at every start, APP/timed.cpp:553).  ms_save_tables writes what the static

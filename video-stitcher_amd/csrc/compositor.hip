@@ -19,6 +19,7 @@
 // multiply/divide + truncation, and int16 accumulation wraps exactly like `short +=`.
 #include <algorithm>
 #include <atomic>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <vector>
@@ -1266,13 +1267,15 @@ __global__ void __launch_bounds__(256) k_acc_weight(const float *__restrict__ w,
 }
 // The same sums for one band in ONE launch (ms_update_mask): dst_w = ((0 + w_0) + w_1) + ... over the views that cover the pixel, in view order --
 // the float additions k_acc_weight performs view after view --, then den = sum + WEIGHT_EPS and (level 0) mask = sum > WEIGHT_EPS.
-__global__ void __launch_bounds__(256) k_den_all(const ViewDesc *__restrict__ views, int n_views, int l, float *den, int dpitch, int rows, int cols,
+// Only the views of `view_set` are summed (ms_set_active_views: a view left out adds nothing, as a view whose feed_online was not called).
+__global__ void __launch_bounds__(256) k_den_all(const ViewDesc *__restrict__ views, int n_views, unsigned view_set, int l, float *den, int dpitch, int rows, int cols,
                                                  uint8_t *mask, int mpitch, int mrows, int mcols)
 {
     const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
     if (x >= cols || y >= rows) return;
     float s = 0.f;
     for (int v = 0; v < n_views; ++v) {
+        if (!((view_set >> v) & 1u)) continue;
         const LevelDesc &L = views[v].lv[l];
         const int lx = x - L.x_tl, ly = y - L.y_tl;
         if (lx < 0 || ly < 0 || lx >= L.w || ly >= L.h) continue;
@@ -1283,7 +1286,8 @@ __global__ void __launch_bounds__(256) k_den_all(const ViewDesc *__restrict__ vi
 }
 // Owner map of one band: one wave per 64 x 16 cell of the pano level.  The cell is owned by view v when v is the only view with a non-zero weight in it,
 // the cell lies inside the pano level and inside v's rect, and all of v's weights there are exactly 1.0f; 255 otherwise (see PanoDesc::pure).
-__global__ void __launch_bounds__(64) k_owner_map(const ViewDesc *__restrict__ views, int n_views, int l, int qw, int qh, uint8_t *__restrict__ pure, int ppitch)
+// Views outside `view_set` do not count (ms_set_active_views): a cell owned by such a view is uncovered in the subset's map.
+__global__ void __launch_bounds__(64) k_owner_map(const ViewDesc *__restrict__ views, int n_views, unsigned view_set, int l, int qw, int qh, uint8_t *__restrict__ pure, int ppitch)
 {
     const int cx = blockIdx.x, cy = blockIdx.y, lane = threadIdx.x;
     const int x0 = cx * 64, y0 = cy * 16;
@@ -1292,6 +1296,7 @@ __global__ void __launch_bounds__(64) k_owner_map(const ViewDesc *__restrict__ v
     bool ones = false, binary = true, clash = false;
     unsigned taken = 0u;                                     // pixels of this lane some view has claimed with a non-zero weight
     for (int v = 0; v < n_views; ++v) {
+        if (!((view_set >> v) & 1u)) continue;
         const LevelDesc &L = views[v].lv[l];
         bool nz = false, one = true;
         const int ly = py - L.y_tl;
@@ -1332,6 +1337,50 @@ __global__ void __launch_bounds__(256) k_finish_den(float *den, int dpitch, int 
     if (mask && x < mcols && y < mrows) mask[(size_t)y * mpitch + x] = s > 1e-5f ? 255 : 0;
     den[(size_t)y * dpitch + x] = s + 1e-5f;
 }
+// ---- camera dropout (ms_set_active_views): the tables of a subset of the views, made on the device from the full-set ones -------------------
+// The tiles of the views in `view_set`, in list order (one workgroup: a few ten thousand records at most, once per subset).
+template <class Tile>
+__global__ void __launch_bounds__(1024) k_filter_tiles(const Tile *__restrict__ in, int n, Tile *__restrict__ out, unsigned view_set)
+{
+    __shared__ int s_cnt[16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int base = 0;
+    for (int i0 = 0; i0 < n; i0 += 1024) {
+        const int i = i0 + (int)threadIdx.x;
+        const bool keep = i < n && ((view_set >> in[i].view) & 1u);
+        const unsigned long long b = __ballot(keep);
+        if (lane == 0) s_cnt[wave] = __popcll(b);
+        __syncthreads();
+        int off = base, total = 0;
+        for (int w = 0; w < 16; ++w) { off += w < wave ? s_cnt[w] : 0; total += s_cnt[w]; }
+        if (keep) out[off + __popcll(b & ((1ull << lane) - 1ull))] = in[i];
+        __syncthreads();
+        base += total;
+    }
+}
+// band tiles keep their place (every tile writes its part of the outputs); only the views of `view_set` are gathered
+__global__ void __launch_bounds__(256) k_filter_blend_tiles(const BlendTile *__restrict__ in, int n, BlendTile *__restrict__ out, unsigned view_set)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    BlendTile t = in[i];
+    t.view_mask &= view_set;
+    out[i] = t;
+}
+// the view table of a subset: a view outside `view_set` keeps its geometry, its weight levels and level-0 mask point at zeros (`zero`, as large as
+// the largest view's level 0).  The per-frame kernels that visit every view then add (short)(L * 0.f) == 0 for it -- what a view that was not fed adds.
+__global__ void __launch_bounds__(64) k_subset_views(const ViewDesc *__restrict__ in, ViewDesc *__restrict__ out, int n_views, int nb, unsigned view_set, const void *zero)
+{
+    const int v = threadIdx.x;
+    if (v >= n_views) return;
+    ViewDesc d = in[v];
+    if (!((view_set >> v) & 1u)) {
+        d.wm0 = (const uint8_t *)zero;
+        for (int l = 0; l <= nb; ++l) d.lv[l].wgt = (const float *)zero;
+    }
+    out[v] = d;
+}
+
 // CPW mesh -> backward map: scatter-average (APP/meshwarper.cpp:859-875)
 __global__ void __launch_bounds__(256) k_mesh_scatter(const float *__restrict__ bx, const float *__restrict__ by, int pitch, int rows, int cols,
                                                       float *sx, float *sy, float *cnt, int hw, int hh)
@@ -1705,6 +1754,31 @@ struct ms_ctx {
     int col_begin = 0, col_end = 0;    // 0, 0 = whole panorama
     unsigned needed_mask = 0xffffffffu;
     long long pacc_stride = 0;         // elements per frame of a partial-accumulator buffer
+    // Camera dropout (ms_set_active_views).  The full-set tables above are never written by it: a subset has tables of its own, made on the device from the
+    // current full-set copy -- weight sums, result mask and owner maps of the active views, a view table whose inactive views have zero weights, and work
+    // lists without the inactive views.  The last few subsets stay cached (LRU), so a camera that drops out again costs a pointer swap.
+    struct SubsetTables {
+        unsigned views = 0, needed = 0;      // the active set; needed_mask & views
+        int gen = -1;                        // tables_gen the tables were made from
+        unsigned long long used = 0;         // LRU stamp
+        DevBuf den, result_mask, pure_maps, view_tab, warp_tiles, stage1_tiles, down_tiles[MAX_LEVELS], blend_tiles[MAX_LEVELS];
+        PanoDesc pano{};
+        int n_warp_tiles = 0, n_stage1_tiles = 0, n_down_tiles[MAX_LEVELS] = {};
+        bool l0_integer_only = false;
+        hipEvent_t ready = nullptr;          // recorded behind the rebuild; every stitch that reads these tables waits for it
+        ~SubsetTables() { if (ready) (void)hipEventDestroy(ready); }
+    };
+    std::vector<std::unique_ptr<SubsetTables>> subsets;
+    SubsetTables *act = nullptr;       // the tables ms_stitch reads: nullptr = all views (the full-set tables).  Written under tables_mu (and act_mu)
+    std::atomic<bool> subset_on{false};      // act != nullptr, for ms_update_mask (which does not take tables_mu on its enqueue-only path)
+    std::mutex act_mu;                 // serialises ms_set_active_views with ms_update_mask; taken BEFORE mesh_update_mu and tables_mu
+    int tables_gen = 0;                // bumped whenever the full-set tables change (ms_init_blender, ms_update_mask): cached subsets are rebuilt
+    unsigned long long subset_clock = 0;
+    DevBuf zero_w;                     // zeros as large as the largest view's level-0 weights (the weights of an inactive view)
+    hipEvent_t subset_built = nullptr; // behind the last subset rebuild: an enqueue-only mask update waits for it before it rewrites the copy the rebuild read
+    bool subset_built_set = false;
+    // tiles per view of the full-set lists: a subset's list sizes without reading the lists back
+    int warp_per_view[MAX_VIEWS] = {}, stage1_per_view[MAX_VIEWS] = {}, down_per_view[MAX_LEVELS][MAX_VIEWS] = {};
 };
 
 namespace ms {
@@ -1816,20 +1890,26 @@ static void xcd_order(std::vector<T> &tiles, int chunk = 0)
 
 static bool sharded_ctx(const ms_ctx *c) { return c->own_mask != ((c->N >= 32) ? 0xffffffffu : ((1u << c->N) - 1u)); }
 
-// k_owner_map for every band that has a map, into `pure` (laid out by build_plan), from the weights `vt` points at
+// k_owner_map for every band that has a map, into `pure` (laid out by build_plan), from the weights `vt` points at, of the views in `view_set`
+static int enqueue_owner_maps(const ms_ctx *c, const ViewDesc *vt, unsigned view_set, uint8_t *pure, hipStream_t st)
+{
+    for (int l = 0; l < c->pano.nb; ++l) {
+        if (!c->pure_off[l]) continue;
+        const int pw_ = div_up(c->pano.qw[l], 64), ph_ = div_up(c->pano.qh[l], 16);
+        k_owner_map<<<dim3(pw_, ph_), 64, 0, st>>>(vt, c->N, view_set, l, c->pano.qw[l], c->pano.qh[l], pure + (c->pure_off[l] - 1), pw_);
+        MS_LAUNCH_CHECK();
+    }
+    return MS_OK;
+}
+
+// the full-set owner maps
 static int launch_owner_maps(ms_ctx *c, const ViewDesc *vt, uint8_t *pure, hipStream_t st)
 {
     // whoever rewrites the owner maps invalidates what the host knows about them: the integer-only level-0 build (k_blend8<true, 0, 1>, which has NO general path and
     // leaves a general cell unwritten) may only run after the caller has looked at the new level-0 map again (build_plan does; the enqueue-only mask update never
     // sees its maps on the host and stays on the all-classes build).  Cleared HERE so that a future caller cannot forget.
     c->l0_integer_only = false;
-    for (int l = 0; l < c->pano.nb; ++l) {
-        if (!c->pure_off[l]) continue;
-        const int pw_ = div_up(c->pano.qw[l], 64), ph_ = div_up(c->pano.qh[l], 16);
-        k_owner_map<<<dim3(pw_, ph_), 64, 0, st>>>(vt, c->N, l, c->pano.qw[l], c->pano.qh[l], pure + (c->pure_off[l] - 1), pw_);
-        MS_LAUNCH_CHECK();
-    }
-    return MS_OK;
+    return enqueue_owner_maps(c, vt, 0xffffffffu, pure, st);
 }
 
 static int build_plan(ms_ctx *c)
@@ -1926,6 +2006,8 @@ static int build_plan(ms_ctx *c)
         }
         c->needed_mask = 0;
         for (const WarpTile &t : tiles) c->needed_mask |= 1u << t.view;
+        for (int v = 0; v < MAX_VIEWS; ++v) c->warp_per_view[v] = 0;
+        for (const WarpTile &t : tiles) ++c->warp_per_view[t.view];
         if (!windowed || !c->warp_tiled) c->needed_mask = 0xffffffffu;      // (the full-grid fallback kernels touch every view)
         // (chunks of 8 tiles dealt round-robin: measured, profiles/r04_warp_experiments.txt -- config 2 k_warp 402 -> 388 us per 32 frames, config 5 -2..-5 %; the CPW mesh remap
         //  of the shipped rig +1.5 %, so CPW contexts keep the eight long runs)
@@ -2004,6 +2086,8 @@ static int build_plan(ms_ctx *c)
             tiles.insert(tiles.end(), b.begin(), b.end());
         }
         c->n_stage1_tiles = (int)tiles.size();
+        for (int v = 0; v < MAX_VIEWS; ++v) c->stage1_per_view[v] = 0;
+        for (const WarpTile &t : tiles) ++c->stage1_per_view[t.view];
         if (int e = c->stage1_tiles.alloc(std::max<size_t>(1, tiles.size()) * sizeof(WarpTile))) return e;
         MS_HIP(hipMemcpy(c->stage1_tiles.p, tiles.data(), tiles.size() * sizeof(WarpTile), hipMemcpyHostToDevice));
         if (!tiles.empty() && c->warp_tiled) {     // flags bit 3 of every stage-1 tile: no sample reads the last source row (aligned tap reads allowed)
@@ -2025,6 +2109,8 @@ static int build_plan(ms_ctx *c)
             }
         if (c->cfg.raster_tile_order == 0) xcd_order(tiles, dev_knob(l == 0 ? "MS_XCD_CHUNK_DOWN0" : "MS_XCD_CHUNK_DOWN", 0));
         c->n_down_tiles[l] = (int)tiles.size();
+        for (int v = 0; v < MAX_VIEWS; ++v) c->down_per_view[l][v] = 0;
+        for (const DownTile &t : tiles) ++c->down_per_view[l][t.view];
         if (int e = c->down_tiles[l].alloc(std::max<size_t>(1, tiles.size()) * sizeof(DownTile))) return e;
         if (!tiles.empty()) MS_HIP(hipMemcpy(c->down_tiles[l].p, tiles.data(), tiles.size() * sizeof(DownTile), hipMemcpyHostToDevice));
     }
@@ -2131,6 +2217,7 @@ void ms_destroy(ms_ctx *c)
     for (int v = 0; v < MAX_VIEWS; ++v) if (c->mesh_ready[v]) (void)hipEventDestroy(c->mesh_ready[v]);
     if (c->mesh_chain) (void)hipEventDestroy(c->mesh_chain);
     if (c->tab_ready) (void)hipEventDestroy(c->tab_ready);
+    if (c->subset_built) (void)hipEventDestroy(c->subset_built);
     if (c->mesh_stage) (void)hipHostFree(c->mesh_stage);
     for (hipEvent_t e : c->mesh_stage_ev) if (e) (void)hipEventDestroy(e);
     delete c;
@@ -2158,6 +2245,11 @@ int ms_set_gain(ms_ctx *c, int view, double gain)
             c->alt.h_views[view].gain = (float)gain;
             MS_HIP(hipMemcpy((ViewDesc *)c->alt.view_tab.p + view, &c->alt.h_views[view], sizeof(ViewDesc), hipMemcpyHostToDevice));
         }
+        // ... and the view tables of the cached subsets (ms_set_active_views), the active one included: a subset made earlier must not bring an old gain back
+        std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);
+        const float g = (float)gain;
+        for (auto &T : c->subsets)
+            if (T->view_tab.p) MS_HIP(hipMemcpy(&((ViewDesc *)T->view_tab.p + view)->gain, &g, sizeof(float), hipMemcpyHostToDevice));
     }
     return MS_OK;
 }
@@ -2356,6 +2448,12 @@ int ms_init_blender(ms_ctx *c, ms_stream stream)
     std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);      // no ms_stitch enqueue while the tables are rebuilt ...
     if (c->stitch_pending) MS_HIP(hipEventSynchronize(c->last_stitch)); // ... and none still reading the old ones on the GPU
     const int nb = c->bg.num_bands, N = c->N, F = c->cfg.max_frames;
+    // new full-set tables: every view active again, the cached subsets (made from the old tables, sized for the old geometry) are gone
+    c->act = nullptr; c->subset_on = false;
+    ++c->tables_gen;
+    if (c->subset_built_set) MS_HIP(hipEventSynchronize(c->subset_built));      // (a subset rebuild may still run on another stream)
+    c->subsets.clear();
+    c->zero_w.release();      // (sized for the old geometry)
 
     // ---- layout of every per-view level -------------------------------------------------------
     c->h_views.assign(N, ViewDesc{});
@@ -2947,6 +3045,7 @@ static int update_mask_async(ms_ctx *c, int view, hipStream_t st)
         if (c->mesh_ready[view] && !c->mesh_ready_via_chain[view]) MS_HIP(hipStreamWaitEvent(st, c->mesh_ready[view], 0));
         if (c->mesh_chain_set) MS_HIP(hipStreamWaitEvent(st, c->mesh_chain, 0));
         if (c->tab_wait) MS_HIP(hipStreamWaitEvent(st, c->tab_ready, 0));
+        if (c->subset_built_set) MS_HIP(hipStreamWaitEvent(st, c->subset_built, 0));      // a subset rebuild may still read the copy written below
     }
     const bool to_alt = from == 0;
     float *w_to = (float *)(to_alt ? A.weights.p : c->weights.p);
@@ -2992,7 +3091,7 @@ static int update_mask_async(ms_ctx *c, int view, hipStream_t st)
     }
     // 3. weight sums, result mask, owner maps from the new set of weights
     for (int l = 0; l <= nb; ++l) {
-        k_den_all<<<dim3(div_up(P.qw[l], 64), div_up(P.qh[l], 4)), dim3(64, 4), 0, st>>>(vt_to, N, l, den_to + c->den_off[l], P.dpitch[l], P.qh[l], P.qw[l],
+        k_den_all<<<dim3(div_up(P.qw[l], 64), div_up(P.qh[l], 4)), dim3(64, 4), 0, st>>>(vt_to, N, 0xffffffffu, l, den_to + c->den_off[l], P.dpitch[l], P.qh[l], P.qw[l],
                                                                                          l == 0 ? rm_to : nullptr, P.mask_pitch, P.fh, P.fw);
         MS_LAUNCH_CHECK();
     }
@@ -3003,6 +3102,7 @@ static int update_mask_async(ms_ctx *c, int view, hipStream_t st)
         MS_HIP(hipEventRecord(c->tab_ready, st));
         c->tab_active = from ^ 1; c->tab_wait = true;
         c->l0_integer_only = false;
+        ++c->tables_gen;      // cached subset tables were made from the other copy
         // the re-warp above READS this view's mesh slot and displacement entry: later mesh updates (any stream) are ordered behind it through the
         // chain event they all wait for, so the second ms_set_mesh from now cannot overwrite the slot under the re-warp
         if (c->mesh_chain) { MS_HIP(hipEventRecord(c->mesh_chain, st)); c->mesh_chain_set = true; }
@@ -3020,6 +3120,8 @@ int ms_update_mask(ms_ctx *c, int view, ms_stream stream)
     if (int e = ctx_check_view(c, view)) return e;
     if (!c->blender_ready || !c->cfg.enable_cpw || !c->mesh_set[view]) return fail(MS_ERR_STATE, "ms_update_mask: needs enable_cpw, ms_init_blender and a mesh for view %d", view);
     hipStream_t st = as_stream(stream);
+    std::lock_guard<std::mutex> alk(c->act_mu);
+    if (c->subset_on) return fail(MS_ERR_STATE, "ms_update_mask: views are left out (ms_set_active_views); make every view active first");
     std::lock_guard<std::mutex> ulk(c->mesh_update_mu);
     if (c->cfg.update_mask_margin > 0) return update_mask_async(c, view, st);
     std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);      // synchronous form: safe against a concurrent ms_stitch, which blocks for the rebuild
@@ -3039,6 +3141,123 @@ int ms_update_mask(ms_ctx *c, int view, ms_stream stream)
     MS_HIP(hipStreamSynchronize(st));
     c->use_eff[view] = true;
     return ms_init_blender(c, stream);
+}
+
+// ---- camera dropout: ms_set_active_views -----------------------------------------------------------------------------------
+// The tables of a view subset, enqueued on `st`, made from the full-set copy that is current (the enqueue-only mask update's pair).  Nothing is read back:
+// list sizes come from the per-view tile counts of build_plan, the level-0 integer-only property from the full set's (a subset's general cells are among the
+// full set's: leaving a view out turns an owned cell into an uncovered one, 254 or the owner of another view, never into a general one -- k_owner_map).
+static int build_subset(ms_ctx *c, ms_ctx::SubsetTables &T, unsigned views, hipStream_t st)
+{
+    const int N = c->N, nb = c->pano.nb;
+    const PanoDesc &P = c->pano;
+    const bool fresh = !T.view_tab.p;
+    int from;
+    {
+        std::lock_guard<std::mutex> mk(c->mesh_mu);
+        from = c->tab_active;
+        if (!fresh && c->stitch_pending) MS_HIP(hipStreamWaitEvent(st, c->last_stitch, 0));      // rebuilt in place: after every stitch that read these tables
+        if (c->tab_wait) MS_HIP(hipStreamWaitEvent(st, c->tab_ready, 0));
+    }
+    if (!c->zero_w.p) {
+        size_t zb = 0;
+        for (int v = 0; v < N; ++v) {
+            const ViewDesc &V = c->h_views[v];
+            zb = std::max(zb, std::max((size_t)V.lv[0].h * V.lv[0].wpitch * sizeof(float), (size_t)V.wm0_pitch * V.ph));
+        }
+        if (int e = c->zero_w.alloc(zb + 256)) return e;
+        MS_HIP(hipMemsetAsync(c->zero_w.p, 0, c->zero_w.bytes, st));
+    }
+    if (fresh) {
+        if (int e = T.den.alloc(c->den_total * sizeof(float))) return e;
+        if (int e = T.result_mask.alloc((size_t)P.mask_pitch * P.fh)) return e;
+        if (int e = T.pure_maps.alloc(std::max<size_t>(1, c->pure_total))) return e;
+        if (int e = T.warp_tiles.alloc(std::max<size_t>(1, c->n_warp_tiles) * sizeof(WarpTile))) return e;
+        if (int e = T.stage1_tiles.alloc(std::max<size_t>(1, c->n_stage1_tiles) * sizeof(WarpTile))) return e;
+        for (int l = 0; l < nb; ++l) {
+            if (int e = T.down_tiles[l].alloc(std::max<size_t>(1, c->n_down_tiles[l]) * sizeof(DownTile))) return e;
+            if (int e = T.blend_tiles[l].alloc(std::max<size_t>(1, c->n_blend_tiles[l]) * sizeof(BlendTile))) return e;
+        }
+        if (int e = T.view_tab.alloc(sizeof(ViewDesc) * N)) return e;
+        if (!T.ready) MS_HIP(hipEventCreateWithFlags(&T.ready, hipEventDisableTiming));
+        MS_HIP(hipMemsetAsync(T.den.p, 0, T.den.bytes, st));      // (row padding: never read)
+        MS_HIP(hipMemsetAsync(T.result_mask.p, 0, T.result_mask.bytes, st));
+    }
+    const ViewDesc *vt = (const ViewDesc *)(from ? c->alt.view_tab.p : c->view_tab.p);
+    T.pano = from ? c->alt.pano : c->pano;
+    k_subset_views<<<1, 64, 0, st>>>(vt, (ViewDesc *)T.view_tab.p, N, nb, views, c->zero_w.p);
+    MS_LAUNCH_CHECK();
+    // weight sums and result mask of the active views, in view order (the oracle's blender fed with them only), then their owner maps
+    for (int l = 0; l <= nb; ++l) {
+        k_den_all<<<dim3(div_up(P.qw[l], 64), div_up(P.qh[l], 4)), dim3(64, 4), 0, st>>>(vt, N, views, l, (float *)T.den.p + c->den_off[l], P.dpitch[l], P.qh[l], P.qw[l],
+                                                                                         l == 0 ? (uint8_t *)T.result_mask.p : nullptr, P.mask_pitch, P.fh, P.fw);
+        MS_LAUNCH_CHECK();
+        T.pano.den[l] = (const float *)T.den.p + c->den_off[l];
+    }
+    T.pano.mask = (const uint8_t *)T.result_mask.p;
+    for (int l = 0; l < nb; ++l) T.pano.pure[l] = c->pure_off[l] ? (const uint8_t *)T.pure_maps.p + (c->pure_off[l] - 1) : nullptr;
+    if (c->pure_total)
+        if (int e = enqueue_owner_maps(c, vt, views, (uint8_t *)T.pure_maps.p, st)) return e;
+    // work lists without the inactive views (same order); the band lists keep every tile and gather the active views only
+    auto count = [&](const int *per_view) { int n = 0; for (int v = 0; v < N; ++v) if ((views >> v) & 1u) n += per_view[v]; return n; };
+    T.n_warp_tiles = count(c->warp_per_view);
+    if (c->n_warp_tiles) k_filter_tiles<WarpTile><<<1, 1024, 0, st>>>((const WarpTile *)c->warp_tiles.p, c->n_warp_tiles, (WarpTile *)T.warp_tiles.p, views);
+    T.n_stage1_tiles = count(c->stage1_per_view);
+    if (c->n_stage1_tiles) k_filter_tiles<WarpTile><<<1, 1024, 0, st>>>((const WarpTile *)c->stage1_tiles.p, c->n_stage1_tiles, (WarpTile *)T.stage1_tiles.p, views);
+    for (int l = 0; l < nb; ++l) {
+        T.n_down_tiles[l] = count(c->down_per_view[l]);
+        if (c->n_down_tiles[l]) k_filter_tiles<DownTile><<<1, 1024, 0, st>>>((const DownTile *)c->down_tiles[l].p, c->n_down_tiles[l], (DownTile *)T.down_tiles[l].p, views);
+        if (c->n_blend_tiles[l])
+            k_filter_blend_tiles<<<div_up(c->n_blend_tiles[l], 256), 256, 0, st>>>((const BlendTile *)c->blend_tiles[l].p, c->n_blend_tiles[l], (BlendTile *)T.blend_tiles[l].p, views);
+    }
+    MS_LAUNCH_CHECK();
+    T.needed = c->needed_mask & views;
+    T.l0_integer_only = c->l0_integer_only.load();
+    T.views = views; T.gen = c->tables_gen;
+    MS_HIP(hipEventRecord(T.ready, st));
+    if (!c->subset_built) MS_HIP(hipEventCreateWithFlags(&c->subset_built, hipEventDisableTiming));
+    MS_HIP(hipEventRecord(c->subset_built, st));
+    c->subset_built_set = true;
+    return MS_OK;
+}
+
+int ms_set_active_views(ms_ctx *c, unsigned mask, ms_stream stream)
+{
+    if (!c) return fail(MS_ERR_INVALID, "null context");
+    const unsigned all = (c->N >= 32) ? 0xffffffffu : ((1u << c->N) - 1u);
+    if (mask == 0 || (mask & ~all)) return fail(MS_ERR_INVALID, "ms_set_active_views: mask 0x%x is empty or names a view >= %d", mask, c->N);
+    std::lock_guard<std::mutex> alk(c->act_mu);
+    std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);      // no stitch is being enqueued while the set changes (held for an enqueue, never for a GPU wait)
+    if (!c->blender_ready) return fail(MS_ERR_STATE, "ms_set_active_views: call ms_init_blender first");
+    if (sharded_ctx(c)) return fail(MS_ERR_UNSUPPORTED, "ms_set_active_views: not for a view-sharded context");
+    if (c->feather_sharpness >= 0.f) return fail(MS_ERR_UNSUPPORTED, "ms_set_active_views: not for FeatherBlender contexts (ms_init_feather)");
+    if (mask == all) { c->act = nullptr; c->subset_on = false; return MS_OK; }
+    ms_ctx::SubsetTables *T = nullptr;
+    for (auto &e : c->subsets) if (e->views == mask && e->gen == c->tables_gen) T = e.get();
+    if (!T) {      // not cached: a stale copy of the same set, a new entry, or the least recently used one -- rebuilt in place
+        for (auto &e : c->subsets) if (!T && e->views == mask) T = e.get();
+        if (!T && c->subsets.size() < (size_t)c->N + 1) {
+            std::unique_ptr<ms_ctx::SubsetTables> e(new (std::nothrow) ms_ctx::SubsetTables());
+            if (!e) return fail(MS_ERR_NOMEM, "ms_set_active_views: out of host memory");
+            T = e.get();
+            c->subsets.push_back(std::move(e));
+        }
+        if (!T) for (auto &e : c->subsets) if (e.get() != c->act && (!T || e->used < T->used)) T = e.get();
+        if (int e = build_subset(c, *T, mask, as_stream(stream))) { T->views = 0; T->gen = -1; return e; }
+    }
+    T->used = ++c->subset_clock;
+    c->act = T; c->subset_on = true;
+    return MS_OK;
+}
+
+int ms_get_active_views(const ms_ctx *c, unsigned *mask)
+{
+    if (!c || !mask) return fail(MS_ERR_INVALID, "ms_get_active_views: null argument");
+    if (!c->blender_ready) return fail(MS_ERR_STATE, "ms_get_active_views: call ms_init_blender first");
+    const unsigned all = (c->N >= 32) ? 0xffffffffu : ((1u << c->N) - 1u);
+    std::lock_guard<std::recursive_mutex> tables_lk(const_cast<ms_ctx *>(c)->tables_mu);
+    *mask = c->act ? c->act->views : all;
+    return MS_OK;
 }
 
 int ms_get_mesh_displacement(ms_ctx *c, int view, float *out_px)
@@ -3074,8 +3293,17 @@ template <class Fn>
 static inline void with_proj(const ms_ctx *c, Fn &&f) { with_value<(int)MS_PROJ_SPHERICAL, (int)MS_PROJ_CYLINDRICAL, (int)MS_PROJ_PLANE>(c->cfg.projection, f); }
 
 // one ms_stitch* call: what check_call establishes before anything is enqueued, and what the enqueue stages share
+// the work lists a call runs: the context's (every view active) or those of the active subset (ms_set_active_views)
+struct WorkLists {
+    const WarpTile *warp, *stage1; const DownTile *down[MAX_LEVELS]; const BlendTile *blend[MAX_LEVELS];
+    int n_warp, n_stage1, n_down[MAX_LEVELS], n_blend[MAX_LEVELS];
+    unsigned reduce_views;            // views k_down_tail reduces
+};
+
 struct StitchCall {
     int F_call;                       // frames of the call (the launches that read the callers' frames take them in chunks: for_each_chunk)
+    const ms_ctx::SubsetTables *sub;  // the active view subset's tables; nullptr = all views
+    WorkLists W;
     hipStream_t st;
     ShardArgs S;
     bool nv12, nv_al, cpw, src_shared, src_steps_equal, int_only;
@@ -3104,6 +3332,7 @@ static int check_call(ms_ctx *c, StitchCall &k, const ms_image *views, const ms_
     for (int i = 0; i < F * N && S.mode != 2; ++i) {
         if (!((c->own_mask >> (i % N)) & 1u)) continue;       // another shard's view: not read
         if (!((c->needed_mask >> (i % N)) & 1u)) continue;    // column sharding: no pixel of this view reaches the window
+        if (k.sub && !((k.sub->views >> (i % N)) & 1u)) continue;      // camera dropout: an inactive view is not read (its image may be all-zero)
         if (k.nv12)
             MS_CHECK(views[i].data && views[i].type == MS_8UC1 && views[i].rows == c->cfg.src_height * 3 / 2 && views[i].cols == c->cfg.src_width && views[i].step == views[i % N].step,
                      "ms_stitch_nv12: view %d must be the NV12 planes of a %dx%d frame (8UC1, %d rows), every frame of a view with the same step", i, c->cfg.src_width, c->cfg.src_height, c->cfg.src_height * 3 / 2);
@@ -3119,6 +3348,13 @@ static int check_call(ms_ctx *c, StitchCall &k, const ms_image *views, const ms_
             while (!((c->own_mask >> owned) & 1u)) ++owned;
             for (int v = 0; v < N; ++v)
                 if (!((c->own_mask >> v) & 1u)) { k.src.p[f * N + v] = k.src.p[f * N + owned]; k.src.step[f * N + v] = k.src.step[f * N + owned]; }
+        }
+    if (k.sub)      // likewise for the views a subset leaves out (the tiled kernels never read them)
+        for (int f = 0; f < F; ++f) {
+            int read = -1;
+            for (int v = 0; v < N && read < 0; ++v) if (k.src.p[f * N + v]) read = v;
+            for (int v = 0; v < N && read >= 0; ++v)
+                if (!k.src.p[f * N + v]) { k.src.p[f * N + v] = k.src.p[f * N + read]; k.src.step[f * N + v] = k.src.step[f * N + read]; }
         }
     for (int f = 0; f < F; ++f) {
         if (out8u && out8u[f].data) {
@@ -3196,6 +3432,24 @@ static int hand_over_tables(ms_ctx *c, StitchCall &k)
         }
     }
     k.int_only = c->l0_integer_only.load() && k.P.pure[0] != nullptr;      // (an enqueue-only mask update clears it before it publishes its tables under mesh_mu: a stale `true` can only meet the old tables)
+    WorkLists &W = k.W;
+    W.warp = (const WarpTile *)c->warp_tiles.p; W.stage1 = (const WarpTile *)c->stage1_tiles.p;
+    W.n_warp = c->n_warp_tiles; W.n_stage1 = c->n_stage1_tiles;
+    for (int l = 0; l < nb; ++l) {
+        W.down[l] = (const DownTile *)c->down_tiles[l].p; W.n_down[l] = c->n_down_tiles[l];
+        W.blend[l] = (const BlendTile *)c->blend_tiles[l].p; W.n_blend[l] = c->n_blend_tiles[l];
+    }
+    W.reduce_views = c->own_mask & c->needed_mask;
+    if (const ms_ctx::SubsetTables *T = k.sub) {      // camera dropout: the subset's tables and lists (made from the full-set copy current when it was set)
+        MS_HIP(hipStreamWaitEvent(k.st, T->ready, 0));      // (on every call: the stitch may run on another stream than the one after the rebuild)
+        k.vt = (const ViewDesc *)T->view_tab.p;
+        k.P = T->pano;
+        k.int_only = T->l0_integer_only && k.P.pure[0] != nullptr;
+        W.warp = (const WarpTile *)T->warp_tiles.p; W.stage1 = (const WarpTile *)T->stage1_tiles.p;
+        W.n_warp = T->n_warp_tiles; W.n_stage1 = T->n_stage1_tiles;
+        for (int l = 0; l < nb; ++l) { W.down[l] = (const DownTile *)T->down_tiles[l].p; W.n_down[l] = T->n_down_tiles[l]; W.blend[l] = (const BlendTile *)T->blend_tiles[l].p; }
+        W.reduce_views = c->own_mask & T->needed;
+    }
     return MS_OK;
 }
 
@@ -3255,9 +3509,9 @@ static KernelForm stage1_form(const ms_ctx *c, const StitchCall &k, int nf)
 
 static void launch_stage1(const ms_ctx *c, const StitchCall &k, const Chunk &ch, const KernelForm &f)
 {
-    const WarpTile *tiles = (const WarpTile *)c->stage1_tiles.p;
+    const WarpTile *tiles = k.W.stage1;
     const int N = c->N, H = c->cfg.src_height, W = c->cfg.src_width;
-    const dim3 g(c->n_stage1_tiles, 1, div_up(ch.nf, f.nf)), b(WARP_BX, S1_BY);
+    const dim3 g(k.W.n_stage1, 1, div_up(ch.nf, f.nf)), b(WARP_BX, S1_BY);
     switch (f.kernel) {
     case MS_WARP_KERNEL_NV12:
         with_proj(c, [&](auto P) { with_value<1, 2>(f.nf, [&](auto NF) { with_value<true, false>(f.al, [&](auto AL) {
@@ -3313,10 +3567,10 @@ static KernelForm warp_form(const ms_ctx *c, const StitchCall &k, const Chunk &c
 
 static void launch_warp(const ms_ctx *c, const StitchCall &k, const Chunk &ch, const KernelForm &f)
 {
-    const WarpTile *tiles = (const WarpTile *)c->warp_tiles.p;
+    const WarpTile *tiles = k.W.warp;
     const float2 *tabs = (const float2 *)c->tabs.p;
     const int N = c->N, H = c->cfg.src_height, W = c->cfg.src_width;
-    const dim3 g(c->n_warp_tiles, WARP_BY / WARP_WY, div_up(ch.nf, f.nf)), b(WARP_BX, WARP_WY);
+    const dim3 g(k.W.n_warp, WARP_BY / WARP_WY, div_up(ch.nf, f.nf)), b(WARP_BX, WARP_WY);
     switch (f.kernel) {
     case MS_WARP_KERNEL_SHARED_ALIGNED:
         if (k.cpw)
@@ -3345,10 +3599,10 @@ static void launch_warp(const ms_ctx *c, const StitchCall &k, const Chunk &ch, c
         }); }); });
         break;
     case MS_WARP_KERNEL_LDS_STAGED: {
-        const long long items = (long long)c->n_warp_tiles * ch.nf;
+        const long long items = (long long)k.W.n_warp * ch.nf;
         const int grid = (int)std::min<long long>(items, (long long)c->n_cus * (160 * 1024 / (2 * WA_BUF_BYTES)));
         with_proj(c, [&](auto P) {
-            k_warp_a<P><<<dim3(grid), dim3(64), f.lds, k.st>>>(tiles, c->n_warp_tiles, k.vt, N, ch.src, H, W, ch.g0, c->g0_stride, tabs, ch.nf);
+            k_warp_a<P><<<dim3(grid), dim3(64), f.lds, k.st>>>(tiles, k.W.n_warp, k.vt, N, ch.src, H, W, ch.g0, c->g0_stride, tabs, ch.nf);
         });
         break;
     }
@@ -3368,7 +3622,7 @@ static int enqueue_warps(ms_ctx *c, StitchCall &k)
         for_each_chunk(c, k, [&](const Chunk &ch) {
             const KernelForm f = stage1_form(c, k, ch.nf);
             if (ch.f0 == 0) c->last_stage1_kernel = f.kernel;
-            launch_stage1(c, k, ch, f);
+            if (k.W.n_stage1 > 0 || f.kernel == MS_WARP_KERNEL_SIMPLE) launch_stage1(c, k, ch, f);
         });
         MS_LAUNCH_CHECK();
         if (int e = mark(k, "k_remap_gain")) return e;
@@ -3376,7 +3630,7 @@ static int enqueue_warps(ms_ctx *c, StitchCall &k)
     for_each_chunk(c, k, [&](const Chunk &ch) {
         const KernelForm f = warp_form(c, k, ch);
         if (ch.f0 == 0) c->last_warp_kernel = f.kernel;
-        launch_warp(c, k, ch, f);
+        if (k.W.n_warp > 0 || f.kernel == MS_WARP_KERNEL_SIMPLE) launch_warp(c, k, ch, f);
     });
     MS_LAUNCH_CHECK();
     return mark(k, "k_warp");
@@ -3396,16 +3650,18 @@ static int enqueue_reduce(ms_ctx *c, StitchCall &k)
     const int dt_l0 = c->tail_l0, dt_lds = dt_wide ? c->tail_lds_b : c->tail_lds, dt_strips = dt_wide ? c->tail_strips_b : c->tail_strips, dt_sw = dt_wide ? c->tail_sw_b : TAIL_STRIP;     // (starting the reduce tail a level finer was measured slower even for one frame)
     for (int l = 0; l < nb; ++l) {
         if (l == dt_l0 && c->cfg.debug_simple_kernels == 0) {
-            k_down_tail<<<dim3(F * N * 3 * dt_strips), (F <= 2 || dt_sw > TAIL_STRIP) ? dim3(64, 16) : blk, dt_lds, k.st>>>(vt, N, l, nb, dt_strips, dt_sw, gl, c->gl_stride, c->own_mask & c->needed_mask);
+            k_down_tail<<<dim3(F * N * 3 * dt_strips), (F <= 2 || dt_sw > TAIL_STRIP) ? dim3(64, 16) : blk, dt_lds, k.st>>>(vt, N, l, nb, dt_strips, dt_sw, gl, c->gl_stride, k.W.reduce_views);
             MS_LAUNCH_CHECK();
             return mark(k, "k_down_tail");
         }
         const int ow = (std::max(c->max_pw >> l, 1) + 1) / 2, oh = (std::max(c->max_ph >> l, 1) + 1) / 2;
         if (c->down_vec[l] && c->cfg.debug_simple_kernels == 0) {   // level-l widths are multiples of 8: tile list, DOWN_ROWS (4) rows x 4 cols per lane
-            const dim3 g(c->n_down_tiles[l], 3, F), b(32, 8);
+            const dim3 g(k.W.n_down[l], 3, F), b(32, 8);
             static const int down_lds = dev_knob("MS_DOWN_LDS", 0);      // occupancy A/B knob (dynamic LDS nobody touches)
-            if (l == 0) k_down_t<true><<<g, b, down_lds, k.st>>>((const DownTile *)c->down_tiles[l].p, vt, l, g0, c->g0_stride, gl, c->gl_stride);
-            else        k_down_t<false><<<g, b, 0, k.st>>>((const DownTile *)c->down_tiles[l].p, vt, l, gl, c->gl_stride, gl, c->gl_stride);
+            if (k.W.n_down[l] > 0) {      // (empty: a subset whose views reach no needed pixel of this level)
+                if (l == 0) k_down_t<true><<<g, b, down_lds, k.st>>>(k.W.down[l], vt, l, g0, c->g0_stride, gl, c->gl_stride);
+                else        k_down_t<false><<<g, b, 0, k.st>>>(k.W.down[l], vt, l, gl, c->gl_stride, gl, c->gl_stride);
+            }
         } else {
             const dim3 g(div_up(ow, 64), div_up(oh, 4), F * N * 3);
             if (l == 0) k_down<<<g, blk, 0, k.st>>>(vt, N, l, g0, c->g0_stride, gl, c->gl_stride);
@@ -3462,11 +3718,11 @@ static int enqueue_bands(ms_ctx *c, StitchCall &k)
     }
     for (int l = l_first; l >= 0; --l) {
         if (c->blend_vec[l] && c->cfg.debug_simple_kernels == 0) {
-            const dim3 g(c->n_blend_tiles[l], 4, F), b(32, 2);
+            const dim3 g(k.W.n_blend[l], 4, F), b(32, 2);
             static const bool no_cls = dev_knob("MS_BLEND_CLS", 1) == 0;      // MS_BLEND_CLS=0: always the all-classes build (A/B)
             // level 0 without general cells (the usual case: binary Voronoi seam masks): the build that has no general path -- 88 instead of 120 VGPRs, 5 waves per SIMD
             static const int blend_lds = dev_knob("MS_BLEND_LDS", 0);      // occupancy A/B knob
-            const BlendTile *tiles = (const BlendTile *)c->blend_tiles[l].p;
+            const BlendTile *tiles = k.W.blend[l];
             if (l == 0 && S.mode == 0 && k.int_only && !no_cls) k_blend8<true, 0, 1><<<g, b, blend_lds, st>>>(tiles, vt, P, l, g0, c->g0_stride, gl, c->gl_stride, cl, c->cl_stride, k.out, S);
             else
                 with_value<true, false>(l == 0, [&](auto L0) { with_value<0, 1, 2>(S.mode, [&](auto M) {
@@ -3491,6 +3747,7 @@ static int stitch_impl(ms_ctx *c, int n_frames, const ms_image *views, ms_image 
     std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);      // a synchronous table rebuild on another thread (ms_update_mask without a margin) waits for this enqueue, and vice versa
     StitchCall k{};
     k.F_call = n_frames; k.st = st; k.S = S; k.nv12 = nv12;
+    k.sub = c->act;      // (set under tables_mu: ms_set_active_views)
     k.cap = cap; k.names = names;
     if (int e = check_call(c, k, views, out8u, out16s, out_i420)) return e;
     // CPW: mesh_mu is held from here to the hipEventRecord(last_stitch) at the end of the enqueue (RAII): a mesh update that starts meanwhile
@@ -3549,7 +3806,8 @@ int ms_get_needed_views(const ms_ctx *c, unsigned *mask)
     if (!c || !mask) return fail(MS_ERR_INVALID, "ms_get_needed_views: null argument");
     if (!c->blender_ready) return fail(MS_ERR_STATE, "ms_get_needed_views: call ms_init_blender first");
     const unsigned all = (c->N >= 32) ? 0xffffffffu : ((1u << c->N) - 1u);
-    *mask = c->own_mask & c->needed_mask & all;
+    std::lock_guard<std::recursive_mutex> tables_lk(const_cast<ms_ctx *>(c)->tables_mu);
+    *mask = c->own_mask & c->needed_mask & all & (c->act ? c->act->views : all);
     return MS_OK;
 }
 
@@ -3587,8 +3845,9 @@ int ms_feed(ms_ctx *c, int view, const ms_image *img, ms_stream)
 int ms_blend(ms_ctx *c, ms_image *out8u, ms_image *out16s, ms_stream stream)
 {
     if (!c) return fail(MS_ERR_INVALID, "null context");
-    const unsigned all = (c->N >= 32) ? 0xffffffffu : ((1u << c->N) - 1u);
-    if ((c->fed_mask & all) != all) return fail(MS_ERR_STATE, "ms_blend: only views 0x%x of 0x%x were fed since the last blend", c->fed_mask, all);
+    std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);      // (the active set cannot change between this check and the enqueue)
+    const unsigned all = (c->N >= 32) ? 0xffffffffu : ((1u << c->N) - 1u), need = c->act ? c->act->views : all;
+    if ((c->fed_mask & need) != need) return fail(MS_ERR_STATE, "ms_blend: only views 0x%x of 0x%x were fed since the last blend", c->fed_mask & all, need);
     c->fed_mask = 0;
     return stitch_impl(c, 1, c->fed, out8u, out16s, as_stream(stream), 0, nullptr, nullptr, nullptr);
 }
@@ -3688,6 +3947,19 @@ int ms_get_result_mask(ms_ctx *c, ms_image *m)
 {
     if (!c || !m) return fail(MS_ERR_INVALID, "null argument");
     if (!c->blender_ready) return fail(MS_ERR_STATE, "ms_get_result_mask: call ms_init_blender first");
+    {
+        void *sub_mask = nullptr;
+        hipEvent_t sub_ready = nullptr;
+        {
+            std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);
+            if (const ms_ctx::SubsetTables *T = c->act) { sub_mask = T->result_mask.p; sub_ready = T->ready; }      // the active subset's mask
+        }
+        if (sub_mask) {      // (the wait outside the lock: a stitch on another thread is not held up by it)
+            MS_HIP(hipEventSynchronize(sub_ready));
+            *m = ms_image{sub_mask, (size_t)c->pano.mask_pitch, c->pano.fw, c->pano.fh, MS_8UC1};
+            return MS_OK;
+        }
+    }
     int active; bool wait;
     { std::lock_guard<std::mutex> mk(c->mesh_mu); active = c->tab_active; wait = c->tab_wait; }
     if (wait) MS_HIP(hipEventSynchronize(c->tab_ready));

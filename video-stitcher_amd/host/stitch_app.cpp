@@ -18,6 +18,10 @@
 // Usage: stitch_app [--views 6] [--size 1920x1080] [--out 3840x1920] [--hfov 90] [--bands 5] [--frames 300] [--cpw]
 //                   [--i420] [--nv12 | --nv12-direct] [--dump pano.bin] [--no-upload] [--solve-mesh]
 //                   [--reference-calib [--work-megapix 0.6] [--seam-megapix 0.01] [--compose-megapix 1.4]]
+//                   [--drop-view V:F0:F1] [--dump-frames frames.bin]
+// --drop-view: camera V delivers no new frame for the stitched frames [F0, F1).  The main loop gives every camera CAMERA_TIMEOUT_MS to deliver the frame it
+// stitches next; a camera that has not is left out (ms_set_active_views), and the full set comes back when it delivers again.  The reference exits instead
+// ("Failed to read all cameras", timed.cpp main loop).  --dump-frames writes every 8U panorama, in frame order, to one file.
 // --reference-calib runs msshim::stitch_calib (calibration.cpp:252-311): the reference's rig and scale bookkeeping, cylindrical warper, seam-scale
 // gains + Voronoi seams from the first frames, the num_bands rule, and -- with the default COMPOSE_MEGAPIX -- cuda::resize of every frame.
 // Prints one JSON line: end-to-end frames/s INCLUDING the PCIe upload of every source frame (unlike bench.py).
@@ -81,7 +85,10 @@ struct Options {
     bool reference_calib = false;               // stitch_calib as the reference ships it: cylindrical warper, megapixel budgets of defs.h, seam-scale pipeline
     double work_mp = 0.6, seam_mp = 0.01, compose_mp = 1.4;      // WORK_MEGAPIX, SEAM_MEAGPIX, COMPOSE_MEGAPIX (defs.h:51-53)
     std::string dump;
+    int drop_view = -1, drop_f0 = 0, drop_f1 = 0;    // --drop-view V:F0:F1
+    std::string dump_frames;
 };
+constexpr int CAMERA_TIMEOUT_MS = 100;               // --drop-view: how long the main loop waits for a camera's frame before it stitches without it
 
 // same pattern as synth.frame(w, h, i, t, noise=False): clip(rint(128 + 60 sin(2pi(x/97 + y/61 + i/7 + c/3)) + 40 checker))
 static void synth_frame(unsigned char *dst, int w, int h, int view)
@@ -190,8 +197,16 @@ int main(int argc, char **argv)
         else if (k == "--work-megapix") o.work_mp = atof(next());
         else if (k == "--seam-megapix") o.seam_mp = atof(next());
         else if (k == "--compose-megapix") o.compose_mp = atof(next());
+        else if (k == "--drop-view") {
+            if (sscanf(next(), "%d:%d:%d", &o.drop_view, &o.drop_f0, &o.drop_f1) != 3 || o.drop_view < 0) { fprintf(stderr, "--drop-view wants V:F0:F1\n"); return 2; }
+        }
+        else if (k == "--dump-frames") o.dump_frames = next();
         else { fprintf(stderr, "unknown option %s\n", k.c_str()); return 2; }
     }
+    if (o.drop_view >= o.views) { fprintf(stderr, "--drop-view: view %d of %d\n", o.drop_view, o.views); return 2; }
+    FILE *frames_file = nullptr;       // --dump-frames (opened before any thread starts)
+    if (!o.dump_frames.empty() && !(frames_file = fopen(o.dump_frames.c_str(), "wb"))) { fprintf(stderr, "cannot write %s\n", o.dump_frames.c_str()); return 2; }
+    bool frames_file_ok = true;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { fprintf(stderr, "stitch_app: no HIP device (libmsstitch has no CPU fallback)\n"); return 3; }
 
@@ -265,9 +280,18 @@ int main(int argc, char **argv)
             f.seq = 0;
         }
         std::atomic<bool> running{true};
+        std::atomic<long long> stitch_frame{0};          // --drop-view: the frame the main loop stitches next
         std::thread capture([&] {                       // "cameras": bump the sequence number of the frames at their own pace
             while (running.load()) {
-                { std::lock_guard<std::mutex> lk(imgs.mu); for (auto &f : imgs.v) ++f.seq; }
+                {
+                    std::lock_guard<std::mutex> lk(imgs.mu);
+                    if (o.drop_view < 0) for (auto &f : imgs.v) ++f.seq;
+                    else {                              // seq = the frame a camera delivered for; camera V stalls for the frames [F0, F1)
+                        const long long t = stitch_frame.load();
+                        for (int i = 0; i < o.views; ++i)
+                            if (!(i == o.drop_view && t >= o.drop_f0 && t < o.drop_f1)) imgs.v[i].seq = t;
+                    }
+                }
                 std::this_thread::sleep_for(std::chrono::microseconds(200));
             }
         });
@@ -342,8 +366,9 @@ int main(int argc, char **argv)
                     HIPCHECK(hipStreamSynchronize(consume_stream));
                     if (s->seq == o.frames - 1) for (unsigned char b : encoder_host) consume_checksum = (consume_checksum ^ b) * 1099511628211ull;
                 }
-                if (s->seq == o.frames - 1) {           // keep the last panorama for the checksum / dump
+                if (s->seq == o.frames - 1 || frames_file) {           // keep the last panorama for the checksum / dump (every one for --dump-frames)
                     HIPCHECK(hipMemcpy2D(last_pano.data(), (size_t)o.out_w * 3, s->pano8u.data, s->pano8u.step, (size_t)o.out_w * 3, o.out_h, hipMemcpyDeviceToHost));
+                    if (frames_file) frames_file_ok = frames_file_ok && fwrite(last_pano.data(), 1, last_pano.size(), frames_file) == last_pano.size();
                 }
                 ++consumed;
                 free_slots.push(s);
@@ -436,9 +461,26 @@ int main(int argc, char **argv)
 
         const auto t0 = std::chrono::steady_clock::now();
         std::string failure;
+        const unsigned all_views = (1u << o.views) - 1u;
+        unsigned active_views = all_views;
+        long long degraded_frames = 0;
         try {
         for (int t = 0; t < o.frames; ++t) {            // main loop: stitch_one per frame
             Slot *s = free_slots.pop();
+            if (o.drop_view >= 0) {     // capture timeout: the cameras that have not delivered frame t within CAMERA_TIMEOUT_MS are left out of it
+                stitch_frame.store(t);
+                const auto deadline = std::chrono::steady_clock::now() + std::chrono::milliseconds(CAMERA_TIMEOUT_MS);
+                unsigned fresh = 0;
+                for (;;) {
+                    fresh = 0;
+                    { std::lock_guard<std::mutex> lk(imgs.mu); for (int i = 0; i < o.views; ++i) if (imgs.v[i].seq >= t) fresh |= 1u << i; }
+                    if (fresh == all_views || std::chrono::steady_clock::now() >= deadline) break;
+                    std::this_thread::sleep_for(std::chrono::microseconds(50));
+                }
+                if (fresh == 0) fresh = active_views;      // (no camera at all: keep the last set)
+                if (fresh != active_views) { comp.setActiveViews(fresh, (ms_stream)stitch_stream); active_views = fresh; }      // enqueue-only
+                degraded_frames += active_views != all_views;
+            }
             const int ib = o.upload ? (t & 1) : 0;
             std::vector<DevMat> &full_imgs = full_imgs_b[ib], &nv12_imgs = nv12_imgs_b[ib];
             if (o.upload || t == 0) {
@@ -483,6 +525,7 @@ int main(int argc, char **argv)
         capture.join();
         if (recalibrater.joinable()) recalibrater.join();
         HIPCHECK(hipDeviceSynchronize());
+        if (frames_file) { frames_file_ok = fclose(frames_file) == 0 && frames_file_ok; if (!frames_file_ok) { fprintf(stderr, "cannot write %s\n", o.dump_frames.c_str()); return 2; } }
         if (!failure.empty()) { fprintf(stderr, "stitch_app: %s\n", failure.c_str()); return 1; }
         if (!recal_failure.empty()) { fprintf(stderr, "stitch_app (recalibration): %s\n", recal_failure.c_str()); return 1; }
 
@@ -530,10 +573,11 @@ int main(int argc, char **argv)
         }
         printf("{\"app\": \"stitch_app\", \"views\": %d, \"src\": \"%dx%d\", \"out\": \"%dx%d\", \"bands\": %d, \"cpw\": %s, \"i420\": %s, \"nv12\": %s, \"nv12_direct\": %s, \"upload\": %s, "
                "\"frames\": %lld, \"seconds\": %.4f, \"frames_per_s\": %.1f, \"recalibrations\": %d, \"mesh_solver_iterations\": %d, \"max_mesh_displacement_px\": %.2f, "
-               "\"orb_keypoints\": %lld, \"ratio_matches\": %lld, \"ransac_inliers\": %lld, \"update_mask_margin\": %d, \"update_mask_equals_sync_rebuild\": %s, \"consume_image_height\": %d, \"consume_checksum\": \"%016llx\", \"checksum\": \"%016llx\"}\n",
+               "\"orb_keypoints\": %lld, \"ratio_matches\": %lld, \"ransac_inliers\": %lld, \"update_mask_margin\": %d, \"update_mask_equals_sync_rebuild\": %s, \"consume_image_height\": %d, \"consume_checksum\": \"%016llx\", \"checksum\": \"%016llx\", \"degraded_frames\": %lld}\n",
                o.views, o.w, o.h, o.out_w, o.out_h, pg.num_bands, o.cpw ? "true" : "false", o.i420 ? "true" : "false", o.nv12 ? "true" : "false", o.nv12_direct ? "true" : "false", o.upload ? "true" : "false",
                consumed, secs, consumed / secs, recalibrations.load(), solver_iterations.load(), (double)max_disp.load(),
-               total_keypoints.load(), total_matches.load(), total_inliers.load(), o.update_mask, selfcheck < 0 ? "null" : (selfcheck ? "true" : "false"), consume_image_height, consume_checksum, checksum);
+               total_keypoints.load(), total_matches.load(), total_inliers.load(), o.update_mask, selfcheck < 0 ? "null" : (selfcheck ? "true" : "false"), consume_image_height, consume_checksum, checksum, degraded_frames);
+        if (o.drop_view >= 0) fprintf(stderr, "stitch_app: %lld of %lld frames stitched without every camera\n", degraded_frames, consumed);
     } catch (const msshim::Error &e) {
         fprintf(stderr, "stitch_app: msstitch error %d: %s\n", e.code, e.what());
         return 1;

@@ -100,6 +100,7 @@ EXPORTS = [
     "ms_selftest_divide", "ms_selftest_divide_range", "ms_calib_copy", "ms_calib_read", "ms_mesh_triangle_masks", "ms_bgr_to_i420", "ms_calibrate_seam", "ms_nv12_to_bgr", "ms_partial_bytes", "ms_stitch_partial", "ms_stitch_finish", "ms_selftest_cvt_u8", "ms_init_feather", "ms_get_mesh_displacement", "ms_set_mesh_interp", "ms_feed", "ms_blend", "ms_update_mask",
     "ms_mesh_default_params", "ms_mesh_saliency", "ms_create_mesh", "ms_knn_match_hamming2", "ms_bgr_to_i420_batch", "ms_bgr_to_gray", "ms_stitch_i420", "ms_get_i420_rows", "ms_get_col_window", "ms_get_needed_views", "ms_consume_i420", "ms_resize_linear_batch", "ms_nv12_to_bgr_batch",
     "ms_save_tables", "ms_load_tables", "ms_calib_shape", "ms_stitch_nv12", "ms_get_plan_stats", "ms_get_stitch_kernels",
+    "ms_set_active_views", "ms_get_active_views",
 ]
 
 _lib = None
@@ -823,6 +824,17 @@ class Compositor:
         a, b = C.c_int(0), C.c_int(0)
         _chk(load().ms_get_col_window(self._ctx, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def set_active_views(self, mask, stream=None):
+        """ms_set_active_views: composite only the views whose bit is set (camera dropout); enqueue-only, takes effect at the next stitch call."""
+        st = _stream() if stream is None else C.c_void_p(getattr(stream, "cuda_stream", stream))      # a torch.cuda.Stream or a raw hipStream_t
+        _chk(load().ms_set_active_views(self._ctx, C.c_uint(mask), st))
+
+    def active_views(self):
+        """Bit mask of the views the next stitch call composites (ms_get_active_views)."""
+        m = C.c_uint(0)
+        _chk(load().ms_get_active_views(self._ctx, C.byref(m)))
+        return m.value
 
     def needed_views(self):
         """Bit mask of the views ms_stitch reads (column / view shards read a subset)."""
