@@ -3,6 +3,12 @@
 (6x1080p synthetic views -> 3840x1920 equirect, CPW off, 5-band multiband blend).
 
   python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run, one rank per GPU; typed as is, it spawns its ranks itself)
+  python bench.py --gpus N --steps K --warmup W --full (the same headline, then everything else the bench measures or checks)
+
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes --dump-outputs and prints the line.  --full adds, after the timed
+region, everything else: `verified`, `live`, `value_distinct`, `pcie_inclusive_fps`, the instrumented per-kernel pass (`kernels_ms_per_call`, `latency`), `ceiling`,
+the in-run PMC pass, `roofline` / `frame_roofline` / `model`, `verified_vs_oracle`, `cpu_baseline` and `other_configs` (N > 1: `value_full_gather` and every rank's
+copy ceiling); the --no-* switches leave single parts of it out.  --view-shards / --col-shards print a line of their own, the same with or without --full.
 
 A "step" = --passes (default 20) passes over a batch of F frames (F = --frames, default 96: 6 views x F frames, inputs already resident in HBM; 20 x 96 = 1920 frames =
 64 s of 30 fps video per step), each pass issued as --streams (default 3) ms_stitch calls of F/streams = 32 frames on separate HIP streams / contexts.  Weak scaling:
@@ -43,6 +49,7 @@ def parse_args():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--passes", type=int, default=None, help="passes over the F-frame batch per step (default 20: a step is 1920 frames, so that the driver's "
                     "short runs still time about a second of GPU work; 1 with --calib / profiling runs)")
+    ap.add_argument("--full", action="store_true", help="after the headline, measure and check everything else (see the top of this file); off: the headline alone")
     ap.add_argument("--no-live", action="store_true", help="skip the one-frame-per-call latency measurement")
     ap.add_argument("--no-pcie", action="store_true", help="skip the PCIe-inclusive run of the C++ host pipeline (stitch_app)")
     ap.add_argument("--no-verify", action="store_true")
@@ -85,7 +92,7 @@ def parse_args():
     ap.add_argument("--streams", type=int, default=None,
                     help="contexts / HIP streams a step's frames are split over (default 3 x 32 frames: the small coarse-level kernels of one batch overlap the large kernels of another: +13 %% over one stream)")
     args = ap.parse_args()
-    # `other_configs` and the in-run PMC pass belong to the DEFAULT launch shape (what the driver runs); a probe that names its own shape (tools/*.sh) gets neither
+    # `other_configs` and the in-run PMC pass belong to the DEFAULT launch shape; a probe that names its own shape (tools/*.sh) gets neither
     if args.frames is not None or args.streams is not None or args.calib or args.emulate_gather or args.view_shards > 1 or args.col_shards > 1 or args.gpus > 1:
         args.no_others = True
         if not args.pmc_child and (args.calib or args.emulate_gather or args.gpus > 1 or args.streams not in (None, 1)):
@@ -103,6 +110,13 @@ def parse_args():
             args.frames = 4 if args.config == "cfg5" else 16
     if args.passes is None:
         args.passes = 1 if (args.calib or args.view_shards > 1 or args.col_shards > 1) else 20
+    return args
+
+
+def headline_only(args):
+    """a plain run (no --full) is the headline alone: every side measurement and check is --full's, whatever the --no-* switches say"""
+    if not args.full:
+        args.no_live = args.no_pcie = args.no_verify = args.no_cpu_baseline = args.no_distinct = args.no_others = args.no_pmc = True
     return args
 
 
@@ -147,7 +161,7 @@ def pcie_inclusive(wl):
 
 
 def main():
-    args = parse_args()
+    args = headline_only(parse_args())
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -213,12 +227,12 @@ def main():
 
     verified, verify_note = (None, None) if args.no_verify else wl.verify()
     live = wl.live() if (not args.no_live and rank == 0) else None
-    gathered_check = wl.gathered_check() if os.environ.get("MS_BENCH_CHECK_GATHERED") == "1" else None
+    gathered_check = wl.gathered_check() if (args.full and os.environ.get("MS_BENCH_CHECK_GATHERED") == "1") else None
     value_d96 = None if (args.no_distinct or args.calib) else wl.distinct_region(max(2, args.steps // 4))
     pcie = pcie_inclusive(wl) if (not args.no_pcie and rank == 0 and world == 1) else None
-    kmean, lat = wl.instrumented(max(5, min(50, args.steps * args.passes)))
-    rank_ceilings = dist_run.rank_copy_ceilings(ms, world, dev) if world > 1 else None
-    ceiling = RL.measure_ceiling(ms, dev) if (rank == 0 and world == 1 and not args.pmc_child) else None
+    kmean, lat = wl.instrumented(max(5, min(50, args.steps * args.passes))) if args.full else (None, None)
+    rank_ceilings = dist_run.rank_copy_ceilings(ms, world, dev) if (args.full and world > 1) else None
+    ceiling = RL.measure_ceiling(ms, dev) if (args.full and rank == 0 and world == 1 and not args.pmc_child) else None
     pmc_run, pmc_why = (None, None)
     if rank == 0 and world == 1 and not args.no_pmc:      # the hardware counters of this workload's launch shape, collected by this very run
         pmc_run, pmc_why = pmc.measure(args.config, Fs, wl.n_distinct, wl.frame_source)
@@ -233,7 +247,6 @@ def main():
                 ("ms_dist / " + dist_info["transport"]) if D is not None else "torch.distributed")
         if share:
             par += " [DEBUG: ranks share one GPU, gloo]"
-        roof, frame, model = RL.blocks(wl, kmean, elapsed, total_frames / world, ceiling, pmc_run, pmc_why)
         res = {
             "metric": METRIC if world == 1 else dist_run.METRIC_N,
             "value": round(total_frames / elapsed, 2), "unit": "frames/s",
@@ -244,11 +257,13 @@ def main():
             "dtype": DTYPE, "data": "synthetic",
             "config": {"workload": wl.workload_string(), "distinct_frame_sets": wl.n_distinct, "frames_per_step": frames_per_step, "frames_per_pass": F,
                        "passes_per_step": args.passes, "streams": S, "parallelism": par, "frame_source": wl.frame_source},
-            "verified": verified, "verified_how": verify_note,
-            "roofline": roof, "ceiling": ceiling, "frame_roofline": frame, "model": model,
-            "kernels_ms_per_call": {k: round(v, 5) for k, v in kmean.items()},
-            "latency": lat,
         }
+        if args.full:
+            roof, frame, model = RL.blocks(wl, kmean, elapsed, total_frames / world, ceiling, pmc_run, pmc_why)
+            res.update({"verified": verified, "verified_how": verify_note,
+                        "roofline": roof, "ceiling": ceiling, "frame_roofline": frame, "model": model,
+                        "kernels_ms_per_call": {k: round(v, 5) for k, v in kmean.items()},
+                        "latency": lat})
         if no_gather is not None:
             res["value_no_gather"] = round(no_gather, 2)
             if state["gather_every"] == 1:

@@ -9,7 +9,7 @@ Order of a multi-rank run -- everything that can fail on plumbing happens, and i
   3. the MAIN region = `value`: exactly K steps, every frame stitched, and the egress of a live stream gathered: the slabs of about 30 batches per second and rank
      travel to the sink (configs[3] asks for ONE 30 fps stream: this is ~100x its bytes and still leaves the links idle); `--gather-every k` (k >= 1) makes the main
      region gather every k-th pass instead (k = 1: the conservative every-frame figure IS `value`);
-  4. `value_full_gather`: every frame of every rank delivered to the ONE sink at benchmark rate -- bound by that GPU's inbound xGMI links
+  4. (--full) `value_full_gather`: every frame of every rank delivered to the ONE sink at benchmark rate -- bound by that GPU's inbound xGMI links
      (7 x ~55 GB/s ~ 100 k frames/s of 3.6 MB slabs), not by the compositor; reported beside `value`, never instead of it.
 A watchdog (MS_BENCH_WATCHDOG_S, default 120 s PER STAGE) turns a hanging transport into a line with `value: null`, `failed: true`, the numbers that exist in side
 fields, and a NON-ZERO exit code on every rank (a hang must not look like a successful run).
@@ -184,7 +184,7 @@ def run_regions(args, wl, rank, world, local_rank, share, dev):
     main_every = st["gather_every"]
     wd.partial["value_main_region"] = round(world * F * passes * args.steps / out["elapsed"], 2)
     wd.partial["main_region_gathers_every"] = main_every
-    if main_every != 1:
+    if main_every != 1 and args.full:
         wd.arm("full gather (every frame to one sink)")
         st["gather_every"] = 1
         el_fg, n_fg = wl.timed_region(half, max(1, args.warmup // 2))

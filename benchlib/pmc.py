@@ -34,7 +34,7 @@ def measure(config, frames_per_call, distinct=8, frame_source="numpy", timeout_s
     env = dict(os.environ, TMPDIR="/tmp")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    child = [sys.executable, os.path.join(ROOT, "bench.py"), "--pmc-child", "--config", config, "--frames", str(frames_per_call), "--streams", "1", "--steps", "3", "--warmup", "1",
+    child = [sys.executable, os.path.join(ROOT, "bench.py"), "--pmc-child", "--full", "--config", config, "--frames", str(frames_per_call), "--streams", "1", "--steps", "3", "--warmup", "1",
              "--passes", "1", "--distinct", str(distinct), "--frame-source", "device", "--calib"]      # (frames generated on the device: the counters see addresses, not content, and 48 numpy frames cost the child 5 s)      # (the SAME number of distinct frame sets as the timed region: frames of one launch that share a set hit in L2)
     got = {}
     try:

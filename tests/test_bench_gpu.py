@@ -41,13 +41,13 @@ def fractions(d, path=""):
 
 
 def test_default_line_is_the_drivers_record():
-    """`python bench.py` AS THE DRIVER RUNS IT (N = 1; only K / W shortened): the contract keys, the headline configuration (BASELINE configs[1]) verified against the one-frame
+    """`python bench.py --full` (N = 1; only K / W shortened): the contract keys, the headline configuration (BASELINE configs[1]) verified against the one-frame
     path and the CPU oracle, a `roofline` block that is physical only (PMC bytes -- collected by this very run -- / measured launch time / 8 TB/s; nothing named frac* above 1; the
     contract-byte model under `model`, as ratios), `cpu_baseline`, and `other_configs`: BASELINE configs[2] (cfg3), configs[4]'s geometry (cfg5, with its two one-GPU shardings)
     and the reference's shipped rig, each measured, verified and bit-identical to the oracle."""
     import time
     t0 = time.time()
-    p = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1"], cwd=ROOT, env=dict(os.environ, MS_BENCH_CPU_BUDGET_S="3"), capture_output=True, text=True, timeout=900)
+    p = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--full"], cwd=ROOT, env=dict(os.environ, MS_BENCH_CPU_BUDGET_S="3"), capture_output=True, text=True, timeout=900)
     wall = time.time() - t0
     assert p.returncode == 0, p.stderr[-2000:]
     assert len([l for l in p.stdout.splitlines() if l.startswith("{")]) == 1, p.stdout[-2000:]
@@ -106,13 +106,37 @@ def test_default_line_is_the_drivers_record():
     sh = oc["shipped"]      # the reference's own configuration (cylindrical, COMPOSE_MEGAPIX 1.4 with the per-frame cuda::resize inside the region, num_bands by the app's rule, CPW 10 x 10)
     assert "cylindrical" in sh["workload"] and "resized per frame to 1578x887" in sh["workload"] and "k_resize_batch" in sh["kernels_ms_per_call"]
     assert "6 bands" in sh["workload"] and "10x10" in sh["workload"]
-    assert wall < 240, "the default bench run took %.0f s" % wall      # (the driver's budget is 1800 s; the verdict asks for <= 120 s of it on a warm box)
+    assert wall < 240, "the --full bench run took %.0f s" % wall      # (the driver's budget is 1800 s; the verdict asks for <= 120 s of it on a warm box)
+
+
+SIDE_KEYS = R05_TOP_KEYS - set(KEYS) - {"ms_per_frame"} | {"roofline", "model", "other_configs", "value_nothing_cached", "gathered_frames_checked"}
+
+
+def test_plain_line_is_the_headline_alone():
+    """`python bench.py --gpus 1 --steps K --warmup W` without --full: set up, warm up, time the K steps, print the one line -- the contract keys with the meaning they have
+    in a --full run (`ms_per_step` = the timed region / K, `value` = the frames of those K steps / the same time), and nothing that takes a run of its own.  The whole process,
+    start to exit, spends at most 30 s outside its K + W steps."""
+    import time
+    t0 = time.time()
+    p = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    wall = time.time() - t0
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert len([l for l in p.stdout.splitlines() if l.startswith("{")]) == 1, p.stdout[-2000:]
+    d = last_json(p.stdout)
+    for k in set(KEYS) - {"roofline"}:
+        assert k in d, k
+    assert not (SIDE_KEYS & set(d)), SIDE_KEYS & set(d)
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 1000 and d["higher_is_better"] is True and d["unit"] == "frames/s"
+    assert d["config"]["frames_per_step"] == 1920 and d["config"]["distinct_frame_sets"] == 8 and d["config"]["streams"] == 3
+    assert abs(d["ms_per_step"] - 1e3 * d["config"]["frames_per_step"] / d["value"]) < 1e-3 * d["ms_per_step"]
+    outside = wall - (d["steps"] + d["warmup"]) * d["ms_per_step"] / 1e3
+    assert outside < 30, "a plain run spent %.1f s outside its steps" % outside
 
 
 def test_committed_traffic_summary_is_the_fallback():
     """--no-pmc: roofline.traffic comes from profiles/traffic_cfg2.json, says so in `traffic_source` and `traffic_measured_in_this_run`, and `traffic_stale` compares the hash of
     csrc/ the summary recorded with the sources that ran."""
-    p = subprocess.run([sys.executable, "bench.py", "--frame-source", "device", "--steps", "2", "--warmup", "1", "--passes", "4", "--no-pmc", "--no-others", "--no-cpu-baseline", "--no-live", "--no-pcie", "--no-distinct"],
+    p = subprocess.run([sys.executable, "bench.py", "--frame-source", "device", "--steps", "2", "--warmup", "1", "--passes", "4", "--full", "--no-pmc", "--no-others", "--no-cpu-baseline", "--no-live", "--no-pcie", "--no-distinct"],
                        cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     r = last_json(p.stdout)["roofline"]
@@ -126,7 +150,7 @@ FAKE_RCCL = os.path.join(ROOT, "tests", "_fake_rccl", "libfake_rccl.so")
 def test_two_ranks_sharing_the_gpu_run_the_multi_rank_path():
     env = dict(os.environ, MS_BENCH_SHARE_GPU="1")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29533",
-                        "bench.py", "--frame-source", "device", "--gpus", "2", "--steps", "2", "--warmup", "1", "--passes", "2", "--gather-every", "1", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+                        "bench.py", "--frame-source", "device", "--gpus", "2", "--steps", "2", "--warmup", "1", "--passes", "2", "--gather-every", "1", "--full", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
     d = last_json(p.stdout)
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["value"] > 0
@@ -145,7 +169,7 @@ def test_plain_invocation_spawns_ranks():
     gathered), the compute-only and the every-frame-to-one-sink rates beside it."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["MS_BENCH_SHARE_GPU"] = "1"
-    p = subprocess.run([sys.executable, "bench.py", "--frame-source", "device", "--gpus", "2", "--steps", "4", "--warmup", "1", "--passes", "4", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+    p = subprocess.run([sys.executable, "bench.py", "--frame-source", "device", "--gpus", "2", "--steps", "4", "--warmup", "1", "--passes", "4", "--full", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
     assert len([l for l in p.stdout.splitlines() if l.startswith("{")]) == 1, p.stdout[-2000:]
     d = last_json(p.stdout)
@@ -170,7 +194,7 @@ def test_scale_shaped_dry_run_and_what_is_printed_before_the_first_timed_region(
     p1 = subprocess.run([sys.executable, "bench.py", "--frame-source", "device", "--gpus", "1", "--no-others", "--no-pmc", "--no-verify"] + common, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert p1.returncode == 0, p1.stderr[-2000:]
     v1 = last_json(p1.stdout)["value"]
-    p2 = subprocess.run([sys.executable, "bench.py", "--frame-source", "device", "--gpus", "2"] + common, cwd=ROOT, env=_fake_env(MS_BENCH_CHECK_GATHERED="1"), capture_output=True, text=True, timeout=900)
+    p2 = subprocess.run([sys.executable, "bench.py", "--frame-source", "device", "--gpus", "2", "--full"] + common, cwd=ROOT, env=_fake_env(MS_BENCH_CHECK_GATHERED="1"), capture_output=True, text=True, timeout=900)
     assert p2.returncode == 0, (p2.stdout + p2.stderr)[-3000:]
     d = last_json(p2.stdout)
     assert 0.85 < d["value_no_gather"] / v1 < 1.15, (d["value_no_gather"], v1)

@@ -63,3 +63,23 @@ def test_command_line_decides_which_runs_carry_the_side_regions():
     assert n["no_others"] is True and n["no_pmc"] is True
     prof = parse([], env=dict(os.environ, LD_PRELOAD="/opt/rocm/lib/librocprofiler-sdk-tool.so.DOES_NOT_EXIST"))      # under a profiler: no profiler inside
     assert prof["no_pmc"] is True and prof["no_others"] is True
+
+
+def test_a_plain_run_is_the_headline_alone():
+    """without --full every side part is off, whatever the --no-* switches say; with --full the command line decides as it always did"""
+    side = ("no_others", "no_pmc", "no_live", "no_pcie", "no_verify", "no_cpu_baseline", "no_distinct")
+    code = ("import sys; sys.argv = ['bench.py'] + %r; import bench; a = bench.headline_only(bench.parse_args()); "
+            "print(__import__('json').dumps({k: getattr(a, k) for k in " + repr(side + ("full", "passes", "steps", "warmup", "gpus")) + "}))")
+
+    def run(argv):
+        p = subprocess.run([sys.executable, "-c", code % (argv,)], cwd=ROOT, capture_output=True, text=True, timeout=300)
+        assert p.returncode == 0, p.stderr[-1500:]
+        return json.loads(p.stdout.strip().splitlines()[-1])
+    common = ["--gpus", "1", "--steps", "20", "--warmup", "5"]
+    plain = dict({k: True for k in side}, full=False, passes=20, steps=20, warmup=5, gpus=1)
+    assert run(common) == plain
+    assert run(common + ["--no-live"]) == plain
+    full = run(common + ["--full"])
+    assert full == dict({k: False for k in side}, full=True, passes=20, steps=20, warmup=5, gpus=1)
+    assert run(common + ["--full", "--no-live", "--no-pmc"]) == dict(full, no_live=True, no_pmc=True)
+    assert run(["--full", "--gpus", "8"])["no_others"] is True

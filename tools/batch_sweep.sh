@@ -2,8 +2,9 @@
 # Run ON THE GPU BOX: frames per ms_stitch call against frames/s, alternating on one box (round 6: the per-call limit went from 32 to 64 frames).
 #   gpurun -- 'bash tools/batch_sweep.sh > gpurun_out/batch_sweep.txt'
 ROUNDS=${ROUNDS:-2}
+ERR=${ERR:-batch_sweep.err}      # the runs' stderr, appended
 run() {   # config streams frames
-  python bench.py --config $1 --streams $2 --frames $3 --steps ${STEPS:-10} --warmup 3 --passes ${4:-10} --no-cpu-baseline --no-live --no-pcie --no-distinct --no-others --no-pmc 2>>gpurun_out/batch_sweep.err | tail -1 |
+  python bench.py --config $1 --streams $2 --frames $3 --steps ${STEPS:-10} --warmup 3 --passes ${4:-10} --full --no-cpu-baseline --no-live --no-pcie --no-distinct --no-others --no-pmc 2>>"$ERR" | tail -1 |
     python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$1 $2x$(( $3 / $2 )):', d['value'], d['verified'], {k: round(v*1e3,1) for k,v in d['kernels_ms_per_call'].items()})"
 }
 for r in $(seq $ROUNDS); do

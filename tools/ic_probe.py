@@ -13,7 +13,7 @@ for r in runs:
     cfg, fl = r.split(":")
     for F in [int(x) for x in fl.split(",")]:
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", cfg, "--streams", "1", "--frames", str(F), "--steps", "5", "--warmup", "2", "--passes", str(max(20, 640 // F)),
-               "--no-live", "--no-pcie", "--no-cpu-baseline", "--no-distinct", "--recalib-every", "0"]
+               "--full", "--no-live", "--no-pcie", "--no-cpu-baseline", "--no-distinct", "--recalib-every", "0"]
         p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
         line = [l for l in p.stdout.splitlines() if l.startswith("{")]
         if not line:

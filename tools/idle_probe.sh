@@ -4,7 +4,7 @@
 set -uo pipefail
 cd "${GRAFT_REPO_ROOT:-.}"
 D=/tmp/idle_tl; rm -rf $D; export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $D -- python bench.py ${BENCH_ARGS:-} --steps 4 --warmup 2 --no-cpu-baseline --no-pcie --no-verify --no-live --no-distinct > /tmp/idle_tl.json 2> /tmp/idle_tl.err
+rocprofv3 --kernel-trace --output-format csv -d $D -- python bench.py ${BENCH_ARGS:-} --steps 4 --warmup 2 --full --no-cpu-baseline --no-pcie --no-verify --no-live --no-distinct > /tmp/idle_tl.json 2> /tmp/idle_tl.err
 python - "$D" <<'PY'
 import csv, glob, sys
 rows = []

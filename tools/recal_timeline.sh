@@ -4,7 +4,7 @@
 set -uo pipefail
 cd "${GRAFT_REPO_ROOT:-.}"
 D=/tmp/recal_tl; rm -rf $D; export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $D -- python bench.py --config ${1:-cfg3} --steps 6 --warmup 2 --no-cpu-baseline --no-pcie --no-verify --no-live --no-distinct > /tmp/recal_tl.json 2> /tmp/recal_tl.err; python -c "import json; d=json.loads(open('/tmp/recal_tl.json').read().strip().splitlines()[-1]); print('bench under rocprofv3:', round(d['value']), 'frames/s')"
+rocprofv3 --kernel-trace --output-format csv -d $D -- python bench.py --config ${1:-cfg3} --steps 6 --warmup 2 --full --no-cpu-baseline --no-pcie --no-verify --no-live --no-distinct > /tmp/recal_tl.json 2> /tmp/recal_tl.err; python -c "import json; d=json.loads(open('/tmp/recal_tl.json').read().strip().splitlines()[-1]); print('bench under rocprofv3:', round(d['value']), 'frames/s')"
 python - "$D" <<'PY'
 import csv, glob, sys
 rows = []

@@ -13,6 +13,6 @@ for t in $TAG ${TAG}_cfg3 ${TAG}_cfg5 ${TAG}_shipped; do python tools/report.py 
 cp profiles/${TAG}_* profiles/traffic_*.json $PO/ 2>/dev/null
 : > $PO/${TAG}_bench_repeats.txt
 for i in $(seq $REPEATS); do
-  python bench.py --no-cpu-baseline --no-pcie 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['value']), (d.get('value_distinct') or {}).get('value'), d['ceiling']['copy_TBps'], d['roofline']['frac'], d['roofline'].get('traffic_stale'), d['frame_roofline']['wall_frac_traffic'], round(d['kernels_ms_per_call']['k_warp']*1e3,1), d['live']['us_per_frame_p50'])" >> $PO/${TAG}_bench_repeats.txt
+  python bench.py --full --no-cpu-baseline --no-pcie 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['value']), (d.get('value_distinct') or {}).get('value'), d['ceiling']['copy_TBps'], d['roofline']['frac'], d['roofline'].get('traffic_stale'), d['frame_roofline']['wall_frac_traffic'], round(d['kernels_ms_per_call']['k_warp']*1e3,1), d['live']['us_per_frame_p50'])" >> $PO/${TAG}_bench_repeats.txt
 done
 cat $PO/${TAG}_bench_repeats.txt

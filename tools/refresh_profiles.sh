@@ -3,7 +3,7 @@
 set -uo pipefail
 TAG=${1:-r01}
 OUT=gpurun_out/refresh; mkdir -p $OUT
-timeout 300 python bench.py > $OUT/${TAG}_bench.json 2> $OUT/bench.err
+timeout 900 python bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/bench.err
 python - "$OUT" "$TAG" <<'PY'
 import json, subprocess, sys
 out, tag = sys.argv[1], sys.argv[2]
@@ -19,7 +19,7 @@ runs = {"cfg2_F1": ["--frames", "1", "--streams", "1", "--steps", "30", "--warmu
 res = {}
 for k, a in runs.items():
     try:
-        p = subprocess.run([sys.executable, "bench.py", "--no-cpu-baseline"] + a, capture_output=True, text=True, timeout=300)
+        p = subprocess.run([sys.executable, "bench.py", "--full", "--no-cpu-baseline"] + a, capture_output=True, text=True, timeout=300)
         res[k] = json.loads(p.stdout.strip().splitlines()[-1])
     except Exception as e:
         res[k] = {"error": str(e)}

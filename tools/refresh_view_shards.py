@@ -8,7 +8,7 @@ runs = {"cfg2_view_shards_2": ["--view-shards", "2"], "cfg5_view_shards_2": ["--
         "cfg2_one_context_16": ["--frames", "16", "--streams", "1"], "cfg5_one_context_4": ["--config", "cfg5", "--frames", "4", "--streams", "1"]}
 res = {}
 for k, a in runs.items():
-    p = subprocess.run([sys.executable, "bench.py", "--no-cpu-baseline", "--no-pcie", "--no-live", "--steps", "60"] + a, capture_output=True, text=True, timeout=300)
+    p = subprocess.run([sys.executable, "bench.py", "--full", "--no-cpu-baseline", "--no-pcie", "--no-live", "--steps", "60"] + a, capture_output=True, text=True, timeout=300)
     res[k] = json.loads(p.stdout.strip().splitlines()[-1])
 json.dump(res, open("gpurun_out/%s_shards.json" % tag, "w"), indent=1)
 print({k: (v["value"], v.get("equals_unsharded")) for k, v in res.items()})
