@@ -504,7 +504,13 @@ MS_API int ms_knn_match_hamming2(const ms_image *query, const ms_image *train, i
  * no blur: the creator's defaults).  gray: DEVICE 8UC1 (ms_bgr_to_gray); mask: DEVICE 8UC1 of the same size or NULL.
  * keypoints_host: max_keypoints x 6 floats (x, y, response, angle in degrees, octave, size), the rows of cuda::ORB's keypoint matrix;
  * descriptors: DEVICE 8UC1 max_keypoints x 32 (row i belongs to keypoint i).  Keypoint order: levels in turn, inside a level by descending Harris
- * response where the level was culled, raster order otherwise (the reference's order is left to atomics and an unstable sort).  Synchronises. */
+ * response where the level was culled, raster order otherwise (the reference's order is left to atomics and an unstable sort).  Synchronises.
+ * Per-level budgets follow orb.cpp:501-512 (a geometric series rounded per level, the last level takes nfeatures minus the others), which gives
+ * some levels 0 at small nfeatures (nfeatures 1: only the last level has a budget) and the last level a negative number at a few (nfeatures 7 at
+ * the defaults: -1), where the reference is undefined.  Here a level whose budget is <= 0 contributes no keypoints and the call succeeds.  The
+ * other levels keep their budgets, so with a negative last budget up to (nlevels - 1) / 2 more than nfeatures keypoints come back (each rounding adds
+ * at most one half): max_keypoints >= nfeatures + nlevels / 2 holds them at any parameters; a smaller buffer that overflows is MS_ERR_INVALID.  The
+ * pyramid ends before the first level narrower or lower than 8 pixels; a level not larger than 2 * edge_threshold in both dimensions has no keypoints. */
 typedef struct ms_orb_params {
     int nfeatures; float scale_factor; int nlevels;      /* ORB::create(2500, 1.2f, 8)  featurefinder.cpp:15 */
     int edge_threshold, first_level, patch_size, fast_threshold;     /* 31, 0, 31, 20 (cuda::ORB::create defaults) */

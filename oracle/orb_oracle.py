@@ -8,7 +8,8 @@ Restates, stage by stage, sources/modules/cudafeatures2d/src/orb.cpp:430-865 (ho
 Where the reference leaves the ORDER of keypoints to atomic counters (fast.cu:294, :333) and an unstable device sort (orb.cu:61-88), this
 oracle fixes it: raster order after FAST, stable descending sort in the culls -- tests compare keypoints as sets.  Transcendentals (atan2f, sincosf of
 the CUDA fast-math build) are taken as correctly rounded floats of the double functions; float expressions are evaluated without contraction.
-Parity unpinned by execution (no CUDA here; opencv_extra's ORB fixtures are absent)."""
+Parity with the reference is unpinned by execution (no CUDA here; opencv_extra's ORB fixtures are absent); every stage function is held to an
+independent statement of its definition (tests/np_ref.py) by tests/test_orb_oracle.py."""
 import math
 import os
 
@@ -59,7 +60,7 @@ def u_max_table(half=15):
 
 
 def has_arc9(mask):
-    """16-bit circular mask (array of ints) contains 9 contiguous set bits: what fast.cu's c_table encodes (tests check it against that table)."""
+    """16-bit circular mask (array of ints) contains 9 contiguous set bits: what fast.cu's c_table encodes (tests/test_orb_oracle.py checks it against that table)."""
     m = mask.astype(np.uint32) & 0xffff
     acc = m.copy()
     for s in range(1, 9):
@@ -107,6 +108,8 @@ def cull(loc, resp, n):
     """orb.cpp:719-733 + thrust::sort_by_key(greater) orb.cu:61-88, made stable."""
     if len(loc) <= n:
         return loc, resp
+    if n <= 0:                                  # (the reference is undefined here; nothing is kept)
+        return loc[:0], resp[:0]
     order = np.argsort(-resp.astype(np.float64), kind="stable")[:n]
     return loc[order], resp[order]
 
@@ -173,6 +176,8 @@ def orb_detect_and_compute(gray, mask=None, nfeatures=2500, scale_factor=1.2, nl
     for level in range(nlevels):
         scale = F(1.0) / get_scale(scale_factor, first_level, level)
         sz = (cv_round(F(gray.shape[1]) * scale), cv_round(F(gray.shape[0]) * scale))
+        if sz[0] < 8 or sz[1] < 8:              # as ms_orb_detect_and_compute: the pyramid ends before a level narrower than 8 pixels (no resize to an empty size)
+            break
         if level == first_level:
             img = gray.copy(); m = None if mask is None else mask.copy()
         else:
@@ -182,6 +187,9 @@ def orb_detect_and_compute(gray, mask=None, nfeatures=2500, scale_factor=1.2, nl
                 m = resize(mask_prev, sz)
                 m = np.where(m > 254, m, 0).astype(np.uint8)              # cuda::threshold(254, THRESH_TOZERO)  orb.cpp:693
         img_prev, mask_prev = img, m
+        n = nper[level]
+        if n <= 0:                              # a budget of 0 or less (n_features_per_level's rounding): the level contributes nothing -- the project's definition, ms_stitch.h
+            continue
         border = np.zeros(img.shape, np.uint8)
         if sz[0] > 2 * edge and sz[1] > 2 * edge:
             border[edge:sz[1] - edge, edge:sz[0] - edge] = 255
@@ -189,7 +197,6 @@ def orb_detect_and_compute(gray, mask=None, nfeatures=2500, scale_factor=1.2, nl
         loc, resp = fast_detect(img, lm, fast_threshold, int(0.05 * img.shape[0] * img.shape[1]))
         if len(loc) == 0:
             continue
-        n = nper[level]
         loc, resp = cull(loc, resp, 2 * n)
         resp = harris_responses(img, loc)
         loc, resp = cull(loc, resp, n)

@@ -502,3 +502,123 @@ def warp_maps_f64(proj, tl_u, tl_v, rows, cols, k_rinv, scale, t=(0, 0, 0)):
     if proj != 0:
         x, y = np.where(z > 0, x, -1.0), np.where(z > 0, y, -1.0)
     return x, y, z
+
+
+# ---- ORB front end (cudafeatures2d: fast.cu, orb.cu, orb.cpp): definitions, not the algorithms oracle/orb_oracle.py and csrc/features.hip share ------------
+def fast_ring():
+    """The 16 pixels of the radius-3 Bresenham circle as (dy, dx), in circular order (by angle): FAST's contiguity is cyclic, so neither the
+    starting point nor the direction matters."""
+    pts = [(dy, dx) for dy in range(-3, 4) for dx in range(-3, 4) if max(abs(dy), abs(dx)) == 3 and min(abs(dy), abs(dx)) <= 1 or (abs(dy), abs(dx)) == (2, 2)]
+    assert len(pts) == 16
+    return sorted(pts, key=lambda p: np.arctan2(p[0], p[1]))
+
+
+def has_arc_by_definition(masks, length=9):
+    """masks: ints, bit k = circle pixel k.  True where some rotation of the 16-bit word has `length` consecutive set bits."""
+    m = np.asarray(masks, np.int64)
+    bits = ((m[..., None] >> np.arange(16)) & 1).astype(bool)
+    out = np.zeros(m.shape, bool)
+    for start in range(16):
+        out |= bits[..., (start + np.arange(length)) % 16].all(axis=-1)
+    return out
+
+
+def fast_is_corner(img, t):
+    """(h, w) bool: 9 contiguous circle pixels all > v + t or all < v - t; False within 3 px of the border."""
+    h, w = img.shape
+    im = img.astype(np.int64)
+    v = im[3:h - 3, 3:w - 3]
+    ring = np.stack([im[3 + dy:h - 3 + dy, 3 + dx:w - 3 + dx] for dy, dx in fast_ring()], axis=-1)
+    wts = 1 << np.arange(16)
+    out = np.zeros((h, w), bool)
+    out[3:h - 3, 3:w - 3] = has_arc_by_definition(((ring > v[..., None] + t) * wts).sum(-1)) | has_arc_by_definition(((ring < v[..., None] - t) * wts).sum(-1))
+    return out
+
+
+def fast_score_brute_force(img, mask=None, threshold=20):
+    """What cornerScore's binary search (fast.cu:195-218) finds: the largest t in [threshold, 255] at which the pixel is still a corner; 0 where it
+    is no corner at `threshold` or the mask is 0.  Every t is tried."""
+    alive = fast_is_corner(img, threshold)
+    if mask is not None:
+        alive &= mask != 0
+    score = np.where(alive, threshold, 0).astype(np.int32)
+    for t in range(threshold + 1, 256):
+        if not alive.any():
+            break
+        alive &= fast_is_corner(img, t)
+        score[alive] = t
+    return score
+
+
+def nms_strict(score):
+    """(n, 2) x, y in raster order: non-zero scores strictly greater than all 8 neighbours (outside the map counts as 0)."""
+    s = np.pad(score.astype(np.int64), 1)
+    h, w = score.shape
+    keep = score != 0
+    for dy in (0, 1, 2):
+        for dx in (0, 1, 2):
+            if (dy, dx) != (1, 1):
+                keep &= s[1:-1, 1:-1] > s[dy:dy + h, dx:dx + w]
+    ys, xs = np.nonzero(keep)             # row-major: raster order
+    return np.stack([xs, ys], axis=1)
+
+
+def fast_keypoints_with_overflow(score, max_points):
+    """The detector's buffer holds max_points raw corners; here the first ones in raster order (the reference leaves which to an atomic counter).
+    Suppression then reads the whole score map, also at corners that did not fit (fast.cu:346-371 reads score(), not the buffer)."""
+    raw = np.argwhere(score != 0)[:max_points]
+    fits = np.zeros(score.shape, bool)
+    fits[raw[:, 0], raw[:, 1]] = True
+    win = nms_strict(score)
+    return win[fits[win[:, 1], win[:, 0]]]
+
+
+U_MAX_15 = [15, 15, 15, 15, 14, 14, 14, 13, 13, 12, 11, 10, 9, 8, 6, 3]      # the circular patch of radius 15, orb.cpp:514-529 evaluated by hand
+
+
+def harris_sums(img, x, y, block=7):
+    """Exact integer sums of Ix^2, Iy^2, Ix Iy over the block x block window centred on (x, y); Ix, Iy = the 3 x 3 Sobel derivatives."""
+    im = img.astype(np.int64)
+    kx = np.array([[-1, 0, 1], [-2, 0, 2], [-1, 0, 1]], np.int64)
+    a = b = c = 0
+    r = block // 2
+    for yy in range(y - r, y + r + 1):
+        for xx in range(x - r, x + r + 1):
+            win = im[yy - 1:yy + 2, xx - 1:xx + 2]
+            ix, iy = int((win * kx).sum()), int((win * kx.T).sum())
+            a += ix * ix; b += iy * iy; c += ix * iy
+    return a, b, c
+
+
+def ic_moments(img, x, y, u_max=U_MAX_15):
+    """(m01, m10) over the pixel set {(u, v): |u| <= u_max[|v|]}."""
+    half = len(u_max) - 1
+    m01 = m10 = 0
+    for v in range(-half, half + 1):
+        for u in range(-u_max[abs(v)], u_max[abs(v)] + 1):
+            p = int(img[y + v, x + u])
+            m01 += v * p; m10 += u * p
+    return m01, m10
+
+
+def orb_descriptor_f64(img, x, y, angle_deg, pattern, margin=1e-3):
+    """(bits (256,) bool, sure (256,) bool): bit i = I(first point of pair i) < I(second), the pattern rotated by the angle in float64 and rounded to
+    the nearest pixel; sure = both points of the pair further than `margin` from a rounding boundary in both coordinates."""
+    a = np.deg2rad(np.float64(angle_deg))
+    px, py = pattern[:, 0].astype(np.float64), pattern[:, 1].astype(np.float64)
+    fx, fy = px * np.cos(a) - py * np.sin(a), px * np.sin(a) + py * np.cos(a)
+    near = (np.abs(np.abs(fx - np.floor(fx)) - 0.5) <= margin) | (np.abs(np.abs(fy - np.floor(fy)) - 0.5) <= margin)
+    val = img[y + np.rint(fy).astype(np.int64), x + np.rint(fx).astype(np.int64)].astype(np.int64)
+    return val[0::2] < val[1::2], ~(near[0::2] | near[1::2])
+
+
+def orb_level_size(cols, rows, scale_factor, level):
+    """Size(cvRound(cols * scale), cvRound(rows * scale)), scale = 1.0f / (float)pow(scaleFactor, level)   orb.cpp:675-677"""
+    scale = np.float32(1.0) / np.float32(float(np.float32(scale_factor)) ** level)
+    return int(np.rint(np.float32(cols) * scale)), int(np.rint(np.float32(rows) * scale))
+
+
+def feature_mask(bgr, a_x0, a_w, b_x0, b_w):
+    x = np.arange(bgr.shape[1])
+    band = ((x >= a_x0) & (x < a_x0 + a_w)) | ((x >= b_x0) & (x < b_x0 + b_w))
+    return np.where(band[None, :] & bgr.any(axis=2), 255, 0).astype(np.uint8)

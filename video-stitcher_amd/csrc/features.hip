@@ -46,7 +46,8 @@ __global__ void __launch_bounds__(256) k_tozero254(uint8_t *m, size_t step, int 
 
 // calcKeypoints<true> (fast.cu:264-307): score map, 0 = no corner.  The mask of the level = user mask AND the inner rectangle left by edgeThreshold
 // (orb.cpp:707-712), applied analytically.  A pixel is a corner when 9 contiguous circle pixels are all darker than v - th or all brighter than v + th
-// (the c_table lookup of fast.cu:201-206 encodes exactly "the 16-bit mask holds 9 contiguous ones", checked against that table in tests);
+// (the c_table lookup of fast.cu:201-206 encodes exactly "the 16-bit mask holds 9 contiguous ones": tests/test_orb_oracle.py::test_arc9_equals_the_references_table
+// holds the rule to that table, tests/test_features_edges_gpu.py::test_every_16_bit_arc_mask holds this kernel to the rule over all 65 536 masks);
 // cornerScore's binary search (fast.cu:208-222) finds the largest threshold that still passes = (best arc's smallest difference) - 1.
 __global__ void __launch_bounds__(256) k_fast_score(const uint8_t *__restrict__ img, size_t step, int rows, int cols, const uint8_t *__restrict__ mask, size_t mstep,
                                                     int edge, int th, uint8_t *__restrict__ score, size_t sstep)
@@ -469,7 +470,7 @@ int ms_orb_detect_and_compute(const ms_image *gray, const ms_image *mask, const 
         float nd = (float)((double)(prm->nfeatures * (1.0f - factor)) / (1.0 - std::pow((double)factor, prm->nlevels)));
         int sum = 0;
         for (int l = 0; l < prm->nlevels - 1; ++l) { nper[l] = (int)std::nearbyint(nd); sum += nper[l]; nd *= factor; }
-        nper[prm->nlevels - 1] = prm->nfeatures - sum;
+        nper[prm->nlevels - 1] = prm->nfeatures - sum;        // may be 0 or negative (the rounding of the other levels): such a level is skipped below
     }
     auto level_scale = [&](int l) { return (float)std::pow((double)prm->scale_factor, l - prm->first_level); };     // getScale: pow(float, int) -> double -> float
     struct Dev { void *p = nullptr; ~Dev() { if (p) (void)hipFree(p); } int alloc(size_t n) { if (p) (void)hipFree(p); p = nullptr; MS_HIP(hipMalloc(&p, n ? n : 16)); return MS_OK; } };
@@ -501,6 +502,9 @@ int ms_orb_detect_and_compute(const ms_image *gray, const ms_image *mask, const 
             }
         }
         prev_img = cur; prev_msk = curm;
+        // A budget <= 0 (nfeatures 7 at the defaults gives the last level -1; the reference is undefined there: its cull() releases the buffer and keeps
+        // the count): the level contributes no keypoints, and nothing but its pyramid image, which the next level is resized from, is computed.
+        if (nper[level] <= 0) continue;
         // FAST 9-16, threshold, score, non-max suppression, raster-ordered compaction
         MS_HIP(hipMemsetAsync(counters.p, 0, 16, st));
         k_fast_score<<<dim3(div_up(w, 64), div_up(h, 4)), dim3(64, 4), 0, st>>>((const uint8_t *)cur.data, cur.step, h, w, mask ? (const uint8_t *)curm.data : nullptr, curm.step,
@@ -542,6 +546,7 @@ int ms_orb_detect_and_compute(const ms_image *gray, const ms_image *mask, const 
         const int n = nper[level];
         auto cull = [&](int keep) -> int {                                  // orb.cpp:719-733; stable instead of thrust's unstable device sort
             if (count <= keep) return MS_OK;
+            if (keep <= 0) { count = 0; return MS_OK; }
             if (hloc.empty()) {
                 hloc.resize(count); hresp.resize(count);
                 MS_HIP(hipMemcpyAsync(hloc.data(), loc.p, sizeof(short2) * (size_t)count, hipMemcpyDeviceToHost, st));
@@ -570,6 +575,7 @@ int ms_orb_detect_and_compute(const ms_image *gray, const ms_image *mask, const 
             MS_HIP(hipStreamSynchronize(st));
         }
         if (int e = cull(2 * n)) return e;                                                                                  // orb.cpp:772
+        if (count == 0) continue;                                           // (never a launch with an empty grid)
         k_harris<<<div_up(count, 64), 64, 0, st>>>((const uint8_t *)cur.data, cur.step, (const short2 *)loc.p, (float *)resp.p, count, 7, 0.04f);   // :774
         MS_LAUNCH_CHECK();
         hloc.clear(); hresp.clear();

@@ -477,7 +477,7 @@ def orb_detect_and_compute(gray, mask=None, nfeatures=2500, scale_factor=1.2, nl
     prm.nfeatures, prm.scale_factor, prm.nlevels, prm.fast_threshold = nfeatures, scale_factor, nlevels, fast_threshold
     if edge_threshold is not None:
         prm.edge_threshold = edge_threshold
-    cap = nfeatures
+    cap = nfeatures + nlevels // 2      # the rounded per-level budgets can add up to (nlevels - 1) / 2 more than nfeatures (ms_stitch.h)
     kp = np.zeros((cap, 6), np.float32)
     desc = torch.zeros((cap, 32), dtype=torch.uint8, device=gray.device)
     n = C.c_int(0)

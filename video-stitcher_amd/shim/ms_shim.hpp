@@ -279,17 +279,18 @@ template <class Mat> void findFeatures(const std::vector<Mat> &images, const std
     check(ms_orb_default_params(&prm));
     prm.nfeatures = nfeatures; prm.scale_factor = scale_factor; prm.nlevels = nlevels;
     Mat gray;
-    std::vector<float> kp((size_t)6 * nfeatures);
+    const int cap = nfeatures + nlevels / 2;        // the rounded per-level budgets can add up to (nlevels - 1) / 2 more than nfeatures (ms_stitch.h)
+    std::vector<float> kp((size_t)6 * cap);
     for (size_t i = 0; i < images.size(); ++i) {
         gray.create(images[i].rows, images[i].cols, MS_8UC1);
         ms_image im = wrap(images[i]), g = wrap(gray);
         check(ms_bgr_to_gray(&im, &g, s));                                             // cuda::cvtColor(gpu_img, gpu_img, CV_BGR2GRAY)
-        features[i].descriptors.create(nfeatures, 32, MS_8UC1);
+        features[i].descriptors.create(cap, 32, MS_8UC1);
         ms_image d = wrap(features[i].descriptors), mk{};
         const bool have_mask = i < masks.size() && masks[i].data;
         if (have_mask) mk = wrap(masks[i]);
         int n = 0;
-        check(ms_orb_detect_and_compute(&g, have_mask ? &mk : nullptr, &prm, kp.data(), nfeatures, &d, &n, s));
+        check(ms_orb_detect_and_compute(&g, have_mask ? &mk : nullptr, &prm, kp.data(), cap, &d, &n, s));
         features[i].img_idx = (int)i;
         features[i].img_size = Size{images[i].cols, images[i].rows};
         features[i].keypoints.resize(n);
