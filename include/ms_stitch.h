@@ -351,6 +351,43 @@ MS_API int ms_update_mask(ms_ctx *ctx, int view, ms_stream stream);
 MS_API int ms_set_active_views(ms_ctx *ctx, unsigned mask, ms_stream stream);
 MS_API int ms_get_active_views(const ms_ctx *ctx, unsigned *mask);
 
+/* Exposure tracking.  The reference estimates the gains once, at calibration, from seam-scale images (GainCompensator::feed,
+ * stitching/src/exposure_compensate.cpp:71-145, called from APP/calibration.cpp:131-132) and keeps them; its once-a-second recalibration touches the
+ * meshes only.  Cameras with auto-exposure drift apart within seconds.  ms_track_gains re-estimates the gains from one set of LIVE source frames at compose
+ * scale, on the caller's stream: overlap statistics -> normal equations -> solve -> smoothing -> the device view tables, with no host wait, so that the next
+ * ms_stitch* on that stream uses the new gains.
+ *   views: num_views DEVICE 8UC3 images of the context's source size, ONE frame (of a batched call normally the last time step).  Views outside the active
+ *     set (ms_set_active_views) are never read.  NV12 sources (ms_stitch_nv12 callers) are out of scope: convert one frame set, or track on BGR copies.
+ *   The statistic.  T = dst_roi_final (ms_get_pano_geom), roi_v = the warped ROI of view v, (mx_v, my_v) the maps of ms_get_maps.  A pano pixel (u, v) in
+ *     warper coordinates is a sample iff (u - T.x) % stride == 0 && (v - T.y) % stride == 0.  View a sees a sample iff it lies in roi_a and the truncated map
+ *     coordinate hits the source -- the warp mask BEFORE seam cutting, as GainCompensator gets it (calibration.cpp:118-132); the blend masks (ms_get_mask) are
+ *     not used.  Its value there is q_a = llrint(sqrt((double)(b*b + g*g + r*r)) * 2^20) of the source pixel at the truncated coordinate: nearest sampling, and
+ *     the CPW mesh is ignored (exposure does not depend on a few pixels of displacement).  For every ordered pair of ACTIVE views whose ROIs intersect as plain
+ *     rectangles (i == j included, exposure_compensate.cpp:90; no wrap across +-pi, as in the reference): cnt = #samples both see, N[i][j] = N[j][i] =
+ *     max(1, cnt), S[i][j] = sum of q_i, S[j][i] = sum of q_j over them; every other entry 0.  I[i][j] = S[i][j] / 2^20 / N[i][j].  The sums are integers:
+ *     independent of the order of the reduction, hence bit-reproducible, and within 2^-21 per pixel of the reference's double sum (:103-117).
+ *   Solve / smooth / publish.  The normal equations and cv::solve of exposure_compensate.cpp:123-139 (alpha 0.01, beta 100) over the active views; an inactive
+ *     view keeps its gain.  g <- g + smoothing * (g_estimated - g) in double; the state starts from ms_set_gain's values, and ms_set_gain after tracking
+ *     overrides it for its view.  A singular system changes nothing and is counted.  The float gain is written into every view table a later stitch may read
+ *     (the full set, its enqueue-only-mask-update copy, every cached subset); ms_init_blender, ms_update_mask, ms_set_active_views and ms_save_tables all
+ *     see the tracked values: no path brings an older gain back.
+ *   ms_track_gains is enqueue-only (no allocation, no copy to the host, no wait for the GPU) and callable while another thread stitches (contract of
+ *     ms_set_active_views).  ms_gain_stats is the statistics alone, blocking, for tests and diagnostics: N and S (num_views x num_views long long each) to the
+ *     HOST.  ms_get_gains waits for `stream` and returns the gains the next stitch on it will use (num_views doubles) and the solve counters (may be NULL).
+ *   ms_gain_track_default_params: stride 4, smoothing 0.25 -- starting values, not tuned on a rig.
+ * MS_ERR_INVALID: null context / params / views, struct_size mismatch, stride < 1, smoothing outside (0, 1], an image of the wrong size or type.
+ * MS_ERR_STATE: before ms_init_blender.  MS_ERR_UNSUPPORTED: view-sharded and column-sharded contexts (a shard does not hold every overlap: track on one
+ * unsharded context and hand the gains out with ms_set_gain) and FeatherBlender contexts (ms_init_feather). */
+typedef struct ms_gain_track_params {
+    unsigned struct_size;   /* sizeof of the caller's struct; mismatch = MS_ERR_INVALID (as ms_config)                   */
+    int stride;             /* >= 1: every stride-th pano column and row is sampled                                      */
+    double smoothing;       /* lambda in (0, 1]: g <- g + lambda * (g_estimated - g); 1 = take the estimate              */
+} ms_gain_track_params;
+MS_API int ms_gain_track_default_params(ms_gain_track_params *prm);
+MS_API int ms_gain_stats(ms_ctx *ctx, const ms_image *views, int stride, long long *N_host, long long *S_host, ms_stream stream);
+MS_API int ms_track_gains(ms_ctx *ctx, const ms_image *views, const ms_gain_track_params *prm, ms_stream stream);
+MS_API int ms_get_gains(ms_ctx *ctx, double *gains_host, int *solves_ok, int *solves_singular, ms_stream stream);
+
 /* MeshWarper::convertMeshesToMap for one view (APP/meshwarper.cpp:823-886): N x M vertex mesh (HOST fp32,
  * forward positions in view-ROI pixels) -> dense backward maps x_mesh/y_mesh, double-buffered; takes
  * effect at the next ms_stitch.  Thread-safe against ms_stitch (recalibration thread, APP/timed.cpp:414-463). */

@@ -14,6 +14,7 @@
 #include <vector>
 #include "common.hpp"
 #include "launchers.hpp"
+#include "descs.hpp"
 
 namespace ms {
 namespace {
@@ -97,9 +98,8 @@ __global__ void __launch_bounds__(64) k_gain_pairs(GainViews V, int *__restrict_
 }
 // the normal equations (:123-139) and cv::solve(A, b, gains) with DECOMP_LU semantics (closed forms up to 3 x 3: lapack.cpp:1107-1237; LU with partial
 // pivoting otherwise: matrix_decomp.cpp:52-112) in one thread; ok = 0 if the system is singular
-__global__ void k_gain_solve(int n, const int *__restrict__ Nm, const double *__restrict__ Im, double *__restrict__ gains, int *__restrict__ ok)
+__device__ void gain_solve(int n, const int *__restrict__ Nm, const double *__restrict__ Im, double *__restrict__ gains, int *__restrict__ ok)
 {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
     double A[MS_MAX_VIEWS * MS_MAX_VIEWS], b[MS_MAX_VIEWS];
     const double alpha = 0.01, beta = 100;
     for (int i = 0; i < n; ++i) { b[i] = 0; for (int j = 0; j < n; ++j) A[i * n + j] = 0; }
@@ -151,6 +151,127 @@ __global__ void k_gain_solve(int n, const int *__restrict__ Nm, const double *__
     }
 #undef AT
     for (int i = 0; i < n; ++i) gains[i] = *ok ? b[i] : 1.0;
+}
+__global__ void k_gain_solve(int n, const int *__restrict__ Nm, const double *__restrict__ Im, double *__restrict__ gains, int *__restrict__ ok)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    gain_solve(n, Nm, Im, gains, ok);
+}
+
+// ---- exposure tracking (ms_track_gains): GainCompensator::feed's statistics at compose scale from live frames, on the caller's stream ---------
+// A lane owns one sample of the pano lattice.  It finds the views that see the sample (k_valid_mask's rule on the static maps), keeps their
+// q = llrint(sqrt(b^2 + g^2 + r^2) * 2^20) (< 2^29, so 32 bits) in its own LDS column, and the wave then walks the pairs some lane of it saw:
+// ballot + popcount for the count, a 64-bit butterfly for the sums, one LDS atomic per pair and wave, one global atomic per non-zero cell and
+// workgroup.  Everything is an integer, so the result does not depend on the order in which workgroups arrive.
+//   acc[0 .. n*n)       cnt of the pair (i, j), stored at i <= j only
+//   acc[n*n .. 2 n*n)   S[i][j] = sum of q_i over the samples i and j both see
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
+{
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+__device__ __forceinline__ bool rects_meet(const ms_rect &a, const ms_rect &b)
+{
+    return max(a.x, b.x) < min(a.x + a.width, b.x + b.width) && max(a.y, b.y) < min(a.y + a.height, b.y + b.height);
+}
+__global__ void __launch_bounds__(256) k_gain_stats(GainTrackViews V, unsigned long long *__restrict__ acc)
+{
+    __shared__ unsigned s_q[MS_MAX_VIEWS][256];
+    __shared__ unsigned long long s_acc[2 * MS_MAX_VIEWS * MS_MAX_VIEWS];
+    const int n = V.n, nn = n * n, tid = threadIdx.y * 64 + threadIdx.x, lane = threadIdx.x;
+    for (int i = tid; i < 2 * nn; i += 256) s_acc[i] = 0ull;
+    const int sx = blockIdx.x * 64 + threadIdx.x, sy = blockIdx.y * 4 + threadIdx.y;
+    const bool inside = sx < V.nsx && sy < V.nsy;
+    const int u = V.T.x + sx * V.stride, v = V.T.y + sy * V.stride;
+    unsigned seen = 0u, wave_seen = 0u;
+    for (int a = 0; a < n; ++a) {
+        if (!((V.active >> a) & 1u)) continue;
+        const ms_rect r = V.roi[a];
+        const int lx = u - r.x, ly = v - r.y;
+        bool s = false;
+        unsigned q = 0u;
+        if (inside && lx >= 0 && ly >= 0 && lx < r.width && ly < r.height) {
+            const size_t at = (size_t)ly * V.pitch[a] + lx;
+            const int xx = f2i_rz(V.xmap[a][at]), yy = f2i_rz(V.xmap[a][at + (size_t)r.height * V.pitch[a]]);      // (ymap follows xmap)
+            if (xx >= 0 && xx < V.src_w && yy >= 0 && yy < V.src_h) {
+                const uint8_t *p = V.src[a] + (size_t)yy * V.step[a] + 3 * xx;
+                const int b0 = p[0], b1 = p[1], b2 = p[2];
+                q = (unsigned)llrint(sqrt(static_cast<double>(b0 * b0 + b1 * b1 + b2 * b2)) * 1048576.0);
+                s = true;
+            }
+        }
+        s_q[a][tid] = q;                                      // (read back by this lane only)
+        if (s) seen |= 1u << a;
+        if (__ballot(s)) wave_seen |= 1u << a;                // (wave-uniform)
+    }
+    __syncthreads();
+    for (unsigned mi = wave_seen; mi; mi &= mi - 1u) {
+        const int i = __ffs(mi) - 1;
+        for (unsigned mj = mi; mj; mj &= mj - 1u) {           // j >= i, i itself included (exposure_compensate.cpp:90)
+            const int j = __ffs(mj) - 1;
+            const bool both = ((seen >> i) & (seen >> j) & 1u) != 0u;
+            const unsigned long long bal = __ballot(both);
+            if (!bal) continue;
+            const unsigned long long si = wave_sum_u64(both ? s_q[i][tid] : 0u);
+            const unsigned long long sj = j != i ? wave_sum_u64(both ? s_q[j][tid] : 0u) : 0ull;
+            if (lane == 0) {
+                atomicAdd(&s_acc[i * n + j], (unsigned long long)__popcll(bal));
+                atomicAdd(&s_acc[nn + i * n + j], si);
+                if (j != i) atomicAdd(&s_acc[nn + j * n + i], sj);
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < 2 * nn; i += 256)
+        if (s_acc[i]) atomicAdd(&acc[i], s_acc[i]);
+}
+// N and S as the header states them, from the accumulators; which are cleared for the next call
+__device__ __forceinline__ void gain_cell(const GainTrackViews &V, const unsigned long long *acc, int i, int j, long long &N, long long &S)
+{
+    N = 0; S = 0;
+    if (!((V.active >> i) & (V.active >> j) & 1u) || !rects_meet(V.roi[i], V.roi[j])) return;
+    const long long cnt = (long long)acc[min(i, j) * V.n + max(i, j)];
+    N = cnt > 1 ? cnt : 1;
+    S = (long long)acc[V.n * V.n + i * V.n + j];
+}
+__global__ void __launch_bounds__(256) k_gain_export(GainTrackViews V, unsigned long long *__restrict__ acc, long long *__restrict__ outN, long long *__restrict__ outS)
+{
+    const int n = V.n, nn = n * n, p = threadIdx.x;
+    if (p < nn) gain_cell(V, acc, p / n, p % n, outN[p], outS[p]);
+    __syncthreads();
+    for (int i = p; i < 2 * nn; i += 256) acc[i] = 0ull;
+}
+// statistics -> I -> solve over the active views -> smooth -> state and every listed view table; one workgroup
+__global__ void __launch_bounds__(256) k_gain_update(GainTrackViews V, GainTrackTables W, unsigned long long *__restrict__ acc, double *__restrict__ state,
+                                                     int *__restrict__ counters, double lambda)
+{
+    __shared__ int s_N[MS_MAX_VIEWS * MS_MAX_VIEWS];
+    __shared__ double s_I[MS_MAX_VIEWS * MS_MAX_VIEWS], s_g[MS_MAX_VIEWS];
+    __shared__ int s_ok;
+    const int n = V.n, nn = n * n, p = threadIdx.x, m = __popc(V.active);
+    if (p < nn) {
+        const int i = p / n, j = p % n;
+        if ((V.active >> i) & (V.active >> j) & 1u) {         // the system holds the active views only, in view order
+            const int ci = __popc(V.active & ((1u << i) - 1u)), cj = __popc(V.active & ((1u << j) - 1u));
+            long long N, S;
+            gain_cell(V, acc, i, j, N, S);
+            s_N[ci * m + cj] = (int)N;
+            s_I[ci * m + cj] = N ? (double)S / 1048576.0 / (double)N : 0.0;
+        }
+    }
+    __syncthreads();
+    if (p == 0) {
+        gain_solve(m, s_N, s_I, s_g, &s_ok);
+        counters[s_ok ? 0 : 1] += 1;
+    }
+    __syncthreads();
+    if (p < n && ((V.active >> p) & 1u) && s_ok) {            // singular: nothing changes; an inactive view keeps its gain
+        double g = state[p];
+        g = g + lambda * (s_g[__popc(V.active & ((1u << p) - 1u))] - g);
+        state[p] = g;
+        for (int t = 0; t < W.n; ++t) W.tab[t][p].gain = (float)g;
+    }
+    for (int i = p; i < 2 * nn; i += 256) acc[i] = 0ull;
 }
 
 }  // namespace
@@ -210,6 +331,27 @@ int estimate_gains_device(int n, const ms_rect *rois, const uint8_t *const *imag
     }
     (void)hipFree(buf);
     return rc;
+}
+
+// ---- exposure tracking: the launches ms_gain_stats / ms_track_gains enqueue (compositor.hip owns the buffers and the ordering) --------------------
+int launch_gain_stats(const GainTrackViews &V, GainTrackBuf *buf, hipStream_t st)
+{
+    if (V.nsx <= 0 || V.nsy <= 0) return MS_OK;
+    k_gain_stats<<<dim3(div_up(V.nsx, 64), div_up(V.nsy, 4)), dim3(64, 4), 0, st>>>(V, buf->acc);
+    MS_LAUNCH_CHECK();
+    return MS_OK;
+}
+int launch_gain_export(const GainTrackViews &V, GainTrackBuf *buf, hipStream_t st)
+{
+    k_gain_export<<<1, 256, 0, st>>>(V, buf->acc, buf->outN, buf->outS);
+    MS_LAUNCH_CHECK();
+    return MS_OK;
+}
+int launch_gain_update(const GainTrackViews &V, const GainTrackTables &W, GainTrackBuf *buf, double lambda, hipStream_t st)
+{
+    k_gain_update<<<1, 256, 0, st>>>(V, W, buf->acc, buf->state, &buf->solves_ok, lambda);
+    MS_LAUNCH_CHECK();
+    return MS_OK;
 }
 
 }  // namespace ms

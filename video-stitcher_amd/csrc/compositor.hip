@@ -1779,6 +1779,14 @@ struct ms_ctx {
     bool subset_built_set = false;
     // tiles per view of the full-set lists: a subset's list sizes without reading the lists back
     int warp_per_view[MAX_VIEWS] = {}, stage1_per_view[MAX_VIEWS] = {}, down_per_view[MAX_LEVELS][MAX_VIEWS] = {};
+    // Exposure tracking (ms_track_gains).  The gains live on the device as doubles (GainTrackBuf::state, seeded from `gain`); a track call's last kernel
+    // writes (float)state into every view table a stitch may read.  `gain` above is the host mirror: whoever uploads a view table from it, or saves it,
+    // calls pull_tracked_gains first, so that no path brings an older gain back.
+    DevBuf gain_buf;                   // one GainTrackBuf, allocated by ms_init_blender
+    hipEvent_t gain_ev = nullptr;      // behind the last ms_track_gains / ms_gain_stats: they share the accumulators, whatever their streams
+    bool gain_ev_set = false;
+    std::atomic<bool> gain_tracked{false};   // the device state may differ from `gain`
+    std::mutex gain_mu;                // guards gain_ev_set, `gain` and the enqueues that use the accumulators; taken AFTER tables_mu, never held across a GPU wait by ms_track_gains
 };
 
 namespace ms {
@@ -2218,6 +2226,7 @@ void ms_destroy(ms_ctx *c)
     if (c->mesh_chain) (void)hipEventDestroy(c->mesh_chain);
     if (c->tab_ready) (void)hipEventDestroy(c->tab_ready);
     if (c->subset_built) (void)hipEventDestroy(c->subset_built);
+    if (c->gain_ev) (void)hipEventDestroy(c->gain_ev);
     if (c->mesh_stage) (void)hipHostFree(c->mesh_stage);
     for (hipEvent_t e : c->mesh_stage_ev) if (e) (void)hipEventDestroy(e);
     delete c;
@@ -2234,10 +2243,27 @@ int ms_set_camera(ms_ctx *c, int view, const float *K, const float *R)
     return MS_OK;
 }
 
+// The host mirror of the gains as the tracker left them (ms_track_gains): waits for the last track call and reads its state back.  For the synchronous
+// paths only -- whatever uploads a view table built from `gain`, saves it, or reports it.  A context that was never tracked is not touched.
+static int pull_tracked_gains(ms_ctx *c)
+{
+    if (!c->gain_tracked.load() || !c->gain_buf.p) return MS_OK;
+    bool wait;
+    { std::lock_guard<std::mutex> gk(c->gain_mu); wait = c->gain_ev_set; }
+    if (wait) MS_HIP(hipEventSynchronize(c->gain_ev));
+    double g[MAX_VIEWS];
+    MS_HIP(hipMemcpy(g, ((GainTrackBuf *)c->gain_buf.p)->state, sizeof(g), hipMemcpyDeviceToHost));
+    std::lock_guard<std::mutex> gk(c->gain_mu);
+    for (int v = 0; v < c->N; ++v) c->gain[v] = g[v];
+    return MS_OK;
+}
+
 int ms_set_gain(ms_ctx *c, int view, double gain)
 {
     if (int e = ctx_check_view(c, view)) return e;
-    c->gain[view] = gain;
+    if (int e = pull_tracked_gains(c)) return e;      // (also: a track call still in flight must not overwrite what is set here)
+    { std::lock_guard<std::mutex> gk(c->gain_mu); c->gain[view] = gain; }
+    if (c->gain_buf.p) MS_HIP(hipMemcpy(&((GainTrackBuf *)c->gain_buf.p)->state[view], &gain, sizeof(double), hipMemcpyHostToDevice));      // the tracker goes on from here
     if (c->blender_ready) {   // keep the device table in sync (gains change at recalibration only)
         c->h_views[view].gain = (float)gain;
         MS_HIP(hipMemcpy((ViewDesc *)c->view_tab.p + view, &c->h_views[view], sizeof(ViewDesc), hipMemcpyHostToDevice));
@@ -2447,6 +2473,7 @@ int ms_init_blender(ms_ctx *c, ms_stream stream)
     hipStream_t st = as_stream(stream);
     std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);      // no ms_stitch enqueue while the tables are rebuilt ...
     if (c->stitch_pending) MS_HIP(hipEventSynchronize(c->last_stitch)); // ... and none still reading the old ones on the GPU
+    if (int e = pull_tracked_gains(c)) return e;                        // ... the tables below take the gains the tracker reached (and no track call still writes the old tables)
     const int nb = c->bg.num_bands, N = c->N, F = c->cfg.max_frames;
     // new full-set tables: every view active again, the cached subsets (made from the old tables, sized for the old geometry) are gone
     c->act = nullptr; c->subset_on = false;
@@ -2685,6 +2712,18 @@ int ms_init_blender(ms_ctx *c, ms_stream stream)
     }
     if (int e = c->view_tab.alloc(sizeof(ViewDesc) * N)) return e;
     MS_HIP(hipMemcpy(c->view_tab.p, c->h_views.data(), sizeof(ViewDesc) * N, hipMemcpyHostToDevice));
+    {   // the exposure tracker's block: once per context (the counters outlive a table rebuild); its state = the gains of the table just uploaded
+        if (!c->gain_buf.p) {      // zeros and the state in one upload, like the view table above
+            if (int e = c->gain_buf.alloc(sizeof(GainTrackBuf))) return e;
+            std::unique_ptr<GainTrackBuf> h(new (std::nothrow) GainTrackBuf());
+            if (!h) return fail(MS_ERR_NOMEM, "ms_init_blender: out of host memory");
+            for (int v = 0; v < MAX_VIEWS; ++v) h->state[v] = c->gain[v];
+            MS_HIP(hipMemcpy(c->gain_buf.p, h.get(), sizeof(GainTrackBuf), hipMemcpyHostToDevice));
+            MS_HIP(hipEventCreateWithFlags(&c->gain_ev, hipEventDisableTiming));
+        } else
+            MS_HIP(hipMemcpy(((GainTrackBuf *)c->gain_buf.p)->state, c->gain, sizeof(double) * MAX_VIEWS, hipMemcpyHostToDevice));
+        c->gain_tracked = false;
+    }
     c->col_begin = c->col_end = 0;
     if (c->cfg.col_shards > 1) {      // shard k composites the pano-ROI columns [bound(k), bound(k+1)); boundaries on multiples of 16 columns
         const int S = c->cfg.col_shards, k = c->cfg.col_shard_index, fw = c->pano.fw;
@@ -3159,6 +3198,10 @@ static int build_subset(ms_ctx *c, ms_ctx::SubsetTables &T, unsigned views, hipS
         if (!fresh && c->stitch_pending) MS_HIP(hipStreamWaitEvent(st, c->last_stitch, 0));      // rebuilt in place: after every stitch that read these tables
         if (c->tab_wait) MS_HIP(hipStreamWaitEvent(st, c->tab_ready, 0));
     }
+    {   // the view table is copied from the full set's: behind the last ms_track_gains, whatever stream it ran on
+        std::lock_guard<std::mutex> gk(c->gain_mu);
+        if (c->gain_ev_set) MS_HIP(hipStreamWaitEvent(st, c->gain_ev, 0));
+    }
     if (!c->zero_w.p) {
         size_t zb = 0;
         for (int v = 0; v < N; ++v) {
@@ -3257,6 +3300,124 @@ int ms_get_active_views(const ms_ctx *c, unsigned *mask)
     const unsigned all = (c->N >= 32) ? 0xffffffffu : ((1u << c->N) - 1u);
     std::lock_guard<std::recursive_mutex> tables_lk(const_cast<ms_ctx *>(c)->tables_mu);
     *mask = c->act ? c->act->views : all;
+    return MS_OK;
+}
+
+// ---- exposure tracking: ms_gain_stats / ms_track_gains / ms_get_gains ---------------------------------------------------------------------------
+int ms_gain_track_default_params(ms_gain_track_params *prm)
+{
+    if (!prm) return fail(MS_ERR_INVALID, "ms_gain_track_default_params: null argument");
+    prm->struct_size = (unsigned)sizeof(ms_gain_track_params);
+    prm->stride = 4;
+    prm->smoothing = 0.25;
+    return MS_OK;
+}
+
+// what both entry points check, and the by-value kernel argument (taken under tables_mu: the active set and the geometry cannot change meanwhile)
+static int gain_track_args(ms_ctx *c, const char *who, const ms_image *views, int stride, GainTrackViews &V)
+{
+    if (!c->blender_ready) return fail(MS_ERR_STATE, "%s: call ms_init_blender first", who);
+    if (sharded_ctx(c) || c->cfg.view_shards > 1 || c->cfg.col_shards > 1)
+        return fail(MS_ERR_UNSUPPORTED, "%s: not for a view- or column-sharded context (a shard does not hold every overlap); track on an unsharded context and hand the gains out with ms_set_gain", who);
+    if (c->feather_sharpness >= 0.f) return fail(MS_ERR_UNSUPPORTED, "%s: not for FeatherBlender contexts (ms_init_feather)", who);
+    MS_CHECK(views, "%s: null views", who);
+    MS_CHECK(stride >= 1, "%s: stride %d < 1", who, stride);
+    const int N = c->N;
+    const unsigned all = (N >= 32) ? 0xffffffffu : ((1u << N) - 1u);
+    V = GainTrackViews{};
+    V.n = N; V.src_w = c->cfg.src_width; V.src_h = c->cfg.src_height;
+    V.active = c->act ? c->act->views : all;
+    V.T = c->bg.dst_roi_final; V.stride = stride;
+    V.nsx = div_up(V.T.width, stride); V.nsy = div_up(V.T.height, stride);
+    for (int v = 0; v < N; ++v) {
+        V.xmap[v] = (const float *)c->maps.p + c->map_off[v]; V.pitch[v] = c->map_pitch[v];
+        V.roi[v] = c->roi[v];
+        if (!((V.active >> v) & 1u)) continue;      // a view left out is never read
+        MS_CHECK(views[v].data && views[v].type == MS_8UC3 && views[v].rows == V.src_h && views[v].cols == V.src_w && views[v].step >= (size_t)V.src_w * 3,
+                 "%s: view %d must be a DEVICE 8UC3 image of %dx%d", who, v, V.src_w, V.src_h);
+        V.src[v] = (const uint8_t *)views[v].data; V.step[v] = (unsigned)views[v].step;
+    }
+    return MS_OK;
+}
+// the accumulators are shared by every call of the context: behind the last one, and behind whatever may still rewrite a view table (gain_mu held)
+static int gain_track_order(ms_ctx *c, hipStream_t st)
+{
+    if (c->gain_ev_set) MS_HIP(hipStreamWaitEvent(st, c->gain_ev, 0));
+    if (c->subset_built_set) MS_HIP(hipStreamWaitEvent(st, c->subset_built, 0));
+    std::lock_guard<std::mutex> mk(c->mesh_mu);
+    if (c->tab_wait) MS_HIP(hipStreamWaitEvent(st, c->tab_ready, 0));
+    return MS_OK;
+}
+
+int ms_gain_stats(ms_ctx *c, const ms_image *views, int stride, long long *N_host, long long *S_host, ms_stream stream)
+{
+    if (!c) return fail(MS_ERR_INVALID, "null context");
+    if (!N_host || !S_host) return fail(MS_ERR_INVALID, "ms_gain_stats: null output");
+    hipStream_t st = as_stream(stream);
+    const size_t nn = (size_t)c->N * c->N;
+    {   // both locks for the enqueue only; the exported block cannot be overwritten before it is read back: the next call waits for gain_ev, recorded behind the copies
+        std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);
+        std::lock_guard<std::mutex> gk(c->gain_mu);
+        GainTrackViews V;
+        if (int e = gain_track_args(c, "ms_gain_stats", views, stride, V)) return e;
+        GainTrackBuf *B = (GainTrackBuf *)c->gain_buf.p;
+        if (int e = gain_track_order(c, st)) return e;
+        if (int e = launch_gain_stats(V, B, st)) return e;
+        if (int e = launch_gain_export(V, B, st)) return e;
+        MS_HIP(hipMemcpyAsync(N_host, B->outN, nn * sizeof(long long), hipMemcpyDeviceToHost, st));
+        MS_HIP(hipMemcpyAsync(S_host, B->outS, nn * sizeof(long long), hipMemcpyDeviceToHost, st));
+        MS_HIP(hipEventRecord(c->gain_ev, st));
+        c->gain_ev_set = true;
+    }
+    MS_HIP(hipStreamSynchronize(st));
+    return MS_OK;
+}
+
+int ms_track_gains(ms_ctx *c, const ms_image *views, const ms_gain_track_params *prm, ms_stream stream)
+{
+    if (!c) return fail(MS_ERR_INVALID, "null context");
+    if (!prm) return fail(MS_ERR_INVALID, "ms_track_gains: null params");
+    MS_CHECK(prm->struct_size == sizeof(ms_gain_track_params), "ms_track_gains: ms_gain_track_params.struct_size is %u, this library expects %zu", prm->struct_size, sizeof(ms_gain_track_params));
+    MS_CHECK(prm->smoothing > 0.0 && prm->smoothing <= 1.0, "ms_track_gains: smoothing %g outside (0, 1]", prm->smoothing);
+    hipStream_t st = as_stream(stream);
+    std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);      // held for the enqueue, never for a GPU wait: the table list below stays valid until the kernels are in the stream
+    GainTrackViews V;
+    if (int e = gain_track_args(c, "ms_track_gains", views, prm->stride, V)) return e;
+    GainTrackTables W{};
+    W.tab[W.n++] = (ViewDesc *)c->view_tab.p;
+    if (c->alt.view_tab.p && (int)c->alt.h_views.size() == c->N) W.tab[W.n++] = (ViewDesc *)c->alt.view_tab.p;
+    for (auto &T : c->subsets)
+        if (T->view_tab.p && W.n < GAIN_TRACK_MAX_TABLES) W.tab[W.n++] = (ViewDesc *)T->view_tab.p;
+    GainTrackBuf *B = (GainTrackBuf *)c->gain_buf.p;
+    std::lock_guard<std::mutex> gk(c->gain_mu);
+    if (int e = gain_track_order(c, st)) return e;
+    if (int e = launch_gain_stats(V, B, st)) return e;
+    if (int e = launch_gain_update(V, W, B, prm->smoothing, st)) return e;
+    MS_HIP(hipEventRecord(c->gain_ev, st));
+    c->gain_ev_set = true;
+    c->gain_tracked = true;
+    return MS_OK;
+}
+
+int ms_get_gains(ms_ctx *c, double *gains_host, int *solves_ok, int *solves_singular, ms_stream stream)
+{
+    if (!c) return fail(MS_ERR_INVALID, "null context");
+    if (!gains_host) return fail(MS_ERR_INVALID, "ms_get_gains: null output");
+    if (!c->blender_ready || !c->gain_buf.p) return fail(MS_ERR_STATE, "ms_get_gains: call ms_init_blender first");
+    hipStream_t st = as_stream(stream);
+    bool wait;
+    { std::lock_guard<std::mutex> gk(c->gain_mu); wait = c->gain_ev_set; }
+    if (wait) MS_HIP(hipStreamWaitEvent(st, c->gain_ev, 0));      // (a track call on another stream)
+    GainTrackBuf *B = (GainTrackBuf *)c->gain_buf.p;
+    double g[MAX_VIEWS];
+    int cnt[2];
+    MS_HIP(hipMemcpyAsync(g, B->state, sizeof(g), hipMemcpyDeviceToHost, st));
+    MS_HIP(hipMemcpyAsync(cnt, &B->solves_ok, sizeof(cnt), hipMemcpyDeviceToHost, st));
+    MS_HIP(hipStreamSynchronize(st));
+    std::lock_guard<std::mutex> gk(c->gain_mu);
+    for (int v = 0; v < c->N; ++v) gains_host[v] = c->gain[v] = g[v];
+    if (solves_ok) *solves_ok = cnt[0];
+    if (solves_singular) *solves_singular = cnt[1];
     return MS_OK;
 }
 
@@ -4005,6 +4166,7 @@ int ms_save_tables(ms_ctx *c, void *buf, size_t cap, size_t *bytes_out)
     *bytes_out = need;
     if (!buf) return MS_OK;                          // size query
     MS_CHECK(cap >= need, "ms_save_tables: buffer of %zu bytes, %zu needed", cap, need);
+    if (int e = pull_tracked_gains(c)) return e;      // TablesView::gain = what the tracker reached (ms_track_gains)
     std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);
     unsigned char *o = static_cast<unsigned char *>(buf);
     TablesHeader h{};

@@ -52,6 +52,27 @@ ViewPad blender_view_pad(const BlendGeom &g, int tl_x, int tl_y, int mask_cols, 
 // VoronoiSeamFinder over device masks, in place
 int voronoi_seams_device(int n, const ms_rect *rois, uint8_t *const *masks_dev, hipStream_t st);                 // calib.hip
 int estimate_gains_device(int n, const ms_rect *rois, const uint8_t *const *images_dev, const uint8_t *const *masks_dev, double *gains_host, hipStream_t st);
+// exposure tracking (ms_gain_stats / ms_track_gains; kernels in calib.hip).  The sample lattice, the views' static maps and this call's frames, by value:
+struct ViewDesc;
+struct GainTrackViews {
+    const float *xmap[MS_MAX_VIEWS]; int pitch[MS_MAX_VIEWS];      // projection maps (ymap follows xmap: roi.height rows further), pitch in elements
+    ms_rect roi[MS_MAX_VIEWS];
+    const uint8_t *src[MS_MAX_VIEWS]; unsigned step[MS_MAX_VIEWS]; // this call's 8UC3 frames (active views only)
+    ms_rect T; int stride, nsx, nsy;                               // pano ROI, lattice step, samples per row / column
+    int n, src_w, src_h; unsigned active;
+};
+constexpr int GAIN_TRACK_MAX_TABLES = MS_MAX_VIEWS + 4;            // full set, its alternate copy, num_views + 1 cached subsets
+struct GainTrackTables { ViewDesc *tab[GAIN_TRACK_MAX_TABLES]; int n; };
+// the tracker's per-context device block: accumulators, the exported statistics, the gains (double) and the solve counters
+struct GainTrackBuf {
+    unsigned long long acc[2 * MS_MAX_VIEWS * MS_MAX_VIEWS];
+    long long outN[MS_MAX_VIEWS * MS_MAX_VIEWS], outS[MS_MAX_VIEWS * MS_MAX_VIEWS];
+    double state[MS_MAX_VIEWS];
+    int solves_ok, solves_singular;
+};
+int launch_gain_stats(const GainTrackViews &V, GainTrackBuf *buf, hipStream_t st);
+int launch_gain_export(const GainTrackViews &V, GainTrackBuf *buf, hipStream_t st);
+int launch_gain_update(const GainTrackViews &V, const GainTrackTables &W, GainTrackBuf *buf, double lambda, hipStream_t st);
 void feather_weight_map(const uint8_t *mask, int rows, int cols, float sharpness, float *w);
 
 }  // namespace ms

@@ -18,7 +18,10 @@
 // Usage: stitch_app [--views 6] [--size 1920x1080] [--out 3840x1920] [--hfov 90] [--bands 5] [--frames 300] [--cpw]
 //                   [--i420] [--nv12 | --nv12-direct] [--dump pano.bin] [--no-upload] [--solve-mesh]
 //                   [--reference-calib [--work-megapix 0.6] [--seam-megapix 0.01] [--compose-megapix 1.4]]
-//                   [--drop-view V:F0:F1] [--dump-frames frames.bin]
+//                   [--drop-view V:F0:F1] [--dump-frames frames.bin] [--track-gains K] [--exposure-ramp V:F]
+// --track-gains K: every K-th stitch call is followed by one ms_track_gains on the stitch stream with that call's frames (exposure tracking; 0 = off, the
+// default: nothing changes).  --exposure-ramp V:F multiplies camera V's synthetic frames by F from the middle of the run on, so that the tracker has a drift
+// to follow without cameras.  With tracking on, the closing JSON line ends with the final gains and the solve counters.
 // --drop-view: camera V delivers no new frame for the stitched frames [F0, F1).  The main loop gives every camera CAMERA_TIMEOUT_MS to deliver the frame it
 // stitches next; a camera that has not is left out (ms_set_active_views), and the full set comes back when it delivers again.  The reference exits instead
 // ("Failed to read all cameras", timed.cpp main loop).  --dump-frames writes every 8U panorama, in frame order, to one file.
@@ -87,6 +90,8 @@ struct Options {
     std::string dump;
     int drop_view = -1, drop_f0 = 0, drop_f1 = 0;    // --drop-view V:F0:F1
     std::string dump_frames;
+    int track_gains = 0;                        // --track-gains K
+    int ramp_view = -1; double ramp_factor = 1.0;      // --exposure-ramp V:F
 };
 constexpr int CAMERA_TIMEOUT_MS = 100;               // --drop-view: how long the main loop waits for a camera's frame before it stitches without it
 
@@ -201,9 +206,16 @@ int main(int argc, char **argv)
             if (sscanf(next(), "%d:%d:%d", &o.drop_view, &o.drop_f0, &o.drop_f1) != 3 || o.drop_view < 0) { fprintf(stderr, "--drop-view wants V:F0:F1\n"); return 2; }
         }
         else if (k == "--dump-frames") o.dump_frames = next();
+        else if (k == "--track-gains") o.track_gains = atoi(next());
+        else if (k == "--exposure-ramp") {
+            if (sscanf(next(), "%d:%lf", &o.ramp_view, &o.ramp_factor) != 2 || o.ramp_view < 0 || o.ramp_factor < 0) { fprintf(stderr, "--exposure-ramp wants V:F\n"); return 2; }
+        }
         else { fprintf(stderr, "unknown option %s\n", k.c_str()); return 2; }
     }
     if (o.drop_view >= o.views) { fprintf(stderr, "--drop-view: view %d of %d\n", o.drop_view, o.views); return 2; }
+    if (o.ramp_view >= o.views) { fprintf(stderr, "--exposure-ramp: view %d of %d\n", o.ramp_view, o.views); return 2; }
+    if (o.track_gains < 0) { fprintf(stderr, "--track-gains wants K >= 0\n"); return 2; }
+    if ((o.track_gains > 0 || o.ramp_view >= 0) && o.nv12) { fprintf(stderr, "--track-gains / --exposure-ramp: BGR cameras only (ms_track_gains reads 8UC3 frames)\n"); return 2; }
     FILE *frames_file = nullptr;       // --dump-frames (opened before any thread starts)
     if (!o.dump_frames.empty() && !(frames_file = fopen(o.dump_frames.c_str(), "wb"))) { fprintf(stderr, "cannot write %s\n", o.dump_frames.c_str()); return 2; }
     bool frames_file_ok = true;
@@ -483,7 +495,14 @@ int main(int argc, char **argv)
             }
             const int ib = o.upload ? (t & 1) : 0;
             std::vector<DevMat> &full_imgs = full_imgs_b[ib], &nv12_imgs = nv12_imgs_b[ib];
-            if (o.upload || t == 0) {
+            const bool ramp_now = o.ramp_view >= 0 && t == o.frames / 2;
+            if (ramp_now) {                         // --exposure-ramp: camera V's exposure changes here
+                std::lock_guard<std::mutex> lk(imgs.mu);
+                HIPCHECK(hipStreamSynchronize(upload_stream));                            // (no copy still reads the pinned frame)
+                unsigned char *p = imgs.v[o.ramp_view].p;
+                for (size_t i = 0; i < host_frame_bytes; ++i) p[i] = (unsigned char)std::min(255.0, std::floor(p[i] * o.ramp_factor + 0.5));
+            }
+            if (o.upload || t == 0 || ramp_now) {
                 std::lock_guard<std::mutex> lk(imgs.mu);                                  // imgs.lock() ... imgs.unlock()
                 if (buf_used[ib]) HIPCHECK(hipStreamWaitEvent(upload_stream, buf_free[ib], 0));     // the stitch of frame t-2 has read this buffer
                 if (o.nv12)               // half the PCIe bytes: upload NV12 (all cameras in one copy), convert on the device / in the warp
@@ -507,6 +526,8 @@ int main(int argc, char **argv)
                 comp.stitch_one_nv12(nv12_imgs, &s->pano8u, (DevMat *)nullptr, (ms_stream)stitch_stream);      // the warp converts each tap itself: no BGR frames on the device at all
             else
                 comp.stitch_one(full_imgs, &s->pano8u, (DevMat *)nullptr, (ms_stream)stitch_stream);
+            if (o.track_gains > 0 && (t + 1) % o.track_gains == 0)      // exposure tracking: enqueue-only, behind the stitch that read the same frames
+                comp.trackGains(resize_in ? small_imgs : full_imgs, 0, 0, (ms_stream)stitch_stream);
             if (o.i420) {
                 ms_image rows{s->pano8u.data + (size_t)ya * s->pano8u.step, s->pano8u.step, o.out_w, yb - ya, MS_8UC3};
                 ms_image dst = msshim::wrap(s->i420);
@@ -573,10 +594,19 @@ int main(int argc, char **argv)
         }
         printf("{\"app\": \"stitch_app\", \"views\": %d, \"src\": \"%dx%d\", \"out\": \"%dx%d\", \"bands\": %d, \"cpw\": %s, \"i420\": %s, \"nv12\": %s, \"nv12_direct\": %s, \"upload\": %s, "
                "\"frames\": %lld, \"seconds\": %.4f, \"frames_per_s\": %.1f, \"recalibrations\": %d, \"mesh_solver_iterations\": %d, \"max_mesh_displacement_px\": %.2f, "
-               "\"orb_keypoints\": %lld, \"ratio_matches\": %lld, \"ransac_inliers\": %lld, \"update_mask_margin\": %d, \"update_mask_equals_sync_rebuild\": %s, \"consume_image_height\": %d, \"consume_checksum\": \"%016llx\", \"checksum\": \"%016llx\", \"degraded_frames\": %lld}\n",
+               "\"orb_keypoints\": %lld, \"ratio_matches\": %lld, \"ransac_inliers\": %lld, \"update_mask_margin\": %d, \"update_mask_equals_sync_rebuild\": %s, \"consume_image_height\": %d, \"consume_checksum\": \"%016llx\", \"checksum\": \"%016llx\", \"degraded_frames\": %lld",
                o.views, o.w, o.h, o.out_w, o.out_h, pg.num_bands, o.cpw ? "true" : "false", o.i420 ? "true" : "false", o.nv12 ? "true" : "false", o.nv12_direct ? "true" : "false", o.upload ? "true" : "false",
                consumed, secs, consumed / secs, recalibrations.load(), solver_iterations.load(), (double)max_disp.load(),
                total_keypoints.load(), total_matches.load(), total_inliers.load(), o.update_mask, selfcheck < 0 ? "null" : (selfcheck ? "true" : "false"), consume_image_height, consume_checksum, checksum, degraded_frames);
+        if (o.track_gains > 0) {
+            std::vector<double> g((size_t)o.views);
+            int ok = 0, singular = 0;
+            msshim::check(ms_get_gains(comp.raw(), g.data(), &ok, &singular, (ms_stream)stitch_stream));
+            printf(", \"track_gains\": %d, \"gain_solves_ok\": %d, \"gain_solves_singular\": %d, \"gains\": [", o.track_gains, ok, singular);
+            for (int i = 0; i < o.views; ++i) printf("%s%.9g", i ? ", " : "", g[i]);
+            printf("]");
+        }
+        printf("}\n");
         if (o.drop_view >= 0) fprintf(stderr, "stitch_app: %lld of %lld frames stitched without every camera\n", degraded_frames, consumed);
     } catch (const msshim::Error &e) {
         fprintf(stderr, "stitch_app: msstitch error %d: %s\n", e.code, e.what());

@@ -88,6 +88,16 @@ class MeshInfo(C.Structure):
     _fields_ = [("rows", C.c_int), ("cols", C.c_int), ("nnz", C.c_int), ("iterations", C.c_int), ("error", C.c_double)]
 
 
+class GainTrackParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("stride", C.c_int), ("smoothing", C.c_double)]
+
+
+def gain_track_default_params():
+    p = GainTrackParams()
+    _chk(load().ms_gain_track_default_params(C.byref(p)))
+    return p
+
+
 EXPORTS = [
     "ms_last_error", "ms_version", "ms_device_count", "ms_remap", "ms_resize_linear", "ms_convert_scale_8u", "ms_convert",
     "ms_copy_make_border", "ms_pyr_down", "ms_pyr_up", "ms_subtract_16s", "ms_add_16s", "ms_add_src_weight_32f",
@@ -101,6 +111,7 @@ EXPORTS = [
     "ms_mesh_default_params", "ms_mesh_saliency", "ms_create_mesh", "ms_knn_match_hamming2", "ms_bgr_to_i420_batch", "ms_bgr_to_gray", "ms_stitch_i420", "ms_get_i420_rows", "ms_get_col_window", "ms_get_needed_views", "ms_consume_i420", "ms_resize_linear_batch", "ms_nv12_to_bgr_batch",
     "ms_save_tables", "ms_load_tables", "ms_calib_shape", "ms_stitch_nv12", "ms_get_plan_stats", "ms_get_stitch_kernels",
     "ms_set_active_views", "ms_get_active_views",
+    "ms_gain_track_default_params", "ms_gain_stats", "ms_track_gains", "ms_get_gains",
 ]
 
 _lib = None
@@ -829,6 +840,42 @@ class Compositor:
         """ms_set_active_views: composite only the views whose bit is set (camera dropout); enqueue-only, takes effect at the next stitch call."""
         st = _stream() if stream is None else C.c_void_p(getattr(stream, "cuda_stream", stream))      # a torch.cuda.Stream or a raw hipStream_t
         _chk(load().ms_set_active_views(self._ctx, C.c_uint(mask), st))
+
+    def _one_frame(self, frames):
+        assert len(frames) == self.n
+        views = (Image * self.n)()
+        for k, t in enumerate(frames):
+            views[k] = img(t) if t is not None else Image()      # None: a view outside the active set (never read)
+        return views
+
+    def gain_stats(self, frames, stride):
+        """ms_gain_stats: the exposure tracker's overlap statistics of one frame set (list per view of uint8 HxWx3 cuda tensors); (N, S) as n x n int64 numpy arrays.  Blocking."""
+        import numpy as np
+        N = np.zeros((self.n, self.n), dtype=np.int64)
+        S = np.zeros((self.n, self.n), dtype=np.int64)
+        views = self._one_frame(frames)
+        _chk(load().ms_gain_stats(self._ctx, views, int(stride), N.ctypes.data_as(C.c_void_p), S.ctypes.data_as(C.c_void_p), _stream()))
+        return N, S
+
+    def track_gains(self, frames, stride=None, smoothing=None, stream=None):
+        """ms_track_gains: re-estimate the view gains from one live frame set on the stream; enqueue-only, the next stitch on that stream uses them."""
+        p = gain_track_default_params()
+        if stride is not None:
+            p.stride = int(stride)
+        if smoothing is not None:
+            p.smoothing = float(smoothing)
+        st = _stream() if stream is None else C.c_void_p(getattr(stream, "cuda_stream", stream))
+        views = self._one_frame(frames)
+        _chk(load().ms_track_gains(self._ctx, views, C.byref(p), st))
+
+    def gains(self, stream=None, counters=False):
+        """ms_get_gains: the gains the next stitch on the stream uses (numpy float64); with counters=True also (solves_ok, solves_singular)."""
+        import numpy as np
+        g = np.zeros(self.n, dtype=np.float64)
+        ok, sing = C.c_int(0), C.c_int(0)
+        st = _stream() if stream is None else C.c_void_p(getattr(stream, "cuda_stream", stream))
+        _chk(load().ms_get_gains(self._ctx, g.ctypes.data_as(C.c_void_p), C.byref(ok), C.byref(sing), st))
+        return (g, ok.value, sing.value) if counters else g
 
     def active_views(self):
         """Bit mask of the views the next stitch call composites (ms_get_active_views)."""

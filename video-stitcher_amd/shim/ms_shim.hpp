@@ -101,6 +101,25 @@ public:
     void update_mask(int img_num, ms_stream s = nullptr) { check(ms_update_mask(ctx_, img_num, s)); }   // mb->update_mask(idx, x_mesh, y_mesh): uses the view's active mesh
     // camera dropout (no reference counterpart: timed.cpp exits when a camera fails): composite only the views whose bit is set, from the next stitch on
     void setActiveViews(unsigned mask, ms_stream s = nullptr) { check(ms_set_active_views(ctx_, mask, s)); }
+    // exposure tracking (no reference counterpart: GainCompensator::feed runs once, calibration.cpp:131-132): re-estimate the gains from one live frame set on `s`;
+    // enqueue-only, the next stitch_one on `s` uses them.  stride / smoothing <= 0: the library's starting values
+    template <class Mat> void trackGains(const std::vector<Mat> &full_imgs, int stride = 0, double smoothing = 0, ms_stream s = nullptr)
+    {
+        ms_gain_track_params prm;
+        check(ms_gain_track_default_params(&prm));
+        if (stride > 0) prm.stride = stride;
+        if (smoothing > 0) prm.smoothing = smoothing;
+        std::vector<ms_image> v;
+        for (const Mat &m : full_imgs) v.push_back(wrap(m));
+        if ((int)v.size() != n_) throw Error(MS_ERR_INVALID, "trackGains: one image per view");
+        check(ms_track_gains(ctx_, v.data(), &prm, s));
+    }
+    std::vector<double> gains(ms_stream s = nullptr)       // gc->gains() as the next stitch on `s` uses them (waits for `s`)
+    {
+        std::vector<double> g((size_t)n_);
+        check(ms_get_gains(ctx_, g.data(), nullptr, nullptr, s));
+        return g;
+    }
     // MeshWarper::convertMeshesToMap (meshwarper.cpp:823): callable from the recalibration thread
     void convertMeshToMap(int i, const float *mesh_x, const float *mesh_y, int N, int M, ms_stream s = nullptr)
     { check(ms_set_mesh(ctx_, i, mesh_x, mesh_y, N, M, s)); }

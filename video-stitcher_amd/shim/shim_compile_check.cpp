@@ -22,6 +22,9 @@ int shim_compile_check()
         std::unique_ptr<msshim::Compositor> calibrated = msshim::stitch_calib(frames, MS_PROJ_CYLINDRICAL, true, cal);      // stitch_calib
         (void)rig; (void)calibrated;
         comp.stitch_one(frames, &a, (FakeGpuMat *)nullptr);
+        comp.trackGains(frames, 4, 0.25);
+        const std::vector<double> tracked = comp.gains();
+        (void)tracked;
         for (int i = 0; i < 6; ++i) comp.feed_online(frames[i], i);
         comp.blend(&a, (FakeGpuMat *)nullptr);
         std::vector<FakeGpuMat> slabs(1);
