@@ -93,6 +93,13 @@ MS_API int ms_resize_linear(const ms_image *src, ms_image *dst, double fx, doubl
 /* The same for n 8UC3 images of one geometry in ONE launch: stitch_online's cuda::resize of every view by compose_scale (APP/timed.cpp:75-85 -- on the
  * per-frame path with the shipped COMPOSE_MEGAPIX, defs.h:53) for all views of a frame (or of a batch of frames).  Bit-identical to n ms_resize_linear calls. */
 MS_API int ms_resize_linear_batch(const ms_image *src, ms_image *dst, int n, double fx, double fy, ms_stream stream);
+/* cvtColor(YUV2BGR_NV12) (APP/networking.cpp:45-47) and that cuda::resize (APP/timed.cpp:75-85) in ONE pass: what a rig with NV12 cameras (defs.h:10-17) and the
+ * shipped COMPOSE_MEGAPIX (defs.h:53) does to every frame before the warp, without the full-size BGR image in between.  src_nv12: n DEVICE 8UC1 images of
+ * (rows * 3 / 2) x cols -- Y plane, then interleaved UV -- with even rows and cols, one geometry and one step; dst_bgr: n 8UC3 images of one size.  The two call
+ * forms are those of ms_resize_linear (fx, fy > 0 with the saturate_cast<int>(cols * fx) size check against the FRAME size rows x cols, or both 0 = dst's size).
+ * Each of the four taps is converted from the planes with cvtColor's integer formula first; coordinates, clamps, weights, fma order and saturation are those of
+ * ms_resize_linear: bit-identical to ms_nv12_to_bgr_batch followed by ms_resize_linear_batch.  Equal sizes are refused as there (ms_nv12_to_bgr_batch is the whole job). */
+MS_API int ms_nv12_resize_linear_batch(const ms_image *src_nv12, ms_image *dst_bgr, int n, double fx, double fy, ms_stream stream);
 
 /* GpuMat::convertTo(dst, same type, alpha)  OCV/core/src/cuda/gpu_mat.cu:488-512 (exposure gain,
  * APP/timed.cpp:94 / GainCompensator::apply_gpu exposure_compensate.cpp:155-160).  8U any channels, in place ok. */
@@ -330,7 +337,7 @@ MS_API int ms_update_mask(ms_ctx *ctx, int view, ms_stream stream);
 /* Camera dropout.  Bit v set = view v is composited.  The views left out are treated exactly as MultiBandBlender treats a view whose feed_online
  * was not called for the frame (blenders.cpp:700-749, 758-832): they add nothing to the band sums or the weight sums; pixels covered only by them
  * come out 0 with result mask 0.  Panorama ROI, canvas placement and output sizes do not change.
- *   - Takes effect at the next ms_stitch / ms_stitch_nv12 / ms_stitch_i420 / ms_blend issued after the call returns, for every frame of that call.
+ *   - Takes effect at the next ms_stitch / ms_stitch_nv12 / ms_stitch_i420 / ms_stitch_nv12_i420 / ms_blend issued after the call returns, for every frame of that call.
  *     The set is per call, not per frame: a caller that sees a camera drop out in the middle of a batch splits the batch there.
  *   - Enqueue-only: the table rebuild runs on `stream`, and the next stitch waits for it on the GPU.  The call never waits for GPU work; it waits
  *     only for a stitch being enqueued on another thread, or a table rebuild (ms_init_blender, synchronous ms_update_mask), to finish.  Safe from
@@ -357,7 +364,7 @@ MS_API int ms_get_active_views(const ms_ctx *ctx, unsigned *mask);
  * scale, on the caller's stream: overlap statistics -> normal equations -> solve -> smoothing -> the device view tables, with no host wait, so that the next
  * ms_stitch* on that stream uses the new gains.
  *   views: num_views DEVICE 8UC3 images of the context's source size, ONE frame (of a batched call normally the last time step).  Views outside the active
- *     set (ms_set_active_views) are never read.  NV12 sources (ms_stitch_nv12 callers) are out of scope: convert one frame set, or track on BGR copies.
+ *     set (ms_set_active_views) are never read.
  *   The statistic.  T = dst_roi_final (ms_get_pano_geom), roi_v = the warped ROI of view v, (mx_v, my_v) the maps of ms_get_maps.  A pano pixel (u, v) in
  *     warper coordinates is a sample iff (u - T.x) % stride == 0 && (v - T.y) % stride == 0.  View a sees a sample iff it lies in roi_a and the truncated map
  *     coordinate hits the source -- the warp mask BEFORE seam cutting, as GainCompensator gets it (calibration.cpp:118-132); the blend masks (ms_get_mask) are
@@ -375,6 +382,13 @@ MS_API int ms_get_active_views(const ms_ctx *ctx, unsigned *mask);
  *     ms_set_active_views).  ms_gain_stats is the statistics alone, blocking, for tests and diagnostics: N and S (num_views x num_views long long each) to the
  *     HOST.  ms_get_gains waits for `stream` and returns the gains the next stitch on it will use (num_views doubles) and the solve counters (may be NULL).
  *   ms_gain_track_default_params: stride 4, smoothing 0.25 -- starting values, not tuned on a rig.
+ *   NV12 sources (the cameras' format, defs.h:10-17; ms_stitch_nv12 callers).  ms_gain_stats_nv12 / ms_track_gains_nv12 are the same statistic, solve, smoothing
+ *     and publication with the pixel read from the planes: views_nv12 = num_views DEVICE 8UC1 images of (src_height * 3 / 2) x src_width, ONE frame.  For the
+ *     truncated source coordinate (xx, yy): Y = plane[yy][xx], (U, V) = plane[src_height + yy / 2][xx & ~1, (xx & ~1) + 1], converted to b, g, r with cvtColor's
+ *     integer formula (the capture threads' cvtColor(COLOR_YUV2BGR_NV12), networking.cpp:45-47), then q as above.  N and S equal, integer for integer,
+ *     ms_gain_stats on the ms_nv12_to_bgr_batch copies of the same frames, so every guarantee above holds (enqueue-only, no allocation, callable while another
+ *     thread stitches, inactive views never read, no path brings an older gain back); both forms share the context's accumulators and gain state and may alternate.
+ *     They read the maps only: they also work where ms_stitch_nv12 is refused (debug_simple_kernels).  MS_ERR_INVALID also for an odd source size.
  * MS_ERR_INVALID: null context / params / views, struct_size mismatch, stride < 1, smoothing outside (0, 1], an image of the wrong size or type.
  * MS_ERR_STATE: before ms_init_blender.  MS_ERR_UNSUPPORTED: view-sharded and column-sharded contexts (a shard does not hold every overlap: track on one
  * unsharded context and hand the gains out with ms_set_gain) and FeatherBlender contexts (ms_init_feather). */
@@ -386,6 +400,8 @@ typedef struct ms_gain_track_params {
 MS_API int ms_gain_track_default_params(ms_gain_track_params *prm);
 MS_API int ms_gain_stats(ms_ctx *ctx, const ms_image *views, int stride, long long *N_host, long long *S_host, ms_stream stream);
 MS_API int ms_track_gains(ms_ctx *ctx, const ms_image *views, const ms_gain_track_params *prm, ms_stream stream);
+MS_API int ms_gain_stats_nv12(ms_ctx *ctx, const ms_image *views_nv12, int stride, long long *N_host, long long *S_host, ms_stream stream);
+MS_API int ms_track_gains_nv12(ms_ctx *ctx, const ms_image *views_nv12, const ms_gain_track_params *prm, ms_stream stream);
 MS_API int ms_get_gains(ms_ctx *ctx, double *gains_host, int *solves_ok, int *solves_singular, ms_stream stream);
 
 /* MeshWarper::convertMeshesToMap for one view (APP/meshwarper.cpp:823-886): N x M vertex mesh (HOST fp32,
@@ -588,6 +604,12 @@ MS_API int ms_stitch_nv12(ms_ctx *ctx, int n_frames, const ms_image *views_nv12,
  * (Y = 16, U = V = 128; equals ms_bgr_to_i420 of a zeroed canvas).  Bit-identical to ms_stitch(out8u) + ms_bgr_to_i420 of those rows.
  * Needs the tiled band path (>= 1 band, panorama width a multiple of 8, no view sharding); MS_ERR_UNSUPPORTED otherwise. */
 MS_API int ms_stitch_i420(ms_ctx *ctx, int n_frames, const ms_image *views, ms_image *out_i420, ms_stream stream);
+/* Both at once: the cameras' NV12 frames in (APP/defs.h:10-17, networking.cpp:45-47), the encoder's planar I420 out (APP/timed.cpp:308-316) -- neither the BGR frames
+ * nor the BGR canvas exist.  Inputs as ms_stitch_nv12, outputs as ms_stitch_i420 (same buffers, same ms_get_i420_rows span, initialise once to black); the same
+ * kernels as those two calls (ms_get_stitch_kernels reports MS_WARP_KERNEL_NV12), under ms_set_active_views subsets, with CPW and up to 64 frames per call.
+ * Bit-identical to ms_stitch_nv12(out8u) followed by ms_bgr_to_i420 of the I420 rows.  MS_ERR_UNSUPPORTED exactly where ms_stitch_nv12 or ms_stitch_i420 is
+ * refused; the message names the condition that failed. */
+MS_API int ms_stitch_nv12_i420(ms_ctx *ctx, int n_frames, const ms_image *views_nv12, ms_image *out_i420, ms_stream stream);
 MS_API int ms_get_i420_rows(const ms_ctx *ctx, int *first_canvas_row, int *rows);
 /* Pano-column sharding: the columns [*begin, *end) of the panorama ROI (= canvas columns [*begin + canvas_x, *end + canvas_x), ms_get_pano_geom) this
  * context composites; the whole ROI for an unsharded context.  Shard boundaries are multiples of 16 columns.  Valid after ms_init_blender. */

@@ -111,6 +111,29 @@ int ms_resize_linear_batch(const ms_image *src, ms_image *dst, int n, double fx,
     return launch_resize_linear_batch(src, dst, n, fx, fy, as_stream(s));
 }
 
+int ms_nv12_resize_linear_batch(const ms_image *src, ms_image *dst, int n, double fx, double fy, ms_stream s)
+{
+    MS_CHECK(src && dst && n >= 1, "ms_nv12_resize_linear_batch: null argument / empty batch");
+    for (int i = 0; i < n; ++i) MS_CHECK(src[i].data && dst[i].data, "ms_nv12_resize_linear_batch: image %d: null image", i);
+    PRE()
+    MS_CHECK((fx > 0 && fy > 0) || (fx == 0 && fy == 0), "ms_nv12_resize_linear_batch: fx, fy must both be > 0 or both be 0");
+    for (int i = 0; i < n; ++i) {
+        MS_CHECK(src[i].type == MS_8UC1 && dst[i].type == MS_8UC3, "ms_nv12_resize_linear_batch: image %d: 8UC1 planes -> 8UC3", i);
+        MS_CHECK(src[i].rows == src[0].rows && src[i].cols == src[0].cols && src[i].step == src[0].step && dst[i].rows == dst[0].rows && dst[i].cols == dst[0].cols &&
+                 dst[i].step == dst[0].step, "ms_nv12_resize_linear_batch: all images of a batch must share one geometry (image %d differs)", i);
+    }
+    MS_CHECK(src[0].rows > 0 && src[0].cols > 0 && src[0].rows % 3 == 0 && (src[0].rows / 3 * 2) % 2 == 0 && (src[0].cols & 1) == 0 && src[0].step >= (size_t)src[0].cols,
+             "ms_nv12_resize_linear_batch: src must be the (rows*3/2) x cols planes of an even-sized frame, got %dx%d", src[0].cols, src[0].rows);
+    const int rows = src[0].rows / 3 * 2, cols = src[0].cols;
+    MS_CHECK(dst[0].rows > 0 && dst[0].cols > 0 && dst[0].step >= (size_t)dst[0].cols * 3, "ms_nv12_resize_linear_batch: empty dst / step smaller than a row");
+    MS_CHECK(dst[0].rows != rows || dst[0].cols != cols, "ms_nv12_resize_linear_batch: equal sizes (cuda::resize copies: ms_nv12_to_bgr_batch is the whole job)");
+    if (fx > 0) {
+        const int w = (int)__builtin_rint(cols * fx), h = (int)__builtin_rint(rows * fy);
+        MS_CHECK(dst[0].cols == w && dst[0].rows == h, "ms_nv12_resize_linear_batch: dst must be %dx%d for fx=%g fy=%g (resize.cpp:74)", w, h, fx, fy);
+    }
+    return launch_nv12_resize_linear_batch(src, dst, n, fx, fy, as_stream(s));
+}
+
 int ms_convert_scale_8u(const ms_image *src, ms_image *dst, double alpha, ms_stream s)
 {
     PRE() IMG(src, "ms_convert_scale_8u src") IMG(dst, "ms_convert_scale_8u dst") SAME(src, dst, "ms_convert_scale_8u")

@@ -174,6 +174,9 @@ __device__ __forceinline__ bool rects_meet(const ms_rect &a, const ms_rect &b)
 {
     return max(a.x, b.x) < min(a.x + a.width, b.x + b.width) && max(a.y, b.y) < min(a.y + a.height, b.y + b.height);
 }
+// NV12: the frames are the cameras' planes (ms_gain_stats_nv12 / ms_track_gains_nv12) -- Y at the truncated coordinate, the UV pair of its 2 x 2 block, through
+// cvtColor's integer formula (nv12_bgr, common.hpp) to the b, g, r the 8UC3 form reads from memory: 1 + 2 bytes per view and sample instead of 3, the same integers.
+template <bool NV12>
 __global__ void __launch_bounds__(256) k_gain_stats(GainTrackViews V, unsigned long long *__restrict__ acc)
 {
     __shared__ unsigned s_q[MS_MAX_VIEWS][256];
@@ -194,8 +197,15 @@ __global__ void __launch_bounds__(256) k_gain_stats(GainTrackViews V, unsigned l
             const size_t at = (size_t)ly * V.pitch[a] + lx;
             const int xx = f2i_rz(V.xmap[a][at]), yy = f2i_rz(V.xmap[a][at + (size_t)r.height * V.pitch[a]]);      // (ymap follows xmap)
             if (xx >= 0 && xx < V.src_w && yy >= 0 && yy < V.src_h) {
-                const uint8_t *p = V.src[a] + (size_t)yy * V.step[a] + 3 * xx;
-                const int b0 = p[0], b1 = p[1], b2 = p[2];
+                int b0, b1, b2;
+                if constexpr (NV12) {
+                    const uint8_t *uv = V.src[a] + (size_t)(V.src_h + (yy >> 1)) * V.step[a] + (xx & ~1);
+                    const NvRGB c = nv12_bgr(V.src[a][(size_t)yy * V.step[a] + xx], (unsigned)uv[0] | ((unsigned)uv[1] << 8));
+                    b0 = (int)c.b; b1 = (int)c.g; b2 = (int)c.r;
+                } else {
+                    const uint8_t *p = V.src[a] + (size_t)yy * V.step[a] + 3 * xx;
+                    b0 = p[0]; b1 = p[1]; b2 = p[2];
+                }
                 q = (unsigned)llrint(sqrt(static_cast<double>(b0 * b0 + b1 * b1 + b2 * b2)) * 1048576.0);
                 s = true;
             }
@@ -334,10 +344,12 @@ int estimate_gains_device(int n, const ms_rect *rois, const uint8_t *const *imag
 }
 
 // ---- exposure tracking: the launches ms_gain_stats / ms_track_gains enqueue (compositor.hip owns the buffers and the ordering) --------------------
-int launch_gain_stats(const GainTrackViews &V, GainTrackBuf *buf, hipStream_t st)
+int launch_gain_stats(const GainTrackViews &V, GainTrackBuf *buf, bool nv12, hipStream_t st)
 {
     if (V.nsx <= 0 || V.nsy <= 0) return MS_OK;
-    k_gain_stats<<<dim3(div_up(V.nsx, 64), div_up(V.nsy, 4)), dim3(64, 4), 0, st>>>(V, buf->acc);
+    const dim3 g(div_up(V.nsx, 64), div_up(V.nsy, 4)), b(64, 4);
+    if (nv12) k_gain_stats<true><<<g, b, 0, st>>>(V, buf->acc);
+    else k_gain_stats<false><<<g, b, 0, st>>>(V, buf->acc);
     MS_LAUNCH_CHECK();
     return MS_OK;
 }

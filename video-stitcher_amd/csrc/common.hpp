@@ -152,6 +152,29 @@ __device__ __forceinline__ int16_t trunc_s16(float v) { return (int16_t)(int)v; 
 __device__ __forceinline__ int f2i_rd(float v) { return (int)__builtin_floorf(v); }
 __device__ __forceinline__ int f2i_rz(float v) { return (int)v; }
 
+// cvtColor(COLOR_YUV2BGR_NV12) of ONE pixel (YUV420sp2RGB888Invoker, imgproc/src/color.cpp; = nv12_to_bgr_cell of prims.hip), as floats ready for a bilinear
+// tap: what every kernel that samples the cameras' NV12 planes itself converts with (the projection warp, the gain statistics, the fused resize)
+struct NvRGB { float b, g, r; };
+struct NvChroma { int b, g, r; };       // the chroma terms of a U, V pair, rounding constant included: shared by the 2 x 2 pixels under it
+__device__ __forceinline__ NvChroma nv12_chroma(unsigned uvp)            // uvp: U in bits 0..7, V in bits 8..15
+{
+    constexpr int SH = 20, CUB = 2116026, CUG = -409993, CVG = -852492, CVR = 1673527;
+    const int u = (int)(uvp & 0xffu) - 128, v = (int)((uvp >> 8) & 0xffu) - 128;
+    return NvChroma{(1 << (SH - 1)) + CUB * u, (1 << (SH - 1)) + CVG * v + CUG * u, (1 << (SH - 1)) + CVR * v};
+}
+__device__ __forceinline__ int nv12_luma(unsigned Y) { constexpr int CY = 1220542; return max(0, (int)Y - 16) * CY; }
+__device__ __forceinline__ NvRGB nv12_bgr(unsigned Y, unsigned uvp)
+{
+    constexpr int SH = 20;
+    const NvChroma c = nv12_chroma(uvp);
+    const int yy = nv12_luma(Y);
+    NvRGB o;
+    o.b = (float)min(max((yy + c.b) >> SH, 0), 255);
+    o.g = (float)min(max((yy + c.g) >> SH, 0), 255);
+    o.r = (float)min(max((yy + c.r) >> SH, 0), 255);
+    return o;
+}
+
 // BORDER_REFLECT (cudev BrdReflect) and BORDER_REFLECT_101 (BrdReflect101) index maps
 __device__ __forceinline__ int reflect_idx(int i, int len)
 {

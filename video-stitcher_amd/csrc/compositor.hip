@@ -3313,8 +3313,9 @@ int ms_gain_track_default_params(ms_gain_track_params *prm)
     return MS_OK;
 }
 
-// what both entry points check, and the by-value kernel argument (taken under tables_mu: the active set and the geometry cannot change meanwhile)
-static int gain_track_args(ms_ctx *c, const char *who, const ms_image *views, int stride, GainTrackViews &V)
+// what every entry point checks, and the by-value kernel argument (taken under tables_mu: the active set and the geometry cannot change meanwhile).
+// nv12: the views are the cameras' planes (8UC1, (src_height * 3 / 2) x src_width); the maps are all the statistic needs, so the tiled warp is not required
+static int gain_track_args(ms_ctx *c, const char *who, const ms_image *views, int stride, bool nv12, GainTrackViews &V)
 {
     if (!c->blender_ready) return fail(MS_ERR_STATE, "%s: call ms_init_blender first", who);
     if (sharded_ctx(c) || c->cfg.view_shards > 1 || c->cfg.col_shards > 1)
@@ -3322,6 +3323,7 @@ static int gain_track_args(ms_ctx *c, const char *who, const ms_image *views, in
     if (c->feather_sharpness >= 0.f) return fail(MS_ERR_UNSUPPORTED, "%s: not for FeatherBlender contexts (ms_init_feather)", who);
     MS_CHECK(views, "%s: null views", who);
     MS_CHECK(stride >= 1, "%s: stride %d < 1", who, stride);
+    if (nv12) MS_CHECK((c->cfg.src_width & 1) == 0 && (c->cfg.src_height & 1) == 0, "%s: NV12 frames have an even size, the context's source size is %dx%d", who, c->cfg.src_width, c->cfg.src_height);
     const int N = c->N;
     const unsigned all = (N >= 32) ? 0xffffffffu : ((1u << N) - 1u);
     V = GainTrackViews{};
@@ -3333,8 +3335,12 @@ static int gain_track_args(ms_ctx *c, const char *who, const ms_image *views, in
         V.xmap[v] = (const float *)c->maps.p + c->map_off[v]; V.pitch[v] = c->map_pitch[v];
         V.roi[v] = c->roi[v];
         if (!((V.active >> v) & 1u)) continue;      // a view left out is never read
-        MS_CHECK(views[v].data && views[v].type == MS_8UC3 && views[v].rows == V.src_h && views[v].cols == V.src_w && views[v].step >= (size_t)V.src_w * 3,
-                 "%s: view %d must be a DEVICE 8UC3 image of %dx%d", who, v, V.src_w, V.src_h);
+        if (nv12)
+            MS_CHECK(views[v].data && views[v].type == MS_8UC1 && views[v].rows == V.src_h * 3 / 2 && views[v].cols == V.src_w && views[v].step >= (size_t)V.src_w,
+                     "%s: view %d must be the NV12 planes of a %dx%d frame (DEVICE 8UC1, %d rows)", who, v, V.src_w, V.src_h, V.src_h * 3 / 2);
+        else
+            MS_CHECK(views[v].data && views[v].type == MS_8UC3 && views[v].rows == V.src_h && views[v].cols == V.src_w && views[v].step >= (size_t)V.src_w * 3,
+                     "%s: view %d must be a DEVICE 8UC3 image of %dx%d", who, v, V.src_w, V.src_h);
         V.src[v] = (const uint8_t *)views[v].data; V.step[v] = (unsigned)views[v].step;
     }
     return MS_OK;
@@ -3349,20 +3355,21 @@ static int gain_track_order(ms_ctx *c, hipStream_t st)
     return MS_OK;
 }
 
-int ms_gain_stats(ms_ctx *c, const ms_image *views, int stride, long long *N_host, long long *S_host, ms_stream stream)
+// ms_gain_stats / ms_gain_stats_nv12: only the kernel that reads the pixels differs
+static int gain_stats_impl(ms_ctx *c, const char *who, const ms_image *views, int stride, bool nv12, long long *N_host, long long *S_host, ms_stream stream)
 {
-    if (!c) return fail(MS_ERR_INVALID, "null context");
-    if (!N_host || !S_host) return fail(MS_ERR_INVALID, "ms_gain_stats: null output");
+    if (!c) return fail(MS_ERR_INVALID, "%s: null context", who);
+    if (!N_host || !S_host) return fail(MS_ERR_INVALID, "%s: null output", who);
     hipStream_t st = as_stream(stream);
     const size_t nn = (size_t)c->N * c->N;
     {   // both locks for the enqueue only; the exported block cannot be overwritten before it is read back: the next call waits for gain_ev, recorded behind the copies
         std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);
         std::lock_guard<std::mutex> gk(c->gain_mu);
         GainTrackViews V;
-        if (int e = gain_track_args(c, "ms_gain_stats", views, stride, V)) return e;
+        if (int e = gain_track_args(c, who, views, stride, nv12, V)) return e;
         GainTrackBuf *B = (GainTrackBuf *)c->gain_buf.p;
         if (int e = gain_track_order(c, st)) return e;
-        if (int e = launch_gain_stats(V, B, st)) return e;
+        if (int e = launch_gain_stats(V, B, nv12, st)) return e;
         if (int e = launch_gain_export(V, B, st)) return e;
         MS_HIP(hipMemcpyAsync(N_host, B->outN, nn * sizeof(long long), hipMemcpyDeviceToHost, st));
         MS_HIP(hipMemcpyAsync(S_host, B->outS, nn * sizeof(long long), hipMemcpyDeviceToHost, st));
@@ -3373,16 +3380,17 @@ int ms_gain_stats(ms_ctx *c, const ms_image *views, int stride, long long *N_hos
     return MS_OK;
 }
 
-int ms_track_gains(ms_ctx *c, const ms_image *views, const ms_gain_track_params *prm, ms_stream stream)
+// ms_track_gains / ms_track_gains_nv12: the same accumulators, solve, smoothing and publication; calls of either form may alternate on one context
+static int track_gains_impl(ms_ctx *c, const char *who, const ms_image *views, const ms_gain_track_params *prm, bool nv12, ms_stream stream)
 {
-    if (!c) return fail(MS_ERR_INVALID, "null context");
-    if (!prm) return fail(MS_ERR_INVALID, "ms_track_gains: null params");
-    MS_CHECK(prm->struct_size == sizeof(ms_gain_track_params), "ms_track_gains: ms_gain_track_params.struct_size is %u, this library expects %zu", prm->struct_size, sizeof(ms_gain_track_params));
-    MS_CHECK(prm->smoothing > 0.0 && prm->smoothing <= 1.0, "ms_track_gains: smoothing %g outside (0, 1]", prm->smoothing);
+    if (!c) return fail(MS_ERR_INVALID, "%s: null context", who);
+    if (!prm) return fail(MS_ERR_INVALID, "%s: null params", who);
+    MS_CHECK(prm->struct_size == sizeof(ms_gain_track_params), "%s: ms_gain_track_params.struct_size is %u, this library expects %zu", who, prm->struct_size, sizeof(ms_gain_track_params));
+    MS_CHECK(prm->smoothing > 0.0 && prm->smoothing <= 1.0, "%s: smoothing %g outside (0, 1]", who, prm->smoothing);
     hipStream_t st = as_stream(stream);
     std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);      // held for the enqueue, never for a GPU wait: the table list below stays valid until the kernels are in the stream
     GainTrackViews V;
-    if (int e = gain_track_args(c, "ms_track_gains", views, prm->stride, V)) return e;
+    if (int e = gain_track_args(c, who, views, prm->stride, nv12, V)) return e;
     GainTrackTables W{};
     W.tab[W.n++] = (ViewDesc *)c->view_tab.p;
     if (c->alt.view_tab.p && (int)c->alt.h_views.size() == c->N) W.tab[W.n++] = (ViewDesc *)c->alt.view_tab.p;
@@ -3391,12 +3399,29 @@ int ms_track_gains(ms_ctx *c, const ms_image *views, const ms_gain_track_params 
     GainTrackBuf *B = (GainTrackBuf *)c->gain_buf.p;
     std::lock_guard<std::mutex> gk(c->gain_mu);
     if (int e = gain_track_order(c, st)) return e;
-    if (int e = launch_gain_stats(V, B, st)) return e;
+    if (int e = launch_gain_stats(V, B, nv12, st)) return e;
     if (int e = launch_gain_update(V, W, B, prm->smoothing, st)) return e;
     MS_HIP(hipEventRecord(c->gain_ev, st));
     c->gain_ev_set = true;
     c->gain_tracked = true;
     return MS_OK;
+}
+
+int ms_gain_stats(ms_ctx *c, const ms_image *views, int stride, long long *N_host, long long *S_host, ms_stream stream)
+{
+    return gain_stats_impl(c, "ms_gain_stats", views, stride, false, N_host, S_host, stream);
+}
+int ms_gain_stats_nv12(ms_ctx *c, const ms_image *views_nv12, int stride, long long *N_host, long long *S_host, ms_stream stream)
+{
+    return gain_stats_impl(c, "ms_gain_stats_nv12", views_nv12, stride, true, N_host, S_host, stream);
+}
+int ms_track_gains(ms_ctx *c, const ms_image *views, const ms_gain_track_params *prm, ms_stream stream)
+{
+    return track_gains_impl(c, "ms_track_gains", views, prm, false, stream);
+}
+int ms_track_gains_nv12(ms_ctx *c, const ms_image *views_nv12, const ms_gain_track_params *prm, ms_stream stream)
+{
+    return track_gains_impl(c, "ms_track_gains_nv12", views_nv12, prm, true, stream);
 }
 
 int ms_get_gains(ms_ctx *c, double *gains_host, int *solves_ok, int *solves_singular, ms_stream stream)
@@ -3950,6 +3975,12 @@ int ms_stitch_i420(ms_ctx *c, int n_frames, const ms_image *views, ms_image *out
 {
     if (!out_i420) return fail(MS_ERR_INVALID, "ms_stitch_i420: null output");
     return stitch_impl(c, n_frames, views, nullptr, nullptr, as_stream(stream), 0, nullptr, nullptr, nullptr, ShardArgs{}, out_i420);
+}
+
+int ms_stitch_nv12_i420(ms_ctx *c, int n_frames, const ms_image *views_nv12, ms_image *out_i420, ms_stream stream)
+{
+    if (!out_i420) return fail(MS_ERR_INVALID, "ms_stitch_nv12_i420: null output");
+    return stitch_impl(c, n_frames, views_nv12, nullptr, nullptr, as_stream(stream), 0, nullptr, nullptr, nullptr, ShardArgs{}, out_i420, true);
 }
 
 int ms_get_col_window(const ms_ctx *c, int *begin, int *end)

@@ -9,6 +9,7 @@ namespace ms {
 int launch_remap(const ms_image &src, const ms_image &xm, const ms_image &ym, ms_image &dst, int interp, int border, hipStream_t st);
 int launch_resize_linear(const ms_image &src, ms_image &dst, double fx, double fy, hipStream_t st);
 int launch_resize_linear_batch(const ms_image *src, ms_image *dst, int n, double fx, double fy, hipStream_t st);
+int launch_nv12_resize_linear_batch(const ms_image *src, ms_image *dst, int n, double fx, double fy, hipStream_t st);
 int launch_convert_scale_8u(const ms_image &src, ms_image &dst, double alpha, hipStream_t st);
 int launch_convert(const ms_image &src, ms_image &dst, double alpha, hipStream_t st);
 int launch_sub_16s(const ms_image &a, const ms_image &b, ms_image &dst, hipStream_t st);
@@ -57,7 +58,7 @@ struct ViewDesc;
 struct GainTrackViews {
     const float *xmap[MS_MAX_VIEWS]; int pitch[MS_MAX_VIEWS];      // projection maps (ymap follows xmap: roi.height rows further), pitch in elements
     ms_rect roi[MS_MAX_VIEWS];
-    const uint8_t *src[MS_MAX_VIEWS]; unsigned step[MS_MAX_VIEWS]; // this call's 8UC3 frames (active views only)
+    const uint8_t *src[MS_MAX_VIEWS]; unsigned step[MS_MAX_VIEWS]; // this call's 8UC3 frames, or their NV12 planes (active views only)
     ms_rect T; int stride, nsx, nsy;                               // pano ROI, lattice step, samples per row / column
     int n, src_w, src_h; unsigned active;
 };
@@ -70,7 +71,7 @@ struct GainTrackBuf {
     double state[MS_MAX_VIEWS];
     int solves_ok, solves_singular;
 };
-int launch_gain_stats(const GainTrackViews &V, GainTrackBuf *buf, hipStream_t st);
+int launch_gain_stats(const GainTrackViews &V, GainTrackBuf *buf, bool nv12, hipStream_t st);
 int launch_gain_export(const GainTrackViews &V, GainTrackBuf *buf, hipStream_t st);
 int launch_gain_update(const GainTrackViews &V, const GainTrackTables &W, GainTrackBuf *buf, double lambda, hipStream_t st);
 void feather_weight_map(const uint8_t *mask, int rows, int cols, float sharpness, float *w);

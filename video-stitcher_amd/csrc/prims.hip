@@ -870,6 +870,187 @@ int launch_nv12_to_bgr(const ms_image &src, ms_image &dst, hipStream_t st)
 }
 
 // ------------------------------------------------------------------------------------------------
+// ms_nv12_resize_linear_batch: cvtColor(YUV2BGR_NV12) + cuda::resize(INTER_LINEAR) of the shipped rig's ingest (networking.cpp:45-47, timed.cpp:75-85) in ONE pass from
+// the planes -- no full-size BGR frame is written or read (per six 1080p frames 18.7 MB in + 25 MB out instead of 18.7 + 37.3 and 37.3 + 25).  Every tap is converted with
+// cvtColor's integer formula (nv12_bgr's pieces, common.hpp), then the coordinates, clamps, weights, fma order and saturation of k_resize_linear3_batch / _x4: bit-identical
+// to ms_nv12_to_bgr_batch followed by ms_resize_linear_batch.
+__device__ __forceinline__ NvRGB nv12_at(const uint8_t *__restrict__ src, size_t sstep, int srows, int x, int y)
+{
+    const uint8_t *uv = src + (size_t)(srows + (y >> 1)) * sstep + (x & ~1);
+    return nv12_bgr(src[(size_t)y * sstep + x], (unsigned)uv[0] | ((unsigned)uv[1] << 8));
+}
+// one output pixel, one converted tap at a time (every scale, every alignment)
+__device__ __forceinline__ void nv12_resize_px(const uint8_t *__restrict__ src, size_t sstep, int srows, int scols, int x, int y, float ifx, float ify, uint8_t *__restrict__ d)
+{
+    const float sx = (float)x * ifx, sy = (float)y * ify;
+    const int x1 = f2i_rd(sx), y1 = f2i_rd(sy);
+    const int x2 = x1 + 1, y2 = y1 + 1;
+    const int x2r = min(x2, scols - 1), y2r = min(y2, srows - 1);
+    const float w11 = ((float)x2 - sx) * ((float)y2 - sy), w12 = (sx - (float)x1) * ((float)y2 - sy);
+    const float w21 = ((float)x2 - sx) * (sy - (float)y1), w22 = (sx - (float)x1) * (sy - (float)y1);
+    const NvRGB a11 = nv12_at(src, sstep, srows, x1, y1), a12 = nv12_at(src, sstep, srows, x2r, y1);
+    const NvRGB a21 = nv12_at(src, sstep, srows, x1, y2r), a22 = nv12_at(src, sstep, srows, x2r, y2r);
+    const float t[4][3] = {{a11.b, a11.g, a11.r}, {a12.b, a12.g, a12.r}, {a21.b, a21.g, a21.r}, {a22.b, a22.g, a22.r}};
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float out = 0.f;
+        out = __builtin_fmaf(t[0][c], w11, out);
+        out = __builtin_fmaf(t[1][c], w12, out);
+        out = __builtin_fmaf(t[2][c], w21, out);
+        out = __builtin_fmaf(t[3][c], w22, out);
+        d[c] = sat_u8(out);
+    }
+}
+__global__ void __launch_bounds__(256) k_nv12_resize_batch(ResizeBatch T, size_t sstep, int srows, int scols, size_t dstep, int drows, int dcols, float ify, float ifx)
+{
+    XY_GUARD(dcols, drows)
+    nv12_resize_px(T.src[blockIdx.z], sstep, srows, scols, x, y, ifx, ify, row_ptr<uint8_t>(T.dst[blockIdx.z], dstep, y) + (size_t)x * 3);
+}
+// The per-frame form, shaped like k_resize_linear3_x4: 4 output pixels x RS_ROWS rows per lane, lanes numbered row-major over (row group, column group).  For downscales
+// up to 1.6 x a lane's four pixels and their right-hand taps lie within the 8 source columns that start at the even column xb = x1[0] & ~1 (x1[3] + 1 <= xb + 1 + 5 + 1), so
+// a source row is ONE 8-byte Y window and ONE 8-byte UV window (four chroma pairs, the same columns), each read as the aligned dwords around it + v_alignbyte.  The UV row of
+// y1 and y2 (and of the lane's next output row) is the same row half the time: its window is read and its chroma terms are built once.  Each of the 8 source pixels is
+// converted ONCE into a packed b | g << 8 | r << 16 dword (through nv12_px: the clamps that get packed must not fuse into v_ashr_pk_u8_i32), a pixel's two taps are picked
+// from the 8 dwords with the two to four candidates its column offset can take (v_cndmask chains over the dwords BY VALUE: selects between array elements would be
+// turned into indexed reads of a scratch copy, see k_resize_linear3_x4), and the bytes come out with v_cvt_f32_ubyteN.  Lanes whose window would leave the source row, ragged right edges and every other scale take nv12_resize_px.
+// Measured (tools/time_nv12_path.py, profiles/nv12_path.jsonl): 6 x 1080p -> 1578 x 887 in 41.3 us against 37.0 us for ms_nv12_to_bgr_batch + ms_resize_linear_batch, 192
+// frames 1 069 against 900 us -- SLOWER, although it moves 44 MB instead of 118: 90 VGPRs, no scratch, 1 305 static VALU instructions per lane (the conversion of 24-32 source
+// pixels, and the three- and four-way selects come out as branches), so it is VALU-bound where the two launches are bandwidth-bound.  Callers that want speed keep the two
+// launches; this entry point is the one-pass form for callers that want the 37 MB BGR frames off the device.
+__device__ __forceinline__ float rs_chan(unsigned p, int c) { return (float)((p >> (8 * c)) & 0xffu); }
+__global__ void __launch_bounds__(256) k_nv12_resize_x4(ResizeBatch T, unsigned sstep, int srows, int scols, unsigned dstep, int drows, int dcols, float ify, float ifx,
+                                                        unsigned lpr, unsigned lpr_magic, unsigned n_lanes)
+{
+    const unsigned idx = blockIdx.x * 256u + threadIdx.x;
+    if (idx >= n_lanes) return;
+    unsigned rg = __umulhi(idx, lpr_magic), lx = idx - rg * lpr;
+    if (lx >= lpr) { ++rg; lx -= lpr; }
+    const int x0 = 4 * (int)lx, yb = (int)rg * RS_ROWS;
+    if (x0 >= dcols || yb >= drows) return;
+    const uint8_t *src = T.src[blockIdx.z];
+    uint8_t *dst = T.dst[blockIdx.z];
+    float sx[4];
+    int x1[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { sx[k] = (float)(x0 + k) * ifx; x1[k] = f2i_rd(sx[k]); }
+    auto step12 = [](int d) { return d == 1 || d == 2; };
+    const int xb = x1[0] & ~1;
+    // (the aligned dwords around a window reach up to 4 bytes past it: xb + 12 <= scols keeps them inside the row, and every right-hand tap left of the x2 clamp)
+    const bool fast = x0 + 3 < dcols && x1[0] >= 0 && xb + 12 <= scols && step12(x1[1] - x1[0]) && step12(x1[2] - x1[1]) && step12(x1[3] - x1[2]) && x1[3] - x1[0] <= 5;
+    if (!fast) {
+        for (int r = 0; r < RS_ROWS && yb + r < drows; ++r)
+            for (int k = 0; k < 4 && x0 + k < dcols; ++k)
+                nv12_resize_px(src, sstep, srows, scols, x0 + k, yb + r, ifx, ify, dst + ((size_t)(yb + r) * dstep + (size_t)(x0 + k) * 3));
+        return;
+    }
+    const int o0 = x1[0] - xb, o1 = x1[1] - xb, o2 = x1[2] - xb, o3 = x1[3] - xb;      // 0..1, 1..3, 2..5, 3..6
+    float wx1[4], wx2[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { wx2[k] = (float)(x1[k] + 1) - sx[k]; wx1[k] = sx[k] - (float)x1[k]; }
+    auto load8 = [&](unsigned off, unsigned &lo, unsigned &hi) {      // the 8 bytes at src + off (32-bit offsets: the launcher checks rows * step < 2^32)
+        const uint8_t *p = src + off;
+        const unsigned sh = (unsigned)(uintptr_t)p & 3u;
+        const unsigned *q = reinterpret_cast<const unsigned *>(p - sh);
+        const unsigned a = q[0], b = q[1], c = q[2];
+        lo = __builtin_amdgcn_alignbyte(b, a, sh); hi = __builtin_amdgcn_alignbyte(c, b, sh);
+    };
+    int crow = -1;
+    NvChroma ch[4];
+    auto load_row = [&](int yy, unsigned (&P)[8]) {      // source row yy of the window, converted
+        if ((yy >> 1) != crow) {
+            crow = yy >> 1;
+            unsigned u0, u1;
+            load8((unsigned)(srows + crow) * sstep + (unsigned)xb, u0, u1);
+            ch[0] = nv12_chroma(u0); ch[1] = nv12_chroma(u0 >> 16); ch[2] = nv12_chroma(u1); ch[3] = nv12_chroma(u1 >> 16);
+        }
+        unsigned y0, y1w;
+        load8((unsigned)yy * sstep + (unsigned)xb, y0, y1w);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int yl = nv12_luma(((i < 4 ? y0 : y1w) >> (8 * (i & 3))) & 0xffu);
+            P[i] = nv12_px(yl, ch[i >> 1].b) | (nv12_px(yl, ch[i >> 1].g) << 8) | (nv12_px(yl, ch[i >> 1].r) << 16);
+        }
+    };
+    int y1[RS_ROWS], y2r[RS_ROWS];
+    float wy1[RS_ROWS], wy2[RS_ROWS];
+    bool live[RS_ROWS];
+#pragma unroll
+    for (int r = 0; r < RS_ROWS; ++r) {
+        const int y = min(yb + r, drows - 1);
+        live[r] = yb + r < drows;
+        const float sy = (float)y * ify;
+        y1[r] = f2i_rd(sy);
+        y2r[r] = min(y1[r] + 1, srows - 1);
+        wy2[r] = (float)(y1[r] + 1) - sy; wy1[r] = sy - (float)y1[r];
+    }
+    // pixel k's left tap is column o_k of the window, its right tap o_k + 1: o_0 in 0..1, o_1 in 1..3, o_2 in 2..5, o_3 in 3..6 (checked above)
+    const bool f0 = o0 == 1, a1 = o1 == 2, b1 = o1 == 3, a2 = o2 == 3, b2 = o2 == 4, c2 = o2 == 5, a3 = o3 == 4, b3 = o3 == 5, c3 = o3 == 6;
+    auto taps = [&](unsigned p0, unsigned p1, unsigned p2, unsigned p3, unsigned p4, unsigned p5, unsigned p6, unsigned p7, unsigned (&lo)[4][2], unsigned (&hi)[4][2], int q) {
+        lo[0][q] = f0 ? p1 : p0;                             hi[0][q] = f0 ? p2 : p1;
+        lo[1][q] = b1 ? p3 : (a1 ? p2 : p1);                 hi[1][q] = b1 ? p4 : (a1 ? p3 : p2);
+        lo[2][q] = c2 ? p5 : (b2 ? p4 : (a2 ? p3 : p2));     hi[2][q] = c2 ? p6 : (b2 ? p5 : (a2 ? p4 : p3));
+        lo[3][q] = c3 ? p6 : (b3 ? p5 : (a3 ? p4 : p3));     hi[3][q] = c3 ? p7 : (b3 ? p6 : (a3 ? p5 : p4));
+    };
+    unsigned W[RS_ROWS][2][8];
+#pragma unroll
+    for (int r = 0; r < RS_ROWS; ++r) {
+        if (r > 0 && y1[r] == y2r[r - 1]) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) W[r][0][i] = W[r - 1][1][i];
+        } else load_row(y1[r], W[r][0]);
+        load_row(y2r[r], W[r][1]);
+    }
+#pragma unroll
+    for (int r = 0; r < RS_ROWS; ++r) {
+        if (!live[r]) break;
+        unsigned lo[4][2], hi[4][2];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) taps(W[r][q][0], W[r][q][1], W[r][q][2], W[r][q][3], W[r][q][4], W[r][q][5], W[r][q][6], W[r][q][7], lo, hi, q);
+        unsigned out3[3] = {0u, 0u, 0u};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float w11 = wx2[k] * wy2[r], w12 = wx1[k] * wy2[r], w21 = wx2[k] * wy1[r], w22 = wx1[k] * wy1[r];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                float out = 0.f;
+                out = __builtin_fmaf(rs_chan(lo[k][0], c), w11, out);
+                out = __builtin_fmaf(rs_chan(hi[k][0], c), w12, out);
+                out = __builtin_fmaf(rs_chan(lo[k][1], c), w21, out);
+                out = __builtin_fmaf(rs_chan(hi[k][1], c), w22, out);
+                const int i = 3 * k + c;
+                out3[i >> 2] = sat_u8_into(out, (unsigned)(i & 3), out3[i >> 2]);
+            }
+        }
+        __builtin_memcpy(dst + ((unsigned)(yb + r) * dstep + (unsigned)x0 * 3u), out3, 12);
+    }
+}
+int launch_nv12_resize_linear_batch(const ms_image *src, ms_image *dst, int n, double fx, double fy, hipStream_t st)
+{
+    const int srows = src[0].rows / 3 * 2, scols = src[0].cols;
+    if (!(fx > 0 && fy > 0)) { fx = (double)dst[0].cols / scols; fy = (double)dst[0].rows / srows; }
+    const float ifx = (float)(1.0 / fx), ify = (float)(1.0 / fy);
+    const unsigned lpr = (unsigned)div_up(dst[0].cols, 4);
+    const unsigned long long n_lanes = (unsigned long long)lpr * (unsigned)div_up(dst[0].rows, RS_ROWS);
+    // the same bounds as launch_resize_linear_batch: downscales whose 4-pixel windows fit 8 columns, lane index times row length and every byte offset within 32 bits
+    const bool x4 = ifx >= 1.f && ifx <= 1.6f && scols >= 16 && n_lanes * lpr < 0x100000000ull &&
+                    (unsigned long long)src[0].rows * src[0].step < 0x100000000ull && (unsigned long long)dst[0].rows * dst[0].step < 0x100000000ull && dev_knob("MS_RESIZE_SIMPLE", 0) == 0;
+    for (int i0 = 0; i0 < n; i0 += RESIZE_BATCH) {
+        const int m = std::min(RESIZE_BATCH, n - i0);
+        ResizeBatch T{};
+        for (int i = 0; i < m; ++i) { T.src[i] = (const uint8_t *)src[i0 + i].data; T.dst[i] = (uint8_t *)dst[i0 + i].data; }
+        if (x4) {
+            k_nv12_resize_x4<<<dim3(div_up((int)n_lanes, 256), 1, m), 256, 0, st>>>(T, (unsigned)src[0].step, srows, scols, (unsigned)dst[0].step, dst[0].rows, dst[0].cols, ify, ifx,
+                                                                                 lpr, (unsigned)(0x100000000ull / lpr), (unsigned)n_lanes);
+        } else {
+            const dim3 g2 = grid2d(dst[0].cols, dst[0].rows);
+            k_nv12_resize_batch<<<dim3(g2.x, g2.y, m), dim3(BX, BY), 0, st>>>(T, src[0].step, srows, scols, dst[0].step, dst[0].rows, dst[0].cols, ify, ifx);
+        }
+        MS_LAUNCH_CHECK();
+    }
+    return MS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // cuda::cvtColor(BGR2GRAY) of featurefinder::findFeatures (APP/featurefinder.cpp:34) -> RGB2GrayConvert<bidx = 0>
 // (core/include/opencv2/core/cuda/detail/color_detail.hpp:97-101, :444-447): CV_DESCALE(b * 1868 + g * 9617 + r * 4899, 14).
 // One lane = 4 pixels (12-byte load, one dword store).

@@ -782,19 +782,7 @@ __device__ __forceinline__ void warp_tabs_load(const WarpTile &T, const ViewDesc
 constexpr int S1_BY_NV = WARP_TH;          // lane rows of a stage-1 workgroup (= S1_BY, declared further down)
 typedef unsigned short ms_u16_a1 __attribute__((aligned(1)));
 typedef unsigned ms_u32_a2 __attribute__((aligned(2)));
-struct NvRGB { float b, g, r; };
-__device__ __forceinline__ NvRGB nv12_bgr(unsigned Y, unsigned uvp)      // uvp: U in bits 0..7, V in bits 8..15
-{
-    constexpr int SH = 20, CY = 1220542, CUB = 2116026, CUG = -409993, CVG = -852492, CVR = 1673527;
-    const int u = (int)(uvp & 0xffu) - 128, v = (int)((uvp >> 8) & 0xffu) - 128;
-    const int ruv = (1 << (SH - 1)) + CVR * v, guv = (1 << (SH - 1)) + CVG * v + CUG * u, buv = (1 << (SH - 1)) + CUB * u;
-    const int yy = max(0, (int)Y - 16) * CY;
-    NvRGB o;
-    o.b = (float)min(max((yy + buv) >> SH, 0), 255);
-    o.g = (float)min(max((yy + guv) >> SH, 0), 255);
-    o.r = (float)min(max((yy + ruv) >> SH, 0), 255);
-    return o;
-}
+// (NvRGB / nv12_bgr: common.hpp -- the gain statistics and the fused resize convert their samples with the same function)
 // one tap with an explicit bounds test (border samples only): BORDER_CONSTANT 0 in BGR space, as the remap of the converted image would see it
 __device__ __forceinline__ NvRGB nv12_tap_checked(ms_gptr_u8 base, unsigned st, int rows, int cols, int xx, int yy)
 {

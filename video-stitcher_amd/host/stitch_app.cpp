@@ -18,7 +18,13 @@
 // Usage: stitch_app [--views 6] [--size 1920x1080] [--out 3840x1920] [--hfov 90] [--bands 5] [--frames 300] [--cpw]
 //                   [--i420] [--nv12 | --nv12-direct] [--dump pano.bin] [--no-upload] [--solve-mesh]
 //                   [--reference-calib [--work-megapix 0.6] [--seam-megapix 0.01] [--compose-megapix 1.4]]
-//                   [--drop-view V:F0:F1] [--dump-frames frames.bin] [--track-gains K] [--exposure-ramp V:F]
+//                   [--drop-view V:F0:F1] [--dump-frames frames.bin] [--track-gains K] [--exposure-ramp V:F] [--dump-i420 planes.bin]
+// --nv12-direct keeps BGR copies of the cameras' frames off the device in every mode: the warp samples the planes (ms_stitch_nv12), --i420 makes the encoder's
+// planes in the same call (ms_stitch_nv12_i420: no 8U canvas is written; --dump, --dump-frames and --consume need the canvas and keep the two-step form
+// ms_stitch_nv12 + ms_bgr_to_i420), --track-gains reads the planes (ms_track_gains_nv12).  With a compose-scale resize (--reference-calib) the frames go
+// through ms_nv12_to_bgr_batch + ms_resize_linear_batch: the one-pass ms_nv12_resize_linear_batch gives the same bytes (--fused-resize selects it) but is
+// measured slower than the two launches (41 against 37 us per six 1080p frames, README).  With --nv12 the exposure ramp scales the Y plane only (the camera's exposure, not its colour).
+// --dump-i420 FILE writes the last frame's I420 planes (every --i420 mode); the JSON line's "i420_call" names the call that produced them.
 // --track-gains K: every K-th stitch call is followed by one ms_track_gains on the stitch stream with that call's frames (exposure tracking; 0 = off, the
 // default: nothing changes).  --exposure-ramp V:F multiplies camera V's synthetic frames by F from the middle of the run on, so that the tracker has a drift
 // to follow without cameras.  With tracking on, the closing JSON line ends with the final gains and the solve counters.
@@ -92,6 +98,8 @@ struct Options {
     std::string dump_frames;
     int track_gains = 0;                        // --track-gains K
     int ramp_view = -1; double ramp_factor = 1.0;      // --exposure-ramp V:F
+    std::string dump_i420;                      // --dump-i420 FILE
+    bool fused_resize = false;                  // --fused-resize: with --nv12-direct and a compose-scale resize, planes -> small_imgs in one pass
 };
 constexpr int CAMERA_TIMEOUT_MS = 100;               // --drop-view: how long the main loop waits for a camera's frame before it stitches without it
 
@@ -207,6 +215,8 @@ int main(int argc, char **argv)
         }
         else if (k == "--dump-frames") o.dump_frames = next();
         else if (k == "--track-gains") o.track_gains = atoi(next());
+        else if (k == "--dump-i420") o.dump_i420 = next();
+        else if (k == "--fused-resize") o.fused_resize = true;
         else if (k == "--exposure-ramp") {
             if (sscanf(next(), "%d:%lf", &o.ramp_view, &o.ramp_factor) != 2 || o.ramp_view < 0 || o.ramp_factor < 0) { fprintf(stderr, "--exposure-ramp wants V:F\n"); return 2; }
         }
@@ -215,7 +225,8 @@ int main(int argc, char **argv)
     if (o.drop_view >= o.views) { fprintf(stderr, "--drop-view: view %d of %d\n", o.drop_view, o.views); return 2; }
     if (o.ramp_view >= o.views) { fprintf(stderr, "--exposure-ramp: view %d of %d\n", o.ramp_view, o.views); return 2; }
     if (o.track_gains < 0) { fprintf(stderr, "--track-gains wants K >= 0\n"); return 2; }
-    if ((o.track_gains > 0 || o.ramp_view >= 0) && o.nv12) { fprintf(stderr, "--track-gains / --exposure-ramp: BGR cameras only (ms_track_gains reads 8UC3 frames)\n"); return 2; }
+    if (!o.dump_i420.empty() && !o.i420) { fprintf(stderr, "--dump-i420 needs --i420\n"); return 2; }
+    if (o.fused_resize && !o.nv12_direct) { fprintf(stderr, "--fused-resize needs --nv12-direct\n"); return 2; }
     FILE *frames_file = nullptr;       // --dump-frames (opened before any thread starts)
     if (!o.dump_frames.empty() && !(frames_file = fopen(o.dump_frames.c_str(), "wb"))) { fprintf(stderr, "cannot write %s\n", o.dump_frames.c_str()); return 2; }
     bool frames_file_ok = true;
@@ -263,6 +274,10 @@ int main(int argc, char **argv)
         const float warp_scale = o.reference_calib ? cal.rig.compose_warp_scale : (float)(o.out_w / (2.0 * M_PI));
         const bool resize_in = o.reference_calib && cal.rig.resize_input;
         const int cw = o.reference_calib ? cal.rig.compose_width : o.w, ch = o.reference_calib ? cal.rig.compose_height : o.h;
+        // --nv12-direct --i420 in one call, where no 8U canvas is needed otherwise (the canvas is what --dump, --dump-frames and --consume read)
+        const bool nv12_i420 = o.nv12_direct && o.i420 && !resize_in && o.dump.empty() && o.dump_frames.empty() && o.consume_w <= 0;
+        const bool fused_resize = o.fused_resize && resize_in;
+        const char *i420_call = !o.i420 ? "none" : (nv12_i420 ? "ms_stitch_nv12_i420" : "ms_bgr_to_i420");
         hipStream_t stitch_stream, recal_stream;
         HIPCHECK(hipStreamCreateWithFlags(&stitch_stream, hipStreamNonBlocking));
         HIPCHECK(hipStreamCreateWithFlags(&recal_stream, hipStreamNonBlocking));
@@ -344,17 +359,25 @@ int main(int argc, char **argv)
         const int RING = 4;
         std::vector<Slot> ring(RING);
         const ms_pano_geom pg = comp.panoGeom();
-        const int ya = pg.canvas_y & ~1, yb = std::min(o.out_h, (pg.canvas_y + pg.dst_roi_final.height + 1) & ~1);
+        int ya = pg.canvas_y & ~1, yb = std::min(o.out_h, (pg.canvas_y + pg.dst_roi_final.height + 1) & ~1);
+        if (nv12_i420) { int rows = 0; comp.i420Rows(ya, rows); yb = ya + rows; }      // the span ms_stitch_nv12_i420 writes (ms_get_i420_rows)
         for (auto &s : ring) {
             s.pano8u.create(o.out_h, o.out_w, MS_8UC3, 3);
             HIPCHECK(hipMemset2D(s.pano8u.data, s.pano8u.step, 0, (size_t)o.out_w * 3, o.out_h));
-            if (o.i420) s.i420.create((yb - ya) * 3 / 2, o.out_w, MS_8UC1, 1, true);
+            if (o.i420) {
+                s.i420.create((yb - ya) * 3 / 2, o.out_w, MS_8UC1, 1, true);
+                if (nv12_i420) {       // ms_stitch_nv12_i420 writes panorama pixels only: black once (Y 16, U = V 128)
+                    HIPCHECK(hipMemset(s.i420.data, 16, (size_t)o.out_w * (yb - ya)));
+                    HIPCHECK(hipMemset(s.i420.data + (size_t)o.out_w * (yb - ya), 128, (size_t)o.out_w * (yb - ya) / 2));
+                }
+            }
             HIPCHECK(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
         }
         BlockingQueue<Slot *> results, free_slots;
         for (auto &s : ring) free_slots.push(&s);
 
         std::vector<unsigned char> last_pano((size_t)o.out_w * o.out_h * 3);
+        std::vector<unsigned char> last_i420(o.i420 ? (size_t)o.out_w * (yb - ya) * 3 / 2 : 0);
         unsigned long long checksum = 0;
         long long consumed = 0;
         DevMat encoder_frame;                           // consume(): the resized, letterboxed I420 frame the encoder gets (one buffer: the consumer is one thread)
@@ -378,9 +401,14 @@ int main(int argc, char **argv)
                     HIPCHECK(hipStreamSynchronize(consume_stream));
                     if (s->seq == o.frames - 1) for (unsigned char b : encoder_host) consume_checksum = (consume_checksum ^ b) * 1099511628211ull;
                 }
+                if (nv12_i420) {                        // the encoder's input is all there is: the planes come to the host, no canvas exists
+                    HIPCHECK(hipMemcpy(last_i420.data(), s->i420.data, last_i420.size(), hipMemcpyDeviceToHost));
+                } else {
+                if (o.i420 && !o.dump_i420.empty() && s->seq == o.frames - 1) HIPCHECK(hipMemcpy(last_i420.data(), s->i420.data, last_i420.size(), hipMemcpyDeviceToHost));
                 if (s->seq == o.frames - 1 || frames_file) {           // keep the last panorama for the checksum / dump (every one for --dump-frames)
                     HIPCHECK(hipMemcpy2D(last_pano.data(), (size_t)o.out_w * 3, s->pano8u.data, s->pano8u.step, (size_t)o.out_w * 3, o.out_h, hipMemcpyDeviceToHost));
                     if (frames_file) frames_file_ok = frames_file_ok && fwrite(last_pano.data(), 1, last_pano.size(), frames_file) == last_pano.size();
+                }
                 }
                 ++consumed;
                 free_slots.push(s);
@@ -500,7 +528,8 @@ int main(int argc, char **argv)
                 std::lock_guard<std::mutex> lk(imgs.mu);
                 HIPCHECK(hipStreamSynchronize(upload_stream));                            // (no copy still reads the pinned frame)
                 unsigned char *p = imgs.v[o.ramp_view].p;
-                for (size_t i = 0; i < host_frame_bytes; ++i) p[i] = (unsigned char)std::min(255.0, std::floor(p[i] * o.ramp_factor + 0.5));
+                const size_t ramp_bytes = o.nv12 ? (size_t)o.w * o.h : host_frame_bytes;      // NV12: the Y plane only
+                for (size_t i = 0; i < ramp_bytes; ++i) p[i] = (unsigned char)std::min(255.0, std::floor(p[i] * o.ramp_factor + 0.5));
             }
             if (o.upload || t == 0 || ramp_now) {
                 std::lock_guard<std::mutex> lk(imgs.mu);                                  // imgs.lock() ... imgs.unlock()
@@ -511,7 +540,7 @@ int main(int argc, char **argv)
                     HIPCHECK(hipMemcpyAsync(full_imgs[0].data, host_slab, host_frame_bytes * o.views, hipMemcpyHostToDevice, upload_stream));
                 HIPCHECK(hipEventRecord(up_done[ib], upload_stream));
                 HIPCHECK(hipStreamWaitEvent(stitch_stream, up_done[ib], 0));
-                if (o.nv12 && !(o.nv12_direct && !resize_in)) {             // cvtColor(YUV2BGR_NV12) of all cameras in one launch (also with --nv12-direct when the frames are resized first: the resize works on BGR) (the reference: per camera, on the CPU, networking.cpp:45-47).
+                if (o.nv12 && !(o.nv12_direct && !resize_in) && !fused_resize) {             // cvtColor(YUV2BGR_NV12) of all cameras in one launch (also with --nv12-direct when the frames are resized first: the resize works on BGR) (the reference: per camera, on the CPU, networking.cpp:45-47).
                                           // On the STITCH stream (round 4): the upload stream then carries nothing but the copies, so the PCIe link -- the limit of
                                           // this path -- never waits for a kernel; the conversion (one latency-bound launch) rides in front of the frame's stitch
                     std::vector<ms_image> a(o.views), d(o.views);
@@ -520,15 +549,21 @@ int main(int argc, char **argv)
                 }
             }
             if (resize_in) {                        // timed.cpp:75-85: cuda::resize(full_imgs[i], resized, Size(), compose_scale, compose_scale)
-                msshim::cuda::resize(full_imgs, small_imgs, cal.rig.compose_scale, cal.rig.compose_scale, (ms_stream)stitch_stream);      // all views, one launch
+                if (fused_resize) msshim::cuda::resize_nv12(nv12_imgs, small_imgs, cal.rig.compose_scale, cal.rig.compose_scale, (ms_stream)stitch_stream);      // planes -> small_imgs, one pass
+                else msshim::cuda::resize(full_imgs, small_imgs, cal.rig.compose_scale, cal.rig.compose_scale, (ms_stream)stitch_stream);      // all views, one launch
                 comp.stitch_one(small_imgs, &s->pano8u, (DevMat *)nullptr, (ms_stream)stitch_stream);
+            } else if (nv12_i420) {        // planes in, planes out: neither BGR frames nor a BGR canvas
+                std::vector<DevMat> planes(1, s->i420);
+                comp.stitch_one_nv12_i420(nv12_imgs, planes, (ms_stream)stitch_stream);
             } else if (o.nv12_direct)      // (resize_in is false here)
                 comp.stitch_one_nv12(nv12_imgs, &s->pano8u, (DevMat *)nullptr, (ms_stream)stitch_stream);      // the warp converts each tap itself: no BGR frames on the device at all
             else
                 comp.stitch_one(full_imgs, &s->pano8u, (DevMat *)nullptr, (ms_stream)stitch_stream);
-            if (o.track_gains > 0 && (t + 1) % o.track_gains == 0)      // exposure tracking: enqueue-only, behind the stitch that read the same frames
-                comp.trackGains(resize_in ? small_imgs : full_imgs, 0, 0, (ms_stream)stitch_stream);
-            if (o.i420) {
+            if (o.track_gains > 0 && (t + 1) % o.track_gains == 0) {    // exposure tracking: enqueue-only, behind the stitch that read the same frames
+                if (o.nv12_direct && !resize_in) comp.trackGainsNv12(nv12_imgs, 0, 0, (ms_stream)stitch_stream);      // (no BGR frames exist)
+                else comp.trackGains(resize_in ? small_imgs : full_imgs, 0, 0, (ms_stream)stitch_stream);
+            }
+            if (o.i420 && !nv12_i420) {
                 ms_image rows{s->pano8u.data + (size_t)ya * s->pano8u.step, s->pano8u.step, o.out_w, yb - ya, MS_8UC3};
                 ms_image dst = msshim::wrap(s->i420);
                 msshim::check(ms_bgr_to_i420(&rows, &dst, (ms_stream)stitch_stream));       // cvtColor(BGR2YUV_I420), timed.cpp:308-316
@@ -587,6 +622,11 @@ int main(int argc, char **argv)
             HIPCHECK(hipFree(a.data)); HIPCHECK(hipFree(b.data));
         }
         for (unsigned char b : last_pano) checksum = (checksum ^ b) * 1099511628211ull;   // FNV-1a over the last 8U panorama
+        if (!o.dump_i420.empty()) {
+            FILE *f = fopen(o.dump_i420.c_str(), "wb");
+            if (!f || fwrite(last_i420.data(), 1, last_i420.size(), f) != last_i420.size()) { fprintf(stderr, "cannot write %s\n", o.dump_i420.c_str()); return 2; }
+            fclose(f);
+        }
         if (!o.dump.empty()) {
             FILE *f = fopen(o.dump.c_str(), "wb");
             if (!f || fwrite(last_pano.data(), 1, last_pano.size(), f) != last_pano.size()) { fprintf(stderr, "cannot write %s\n", o.dump.c_str()); return 2; }
@@ -594,10 +634,10 @@ int main(int argc, char **argv)
         }
         printf("{\"app\": \"stitch_app\", \"views\": %d, \"src\": \"%dx%d\", \"out\": \"%dx%d\", \"bands\": %d, \"cpw\": %s, \"i420\": %s, \"nv12\": %s, \"nv12_direct\": %s, \"upload\": %s, "
                "\"frames\": %lld, \"seconds\": %.4f, \"frames_per_s\": %.1f, \"recalibrations\": %d, \"mesh_solver_iterations\": %d, \"max_mesh_displacement_px\": %.2f, "
-               "\"orb_keypoints\": %lld, \"ratio_matches\": %lld, \"ransac_inliers\": %lld, \"update_mask_margin\": %d, \"update_mask_equals_sync_rebuild\": %s, \"consume_image_height\": %d, \"consume_checksum\": \"%016llx\", \"checksum\": \"%016llx\", \"degraded_frames\": %lld",
+               "\"orb_keypoints\": %lld, \"ratio_matches\": %lld, \"ransac_inliers\": %lld, \"update_mask_margin\": %d, \"update_mask_equals_sync_rebuild\": %s, \"consume_image_height\": %d, \"consume_checksum\": \"%016llx\", \"checksum\": \"%016llx\", \"degraded_frames\": %lld, \"i420_call\": \"%s\", \"fused_resize\": %s",
                o.views, o.w, o.h, o.out_w, o.out_h, pg.num_bands, o.cpw ? "true" : "false", o.i420 ? "true" : "false", o.nv12 ? "true" : "false", o.nv12_direct ? "true" : "false", o.upload ? "true" : "false",
                consumed, secs, consumed / secs, recalibrations.load(), solver_iterations.load(), (double)max_disp.load(),
-               total_keypoints.load(), total_matches.load(), total_inliers.load(), o.update_mask, selfcheck < 0 ? "null" : (selfcheck ? "true" : "false"), consume_image_height, consume_checksum, checksum, degraded_frames);
+               total_keypoints.load(), total_matches.load(), total_inliers.load(), o.update_mask, selfcheck < 0 ? "null" : (selfcheck ? "true" : "false"), consume_image_height, consume_checksum, checksum, degraded_frames, i420_call, fused_resize ? "true" : "false");
         if (o.track_gains > 0) {
             std::vector<double> g((size_t)o.views);
             int ok = 0, singular = 0;

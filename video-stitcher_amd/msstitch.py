@@ -112,6 +112,7 @@ EXPORTS = [
     "ms_save_tables", "ms_load_tables", "ms_calib_shape", "ms_stitch_nv12", "ms_get_plan_stats", "ms_get_stitch_kernels",
     "ms_set_active_views", "ms_get_active_views",
     "ms_gain_track_default_params", "ms_gain_stats", "ms_track_gains", "ms_get_gains",
+    "ms_stitch_nv12_i420", "ms_gain_stats_nv12", "ms_track_gains_nv12", "ms_nv12_resize_linear_batch",
 ]
 
 _lib = None
@@ -432,6 +433,37 @@ def resize_linear_batch_prepared(srcs, dsts, fx=0.0, fy=0.0):
     n = len(srcs)
     a = (Image * n)(*[img(t) for t in srcs]); b = (Image * n)(*[img(t) for t in dsts])
     fn = load().ms_resize_linear_batch
+    cfx, cfy = C.c_double(fx), C.c_double(fy)
+
+    def run(stream=None):
+        _chk(fn(a, b, n, cfx, cfy, stream if stream is not None else _stream()))
+    run.keep = (srcs, dsts)
+    return run
+
+
+def _nv12_resize_dsts(srcs, dsize, fx, fy):
+    import numpy as np
+    rows, cols = srcs[0].shape[0] * 2 // 3, srcs[0].shape[1]
+    if dsize is None:
+        dsize = (int(np.rint(cols * fx)), int(np.rint(rows * fy)))
+    else:
+        fx = fy = 0.0
+    return [_new((dsize[1], dsize[0], 3), _torch().uint8) for _ in srcs], fx, fy
+
+
+def nv12_resize_linear_batch(srcs, dsize=None, fx=0.0, fy=0.0):
+    """ms_nv12_resize_linear_batch: cvtColor(YUV2BGR_NV12) + cuda::resize of n NV12 frames ((H * 3 / 2) x W uint8 tensors, one geometry) in one pass; returns
+    the list of resized BGR tensors (= resize_linear_batch(nv12_to_bgr_batch(srcs), ...), bit for bit)."""
+    dsts, fx, fy = _nv12_resize_dsts(srcs, dsize, fx, fy)
+    nv12_resize_linear_batch_prepared(srcs, dsts, fx, fy)()
+    return dsts
+
+
+def nv12_resize_linear_batch_prepared(srcs, dsts, fx=0.0, fy=0.0):
+    """ms_nv12_resize_linear_batch with the descriptors marshalled once; returns a callable(stream_handle=None) for timed loops."""
+    n = len(srcs)
+    a = (Image * n)(*[img(t) for t in srcs]); b = (Image * n)(*[img(t) for t in dsts])
+    fn = load().ms_nv12_resize_linear_batch
     cfx, cfy = C.c_double(fx), C.c_double(fy)
 
     def run(stream=None):
@@ -868,6 +900,26 @@ class Compositor:
         views = self._one_frame(frames)
         _chk(load().ms_track_gains(self._ctx, views, C.byref(p), st))
 
+    def gain_stats_nv12(self, frames_nv12, stride):
+        """ms_gain_stats_nv12: gain_stats with the frames given as the cameras' NV12 planes (list per view of uint8 (H * 3 / 2) x W cuda tensors)."""
+        import numpy as np
+        N = np.zeros((self.n, self.n), dtype=np.int64)
+        S = np.zeros((self.n, self.n), dtype=np.int64)
+        views = self._one_frame(frames_nv12)
+        _chk(load().ms_gain_stats_nv12(self._ctx, views, int(stride), N.ctypes.data_as(C.c_void_p), S.ctypes.data_as(C.c_void_p), _stream()))
+        return N, S
+
+    def track_gains_nv12(self, frames_nv12, stride=None, smoothing=None, stream=None):
+        """ms_track_gains_nv12: track_gains from the cameras' NV12 planes; shares the gain state with track_gains (calls may alternate)."""
+        p = gain_track_default_params()
+        if stride is not None:
+            p.stride = int(stride)
+        if smoothing is not None:
+            p.smoothing = float(smoothing)
+        st = _stream() if stream is None else C.c_void_p(getattr(stream, "cuda_stream", stream))
+        views = self._one_frame(frames_nv12)
+        _chk(load().ms_track_gains_nv12(self._ctx, views, C.byref(p), st))
+
     def gains(self, stream=None, counters=False):
         """ms_get_gains: the gains the next stitch on the stream uses (numpy float64); with counters=True also (solves_ok, solves_singular)."""
         import numpy as np
@@ -916,6 +968,20 @@ class Compositor:
             _chk(fn(ctx, n, views, oi, stream if stream is not None else _stream()))
         run.keepalive = (frames, out_i420, views, oi)
         return run
+
+    def prepared_nv12_i420(self, frames_nv12, out_i420):
+        n, views, _, _ = self._tables(frames_nv12, None, None)
+        oi = (Image * n)(*[img(t) for t in out_i420])
+        fn, ctx = load().ms_stitch_nv12_i420, self._ctx
+
+        def run(stream=None):
+            _chk(fn(ctx, n, views, oi, stream if stream is not None else _stream()))
+        run.keepalive = (frames_nv12, out_i420, views, oi)
+        return run
+
+    def stitch_nv12_i420(self, frames_nv12, out_i420):
+        """ms_stitch_nv12_i420: the cameras' NV12 planes in, the encoder's planar I420 out (buffers as stitch_i420)."""
+        self.prepared_nv12_i420(frames_nv12, out_i420)()
 
     def stitch_i420(self, frames, out_i420):
         """The panorama as planar I420 (encoder input), written by the level-0 band kernel: no 8UC3 canvas, no conversion pass."""

@@ -37,6 +37,13 @@ template <class Mat> void resize(const std::vector<Mat> &src, std::vector<Mat> &
     for (size_t i = 0; i < src.size(); ++i) { a[i] = wrap(src[i]); d[i] = wrap(dst[i]); }
     check(ms_resize_linear_batch(a.data(), d.data(), (int)src.size(), fx, fy, s));
 }
+// the same for cameras that deliver NV12 (defs.h:10-17): cvtColor(YUV2BGR_NV12) (networking.cpp:45-47) + that resize in one pass from the planes; src[i] = 8UC1 (rows * 3 / 2) x cols
+template <class Mat> void resize_nv12(const std::vector<Mat> &src_nv12, std::vector<Mat> &dst, double fx, double fy, ms_stream s = nullptr)
+{
+    std::vector<ms_image> a(src_nv12.size()), d(dst.size());
+    for (size_t i = 0; i < src_nv12.size(); ++i) { a[i] = wrap(src_nv12[i]); d[i] = wrap(dst[i]); }
+    check(ms_nv12_resize_linear_batch(a.data(), d.data(), (int)src_nv12.size(), fx, fy, s));
+}
 template <class Mat> void copyMakeBorder(const Mat &src, Mat &dst, int top, int bottom, int left, int right, int borderType, ms_stream s = nullptr)
 { ms_image a = wrap(src), d = wrap(dst); check(ms_copy_make_border(&a, &d, top, bottom, left, right, borderType, s)); }
 template <class Mat> void pyrDown(const Mat &src, Mat &dst, ms_stream s = nullptr)
@@ -114,6 +121,18 @@ public:
         if ((int)v.size() != n_) throw Error(MS_ERR_INVALID, "trackGains: one image per view");
         check(ms_track_gains(ctx_, v.data(), &prm, s));
     }
+    // ... from the cameras' NV12 frames (8UC1, (rows * 3 / 2) x cols): the same statistic and gain state, no BGR copy
+    template <class Mat> void trackGainsNv12(const std::vector<Mat> &nv12_imgs, int stride = 0, double smoothing = 0, ms_stream s = nullptr)
+    {
+        ms_gain_track_params prm;
+        check(ms_gain_track_default_params(&prm));
+        if (stride > 0) prm.stride = stride;
+        if (smoothing > 0) prm.smoothing = smoothing;
+        std::vector<ms_image> v;
+        for (const Mat &m : nv12_imgs) v.push_back(wrap(m));
+        if ((int)v.size() != n_) throw Error(MS_ERR_INVALID, "trackGainsNv12: one image per view");
+        check(ms_track_gains_nv12(ctx_, v.data(), &prm, s));
+    }
     std::vector<double> gains(ms_stream s = nullptr)       // gc->gains() as the next stitch on `s` uses them (waits for `s`)
     {
         std::vector<double> g((size_t)n_);
@@ -153,6 +172,14 @@ public:
         for (const Mat &m : full_imgs) v.push_back(wrap(m));
         for (const Mat &m : i420) o.push_back(wrap(m));
         check(ms_stitch_i420(ctx_, (int)(v.size() / n_), v.data(), o.data(), s));
+    }
+    // ... with the cameras' NV12 frames as input: neither BGR frames nor a BGR canvas
+    template <class Mat> void stitch_one_nv12_i420(const std::vector<Mat> &nv12_imgs, std::vector<Mat> &i420, ms_stream s = nullptr)
+    {
+        std::vector<ms_image> v, o;
+        for (const Mat &m : nv12_imgs) v.push_back(wrap(m));
+        for (const Mat &m : i420) o.push_back(wrap(m));
+        check(ms_stitch_nv12_i420(ctx_, (int)(v.size() / n_), v.data(), o.data(), s));
     }
     void i420Rows(int &first_canvas_row, int &rows) const { check(ms_get_i420_rows(ctx_, &first_canvas_row, &rows)); }
     // MultiBandBlender::feed_online(img, idx, stream) / blend(dst, dst_mask, gpuOut, true) call shape (timed.cpp:110,137)

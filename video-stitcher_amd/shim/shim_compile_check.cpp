@@ -29,6 +29,9 @@ int shim_compile_check()
         comp.blend(&a, (FakeGpuMat *)nullptr);
         std::vector<FakeGpuMat> slabs(1);
         comp.stitch_one_i420(frames, slabs);
+        comp.stitch_one_nv12_i420(frames, slabs);
+        comp.trackGainsNv12(frames, 4, 0.25);
+        msshim::cuda::resize_nv12(frames, frames, 0.82, 0.82);
         // MeshWarper over ImageFeatures / MatchesInfo shaped types
         struct Pt { float x, y; }; struct KeyPoint { Pt pt; }; struct Size { int width, height; };
         struct Features { Size img_size; std::vector<KeyPoint> keypoints; };
