@@ -90,6 +90,23 @@ MS_API int ms_dist_mesh_exchange(ms_dist *d, int root, const ms_dist_mesh_update
  * (the caller drops the update). */
 MS_API int ms_dist_apply_meshes(ms_ctx *ctx, const ms_dist_mesh_update *upd, long long next_frame, int *applied, ms_stream stream);
 
+/* ---- exposure tracking of one column group (extends ms_track_gains to ranks; ms_stitch.h "Exposure tracking on column shards") -----------------------
+ * Collective over the n_peers ranks of ONE column group, called by each of them at the same point of its frame sequence with the same `peers` (the ranks of the
+ * group in column-shard order, this rank among them), stride and smoothing: this rank's partial statistic (ms_gain_stats_partial / _nv12 of `views`, one frame
+ * set), an all-gather of the partials inside the group -- one grouped exchange of ms_dist_send / ms_dist_recv per peer, device memory -- and
+ * ms_track_gains_from_partials over all of them in `peers` order.  Every rank adds the same integers in the same order and runs the same solve: the gain states
+ * of the group stay bit-identical, and no gain ever crosses the wire (n_peers x ms_gain_partial_bytes do: 4.1 KB per peer for 16 views).
+ *   scratch_dev: DEVICE, n_peers * ms_gain_partial_bytes(ctx) bytes, 8-byte aligned, owned by the caller, not reused before `stream` has passed the call.
+ *   RCCL transport: the call only enqueues on `stream`.  HOST transport: it waits for `stream` inside its sends / receives, as for every device buffer.
+ *   A rank whose own arguments are refused (a frame of the wrong size, a view-sharded context ...) still takes part, with a zeroed partial: every rank of the
+ *   group, this one included where its context can count (not a view-sharded / FeatherBlender / uninitialised one), then counts one rejected update and keeps its
+ *   gains, nobody is left waiting, and this rank returns the error.  Null pointers, a bad `peers` list and
+ *   a struct_size mismatch are refused before anything is posted: they are programming errors the peers would see as a timeout.
+ * Not covered: several frame-parallel groups are independent trackers -- keep them in step with ms_get_gains on one group, a host broadcast
+ * and ms_set_gain -- and the active-view set is not carried across ranks: the caller applies ms_set_active_views on every rank itself. */
+MS_API int ms_dist_track_gains(ms_dist *d, ms_ctx *ctx, const int *peers, int n_peers, const ms_image *views, int nv12, const ms_gain_track_params *prm,
+                               void *scratch_dev, ms_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

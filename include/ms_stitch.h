@@ -381,6 +381,9 @@ MS_API int ms_get_active_views(const ms_ctx *ctx, unsigned *mask);
  *   ms_track_gains is enqueue-only (no allocation, no copy to the host, no wait for the GPU) and callable while another thread stitches (contract of
  *     ms_set_active_views).  ms_gain_stats is the statistics alone, blocking, for tests and diagnostics: N and S (num_views x num_views long long each) to the
  *     HOST.  ms_get_gains waits for `stream` and returns the gains the next stitch on it will use (num_views doubles) and the solve counters (may be NULL).
+ *     Ordering against stitches on ANOTHER stream: the kernel that publishes the gains runs behind the last ms_stitch* enqueued on the context, and the next
+ *     ms_stitch* waits for it, so every frame is composited with the gains before or after an update, never a mix of the two; the statistics kernel still overlaps
+ *     the stitch, the publication does not.  On one stream nothing is added.
  *   ms_gain_track_default_params: stride 4, smoothing 0.25 -- starting values, not tuned on a rig.
  *   NV12 sources (the cameras' format, defs.h:10-17; ms_stitch_nv12 callers).  ms_gain_stats_nv12 / ms_track_gains_nv12 are the same statistic, solve, smoothing
  *     and publication with the pixel read from the planes: views_nv12 = num_views DEVICE 8UC1 images of (src_height * 3 / 2) x src_width, ONE frame.  For the
@@ -390,8 +393,8 @@ MS_API int ms_get_active_views(const ms_ctx *ctx, unsigned *mask);
  *     thread stitches, inactive views never read, no path brings an older gain back); both forms share the context's accumulators and gain state and may alternate.
  *     They read the maps only: they also work where ms_stitch_nv12 is refused (debug_simple_kernels).  MS_ERR_INVALID also for an odd source size.
  * MS_ERR_INVALID: null context / params / views, struct_size mismatch, stride < 1, smoothing outside (0, 1], an image of the wrong size or type.
- * MS_ERR_STATE: before ms_init_blender.  MS_ERR_UNSUPPORTED: view-sharded and column-sharded contexts (a shard does not hold every overlap: track on one
- * unsharded context and hand the gains out with ms_set_gain) and FeatherBlender contexts (ms_init_feather). */
+ * MS_ERR_STATE: before ms_init_blender.  MS_ERR_UNSUPPORTED: view-sharded and column-sharded contexts (a shard does not hold every overlap: column shards
+ * track with ms_gain_stats_partial / ms_track_gains_from_partials below, ranks with ms_dist_track_gains) and FeatherBlender contexts (ms_init_feather). */
 typedef struct ms_gain_track_params {
     unsigned struct_size;   /* sizeof of the caller's struct; mismatch = MS_ERR_INVALID (as ms_config)                   */
     int stride;             /* >= 1: every stride-th pano column and row is sampled                                      */
@@ -403,6 +406,49 @@ MS_API int ms_track_gains(ms_ctx *ctx, const ms_image *views, const ms_gain_trac
 MS_API int ms_gain_stats_nv12(ms_ctx *ctx, const ms_image *views_nv12, int stride, long long *N_host, long long *S_host, ms_stream stream);
 MS_API int ms_track_gains_nv12(ms_ctx *ctx, const ms_image *views_nv12, const ms_gain_track_params *prm, ms_stream stream);
 MS_API int ms_get_gains(ms_ctx *ctx, double *gains_host, int *solves_ok, int *solves_singular, ms_stream stream);
+
+/* Exposure tracking on column shards (extends ms_track_gains / ms_gain_stats above to ms_config.col_shards > 1; allowed on unsharded contexts too).  The statistic
+ * is a set of integer sums, and the column windows (ms_get_col_window) partition the ROI columns: a pano pixel (u, v) is a sample of shard k iff it is a sample as
+ * defined above and col_begin <= u - T.x < col_end.  Every sample belongs to exactly one shard, so the shards' raw sums add up, integer for integer, to the
+ * unsharded cnt and S; every shard then runs the same deterministic solve on the same integers and reaches bit-identical gains, with no host in the loop and no
+ * gain ever exchanged.  On a context without column shards the window is the whole ROI.
+ *   A partial: ms_gain_partial_bytes(ctx) bytes of caller-owned DEVICE memory, 8-byte aligned (valid after ms_create: it depends on num_views only; 0 for a null
+ *     context).  Eight 32-bit words -- magic, num_views, the active-view mask, stride, T.x, T.y, T.width, T.height -- then cnt[i][j] (symmetric) and S[i][j],
+ *     num_views x num_views unsigned 64-bit each: the raw accumulators, BEFORE the max(1, cnt) rule.  The size is the caller's responsibility: only the header
+ *     is checked, a shorter buffer is read or written past its end.
+ *   ms_gain_stats_partial / ms_gain_stats_partial_nv12 write this context's partial from one frame set on `stream` (the kernel of ms_track_gains over the window's
+ *     lattice columns, then one small launch that stores header and sums).  ms_track_gains_from_partials takes n_partials (1 .. 16) DEVICE pointers in a HOST array
+ *     -- normally one per shard of the group, in the same order on every shard -- and on `stream`: checks that every header equals what this context and this call
+ *     expect (magic, num_views, active set, prm->stride, T), adds the integers partial by partial, then does exactly what ms_track_gains does behind its
+ *     statistics: N = max(1, cnt) on the pairs whose ROIs meet, I, the solve over the active views, smoothing in double, publication into every view table a
+ *     stitch may read.  On a header mismatch nothing changes and one rejected update is counted (ms_get_gain_track_counters); no error surfaces later.
+ *     ms_gain_stats_partial + ms_track_gains_from_partials of that one partial on an unsharded context == ms_track_gains, bit for bit.
+ *   Both are enqueue-only (no allocation, no copy to the host, no wait for the GPU) and callable while another thread stitches: the contract of ms_track_gains.
+ *     They share the context's accumulators and gain state with ms_track_gains / ms_gain_stats, and every "no older gain comes back" guarantee above holds.
+ *     The caller orders the partials' producers before ms_track_gains_from_partials (same stream, or an event); partials that arrive from other GPUs are moved
+ *     by the caller (ms_dist_track_gains does it for a column group).
+ *   ms_get_gain_views: the views the caller uploads for a time step it tracks on.  Bit v set = view v is active and either its warped ROI meets the window's
+ *     columns (these, and no others, are read by ms_gain_stats_partial) or ms_stitch reads it (ms_get_needed_views).  The first set is defined on the warp ROI
+ *     BEFORE seam cutting, so it holds views ms_get_needed_views lacks; the second holds views whose ROI ends just outside the window but whose blend weights
+ *     reach into the pyramid halo of the window.  The union is what a step that is both stitched and tracked needs.  Views outside the mask are never read by
+ *     ms_gain_stats_partial: their ms_image may be all-zero.
+ *   ms_get_gain_track_counters waits for `stream` (as ms_get_gains): updates solved, singular systems, rejected updates since ms_create.
+ * View shards stay out: a pair statistic needs both views' pixels at the same sample, and a view shard holds only its own views' pixels.
+ * MS_ERR_INVALID: null context / params / views / partial(s), a partial not 8-byte aligned, n_partials outside [1, 16], struct_size mismatch, stride < 1,
+ * smoothing outside (0, 1], an image of the wrong size or type (views the statistic reads only).  MS_ERR_STATE: before ms_init_blender.  MS_ERR_UNSUPPORTED:
+ * view-sharded contexts and FeatherBlender contexts. */
+typedef struct ms_gain_track_counters {
+    unsigned struct_size;   /* sizeof of the caller's struct, set by the caller; mismatch = MS_ERR_INVALID                */
+    int solves_ok;          /* updates that solved and published (ms_track_gains* and ms_track_gains_from_partials)      */
+    int solves_singular;    /* singular systems: nothing changed                                                         */
+    int updates_rejected;   /* ms_track_gains_from_partials calls whose partials' headers did not agree: nothing changed */
+} ms_gain_track_counters;
+MS_API size_t ms_gain_partial_bytes(const ms_ctx *ctx);
+MS_API int ms_get_gain_views(const ms_ctx *ctx, unsigned *mask);
+MS_API int ms_gain_stats_partial(ms_ctx *ctx, const ms_image *views, int stride, void *partial_dev, ms_stream stream);
+MS_API int ms_gain_stats_partial_nv12(ms_ctx *ctx, const ms_image *views_nv12, int stride, void *partial_dev, ms_stream stream);
+MS_API int ms_track_gains_from_partials(ms_ctx *ctx, const void *const *partials_dev, int n_partials, const ms_gain_track_params *prm, ms_stream stream);
+MS_API int ms_get_gain_track_counters(ms_ctx *ctx, ms_gain_track_counters *out, ms_stream stream);
 
 /* MeshWarper::convertMeshesToMap for one view (APP/meshwarper.cpp:823-886): N x M vertex mesh (HOST fp32,
  * forward positions in view-ROI pixels) -> dense backward maps x_mesh/y_mesh, double-buffered; takes

@@ -251,9 +251,10 @@ __global__ void __launch_bounds__(256) k_gain_export(GainTrackViews V, unsigned 
     __syncthreads();
     for (int i = p; i < 2 * nn; i += 256) acc[i] = 0ull;
 }
-// statistics -> I -> solve over the active views -> smooth -> state and every listed view table; one workgroup
-__global__ void __launch_bounds__(256) k_gain_update(GainTrackViews V, GainTrackTables W, unsigned long long *__restrict__ acc, double *__restrict__ state,
-                                                     int *__restrict__ counters, double lambda)
+// statistics -> I -> solve over the active views -> smooth -> state and every listed view table; one workgroup of 256.  `acc` = the accumulators of this
+// context (k_gain_update) or the sum of the shards' partials in LDS (k_gain_update_partials): one body, so both routes run the same arithmetic in the same order.
+__device__ __forceinline__ void gain_update_body(const GainTrackViews &V, const GainTrackTables &W, const unsigned long long *acc, double *__restrict__ state,
+                                                 int *__restrict__ counters, double lambda)
 {
     __shared__ int s_N[MS_MAX_VIEWS * MS_MAX_VIEWS];
     __shared__ double s_I[MS_MAX_VIEWS * MS_MAX_VIEWS], s_g[MS_MAX_VIEWS];
@@ -281,7 +282,54 @@ __global__ void __launch_bounds__(256) k_gain_update(GainTrackViews V, GainTrack
         state[p] = g;
         for (int t = 0; t < W.n; ++t) W.tab[t][p].gain = (float)g;
     }
+}
+__global__ void __launch_bounds__(256) k_gain_update(GainTrackViews V, GainTrackTables W, unsigned long long *__restrict__ acc, double *__restrict__ state,
+                                                     int *__restrict__ counters, double lambda)
+{
+    gain_update_body(V, W, acc, state, counters, lambda);
+    for (int i = threadIdx.x; i < 2 * V.n * V.n; i += 256) acc[i] = 0ull;      // (behind the body's barriers: every read of a cell is done)
+}
+
+// ---- partial statistics: column shards (ms_gain_stats_partial / ms_track_gains_from_partials) ------------------------------------------------------
+// k_gain_stats over the lattice columns of this context's window IS the partial statistic: the launcher hands it a lattice whose origin is the window's first
+// sample column (V.T.x, V.nsx), so the kernel that reads the pixels is the one ms_track_gains runs.  k_gain_partial_export moves the raw accumulators into the
+// caller's buffer behind a header and clears them for the next call; plain vector stores.
+__global__ void __launch_bounds__(256) k_gain_partial_export(int n, GainPartialHeader H, unsigned long long *__restrict__ acc, unsigned *__restrict__ out)
+{
+    const int nn = n * n, p = threadIdx.x;
+    unsigned long long *body = reinterpret_cast<unsigned long long *>(out + sizeof(GainPartialHeader) / sizeof(unsigned));
+    if (p == 0) { out[0] = H.magic; out[1] = H.n; out[2] = H.active; out[3] = H.stride; out[4] = (unsigned)H.tx; out[5] = (unsigned)H.ty; out[6] = (unsigned)H.tw; out[7] = (unsigned)H.th; }
+    if (p < nn) {
+        const int i = p / n, j = p % n;
+        body[p] = acc[min(i, j) * n + max(i, j)];             // (k_gain_stats keeps cnt at i <= j only)
+        body[nn + p] = acc[nn + p];
+    }
+    __syncthreads();
     for (int i = p; i < 2 * nn; i += 256) acc[i] = 0ull;
+}
+// P partials -> header check -> integer sums in LDS, partial by partial in the order given -> gain_update_body.  One workgroup of 256.  A header that differs from
+// what this context and this call expect (another rig, active set, stride or lattice origin; or not a partial at all): nothing changes, one rejected update counted.
+__global__ void __launch_bounds__(256) k_gain_update_partials(GainTrackViews V, GainTrackTables W, GainPartialHeader H, GainPartials P, double *__restrict__ state,
+                                                              int *__restrict__ counters, double lambda)
+{
+    __shared__ unsigned long long s_sum[2 * MS_MAX_VIEWS * MS_MAX_VIEWS];
+    const int nn = V.n * V.n, p = threadIdx.x;
+    constexpr int HW = sizeof(GainPartialHeader) / sizeof(unsigned);
+    const unsigned want[HW] = {H.magic, H.n, H.active, H.stride, (unsigned)H.tx, (unsigned)H.ty, (unsigned)H.tw, (unsigned)H.th};
+    int bad = 0;
+    for (int k = p; k < P.n * HW; k += 256)
+        bad |= reinterpret_cast<const unsigned *>(P.p[k / HW])[k % HW] != want[k % HW];
+    if (__syncthreads_or(bad)) {                              // (uniform: every thread leaves)
+        if (p == 0) counters[2] += 1;
+        return;
+    }
+    for (int i = p; i < 2 * nn; i += 256) {
+        unsigned long long s = 0ull;
+        for (int k = 0; k < P.n; ++k) s += P.p[k][HW / 2 + i];
+        s_sum[i] = s;
+    }
+    __syncthreads();
+    gain_update_body(V, W, s_sum, state, counters, lambda);
 }
 
 }  // namespace
@@ -362,6 +410,18 @@ int launch_gain_export(const GainTrackViews &V, GainTrackBuf *buf, hipStream_t s
 int launch_gain_update(const GainTrackViews &V, const GainTrackTables &W, GainTrackBuf *buf, double lambda, hipStream_t st)
 {
     k_gain_update<<<1, 256, 0, st>>>(V, W, buf->acc, buf->state, &buf->solves_ok, lambda);
+    MS_LAUNCH_CHECK();
+    return MS_OK;
+}
+int launch_gain_partial_export(const GainTrackViews &V, const GainPartialHeader &H, GainTrackBuf *buf, void *partial, hipStream_t st)
+{
+    k_gain_partial_export<<<1, 256, 0, st>>>(V.n, H, buf->acc, (unsigned *)partial);
+    MS_LAUNCH_CHECK();
+    return MS_OK;
+}
+int launch_gain_update_partials(const GainTrackViews &V, const GainTrackTables &W, const GainPartialHeader &H, const GainPartials &P, GainTrackBuf *buf, double lambda, hipStream_t st)
+{
+    k_gain_update_partials<<<1, 256, 0, st>>>(V, W, H, P, buf->state, &buf->solves_ok, lambda);
     MS_LAUNCH_CHECK();
     return MS_OK;
 }

@@ -1786,6 +1786,10 @@ struct ms_ctx {
     hipEvent_t gain_ev = nullptr;      // behind the last ms_track_gains / ms_gain_stats: they share the accumulators, whatever their streams
     bool gain_ev_set = false;
     std::atomic<bool> gain_tracked{false};   // the device state may differ from `gain`
+    // A gain update publishes into view tables a stitch reads: on another stream than the stitches it runs behind the last stitch enqueued, and the next stitch waits for
+    // it (gain_ev), so a frame is composited with the gains before or after an update, never a mix.  Guarded by tables_mu, which both enqueues hold.
+    hipStream_t gain_pub_stream = nullptr;
+    bool gain_pub_pending = false;
     std::mutex gain_mu;                // guards gain_ev_set, `gain` and the enqueues that use the accumulators; taken AFTER tables_mu, never held across a GPU wait by ms_track_gains
 };
 
@@ -3314,14 +3318,30 @@ int ms_gain_track_default_params(ms_gain_track_params *prm)
 }
 
 // what every entry point checks, and the by-value kernel argument (taken under tables_mu: the active set and the geometry cannot change meanwhile).
-// nv12: the views are the cameras' planes (8UC1, (src_height * 3 / 2) x src_width); the maps are all the statistic needs, so the tiled warp is not required
-static int gain_track_args(ms_ctx *c, const char *who, const ms_image *views, int stride, bool nv12, GainTrackViews &V)
+// nv12: the views are the cameras' planes (8UC1, (src_height * 3 / 2) x src_width); the maps are all the statistic needs, so the tiled warp is not required.
+// mode GAIN_FULL: ms_gain_stats / ms_track_gains, the whole lattice, no shards.  GAIN_WINDOW: ms_gain_stats_partial, the lattice columns of this context's column
+// window (the whole ROI without column shards); only the views whose ROI meets those columns are checked and read.  GAIN_GEOM: ms_track_gains_from_partials, no frames.
+enum { GAIN_FULL = 0, GAIN_WINDOW = 1, GAIN_GEOM = 2 };
+static unsigned gain_window_reads(const ms_ctx *c, unsigned active)      // the active views whose warped ROI meets the window's columns
+{
+    const ms_rect T = c->bg.dst_roi_final;
+    const bool windowed = c->col_end > c->col_begin;
+    const int x0 = T.x + (windowed ? c->col_begin : 0), x1 = T.x + (windowed ? c->col_end : T.width);
+    unsigned m = 0;
+    for (int v = 0; v < c->N; ++v)
+        if (((active >> v) & 1u) && c->roi[v].x < x1 && c->roi[v].x + c->roi[v].width > x0) m |= 1u << v;
+    return m;
+}
+static int gain_track_args(ms_ctx *c, const char *who, const ms_image *views, int stride, bool nv12, GainTrackViews &V, int mode = GAIN_FULL, GainPartialHeader *H = nullptr)
 {
     if (!c->blender_ready) return fail(MS_ERR_STATE, "%s: call ms_init_blender first", who);
-    if (sharded_ctx(c) || c->cfg.view_shards > 1 || c->cfg.col_shards > 1)
-        return fail(MS_ERR_UNSUPPORTED, "%s: not for a view- or column-sharded context (a shard does not hold every overlap); track on an unsharded context and hand the gains out with ms_set_gain", who);
+    if (mode == GAIN_FULL) {
+        if (sharded_ctx(c) || c->cfg.view_shards > 1 || c->cfg.col_shards > 1)
+            return fail(MS_ERR_UNSUPPORTED, "%s: not for a view- or column-sharded context (a shard does not hold every overlap); column shards track with ms_gain_stats_partial / ms_track_gains_from_partials", who);
+    } else if (sharded_ctx(c) || c->cfg.view_shards > 1)
+        return fail(MS_ERR_UNSUPPORTED, "%s: not for a view-sharded context (a pair statistic needs both views' pixels at one sample; a view shard holds only its own)", who);
     if (c->feather_sharpness >= 0.f) return fail(MS_ERR_UNSUPPORTED, "%s: not for FeatherBlender contexts (ms_init_feather)", who);
-    MS_CHECK(views, "%s: null views", who);
+    if (mode != GAIN_GEOM) MS_CHECK(views, "%s: null views", who);
     MS_CHECK(stride >= 1, "%s: stride %d < 1", who, stride);
     if (nv12) MS_CHECK((c->cfg.src_width & 1) == 0 && (c->cfg.src_height & 1) == 0, "%s: NV12 frames have an even size, the context's source size is %dx%d", who, c->cfg.src_width, c->cfg.src_height);
     const int N = c->N;
@@ -3331,10 +3351,19 @@ static int gain_track_args(ms_ctx *c, const char *who, const ms_image *views, in
     V.active = c->act ? c->act->views : all;
     V.T = c->bg.dst_roi_final; V.stride = stride;
     V.nsx = div_up(V.T.width, stride); V.nsy = div_up(V.T.height, stride);
+    if (H) *H = GainPartialHeader{GAIN_PARTIAL_MAGIC, (unsigned)N, V.active, (unsigned)stride, V.T.x, V.T.y, V.T.width, V.T.height};
+    unsigned reads = V.active;
+    if (mode == GAIN_WINDOW) {
+        reads = gain_window_reads(c, V.active);
+        if (c->col_end > c->col_begin) {      // the samples with col_begin <= u - T.x < col_end: the lattice starts at the window's first sample column
+            const int s0 = div_up(c->col_begin, stride), s1 = div_up(c->col_end, stride);
+            V.T.x += s0 * stride; V.nsx = s1 - s0;
+        }
+    }
     for (int v = 0; v < N; ++v) {
         V.xmap[v] = (const float *)c->maps.p + c->map_off[v]; V.pitch[v] = c->map_pitch[v];
         V.roi[v] = c->roi[v];
-        if (!((V.active >> v) & 1u)) continue;      // a view left out is never read
+        if (mode == GAIN_GEOM || !((reads >> v) & 1u)) continue;      // a view left out, or one no sample of the window lies in, is never read
         if (nv12)
             MS_CHECK(views[v].data && views[v].type == MS_8UC1 && views[v].rows == V.src_h * 3 / 2 && views[v].cols == V.src_w && views[v].step >= (size_t)V.src_w,
                      "%s: view %d must be the NV12 planes of a %dx%d frame (DEVICE 8UC1, %d rows)", who, v, V.src_w, V.src_h, V.src_h * 3 / 2);
@@ -3345,6 +3374,16 @@ static int gain_track_args(ms_ctx *c, const char *who, const ms_image *views, in
     }
     return MS_OK;
 }
+// every view table a later stitch may read (tables_mu held): the full set, its enqueue-only-mask-update copy, the cached subsets
+static GainTrackTables gain_track_tables(ms_ctx *c)
+{
+    GainTrackTables W{};
+    W.tab[W.n++] = (ViewDesc *)c->view_tab.p;
+    if (c->alt.view_tab.p && (int)c->alt.h_views.size() == c->N) W.tab[W.n++] = (ViewDesc *)c->alt.view_tab.p;
+    for (auto &T : c->subsets)
+        if (T->view_tab.p && W.n < GAIN_TRACK_MAX_TABLES) W.tab[W.n++] = (ViewDesc *)T->view_tab.p;
+    return W;
+}
 // the accumulators are shared by every call of the context: behind the last one, and behind whatever may still rewrite a view table (gain_mu held)
 static int gain_track_order(ms_ctx *c, hipStream_t st)
 {
@@ -3353,6 +3392,20 @@ static int gain_track_order(ms_ctx *c, hipStream_t st)
     std::lock_guard<std::mutex> mk(c->mesh_mu);
     if (c->tab_wait) MS_HIP(hipStreamWaitEvent(st, c->tab_ready, 0));
     return MS_OK;
+}
+
+// a call that publishes gains (tables_mu and gain_mu held): behind every stitch that may still read the view tables, when that stitch runs on another stream
+static int gain_publish_order(ms_ctx *c, hipStream_t st)
+{
+    if (c->stitch_pending && c->last_stream_set && c->last_stream != st) MS_HIP(hipStreamWaitEvent(st, c->last_stitch, 0));
+    return MS_OK;
+}
+// ... and once gain_ev is recorded behind it, the next stitch on another stream waits for that event
+static void gain_published(ms_ctx *c, hipStream_t st)
+{
+    c->gain_ev_set = true;
+    c->gain_tracked = true;
+    c->gain_pub_stream = st; c->gain_pub_pending = true;
 }
 
 // ms_gain_stats / ms_gain_stats_nv12: only the kernel that reads the pixels differs
@@ -3391,19 +3444,15 @@ static int track_gains_impl(ms_ctx *c, const char *who, const ms_image *views, c
     std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);      // held for the enqueue, never for a GPU wait: the table list below stays valid until the kernels are in the stream
     GainTrackViews V;
     if (int e = gain_track_args(c, who, views, prm->stride, nv12, V)) return e;
-    GainTrackTables W{};
-    W.tab[W.n++] = (ViewDesc *)c->view_tab.p;
-    if (c->alt.view_tab.p && (int)c->alt.h_views.size() == c->N) W.tab[W.n++] = (ViewDesc *)c->alt.view_tab.p;
-    for (auto &T : c->subsets)
-        if (T->view_tab.p && W.n < GAIN_TRACK_MAX_TABLES) W.tab[W.n++] = (ViewDesc *)T->view_tab.p;
+    const GainTrackTables W = gain_track_tables(c);
     GainTrackBuf *B = (GainTrackBuf *)c->gain_buf.p;
     std::lock_guard<std::mutex> gk(c->gain_mu);
     if (int e = gain_track_order(c, st)) return e;
     if (int e = launch_gain_stats(V, B, nv12, st)) return e;
+    if (int e = gain_publish_order(c, st)) return e;
     if (int e = launch_gain_update(V, W, B, prm->smoothing, st)) return e;
     MS_HIP(hipEventRecord(c->gain_ev, st));
-    c->gain_ev_set = true;
-    c->gain_tracked = true;
+    gain_published(c, st);
     return MS_OK;
 }
 
@@ -3443,6 +3492,104 @@ int ms_get_gains(ms_ctx *c, double *gains_host, int *solves_ok, int *solves_sing
     for (int v = 0; v < c->N; ++v) gains_host[v] = c->gain[v] = g[v];
     if (solves_ok) *solves_ok = cnt[0];
     if (solves_singular) *solves_singular = cnt[1];
+    return MS_OK;
+}
+
+// ---- exposure tracking on column shards: partial statistics in caller-owned device memory, summed and solved on the device ---------------------------------------
+size_t ms_gain_partial_bytes(const ms_ctx *c)
+{
+    if (!c) { (void)fail(MS_ERR_INVALID, "ms_gain_partial_bytes: null context"); return 0; }
+    return gain_partial_bytes(c->N);
+}
+
+int ms_get_gain_views(const ms_ctx *cc, unsigned *mask)
+{
+    if (!mask) return fail(MS_ERR_INVALID, "ms_get_gain_views: null output");
+    if (!cc) return fail(MS_ERR_INVALID, "ms_get_gain_views: null context");
+    ms_ctx *c = const_cast<ms_ctx *>(cc);
+    std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);
+    GainTrackViews V;
+    if (int e = gain_track_args(c, "ms_get_gain_views", nullptr, 1, false, V, GAIN_GEOM)) return e;
+    *mask = gain_window_reads(c, V.active) | (c->own_mask & c->needed_mask & V.active);
+    return MS_OK;
+}
+
+static int gain_partial_impl(ms_ctx *c, const char *who, const ms_image *views, int stride, bool nv12, void *partial, ms_stream stream)
+{
+    // (what does not depend on the context first: these checks run, and are tested, without a device)
+    MS_CHECK(partial && ((uintptr_t)partial & 7u) == 0, "%s: the partial must be a DEVICE buffer of ms_gain_partial_bytes, 8-byte aligned", who);
+    MS_CHECK(views, "%s: null views", who);
+    MS_CHECK(stride >= 1, "%s: stride %d < 1", who, stride);
+    if (!c) return fail(MS_ERR_INVALID, "%s: null context", who);
+    hipStream_t st = as_stream(stream);
+    std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);      // both locks for the enqueue only (as ms_track_gains)
+    GainTrackViews V;
+    GainPartialHeader H;
+    if (int e = gain_track_args(c, who, views, stride, nv12, V, GAIN_WINDOW, &H)) return e;
+    GainTrackBuf *B = (GainTrackBuf *)c->gain_buf.p;
+    std::lock_guard<std::mutex> gk(c->gain_mu);
+    if (int e = gain_track_order(c, st)) return e;
+    if (int e = launch_gain_stats(V, B, nv12, st)) return e;
+    if (int e = launch_gain_partial_export(V, H, B, partial, st)) return e;
+    MS_HIP(hipEventRecord(c->gain_ev, st));
+    c->gain_ev_set = true;
+    return MS_OK;
+}
+int ms_gain_stats_partial(ms_ctx *c, const ms_image *views, int stride, void *partial_dev, ms_stream stream)
+{
+    return gain_partial_impl(c, "ms_gain_stats_partial", views, stride, false, partial_dev, stream);
+}
+int ms_gain_stats_partial_nv12(ms_ctx *c, const ms_image *views_nv12, int stride, void *partial_dev, ms_stream stream)
+{
+    return gain_partial_impl(c, "ms_gain_stats_partial_nv12", views_nv12, stride, true, partial_dev, stream);
+}
+
+int ms_track_gains_from_partials(ms_ctx *c, const void *const *partials, int n_partials, const ms_gain_track_params *prm, ms_stream stream)
+{
+    const char *who = "ms_track_gains_from_partials";
+    if (!prm) return fail(MS_ERR_INVALID, "%s: null params", who);
+    MS_CHECK(prm->struct_size == sizeof(ms_gain_track_params), "%s: ms_gain_track_params.struct_size is %u, this library expects %zu", who, prm->struct_size, sizeof(ms_gain_track_params));
+    MS_CHECK(prm->smoothing > 0.0 && prm->smoothing <= 1.0, "%s: smoothing %g outside (0, 1]", who, prm->smoothing);
+    MS_CHECK(partials, "%s: null partials", who);
+    MS_CHECK(n_partials >= 1 && n_partials <= GAIN_MAX_PARTIALS, "%s: %d partials, not in [1, %d]", who, n_partials, GAIN_MAX_PARTIALS);
+    GainPartials P{};
+    P.n = n_partials;
+    for (int k = 0; k < n_partials; ++k) {
+        MS_CHECK(partials[k] && ((uintptr_t)partials[k] & 7u) == 0, "%s: partial %d is null or not 8-byte aligned", who, k);
+        P.p[k] = (const unsigned long long *)partials[k];
+    }
+    MS_CHECK(prm->stride >= 1, "%s: stride %d < 1", who, prm->stride);
+    if (!c) return fail(MS_ERR_INVALID, "%s: null context", who);
+    hipStream_t st = as_stream(stream);
+    std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);      // held for the enqueue, never for a GPU wait (as ms_track_gains)
+    GainTrackViews V;
+    GainPartialHeader H;
+    if (int e = gain_track_args(c, who, nullptr, prm->stride, false, V, GAIN_GEOM, &H)) return e;
+    const GainTrackTables W = gain_track_tables(c);
+    GainTrackBuf *B = (GainTrackBuf *)c->gain_buf.p;
+    std::lock_guard<std::mutex> gk(c->gain_mu);
+    if (int e = gain_track_order(c, st)) return e;      // (the partials are the caller's: whatever wrote them is ordered before this call by the caller's stream)
+    if (int e = gain_publish_order(c, st)) return e;
+    if (int e = launch_gain_update_partials(V, W, H, P, B, prm->smoothing, st)) return e;
+    MS_HIP(hipEventRecord(c->gain_ev, st));
+    gain_published(c, st);
+    return MS_OK;
+}
+
+int ms_get_gain_track_counters(ms_ctx *c, ms_gain_track_counters *out, ms_stream stream)
+{
+    if (!out) return fail(MS_ERR_INVALID, "ms_get_gain_track_counters: null output");
+    MS_CHECK(out->struct_size == sizeof(ms_gain_track_counters), "ms_get_gain_track_counters: ms_gain_track_counters.struct_size is %u, this library expects %zu", out->struct_size, sizeof(ms_gain_track_counters));
+    if (!c) return fail(MS_ERR_INVALID, "ms_get_gain_track_counters: null context");
+    if (!c->blender_ready || !c->gain_buf.p) return fail(MS_ERR_STATE, "ms_get_gain_track_counters: call ms_init_blender first");
+    hipStream_t st = as_stream(stream);
+    bool wait;
+    { std::lock_guard<std::mutex> gk(c->gain_mu); wait = c->gain_ev_set; }
+    if (wait) MS_HIP(hipStreamWaitEvent(st, c->gain_ev, 0));      // (a track call on another stream)
+    int cnt[3];
+    MS_HIP(hipMemcpyAsync(cnt, &((GainTrackBuf *)c->gain_buf.p)->solves_ok, sizeof(cnt), hipMemcpyDeviceToHost, st));
+    MS_HIP(hipStreamSynchronize(st));
+    out->solves_ok = cnt[0]; out->solves_singular = cnt[1]; out->updates_rejected = cnt[2];
     return MS_OK;
 }
 
@@ -3947,6 +4094,8 @@ static int stitch_impl(ms_ctx *c, int n_frames, const ms_image *views, ms_image 
     // (the reference makes a fresh cuda::Stream per stitch_online call, timed.cpp:64, and relies on the NULL stream for ordering)
     if (c->last_stream_set && c->last_stream != st && c->stitch_pending) MS_HIP(hipStreamWaitEvent(st, c->last_stitch, 0));
     c->last_stream = st; c->last_stream_set = true;
+    if (c->gain_pub_pending && c->gain_pub_stream != st) MS_HIP(hipStreamWaitEvent(st, c->gain_ev, 0));      // a gain update on another stream: this call sees all of it (gain_ev is recorded under tables_mu)
+    c->gain_pub_pending = false;
 
     if (int e = mark(k, nullptr)) return e;
     if (k.S.mode != 2) {       // (finish mode starts from the partial sums: no warp, no pyramids)

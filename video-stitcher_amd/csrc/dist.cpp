@@ -659,4 +659,53 @@ int ms_dist_apply_meshes(ms_ctx *ctx, const ms_dist_mesh_update *upd, long long 
     return MS_OK;
 }
 
+// The partial of this rank, an all-gather inside the column group built from send / recv, then the solve every rank runs on the same integers.
+int ms_dist_track_gains(ms_dist *d, ms_ctx *ctx, const int *peers, int n_peers, const ms_image *views, int nv12, const ms_gain_track_params *prm, void *scratch_dev, ms_stream stream)
+{
+    const char *who = "ms_dist_track_gains";
+    MS_CHECK(d && ctx && peers && prm && scratch_dev, "%s: null argument", who);
+    MS_CHECK(!d->grouping, "%s: inside a group", who);
+    MS_CHECK(n_peers >= 1 && n_peers <= MS_DIST_MAX_RANKS, "%s: %d peers, not in [1, %d]", who, n_peers, MS_DIST_MAX_RANKS);
+    MS_CHECK(prm->struct_size == sizeof(ms_gain_track_params), "%s: ms_gain_track_params.struct_size is %u, this library expects %zu", who, prm->struct_size, sizeof(ms_gain_track_params));
+    MS_CHECK(((uintptr_t)scratch_dev & 7u) == 0, "%s: scratch_dev is not 8-byte aligned", who);
+    int me = -1;
+    for (int k = 0; k < n_peers; ++k) {
+        if (int e = check_peer(d, peers[k], who)) return e;
+        for (int q = 0; q < k; ++q) MS_CHECK(peers[q] != peers[k], "%s: rank %d is listed twice", who, peers[k]);
+        if (peers[k] == d->rank) me = k;
+    }
+    MS_CHECK(me >= 0, "%s: rank %d is not one of the peers", who, d->rank);
+    const size_t pb = ms_gain_partial_bytes(ctx);
+    unsigned char *base = static_cast<unsigned char *>(scratch_dev);
+    // A rank whose partial is refused still takes part, with a zeroed one (no magic word): every rank of the group, this one included, rejects the update alike and
+    // none is left waiting.  (A failing memset is not fatal here: whatever the slot then holds is exchanged, and the error below is returned all the same.)
+    int bad = (nv12 ? ms_gain_stats_partial_nv12 : ms_gain_stats_partial)(ctx, views, prm->stride, base + (size_t)me * pb, stream);
+    std::string why;
+    if (bad) {
+        why = ms_last_error();
+        (void)hipMemsetAsync(base + (size_t)me * pb, 0, pb, as_stream(stream));
+    }
+    if (n_peers > 1) {
+        if (int e = ms_dist_group_begin(d)) return e;
+        int err = MS_OK;
+        for (int k = 0; k < n_peers && !err; ++k) {
+            if (k == me) continue;
+            err = ms_dist_send(d, base + (size_t)me * pb, pb, peers[k], MS_DIST_MEM_DEVICE, stream);
+            if (!err) err = ms_dist_recv(d, base + (size_t)k * pb, pb, peers[k], MS_DIST_MEM_DEVICE, stream);
+        }
+        if (err) {                  // close the group without running it (as ms_dist_gather_slabs)
+            d->grouping = false;
+            d->ops.clear();
+            if (d->transport == MS_DIST_RCCL) (void)rccl().GroupEnd();
+            return err;
+        }
+        if (int e = ms_dist_group_end(d)) return e;
+    }
+    const void *ptrs[MS_DIST_MAX_RANKS];
+    for (int k = 0; k < n_peers; ++k) ptrs[k] = base + (size_t)k * pb;
+    const int rc = ms_track_gains_from_partials(ctx, ptrs, n_peers, prm, stream);      // (with a zeroed partial among them: counts the rejection here as on the peers)
+    if (bad) return fail(bad, "%s: this rank's partial was refused, the group rejects the update: %s", who, why.c_str());
+    return rc;
+}
+
 }  // extern "C"

@@ -69,11 +69,21 @@ struct GainTrackBuf {
     unsigned long long acc[2 * MS_MAX_VIEWS * MS_MAX_VIEWS];
     long long outN[MS_MAX_VIEWS * MS_MAX_VIEWS], outS[MS_MAX_VIEWS * MS_MAX_VIEWS];
     double state[MS_MAX_VIEWS];
-    int solves_ok, solves_singular;
+    int solves_ok, solves_singular, rejected, pad_;
 };
 int launch_gain_stats(const GainTrackViews &V, GainTrackBuf *buf, bool nv12, hipStream_t st);
 int launch_gain_export(const GainTrackViews &V, GainTrackBuf *buf, hipStream_t st);
 int launch_gain_update(const GainTrackViews &V, const GainTrackTables &W, GainTrackBuf *buf, double lambda, hipStream_t st);
+// Partial statistics (ms_gain_stats_partial / ms_track_gains_from_partials): the raw accumulators of one column window in a caller-owned device buffer, so that
+// the windows' integers add up on the device to the unsharded statistic.  Layout of a partial of an n-view context (ms_gain_partial_bytes):
+//   GainPartialHeader, cnt[n * n] (symmetric), S[n * n]  -- unsigned 64-bit each, before the max(1, cnt) rule
+constexpr unsigned GAIN_PARTIAL_MAGIC = 0x50474d53u;               // "SMGP"
+constexpr int GAIN_MAX_PARTIALS = 16;                              // = the largest ms_config.col_shards
+struct GainPartialHeader { unsigned magic, n, active, stride; int tx, ty, tw, th; };      // T = the pano ROI the lattice starts from (the same on every shard)
+struct GainPartials { const unsigned long long *p[GAIN_MAX_PARTIALS]; int n; };
+inline size_t gain_partial_bytes(int n) { return sizeof(GainPartialHeader) + 2 * (size_t)n * n * sizeof(unsigned long long); }
+int launch_gain_partial_export(const GainTrackViews &V, const GainPartialHeader &H, GainTrackBuf *buf, void *partial, hipStream_t st);
+int launch_gain_update_partials(const GainTrackViews &V, const GainTrackTables &W, const GainPartialHeader &H, const GainPartials &P, GainTrackBuf *buf, double lambda, hipStream_t st);
 void feather_weight_map(const uint8_t *mask, int rows, int cols, float sharpness, float *w);
 
 }  // namespace ms

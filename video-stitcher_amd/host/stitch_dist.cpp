@@ -49,6 +49,7 @@ struct Options {
     bool share_gpu = false, cpw = false, checksum = true;
     bool frame_sums = false;          // --frame-sums: print every frame's checksum on stderr (diagnostic)
     bool tables_from_rank0 = false;   // --tables-from-rank0: only rank 0 calibrates; the others build their context from its table blob (ms_save_tables -> ms_dist_broadcast -> ms_load_tables)
+    int track_gains = 0;              // --track-gains K: after every K-th batch each column group re-estimates its gains from the last time step of its batch (ms_dist_track_gains)
     std::string rccl_lib;             // --rccl-lib FILE: ms_dist_set_rccl_library (a deployment's own RCCL, or the loopback implementation the tests substitute)
 };
 
@@ -101,6 +102,9 @@ struct Shared {                                // what the rank threads share: t
     ms_dist_info info{};
     int bands = 0, i_rows = 0, recalibrations = 0;
     std::vector<int> views_read;
+    // --track-gains: every rank's final gains and solve counters (the ranks of one column group must agree bit for bit; frame-parallel groups track on their own frames)
+    std::vector<std::vector<double>> gains;
+    std::vector<ms_gain_track_counters> gain_counters;
     // where each rank's time went (the first real multi-GPU run should explain itself): GPU time of the stitch kernels (events on the
     // stitch stream), time of the gather on the communication stream (events; on the host transport this is host-staged copies), host time blocked in the
     // mesh exchange / the column-shard exchange / the sink's consume loop
@@ -152,6 +156,8 @@ void rank_main(const Options &o, int rank, Shared &sh)
     MSC(ms_get_col_window(ctx, &win_b, &win_e));
     unsigned need = 0;
     MSC(ms_get_needed_views(ctx, &need));
+    unsigned upload = need;                    // with tracking: also the views the partial statistic reads on the time step it tracks on (a superset of `need`)
+    if (o.track_gains > 0) { unsigned gv = 0; MSC(ms_get_gain_views(ctx, &gv)); upload |= gv; }
     std::vector<ms_view_geom> vg(N);
     for (int i = 0; i < N; ++i) MSC(ms_get_view_geom(ctx, i, &vg[i]));
     const size_t per_mesh = (size_t)o.mesh_rows * o.mesh_cols;
@@ -175,7 +181,7 @@ void rank_main(const Options &o, int rank, Shared &sh)
         std::vector<unsigned char> host((size_t)o.w * o.h * 3);
         for (int p = 0; p < POOL; ++p)
             for (int i = 0; i < N; ++i) {
-                if (!((need >> i) & 1u)) continue;
+                if (!((upload >> i) & 1u)) continue;
                 synth_frame(host.data(), o.w, o.h, i, p);
                 HIPC(hipMalloc((void **)&src[(size_t)p * N + i], host.size()));
                 HIPC(hipMemcpy(src[(size_t)p * N + i], host.data(), host.size(), hipMemcpyHostToDevice));
@@ -209,6 +215,13 @@ void rank_main(const Options &o, int rank, Shared &sh)
     auto chroma_span = [&](int b, int e, int *x0) { const int cb = b + pg.canvas_x, ce = e + pg.canvas_x; *x0 = (cb + 1) >> 1; return ((ce + 1) >> 1) - ((cb + 1) >> 1); };
     auto win_bytes = [&](int k) { int x0; const int cw2 = chroma_span(bound(k), bound(k + 1), &x0); return ((size_t)(bound(k + 1) - bound(k)) * i_rows + (size_t)cw2 * i_rows) * F; };
     if (bound(shard) != win_b || bound(shard + 1) != win_e) throw Fail("column window rule out of step with ms_get_col_window");
+    // exposure tracking: the column group's ranks in shard order, room for one partial statistic per rank
+    std::vector<int> peers(S);
+    for (int k = 0; k < S; ++k) peers[k] = leader + k;
+    ms_gain_track_params gprm;
+    MSC(ms_gain_track_default_params(&gprm));
+    void *gain_scratch = nullptr;
+    if (o.track_gains > 0) HIPC(hipMalloc(&gain_scratch, (size_t)S * ms_gain_partial_bytes(ctx)));
     std::vector<unsigned char *> from_shard(S, nullptr);            // leader: packed windows of its shards; shard: its own packed window
     if (S > 1) {
         if (rank == leader) { for (int k = 1; k < S; ++k) HIPC(hipMalloc((void **)&from_shard[k], win_bytes(k))); }
@@ -316,6 +329,9 @@ void rank_main(const Options &o, int rank, Shared &sh)
         t_stitch.begin(st);
         MSC(ms_stitch_i420(ctx, F, views.data(), outs.data(), st));
         t_stitch.end(st);
+        // 3b. exposure tracking: the group's partial statistics of the batch's last time step, all-gathered and solved on every rank; the next batch uses the new gains
+        if (o.track_gains > 0 && (k + 1) % o.track_gains == 0)
+            MSC(ms_dist_track_gains(dist, ctx, peers.data(), S, views.data() + (size_t)(F - 1) * N, 0, &gprm, gain_scratch, st));
         const auto t_shard = tick();
         // 4. column shards: windows to the group's first rank
         if (S > 1) {
@@ -373,6 +389,16 @@ void rank_main(const Options &o, int rank, Shared &sh)
         std::lock_guard<std::mutex> lk(sh.mu);
         sh.frame_sums = sums; sh.seconds = secs; sh.info = info; sh.bands = pg.num_bands; sh.i_rows = i_rows; sh.recalibrations = applied_rounds;
     }
+    if (o.track_gains > 0) {
+        std::vector<double> g(N);
+        ms_gain_track_counters gc{};
+        gc.struct_size = (unsigned)sizeof(gc);
+        MSC(ms_get_gains(ctx, g.data(), nullptr, nullptr, st));
+        MSC(ms_get_gain_track_counters(ctx, &gc, st));
+        std::lock_guard<std::mutex> lk(sh.mu);
+        if ((int)sh.gains.size() < o.gpus) { sh.gains.resize(o.gpus); sh.gain_counters.resize(o.gpus); }
+        sh.gains[rank] = g; sh.gain_counters[rank] = gc;
+    }
     { std::lock_guard<std::mutex> lk(sh.mu); if ((int)sh.views_read.size() < o.gpus) sh.views_read.resize(o.gpus); sh.views_read[rank] = __builtin_popcount(need);
       if ((int)sh.times.size() < o.gpus) sh.times.resize(o.gpus); sh.times[rank] = rt; }
     ms_dist_destroy(dist);
@@ -384,6 +410,7 @@ void rank_main(const Options &o, int rank, Shared &sh)
         (void)hipEventDestroy(stitched[b]); (void)hipEventDestroy(sent[b]);
     }
     for (unsigned char *p : from_shard) if (p) (void)hipFree(p);
+    if (gain_scratch) (void)hipFree(gain_scratch);
     (void)hipStreamDestroy(cs);
     (void)hipStreamDestroy(st);
 }
@@ -414,6 +441,7 @@ int main(int argc, char **argv)
         else if (k == "--frame-sums") o.frame_sums = true;
         else if (k == "--tables-from-rank0") o.tables_from_rank0 = true;
         else if (k == "--rccl-lib") o.rccl_lib = next();
+        else if (k == "--track-gains") o.track_gains = atoi(next());
         else { fprintf(stderr, "unknown option %s\n", k.c_str()); return 2; }
     }
     int ndev = 0;
@@ -458,7 +486,21 @@ int main(int argc, char **argv)
     const long long frames_done = o.checksum ? (long long)sh.frame_sums.size() : o.frames;
     char rccl_path[1024] = "";      // the file the RCCL entry points were resolved from (host transport: never resolved, stays empty)
     if (sh.info.transport == MS_DIST_RCCL) (void)ms_dist_rccl_library_path(rccl_path, sizeof rccl_path);
-    printf("{\"app\": \"stitch_dist\", \"gpus\": %d, \"col_shards\": %d, \"groups\": %d, \"share_gpu\": %s, \"views\": %d, \"src\": \"%dx%d\", \"out\": \"%dx%d\", \"bands\": %d, "
+    std::string gains_json;       // --track-gains: the first group's gains (%.17g: the doubles round-trip), whether every rank of each group holds the same bits, rank 0's counters
+    if (o.track_gains > 0) {
+        bool equal = true;
+        for (int r = 0; r < o.gpus; ++r) {
+            const std::vector<double> &a = sh.gains[r], &b = sh.gains[r / o.col_shards * o.col_shards];
+            equal = equal && a.size() == b.size() && memcmp(a.data(), b.data(), a.size() * sizeof(double)) == 0;
+            equal = equal && memcmp(&sh.gain_counters[r], &sh.gain_counters[r / o.col_shards * o.col_shards], sizeof(ms_gain_track_counters)) == 0;
+        }
+        gains_json = "\"track_gains\": " + std::to_string(o.track_gains) + ", \"gains\": [";
+        for (size_t i = 0; i < sh.gains[0].size(); ++i) { char b[40]; snprintf(b, sizeof(b), "%s%.17g", i ? ", " : "", sh.gains[0][i]); gains_json += b; }
+        gains_json += std::string("], \"gain_ranks_equal\": ") + (equal ? "true" : "false") + ", \"gain_solves_ok\": " + std::to_string(sh.gain_counters[0].solves_ok) +
+                      ", \"gain_solves_singular\": " + std::to_string(sh.gain_counters[0].solves_singular) + ", \"gain_updates_rejected\": " + std::to_string(sh.gain_counters[0].updates_rejected) + ", ";
+    }
+    printf("{\"app\": \"stitch_dist\", %s", gains_json.c_str());
+    printf("\"gpus\": %d, \"col_shards\": %d, \"groups\": %d, \"share_gpu\": %s, \"views\": %d, \"src\": \"%dx%d\", \"out\": \"%dx%d\", \"bands\": %d, "
            "\"cpw\": %s, \"recalib_every\": %d, \"recalibrations_applied\": %d, \"batch\": %d, \"frames\": %lld, \"seconds\": %.4f, \"frames_per_s\": %.1f, "
            "\"dist\": {\"transport\": \"%s\", \"nranks\": %d, \"comm_nranks\": %d, \"rccl_version\": %d, \"librccl_path\": \"%s\", \"devices\": %s, \"pci_bus_ids\": %s}, "
            "\"views_read_per_rank\": %s, \"per_rank\": %s, \"i420_rows\": %d, \"first_frame_checksum\": \"%016llx\", \"last_frame_checksum\": \"%016llx\", \"checksum_all\": \"%016llx\"}\n",

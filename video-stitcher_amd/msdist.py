@@ -15,7 +15,7 @@ MAX_RANKS = 16
 EXPORTS = [
     "ms_dist_unique_id", "ms_dist_create", "ms_dist_destroy", "ms_dist_get_info", "ms_dist_send", "ms_dist_recv", "ms_dist_group_begin",
     "ms_dist_group_end", "ms_dist_broadcast", "ms_dist_barrier", "ms_dist_gather_slabs", "ms_dist_mesh_exchange", "ms_dist_apply_meshes",
-    "ms_dist_set_rccl_library", "ms_dist_rccl_library_path",
+    "ms_dist_set_rccl_library", "ms_dist_rccl_library_path", "ms_dist_track_gains",
 ]
 
 
@@ -123,6 +123,23 @@ class Dist:
         if self.rank == sink:
             arr = (C.c_void_p * self.nranks)(*[None if (t is None) else t.data_ptr() for t in recv])
         ms._chk(ms.load().ms_dist_gather_slabs(self._h, p, C.c_size_t(n), arr, int(sink), _stream(slab)))
+
+    def track_gains(self, comp, peers, frames, scratch=None, nv12=False, stride=None, smoothing=None):
+        """ms_dist_track_gains: collective over the ranks `peers` of one column group (shard order, the same list on every rank).  comp: this rank's
+        msstitch.Compositor; frames: one frame set (views outside comp.gain_views() may be None); scratch: int64 cuda tensor of
+        len(peers) * comp.gain_partial_bytes() bytes (allocated if None).  Returns the scratch tensor: it must stay alive until the stream has passed the call."""
+        import torch
+        p = ms.gain_track_default_params()
+        if stride is not None:
+            p.stride = int(stride)
+        if smoothing is not None:
+            p.smoothing = float(smoothing)
+        if scratch is None:
+            scratch = torch.zeros(len(peers) * comp.gain_partial_bytes() // 8, dtype=torch.int64, device="cuda")
+        arr = (C.c_int * len(peers))(*[int(r) for r in peers])
+        views = comp._one_frame(frames)
+        ms._chk(ms.load().ms_dist_track_gains(self._h, comp._ctx, arr, len(peers), views, int(bool(nv12)), C.byref(p), C.c_void_p(scratch.data_ptr()), ms._stream()))
+        return scratch
 
     def mesh_exchange(self, root, update, n_views, rows, cols):
         """Collective.  update (root only, or None): (swap_frame, version, mesh_x, mesh_y) with float32 arrays (n_views, rows, cols).

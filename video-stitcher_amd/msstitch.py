@@ -98,6 +98,25 @@ def gain_track_default_params():
     return p
 
 
+class GainTrackCounters(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("solves_ok", C.c_int), ("solves_singular", C.c_int), ("updates_rejected", C.c_int)]
+
+
+GAIN_PARTIAL_MAGIC = 0x50474d53
+GAIN_PARTIAL_HEADER_WORDS = 8       # magic, num_views, active mask, stride, T.x, T.y, T.width, T.height
+
+
+def parse_gain_partial(partial, n):
+    """A partial of an n-view context (int64 cuda tensor or numpy array) -> (header dict, cnt, S) with cnt / S as n x n int64 numpy arrays (the raw sums)."""
+    import numpy as np
+    a = partial.cpu().numpy() if hasattr(partial, "cpu") else np.asarray(partial)
+    w = a[:GAIN_PARTIAL_HEADER_WORDS // 2].view(np.uint32)
+    i = w[4:8].view(np.int32)
+    hdr = {"magic": int(w[0]), "num_views": int(w[1]), "active": int(w[2]), "stride": int(w[3]), "T": (int(i[0]), int(i[1]), int(i[2]), int(i[3]))}
+    body = a[GAIN_PARTIAL_HEADER_WORDS // 2:]
+    return hdr, body[:n * n].reshape(n, n).copy(), body[n * n:2 * n * n].reshape(n, n).copy()
+
+
 EXPORTS = [
     "ms_last_error", "ms_version", "ms_device_count", "ms_remap", "ms_resize_linear", "ms_convert_scale_8u", "ms_convert",
     "ms_copy_make_border", "ms_pyr_down", "ms_pyr_up", "ms_subtract_16s", "ms_add_16s", "ms_add_src_weight_32f",
@@ -113,6 +132,7 @@ EXPORTS = [
     "ms_set_active_views", "ms_get_active_views",
     "ms_gain_track_default_params", "ms_gain_stats", "ms_track_gains", "ms_get_gains",
     "ms_stitch_nv12_i420", "ms_gain_stats_nv12", "ms_track_gains_nv12", "ms_nv12_resize_linear_batch",
+    "ms_gain_partial_bytes", "ms_get_gain_views", "ms_gain_stats_partial", "ms_gain_stats_partial_nv12", "ms_track_gains_from_partials", "ms_get_gain_track_counters",
 ]
 
 _lib = None
@@ -928,6 +948,51 @@ class Compositor:
         st = _stream() if stream is None else C.c_void_p(getattr(stream, "cuda_stream", stream))
         _chk(load().ms_get_gains(self._ctx, g.ctypes.data_as(C.c_void_p), C.byref(ok), C.byref(sing), st))
         return (g, ok.value, sing.value) if counters else g
+
+    def gain_partial_bytes(self):
+        """ms_gain_partial_bytes: size of one partial statistic of this context."""
+        fn = load().ms_gain_partial_bytes
+        fn.restype = C.c_size_t
+        return int(fn(self._ctx))
+
+    def new_gain_partial(self):
+        """A zeroed device buffer for one partial (int64 elements: 8-byte aligned)."""
+        torch = _torch()
+        return torch.zeros(self.gain_partial_bytes() // 8, dtype=torch.int64, device="cuda")
+
+    def gain_views(self):
+        """ms_get_gain_views: bit mask of the views to upload for a time step that is tracked on (those the partial statistic reads, and those ms_stitch reads)."""
+        m = C.c_uint(0)
+        _chk(load().ms_get_gain_views(self._ctx, C.byref(m)))
+        return m.value
+
+    def gain_stats_partial(self, frames, stride, partial=None, nv12=False, stream=None):
+        """ms_gain_stats_partial[_nv12]: this context's column-window share of the overlap statistics into `partial` (new_gain_partial() if None); enqueue-only.  Returns the partial."""
+        if partial is None:
+            partial = self.new_gain_partial()
+        st = _stream() if stream is None else C.c_void_p(getattr(stream, "cuda_stream", stream))
+        views = self._one_frame(frames)
+        fn = load().ms_gain_stats_partial_nv12 if nv12 else load().ms_gain_stats_partial
+        _chk(fn(self._ctx, views, int(stride), C.c_void_p(partial.data_ptr()), st))
+        return partial
+
+    def track_gains_from_partials(self, partials, stride=None, smoothing=None, stream=None):
+        """ms_track_gains_from_partials: sum the partials (device tensors, the same order on every shard), solve, smooth and publish on the stream; enqueue-only."""
+        p = gain_track_default_params()
+        if stride is not None:
+            p.stride = int(stride)
+        if smoothing is not None:
+            p.smoothing = float(smoothing)
+        st = _stream() if stream is None else C.c_void_p(getattr(stream, "cuda_stream", stream))
+        arr = (C.c_void_p * len(partials))(*[t.data_ptr() for t in partials])
+        _chk(load().ms_track_gains_from_partials(self._ctx, arr, len(partials), C.byref(p), st))
+
+    def gain_track_counters(self, stream=None):
+        """ms_get_gain_track_counters: (solves_ok, solves_singular, updates_rejected); waits for the stream."""
+        k = GainTrackCounters(struct_size=C.sizeof(GainTrackCounters))
+        st = _stream() if stream is None else C.c_void_p(getattr(stream, "cuda_stream", stream))
+        _chk(load().ms_get_gain_track_counters(self._ctx, C.byref(k), st))
+        return k.solves_ok, k.solves_singular, k.updates_rejected
 
     def active_views(self):
         """Bit mask of the views the next stitch call composites (ms_get_active_views)."""
