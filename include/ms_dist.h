@@ -103,9 +103,28 @@ MS_API int ms_dist_apply_meshes(ms_ctx *ctx, const ms_dist_mesh_update *upd, lon
  *   gains, nobody is left waiting, and this rank returns the error.  Null pointers, a bad `peers` list and
  *   a struct_size mismatch are refused before anything is posted: they are programming errors the peers would see as a timeout.
  * Not covered: several frame-parallel groups are independent trackers -- keep them in step with ms_get_gains on one group, a host broadcast
- * and ms_set_gain -- and the active-view set is not carried across ranks: the caller applies ms_set_active_views on every rank itself. */
+ * and ms_set_gain -- and the active-view set is not carried across ranks: the caller applies ms_set_active_views on every rank itself.  View-shard groups
+ * track with ms_dist_track_gains_views below. */
 MS_API int ms_dist_track_gains(ms_dist *d, ms_ctx *ctx, const int *peers, int n_peers, const ms_image *views, int nv12, const ms_gain_track_params *prm,
                                void *scratch_dev, ms_stream stream);
+
+/* ---- exposure tracking of one view-shard group (ms_stitch.h "Exposure tracking on view shards") ------------------------------------------------------------------
+ * Collective over the n_peers (1 .. 4) ranks of ONE view-shard group, called by each of them at the same point of its frame sequence with the same `peers` (the
+ * ranks of the group in view-shard order: peers[k] runs the context with view_shard_index k and view_shards = n_peers; this rank among them), stride and
+ * smoothing: this rank's ms_gain_samples / _nv12 of `views` (one frame set; only the views of ms_get_gain_sample_views are read), an all-gather of the sample
+ * buffers inside the group -- one grouped exchange of ms_dist_send / ms_dist_recv per peer, device memory -- and ms_track_gains_from_samples over all of them in
+ * `peers` order.  Every rank forms the same integers and runs the same solve: the gain states of the group stay bit-identical, and no gain crosses the wire.
+ *   scratch_dev: DEVICE, the sum over k of ms_gain_samples_bytes(ctx, prm->stride, k) bytes (sizes differ per peer; any rank can compute all of them), 4-byte
+ *     aligned, owned by the caller, not reused before `stream` has passed the call.  Peer k's buffer starts behind those of the peers before it.
+ *   RCCL transport: the call only enqueues on `stream`.  HOST transport: it waits for `stream` inside its sends / receives, as for every device buffer.
+ *   A rank whose own arguments are refused (a frame of the wrong size ...) still takes part, with a zeroed buffer: every rank of the group, this one included
+ *   where its context can count, then counts one rejected update and keeps its gains, nobody is left waiting, and this rank returns the error.  Null pointers,
+ *   a bad `peers` list (a rank twice, this rank missing, this rank at another position than its context's view_shard_index), a struct_size mismatch, stride < 1
+ *   and a context whose view_shards is not n_peers (1 for an unsharded context) are refused before the producer runs and before anything is posted: they are
+ *   programming errors the peers would see as a timeout, and slots sized for other blocks of views than the producer writes.
+ * Not covered: keeping several frame-parallel groups in step, and carrying the active-view set across ranks (as for ms_dist_track_gains). */
+MS_API int ms_dist_track_gains_views(ms_dist *d, ms_ctx *ctx, const int *peers, int n_peers, const ms_image *views, int nv12, const ms_gain_track_params *prm,
+                                     void *scratch_dev, ms_stream stream);
 
 #ifdef __cplusplus
 }

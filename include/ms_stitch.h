@@ -394,7 +394,8 @@ MS_API int ms_get_active_views(const ms_ctx *ctx, unsigned *mask);
  *     They read the maps only: they also work where ms_stitch_nv12 is refused (debug_simple_kernels).  MS_ERR_INVALID also for an odd source size.
  * MS_ERR_INVALID: null context / params / views, struct_size mismatch, stride < 1, smoothing outside (0, 1], an image of the wrong size or type.
  * MS_ERR_STATE: before ms_init_blender.  MS_ERR_UNSUPPORTED: view-sharded and column-sharded contexts (a shard does not hold every overlap: column shards
- * track with ms_gain_stats_partial / ms_track_gains_from_partials below, ranks with ms_dist_track_gains) and FeatherBlender contexts (ms_init_feather). */
+ * track with ms_gain_stats_partial / ms_track_gains_from_partials below, view shards with ms_gain_samples / ms_track_gains_from_samples further below, ranks
+ * with ms_dist_track_gains / ms_dist_track_gains_views) and FeatherBlender contexts (ms_init_feather). */
 typedef struct ms_gain_track_params {
     unsigned struct_size;   /* sizeof of the caller's struct; mismatch = MS_ERR_INVALID (as ms_config)                   */
     int stride;             /* >= 1: every stride-th pano column and row is sampled                                      */
@@ -433,15 +434,16 @@ MS_API int ms_get_gains(ms_ctx *ctx, double *gains_host, int *solves_ok, int *so
  *     reach into the pyramid halo of the window.  The union is what a step that is both stitched and tracked needs.  Views outside the mask are never read by
  *     ms_gain_stats_partial: their ms_image may be all-zero.
  *   ms_get_gain_track_counters waits for `stream` (as ms_get_gains): updates solved, singular systems, rejected updates since ms_create.
- * View shards stay out: a pair statistic needs both views' pixels at the same sample, and a view shard holds only its own views' pixels.
+ * View shards stay out of THESE calls: a pair statistic needs both views' pixels at the same sample, and a view shard holds only its own views' pixels.  They
+ * track through per-view sample vectors: "Exposure tracking on view shards" below.
  * MS_ERR_INVALID: null context / params / views / partial(s), a partial not 8-byte aligned, n_partials outside [1, 16], struct_size mismatch, stride < 1,
  * smoothing outside (0, 1], an image of the wrong size or type (views the statistic reads only).  MS_ERR_STATE: before ms_init_blender.  MS_ERR_UNSUPPORTED:
- * view-sharded contexts and FeatherBlender contexts. */
+ * view-sharded contexts (they have ms_gain_samples / ms_track_gains_from_samples) and FeatherBlender contexts. */
 typedef struct ms_gain_track_counters {
     unsigned struct_size;   /* sizeof of the caller's struct, set by the caller; mismatch = MS_ERR_INVALID                */
     int solves_ok;          /* updates that solved and published (ms_track_gains* and ms_track_gains_from_partials)      */
     int solves_singular;    /* singular systems: nothing changed                                                         */
-    int updates_rejected;   /* ms_track_gains_from_partials calls whose partials' headers did not agree: nothing changed */
+    int updates_rejected;   /* ms_track_gains_from_partials / _from_samples calls whose buffers did not agree: nothing changed */
 } ms_gain_track_counters;
 MS_API size_t ms_gain_partial_bytes(const ms_ctx *ctx);
 MS_API int ms_get_gain_views(const ms_ctx *ctx, unsigned *mask);
@@ -449,6 +451,50 @@ MS_API int ms_gain_stats_partial(ms_ctx *ctx, const ms_image *views, int stride,
 MS_API int ms_gain_stats_partial_nv12(ms_ctx *ctx, const ms_image *views_nv12, int stride, void *partial_dev, ms_stream stream);
 MS_API int ms_track_gains_from_partials(ms_ctx *ctx, const void *const *partials_dev, int n_partials, const ms_gain_track_params *prm, ms_stream stream);
 MS_API int ms_get_gain_track_counters(ms_ctx *ctx, ms_gain_track_counters *out, ms_stream stream);
+
+/* Exposure tracking on view shards (extends ms_track_gains / ms_gain_stats above to ms_config.view_shards > 1 with ms_stitch_partial / ms_stitch_finish; allowed
+ * on unsharded contexts too, which own every view).  A pair statistic needs both views' pixels at one sample, and a view shard holds only its own views' -- but
+ * what a pair needs of view a at a lattice sample is ONE integer: q_a as defined above, or "not seen".  The owner of a view computes it alone, from its own
+ * pixels and the static maps, which every context of the group holds (the shards are created from the same cameras).  So each shard stores the q of its own
+ * views on the lattice (a "sample vector" per view), the buffers are exchanged, and every shard forms cnt and S of every pair from all of them: the integers
+ * k_gain_stats produces on an unsharded context, then the one solve of ms_track_gains.  Gains are bit-identical on every shard and on a single GPU; no host in
+ * the loop, no gain on the wire.
+ *   A sample buffer: ms_gain_samples_bytes(ctx, stride, view_shard_index) bytes of caller-owned DEVICE memory, 4-byte aligned; -1 = this context's own shard, and
+ *     any rank can size any peer's buffer: the size depends on the geometry (cameras, stride, the shard's block of views, the active set) only.  Valid after
+ *     ms_build_maps; 0 for a null context, stride < 1, an index outside [-1, view_shards), a buffer beyond 4 GiB, and the contexts every call below refuses
+ *     (column shards, FeatherBlender).  ms_get_view_shard: the context's (view_shards, view_shard_index); (1, 0) without view sharding.  32-bit words:
+ *       [0] magic 0x56474d53  [1] num_views  [2] active-view mask  [3] stride  [4..7] T.x, T.y, T.width, T.height (dst_roi_final)
+ *       [8] the mask of the views held = owned & active  [9] total bytes  [10..15] 0
+ *       [16 + v], v < num_views: the word offset of view v's data from the start of the buffer; 0 = not held
+ *       then, per held view v in view order, row-major, one word per lattice sample of the rectangle R_v: R_v = the lattice indices (sx, sy), 0 <= sx <
+ *       ceil(T.width / stride), 0 <= sy < ceil(T.height / stride), whose pano pixel (T.x + sx * stride, T.y + sy * stride) lies in roi_v; it may be empty.
+ *       A word is 0 when the view does not see the sample (the truncated map coordinate is outside the source: the rule above), q + 1 otherwise (q < 2^29).
+ *     The size is the caller's responsibility, and every buffer handed to a consumer holds at least 64 + 4 * num_views readable bytes: behind a header that
+ *     passes the checks below, only words inside the stated size are read; behind one that does not, none.
+ *   ms_get_gain_sample_views: the views ms_gain_samples reads = owned & active.  The other entries of `views` are never dereferenced: their ms_image may be
+ *     all-zero.  ms_gain_samples / ms_gain_samples_nv12 (views as for ms_gain_stats_nv12) write this context's buffer from one frame set on `stream`: one launch.
+ *   ms_track_gains_from_samples takes n (1 .. 4 = the largest view_shards) DEVICE pointers in a HOST array, in any order, and on `stream`: checks the headers on
+ *     the device, forms cnt / S over the whole lattice, then does exactly what ms_track_gains does behind its statistics: N = max(1, cnt) on the pairs whose ROIs
+ *     meet, I, the solve over the active views, smoothing in double, publication into every view table a stitch may read.  Rejected -- nothing changes, one
+ *     rejected update is counted (ms_get_gain_track_counters), no error surfaces later -- when a header differs from what this context and this call expect
+ *     (magic, num_views, active set, prm->stride, T, offsets, size), two buffers hold the same view, or an active view is held by none.
+ *     ms_gain_samples + ms_track_gains_from_samples of that one buffer on an unsharded context == ms_track_gains, bit for bit; with views left out
+ *     (ms_set_active_views) those are neither written nor paired.
+ *   ms_gain_stats_from_samples: the statistics alone, blocking, N and S to the HOST as ms_gain_stats; a rejected set reports zeros and is counted.
+ *   All but ms_gain_stats_from_samples are enqueue-only (no allocation, no copy to the host, no wait for the GPU) and callable while another thread stitches.
+ *     They share the context's accumulators, gain state and counters with the routes above and keep their ordering guarantees: no older gain comes back, and a
+ *     frame is composited with the gains before or after an update, never a mix.  The caller orders the buffers' producers before the consumer (same stream,
+ *     or an event); buffers from other GPUs are moved by the caller (ms_dist_track_gains_views does it for a view-shard group).
+ * MS_ERR_INVALID: null context / params / views / buffer(s), a buffer not 4-byte aligned, n outside [1, 4], struct_size mismatch, stride < 1, smoothing outside
+ * (0, 1], an image of the wrong size or type among the views read.  MS_ERR_STATE: before ms_init_blender.  MS_ERR_UNSUPPORTED: FeatherBlender contexts and
+ * contexts with col_shards > 1 (they have the partial route; a combination of the two shardings does not exist). */
+MS_API size_t ms_gain_samples_bytes(const ms_ctx *ctx, int stride, int view_shard_index);
+MS_API int ms_get_view_shard(const ms_ctx *ctx, int *view_shards, int *view_shard_index);
+MS_API int ms_get_gain_sample_views(const ms_ctx *ctx, unsigned *mask);
+MS_API int ms_gain_samples(ms_ctx *ctx, const ms_image *views, int stride, void *samples_dev, ms_stream stream);
+MS_API int ms_gain_samples_nv12(ms_ctx *ctx, const ms_image *views_nv12, int stride, void *samples_dev, ms_stream stream);
+MS_API int ms_gain_stats_from_samples(ms_ctx *ctx, const void *const *samples_dev, int n, int stride, long long *N_host, long long *S_host, ms_stream stream);
+MS_API int ms_track_gains_from_samples(ms_ctx *ctx, const void *const *samples_dev, int n, const ms_gain_track_params *prm, ms_stream stream);
 
 /* MeshWarper::convertMeshesToMap for one view (APP/meshwarper.cpp:823-886): N x M vertex mesh (HOST fp32,
  * forward positions in view-ROI pixels) -> dense backward maps x_mesh/y_mesh, double-buffered; takes

@@ -176,44 +176,31 @@ __device__ __forceinline__ bool rects_meet(const ms_rect &a, const ms_rect &b)
 }
 // NV12: the frames are the cameras' planes (ms_gain_stats_nv12 / ms_track_gains_nv12) -- Y at the truncated coordinate, the UV pair of its 2 x 2 block, through
 // cvtColor's integer formula (nv12_bgr, common.hpp) to the b, g, r the 8UC3 form reads from memory: 1 + 2 bytes per view and sample instead of 3, the same integers.
+// q of view a at the pixel (lx, ly) of its warped ROI, or "not seen": the one copy of map -> source pixel -> q (k_gain_stats and k_gain_samples)
 template <bool NV12>
-__global__ void __launch_bounds__(256) k_gain_stats(GainTrackViews V, unsigned long long *__restrict__ acc)
+__device__ __forceinline__ bool gain_sample_q(const GainTrackViews &V, int a, int lx, int ly, unsigned &q)
 {
-    __shared__ unsigned s_q[MS_MAX_VIEWS][256];
-    __shared__ unsigned long long s_acc[2 * MS_MAX_VIEWS * MS_MAX_VIEWS];
-    const int n = V.n, nn = n * n, tid = threadIdx.y * 64 + threadIdx.x, lane = threadIdx.x;
-    for (int i = tid; i < 2 * nn; i += 256) s_acc[i] = 0ull;
-    const int sx = blockIdx.x * 64 + threadIdx.x, sy = blockIdx.y * 4 + threadIdx.y;
-    const bool inside = sx < V.nsx && sy < V.nsy;
-    const int u = V.T.x + sx * V.stride, v = V.T.y + sy * V.stride;
-    unsigned seen = 0u, wave_seen = 0u;
-    for (int a = 0; a < n; ++a) {
-        if (!((V.active >> a) & 1u)) continue;
-        const ms_rect r = V.roi[a];
-        const int lx = u - r.x, ly = v - r.y;
-        bool s = false;
-        unsigned q = 0u;
-        if (inside && lx >= 0 && ly >= 0 && lx < r.width && ly < r.height) {
-            const size_t at = (size_t)ly * V.pitch[a] + lx;
-            const int xx = f2i_rz(V.xmap[a][at]), yy = f2i_rz(V.xmap[a][at + (size_t)r.height * V.pitch[a]]);      // (ymap follows xmap)
-            if (xx >= 0 && xx < V.src_w && yy >= 0 && yy < V.src_h) {
-                int b0, b1, b2;
-                if constexpr (NV12) {
-                    const uint8_t *uv = V.src[a] + (size_t)(V.src_h + (yy >> 1)) * V.step[a] + (xx & ~1);
-                    const NvRGB c = nv12_bgr(V.src[a][(size_t)yy * V.step[a] + xx], (unsigned)uv[0] | ((unsigned)uv[1] << 8));
-                    b0 = (int)c.b; b1 = (int)c.g; b2 = (int)c.r;
-                } else {
-                    const uint8_t *p = V.src[a] + (size_t)yy * V.step[a] + 3 * xx;
-                    b0 = p[0]; b1 = p[1]; b2 = p[2];
-                }
-                q = (unsigned)llrint(sqrt(static_cast<double>(b0 * b0 + b1 * b1 + b2 * b2)) * 1048576.0);
-                s = true;
-            }
-        }
-        s_q[a][tid] = q;                                      // (read back by this lane only)
-        if (s) seen |= 1u << a;
-        if (__ballot(s)) wave_seen |= 1u << a;                // (wave-uniform)
+    const ms_rect r = V.roi[a];
+    const size_t at = (size_t)ly * V.pitch[a] + lx;
+    const int xx = f2i_rz(V.xmap[a][at]), yy = f2i_rz(V.xmap[a][at + (size_t)r.height * V.pitch[a]]);      // (ymap follows xmap)
+    if (!(xx >= 0 && xx < V.src_w && yy >= 0 && yy < V.src_h)) return false;
+    int b0, b1, b2;
+    if constexpr (NV12) {
+        const uint8_t *uv = V.src[a] + (size_t)(V.src_h + (yy >> 1)) * V.step[a] + (xx & ~1);
+        const NvRGB c = nv12_bgr(V.src[a][(size_t)yy * V.step[a] + xx], (unsigned)uv[0] | ((unsigned)uv[1] << 8));
+        b0 = (int)c.b; b1 = (int)c.g; b2 = (int)c.r;
+    } else {
+        const uint8_t *p = V.src[a] + (size_t)yy * V.step[a] + 3 * xx;
+        b0 = p[0]; b1 = p[1]; b2 = p[2];
     }
+    q = (unsigned)llrint(sqrt(static_cast<double>(b0 * b0 + b1 * b1 + b2 * b2)) * 1048576.0);
+    return true;
+}
+// the pair walk behind the lanes' s_q columns: the one copy of it (k_gain_stats and k_gain_stats_from_samples).  s_acc is zeroed by the caller before.
+__device__ __forceinline__ void gain_pair_sums(int n, unsigned seen, unsigned wave_seen, const unsigned (*s_q)[256], unsigned long long *s_acc,
+                                               unsigned long long *__restrict__ acc, int tid, int lane)
+{
+    const int nn = n * n;
     __syncthreads();
     for (unsigned mi = wave_seen; mi; mi &= mi - 1u) {
         const int i = __ffs(mi) - 1;
@@ -234,6 +221,30 @@ __global__ void __launch_bounds__(256) k_gain_stats(GainTrackViews V, unsigned l
     __syncthreads();
     for (int i = tid; i < 2 * nn; i += 256)
         if (s_acc[i]) atomicAdd(&acc[i], s_acc[i]);
+}
+template <bool NV12>
+__global__ void __launch_bounds__(256) k_gain_stats(GainTrackViews V, unsigned long long *__restrict__ acc)
+{
+    __shared__ unsigned s_q[MS_MAX_VIEWS][256];
+    __shared__ unsigned long long s_acc[2 * MS_MAX_VIEWS * MS_MAX_VIEWS];
+    const int n = V.n, nn = n * n, tid = threadIdx.y * 64 + threadIdx.x, lane = threadIdx.x;
+    for (int i = tid; i < 2 * nn; i += 256) s_acc[i] = 0ull;
+    const int sx = blockIdx.x * 64 + threadIdx.x, sy = blockIdx.y * 4 + threadIdx.y;
+    const bool inside = sx < V.nsx && sy < V.nsy;
+    const int u = V.T.x + sx * V.stride, v = V.T.y + sy * V.stride;
+    unsigned seen = 0u, wave_seen = 0u;
+    for (int a = 0; a < n; ++a) {
+        if (!((V.active >> a) & 1u)) continue;
+        const ms_rect r = V.roi[a];
+        const int lx = u - r.x, ly = v - r.y;
+        bool s = false;
+        unsigned q = 0u;
+        if (inside && lx >= 0 && ly >= 0 && lx < r.width && ly < r.height) s = gain_sample_q<NV12>(V, a, lx, ly, q);
+        s_q[a][tid] = q;                                      // (read back by this lane only)
+        if (s) seen |= 1u << a;
+        if (__ballot(s)) wave_seen |= 1u << a;                // (wave-uniform)
+    }
+    gain_pair_sums(n, seen, wave_seen, s_q, s_acc, acc, tid, lane);
 }
 // N and S as the header states them, from the accumulators; which are cleared for the next call
 __device__ __forceinline__ void gain_cell(const GainTrackViews &V, const unsigned long long *acc, int i, int j, long long &N, long long &S)
@@ -332,6 +343,126 @@ __global__ void __launch_bounds__(256) k_gain_update_partials(GainTrackViews V, 
     gain_update_body(V, W, s_sum, state, counters, lambda);
 }
 
+
+// ---- sample vectors: view shards (ms_gain_samples / ms_track_gains_from_samples) -------------------------------------------------------------------------
+// A view shard holds the pixels of its own views only, so it cannot form a pair sum; it can store what a pair needs of each of its views, q or "not seen" at
+// every lattice sample of the view's rectangle R_v (launchers.hpp).  k_gain_samples: a lane owns one sample of one held view, lanes along sx, so a wave stores
+// one contiguous run of 4-byte words and reads the maps as k_gain_stats does.  The grid is the held views' own 64 x 4 tiles one after the other (first[i] = the
+// first workgroup of the i-th held view): no workgroup for a view of another shard, none beyond a small rectangle because another view's is large.  Workgroup 0
+// also stores header and offset table.
+struct GainSampleOut { unsigned off[MS_MAX_VIEWS]; unsigned held, words; int nheld; unsigned char view[MS_MAX_VIEWS]; unsigned first[MS_MAX_VIEWS + 1]; };
+template <bool NV12>
+__global__ void __launch_bounds__(256) k_gain_samples(GainTrackViews V, GainSampleRects R, GainSampleOut O, unsigned *__restrict__ out)
+{
+    const int tid = threadIdx.y * 64 + threadIdx.x;
+    if (blockIdx.x == 0) {
+        const unsigned hdr[GAIN_SAMPLES_HEADER_WORDS] = {GAIN_SAMPLES_MAGIC, (unsigned)V.n, V.active, (unsigned)V.stride, (unsigned)V.T.x, (unsigned)V.T.y,
+                                                         (unsigned)V.T.width, (unsigned)V.T.height, O.held, O.words * 4u, 0u, 0u, 0u, 0u, 0u, 0u};
+        if (tid < GAIN_SAMPLES_HEADER_WORDS) out[tid] = hdr[tid];
+        else if (tid < GAIN_SAMPLES_HEADER_WORDS + V.n) out[tid] = O.off[tid - GAIN_SAMPLES_HEADER_WORDS];
+    }
+    int i = 0;
+    while (i < O.nheld && blockIdx.x >= O.first[i + 1]) ++i;      // (uniform; <= 16 steps)
+    if (i >= O.nheld) return;                                     // (the lone workgroup of a buffer without samples)
+    const int a = O.view[i], tile = blockIdx.x - O.first[i], tiles_x = (R.w[a] + 63) / 64;
+    const int rx = (tile % tiles_x) * 64 + threadIdx.x, ry = (tile / tiles_x) * 4 + threadIdx.y;
+    if (rx >= R.w[a] || ry >= R.h[a]) return;
+    const ms_rect r = V.roi[a];
+    const int lx = V.T.x + (R.x0[a] + rx) * V.stride - r.x, ly = V.T.y + (R.y0[a] + ry) * V.stride - r.y;
+    unsigned q = 0u;
+    bool s = false;
+    if (lx >= 0 && ly >= 0 && lx < r.width && ly < r.height) s = gain_sample_q<NV12>(V, a, lx, ly, q);      // (holds by the definition of R_v)
+    out[O.off[a] + (size_t)ry * R.w[a] + rx] = s ? q + 1u : 0u;
+}
+// The headers of the buffers against what this context and this call expect, and which buffer holds which view: s_src[v] = the data of view v.  Every thread of
+// the workgroup (<= 256, at least 128) calls it; the answer is uniform.  Refused: a header word that differs (magic, views, active set, stride, T, padding), a
+// view held twice or held but not active, an active view nobody holds, an offset table or a size other than what gain_sample_offsets gives for the views held
+// -- so behind a header that passes, every word this call reads lies inside the size the producer was given.
+__device__ __forceinline__ bool gain_samples_resolve(const GainTrackViews &V, const GainSampleRects &R, const GainSampleBufs &P, const unsigned **s_src)
+{
+    constexpr int HW = GAIN_SAMPLES_HEADER_WORDS, TW = HW + MS_MAX_VIEWS;
+    __shared__ unsigned s_h[GAIN_MAX_SAMPLE_BUFS][TW];
+    __shared__ int s_good;
+    const int tid = threadIdx.y * blockDim.x + threadIdx.x;
+    if (tid < P.n * TW && tid % TW < HW + V.n) s_h[tid / TW][tid % TW] = P.p[tid / TW][tid % TW];
+    __syncthreads();
+    if (tid == 0) {
+        const unsigned want[8] = {GAIN_SAMPLES_MAGIC, (unsigned)V.n, V.active, (unsigned)V.stride, (unsigned)V.T.x, (unsigned)V.T.y, (unsigned)V.T.width, (unsigned)V.T.height};
+        bool good = true;
+        unsigned have = 0u;
+        for (int k = 0; k < P.n; ++k) {
+            const unsigned *h = s_h[k], held = h[8];
+            for (int w = 0; w < 8; ++w) good = good && h[w] == want[w];
+            for (int w = 10; w < HW; ++w) good = good && h[w] == 0u;
+            good = good && !(held & ~V.active) && !(held & have);
+            unsigned at = HW + V.n;
+            for (int v = 0; v < V.n; ++v) {
+                if ((held >> v) & 1u) {
+                    good = good && h[HW + v] == at;
+                    s_src[v] = P.p[k] + at;
+                    at += (unsigned)R.w[v] * (unsigned)R.h[v];
+                } else
+                    good = good && h[HW + v] == 0u;
+            }
+            good = good && h[9] == at * 4u;
+            have |= held;
+        }
+        s_good = good && have == V.active;
+    }
+    __syncthreads();
+    return s_good != 0;
+}
+// k_gain_stats' lattice walk with s_q filled from the buffers.  Every workgroup checks the headers itself (a few hundred bytes out of L2) before it reads a data
+// word: a set that the update below will reject adds nothing to the accumulators, and no launch has to run between "checked" and "summed".
+__global__ void __launch_bounds__(256) k_gain_stats_from_samples(GainTrackViews V, GainSampleRects R, GainSampleBufs P, unsigned long long *__restrict__ acc)
+{
+    __shared__ unsigned s_q[MS_MAX_VIEWS][256];
+    __shared__ unsigned long long s_acc[2 * MS_MAX_VIEWS * MS_MAX_VIEWS];
+    __shared__ const unsigned *s_src[MS_MAX_VIEWS];
+    const int n = V.n, nn = n * n, tid = threadIdx.y * 64 + threadIdx.x, lane = threadIdx.x;
+    for (int i = tid; i < 2 * nn; i += 256) s_acc[i] = 0ull;
+    if (!gain_samples_resolve(V, R, P, s_src)) return;        // (uniform)
+    const int sx = blockIdx.x * 64 + threadIdx.x, sy = blockIdx.y * 4 + threadIdx.y;
+    const bool inside = sx < V.nsx && sy < V.nsy;
+    unsigned seen = 0u, wave_seen = 0u;
+    for (int a = 0; a < n; ++a) {
+        if (!((V.active >> a) & 1u)) continue;
+        const int rx = sx - R.x0[a], ry = sy - R.y0[a];
+        unsigned word = 0u;
+        if (inside && rx >= 0 && ry >= 0 && rx < R.w[a] && ry < R.h[a]) word = s_src[a][(size_t)ry * R.w[a] + rx];
+        const bool s = word != 0u;
+        s_q[a][tid] = s ? word - 1u : 0u;
+        if (s) seen |= 1u << a;
+        if (__ballot(s)) wave_seen |= 1u << a;                // (wave-uniform)
+    }
+    gain_pair_sums(n, seen, wave_seen, s_q, s_acc, acc, tid, lane);
+}
+// the update behind k_gain_stats_from_samples; one workgroup of 256.  The same check decides: rejected = the accumulators are cleared (nothing was added), one
+// rejected update is counted, gains and tables stay; otherwise k_gain_update.
+__global__ void __launch_bounds__(256) k_gain_update_samples(GainTrackViews V, GainTrackTables W, GainSampleRects R, GainSampleBufs P, unsigned long long *__restrict__ acc,
+                                                             double *__restrict__ state, int *__restrict__ counters, double lambda)
+{
+    __shared__ const unsigned *s_src[MS_MAX_VIEWS];
+    if (gain_samples_resolve(V, R, P, s_src)) gain_update_body(V, W, acc, state, counters, lambda);
+    else if (threadIdx.x == 0) counters[2] += 1;
+    __syncthreads();
+    for (int i = threadIdx.x; i < 2 * V.n * V.n; i += 256) acc[i] = 0ull;
+}
+// ms_gain_stats_from_samples: k_gain_export behind the same check; a rejected set reports zeros and is counted
+__global__ void __launch_bounds__(256) k_gain_export_samples(GainTrackViews V, GainSampleRects R, GainSampleBufs P, unsigned long long *__restrict__ acc,
+                                                             long long *__restrict__ outN, long long *__restrict__ outS, int *__restrict__ counters)
+{
+    __shared__ const unsigned *s_src[MS_MAX_VIEWS];
+    const int n = V.n, nn = n * n, p = threadIdx.x;
+    const bool good = gain_samples_resolve(V, R, P, s_src);
+    if (p < nn) {
+        if (good) gain_cell(V, acc, p / n, p % n, outN[p], outS[p]);
+        else outN[p] = outS[p] = 0;
+    }
+    if (!good && p == 0) counters[2] += 1;
+    __syncthreads();
+    for (int i = p; i < 2 * nn; i += 256) acc[i] = 0ull;
+}
 }  // namespace
 
 // VoronoiSeamFinder over DEVICE masks (contiguous, roi-sized), in place, pairs in the reference's order (PairwiseSeamFinder::run: i < j, overlapping rois)
@@ -426,4 +557,40 @@ int launch_gain_update_partials(const GainTrackViews &V, const GainTrackTables &
     return MS_OK;
 }
 
+int launch_gain_samples(const GainTrackViews &V, const GainSampleRects &R, unsigned held, bool nv12, void *samples, hipStream_t st)
+{
+    GainSampleOut O{};
+    O.held = held;
+    O.words = (unsigned)gain_sample_offsets(V, R, held, O.off);
+    for (int v = 0; v < V.n; ++v) {
+        if (!((held >> v) & 1u) || R.w[v] == 0 || R.h[v] == 0) continue;
+        O.view[O.nheld] = (unsigned char)v;
+        O.first[O.nheld + 1] = O.first[O.nheld] + (unsigned)div_up(R.w[v], 64) * (unsigned)div_up(R.h[v], 4);
+        ++O.nheld;
+    }
+    dim3 b(64, 4), g(std::max(1u, O.first[O.nheld]));
+    if (nv12) k_gain_samples<true><<<g, b, 0, st>>>(V, R, O, (unsigned *)samples);
+    else k_gain_samples<false><<<g, b, 0, st>>>(V, R, O, (unsigned *)samples);
+    MS_LAUNCH_CHECK();
+    return MS_OK;
+}
+int launch_gain_stats_from_samples(const GainTrackViews &V, const GainSampleRects &R, const GainSampleBufs &P, GainTrackBuf *buf, hipStream_t st)
+{
+    dim3 b(64, 4), g(div_up(V.nsx, 64), div_up(V.nsy, 4));
+    k_gain_stats_from_samples<<<g, b, 0, st>>>(V, R, P, buf->acc);
+    MS_LAUNCH_CHECK();
+    return MS_OK;
+}
+int launch_gain_update_samples(const GainTrackViews &V, const GainTrackTables &W, const GainSampleRects &R, const GainSampleBufs &P, GainTrackBuf *buf, double lambda, hipStream_t st)
+{
+    k_gain_update_samples<<<1, 256, 0, st>>>(V, W, R, P, buf->acc, buf->state, &buf->solves_ok, lambda);
+    MS_LAUNCH_CHECK();
+    return MS_OK;
+}
+int launch_gain_export_samples(const GainTrackViews &V, const GainSampleRects &R, const GainSampleBufs &P, GainTrackBuf *buf, hipStream_t st)
+{
+    k_gain_export_samples<<<1, 256, 0, st>>>(V, R, P, buf->acc, buf->outN, buf->outS, &buf->solves_ok);
+    MS_LAUNCH_CHECK();
+    return MS_OK;
+}
 }  // namespace ms

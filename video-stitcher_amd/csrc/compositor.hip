@@ -3321,7 +3321,8 @@ int ms_gain_track_default_params(ms_gain_track_params *prm)
 // nv12: the views are the cameras' planes (8UC1, (src_height * 3 / 2) x src_width); the maps are all the statistic needs, so the tiled warp is not required.
 // mode GAIN_FULL: ms_gain_stats / ms_track_gains, the whole lattice, no shards.  GAIN_WINDOW: ms_gain_stats_partial, the lattice columns of this context's column
 // window (the whole ROI without column shards); only the views whose ROI meets those columns are checked and read.  GAIN_GEOM: ms_track_gains_from_partials, no frames.
-enum { GAIN_FULL = 0, GAIN_WINDOW = 1, GAIN_GEOM = 2 };
+// GAIN_SAMPLES: ms_gain_samples, the whole lattice, the views this context owns (view shards allowed, column shards not); GAIN_SAMPLES_GEOM: the same without frames.
+enum { GAIN_FULL = 0, GAIN_WINDOW = 1, GAIN_GEOM = 2, GAIN_SAMPLES = 3, GAIN_SAMPLES_GEOM = 4 };
 static unsigned gain_window_reads(const ms_ctx *c, unsigned active)      // the active views whose warped ROI meets the window's columns
 {
     const ms_rect T = c->bg.dst_roi_final;
@@ -3338,10 +3339,13 @@ static int gain_track_args(ms_ctx *c, const char *who, const ms_image *views, in
     if (mode == GAIN_FULL) {
         if (sharded_ctx(c) || c->cfg.view_shards > 1 || c->cfg.col_shards > 1)
             return fail(MS_ERR_UNSUPPORTED, "%s: not for a view- or column-sharded context (a shard does not hold every overlap); column shards track with ms_gain_stats_partial / ms_track_gains_from_partials", who);
+    } else if (mode == GAIN_SAMPLES || mode == GAIN_SAMPLES_GEOM) {
+        if (c->cfg.col_shards > 1) return fail(MS_ERR_UNSUPPORTED, "%s: not for a column-sharded context (column shards track with ms_gain_stats_partial / ms_track_gains_from_partials)", who);
     } else if (sharded_ctx(c) || c->cfg.view_shards > 1)
         return fail(MS_ERR_UNSUPPORTED, "%s: not for a view-sharded context (a pair statistic needs both views' pixels at one sample; a view shard holds only its own)", who);
     if (c->feather_sharpness >= 0.f) return fail(MS_ERR_UNSUPPORTED, "%s: not for FeatherBlender contexts (ms_init_feather)", who);
-    if (mode != GAIN_GEOM) MS_CHECK(views, "%s: null views", who);
+    const bool geom = mode == GAIN_GEOM || mode == GAIN_SAMPLES_GEOM;
+    if (!geom) MS_CHECK(views, "%s: null views", who);
     MS_CHECK(stride >= 1, "%s: stride %d < 1", who, stride);
     if (nv12) MS_CHECK((c->cfg.src_width & 1) == 0 && (c->cfg.src_height & 1) == 0, "%s: NV12 frames have an even size, the context's source size is %dx%d", who, c->cfg.src_width, c->cfg.src_height);
     const int N = c->N;
@@ -3353,6 +3357,7 @@ static int gain_track_args(ms_ctx *c, const char *who, const ms_image *views, in
     V.nsx = div_up(V.T.width, stride); V.nsy = div_up(V.T.height, stride);
     if (H) *H = GainPartialHeader{GAIN_PARTIAL_MAGIC, (unsigned)N, V.active, (unsigned)stride, V.T.x, V.T.y, V.T.width, V.T.height};
     unsigned reads = V.active;
+    if (mode == GAIN_SAMPLES) reads = V.active & c->own_mask;
     if (mode == GAIN_WINDOW) {
         reads = gain_window_reads(c, V.active);
         if (c->col_end > c->col_begin) {      // the samples with col_begin <= u - T.x < col_end: the lattice starts at the window's first sample column
@@ -3363,7 +3368,7 @@ static int gain_track_args(ms_ctx *c, const char *who, const ms_image *views, in
     for (int v = 0; v < N; ++v) {
         V.xmap[v] = (const float *)c->maps.p + c->map_off[v]; V.pitch[v] = c->map_pitch[v];
         V.roi[v] = c->roi[v];
-        if (mode == GAIN_GEOM || !((reads >> v) & 1u)) continue;      // a view left out, or one no sample of the window lies in, is never read
+        if (geom || !((reads >> v) & 1u)) continue;      // a view left out, one no sample of the window lies in, or another shard's, is never read
         if (nv12)
             MS_CHECK(views[v].data && views[v].type == MS_8UC1 && views[v].rows == V.src_h * 3 / 2 && views[v].cols == V.src_w && views[v].step >= (size_t)V.src_w,
                      "%s: view %d must be the NV12 planes of a %dx%d frame (DEVICE 8UC1, %d rows)", who, v, V.src_w, V.src_h, V.src_h * 3 / 2);
@@ -3571,6 +3576,169 @@ int ms_track_gains_from_partials(ms_ctx *c, const void *const *partials, int n_p
     if (int e = gain_track_order(c, st)) return e;      // (the partials are the caller's: whatever wrote them is ordered before this call by the caller's stream)
     if (int e = gain_publish_order(c, st)) return e;
     if (int e = launch_gain_update_partials(V, W, H, P, B, prm->smoothing, st)) return e;
+    MS_HIP(hipEventRecord(c->gain_ev, st));
+    gain_published(c, st);
+    return MS_OK;
+}
+
+// ---- exposure tracking on view shards: per-view sample vectors in caller-owned device memory, paired, summed and solved on the device -------------------------------
+static unsigned view_shard_mask(int N, int S, int k)      // the block of views of shard k of S (ms_create)
+{
+    unsigned m = 0;
+    for (int v = k * N / S; v < (k + 1) * N / S; ++v) m |= 1u << v;
+    return m;
+}
+// the lattice geometry of a stride without a call's checks (maps built): what the sizes depend on
+static void gain_lattice(const ms_ctx *c, int stride, unsigned active, GainTrackViews &V)
+{
+    V = GainTrackViews{};
+    V.n = c->N; V.active = active;
+    V.T = c->bg.dst_roi_final; V.stride = stride;
+    V.nsx = div_up(V.T.width, stride); V.nsy = div_up(V.T.height, stride);
+    for (int v = 0; v < c->N; ++v) V.roi[v] = c->roi[v];
+}
+static size_t gain_samples_words(const GainTrackViews &V, unsigned held)
+{
+    GainSampleRects R;
+    unsigned off[MS_MAX_VIEWS];
+    gain_sample_rects(V, R);
+    return gain_sample_offsets(V, R, held, off);
+}
+size_t ms_gain_samples_bytes(const ms_ctx *c, int stride, int view_shard_index)
+{
+    const char *who = "ms_gain_samples_bytes";
+    if (!c) { (void)fail(MS_ERR_INVALID, "%s: null context", who); return 0; }
+    if (stride < 1) { (void)fail(MS_ERR_INVALID, "%s: stride %d < 1", who, stride); return 0; }
+    const int S = c->cfg.view_shards > 1 ? c->cfg.view_shards : 1;
+    if (view_shard_index < -1 || view_shard_index >= S) { (void)fail(MS_ERR_INVALID, "%s: view shard %d of %d", who, view_shard_index, S); return 0; }
+    if (!c->maps_built) { (void)fail(MS_ERR_STATE, "%s: call ms_build_maps first", who); return 0; }
+    if (c->cfg.col_shards > 1 || c->feather_sharpness >= 0.f) { (void)fail(MS_ERR_UNSUPPORTED, "%s: not for column-sharded or FeatherBlender contexts", who); return 0; }
+    std::lock_guard<std::recursive_mutex> tables_lk(const_cast<ms_ctx *>(c)->tables_mu);
+    const unsigned all = (c->N >= 32) ? 0xffffffffu : ((1u << c->N) - 1u);
+    const unsigned active = c->act ? c->act->views : all;
+    const unsigned own = view_shard_index < 0 ? c->own_mask & all : view_shard_mask(c->N, S, view_shard_index);
+    GainTrackViews V;
+    gain_lattice(c, stride, active, V);
+    const size_t words = gain_samples_words(V, own & active);
+    if (words > 0xffffffffu / 4u) { (void)fail(MS_ERR_INVALID, "%s: the buffer would exceed 4 GiB at stride %d; use a larger stride", who, stride); return 0; }
+    return words * 4;
+}
+
+int ms_get_view_shard(const ms_ctx *c, int *view_shards, int *view_shard_index)
+{
+    if (!view_shards || !view_shard_index) return fail(MS_ERR_INVALID, "ms_get_view_shard: null output");
+    if (!c) return fail(MS_ERR_INVALID, "ms_get_view_shard: null context");
+    const bool sharded = c->cfg.view_shards > 1;
+    *view_shards = sharded ? c->cfg.view_shards : 1;
+    *view_shard_index = sharded ? c->cfg.view_shard_index : 0;
+    return MS_OK;
+}
+
+int ms_get_gain_sample_views(const ms_ctx *cc, unsigned *mask)
+{
+    const char *who = "ms_get_gain_sample_views";
+    if (!mask) return fail(MS_ERR_INVALID, "%s: null output", who);
+    if (!cc) return fail(MS_ERR_INVALID, "%s: null context", who);
+    ms_ctx *c = const_cast<ms_ctx *>(cc);
+    std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);
+    GainTrackViews V;
+    if (int e = gain_track_args(c, who, nullptr, 1, false, V, GAIN_SAMPLES_GEOM)) return e;
+    *mask = V.active & c->own_mask;
+    return MS_OK;
+}
+
+static int gain_samples_impl(ms_ctx *c, const char *who, const ms_image *views, int stride, bool nv12, void *samples, ms_stream stream)
+{
+    // (what does not depend on the context first: these checks run, and are tested, without a device)
+    MS_CHECK(samples && ((uintptr_t)samples & 3u) == 0, "%s: the samples must be a DEVICE buffer of ms_gain_samples_bytes, 4-byte aligned", who);
+    MS_CHECK(views, "%s: null views", who);
+    MS_CHECK(stride >= 1, "%s: stride %d < 1", who, stride);
+    if (!c) return fail(MS_ERR_INVALID, "%s: null context", who);
+    hipStream_t st = as_stream(stream);
+    std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);      // for the enqueue only (as ms_track_gains); the accumulators are not used: no gain_mu
+    GainTrackViews V;
+    if (int e = gain_track_args(c, who, views, stride, nv12, V, GAIN_SAMPLES)) return e;
+    GainSampleRects R;
+    gain_sample_rects(V, R);
+    const unsigned held = V.active & c->own_mask;
+    MS_CHECK(gain_samples_words(V, held) <= 0xffffffffu / 4u, "%s: the buffer would exceed 4 GiB at stride %d; use a larger stride", who, stride);
+    return launch_gain_samples(V, R, held, nv12, samples, st);
+}
+int ms_gain_samples(ms_ctx *c, const ms_image *views, int stride, void *samples_dev, ms_stream stream)
+{
+    return gain_samples_impl(c, "ms_gain_samples", views, stride, false, samples_dev, stream);
+}
+int ms_gain_samples_nv12(ms_ctx *c, const ms_image *views_nv12, int stride, void *samples_dev, ms_stream stream)
+{
+    return gain_samples_impl(c, "ms_gain_samples_nv12", views_nv12, stride, true, samples_dev, stream);
+}
+
+// the checks both consumers share; everything that needs no context first
+static int gain_sample_bufs(const char *who, const void *const *samples, int n, int stride, GainSampleBufs &P)
+{
+    MS_CHECK(samples, "%s: null samples", who);
+    MS_CHECK(n >= 1 && n <= GAIN_MAX_SAMPLE_BUFS, "%s: %d sample buffers, not in [1, %d]", who, n, GAIN_MAX_SAMPLE_BUFS);
+    P = GainSampleBufs{};
+    P.n = n;
+    for (int k = 0; k < n; ++k) {
+        MS_CHECK(samples[k] && ((uintptr_t)samples[k] & 3u) == 0, "%s: sample buffer %d is null or not 4-byte aligned", who, k);
+        P.p[k] = (const unsigned *)samples[k];
+    }
+    MS_CHECK(stride >= 1, "%s: stride %d < 1", who, stride);
+    return MS_OK;
+}
+
+int ms_gain_stats_from_samples(ms_ctx *c, const void *const *samples, int n, int stride, long long *N_host, long long *S_host, ms_stream stream)
+{
+    const char *who = "ms_gain_stats_from_samples";
+    if (!N_host || !S_host) return fail(MS_ERR_INVALID, "%s: null output", who);
+    GainSampleBufs P;
+    if (int e = gain_sample_bufs(who, samples, n, stride, P)) return e;
+    if (!c) return fail(MS_ERR_INVALID, "%s: null context", who);
+    hipStream_t st = as_stream(stream);
+    const size_t nn = (size_t)c->N * c->N;
+    {   // (as ms_gain_stats)
+        std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);
+        std::lock_guard<std::mutex> gk(c->gain_mu);
+        GainTrackViews V;
+        if (int e = gain_track_args(c, who, nullptr, stride, false, V, GAIN_SAMPLES_GEOM)) return e;
+        GainSampleRects R;
+        gain_sample_rects(V, R);
+        GainTrackBuf *B = (GainTrackBuf *)c->gain_buf.p;
+        if (int e = gain_track_order(c, st)) return e;
+        if (int e = launch_gain_stats_from_samples(V, R, P, B, st)) return e;
+        if (int e = launch_gain_export_samples(V, R, P, B, st)) return e;
+        MS_HIP(hipMemcpyAsync(N_host, B->outN, nn * sizeof(long long), hipMemcpyDeviceToHost, st));
+        MS_HIP(hipMemcpyAsync(S_host, B->outS, nn * sizeof(long long), hipMemcpyDeviceToHost, st));
+        MS_HIP(hipEventRecord(c->gain_ev, st));
+        c->gain_ev_set = true;
+    }
+    MS_HIP(hipStreamSynchronize(st));
+    return MS_OK;
+}
+
+int ms_track_gains_from_samples(ms_ctx *c, const void *const *samples, int n, const ms_gain_track_params *prm, ms_stream stream)
+{
+    const char *who = "ms_track_gains_from_samples";
+    if (!prm) return fail(MS_ERR_INVALID, "%s: null params", who);
+    MS_CHECK(prm->struct_size == sizeof(ms_gain_track_params), "%s: ms_gain_track_params.struct_size is %u, this library expects %zu", who, prm->struct_size, sizeof(ms_gain_track_params));
+    MS_CHECK(prm->smoothing > 0.0 && prm->smoothing <= 1.0, "%s: smoothing %g outside (0, 1]", who, prm->smoothing);
+    GainSampleBufs P;
+    if (int e = gain_sample_bufs(who, samples, n, prm->stride, P)) return e;
+    if (!c) return fail(MS_ERR_INVALID, "%s: null context", who);
+    hipStream_t st = as_stream(stream);
+    std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);      // held for the enqueue, never for a GPU wait (as ms_track_gains)
+    GainTrackViews V;
+    if (int e = gain_track_args(c, who, nullptr, prm->stride, false, V, GAIN_SAMPLES_GEOM)) return e;
+    GainSampleRects R;
+    gain_sample_rects(V, R);
+    const GainTrackTables W = gain_track_tables(c);
+    GainTrackBuf *B = (GainTrackBuf *)c->gain_buf.p;
+    std::lock_guard<std::mutex> gk(c->gain_mu);
+    if (int e = gain_track_order(c, st)) return e;      // (the buffers are the caller's: whatever wrote them is ordered before this call by the caller's stream)
+    if (int e = launch_gain_stats_from_samples(V, R, P, B, st)) return e;
+    if (int e = gain_publish_order(c, st)) return e;
+    if (int e = launch_gain_update_samples(V, W, R, P, B, prm->smoothing, st)) return e;
     MS_HIP(hipEventRecord(c->gain_ev, st));
     gain_published(c, st);
     return MS_OK;

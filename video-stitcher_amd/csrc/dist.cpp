@@ -708,4 +708,67 @@ int ms_dist_track_gains(ms_dist *d, ms_ctx *ctx, const int *peers, int n_peers, 
     return rc;
 }
 
+// View shards: the sample vectors of this rank's views, an all-gather of buffers of different sizes inside the group, then pair sums and solve on every rank.
+int ms_dist_track_gains_views(ms_dist *d, ms_ctx *ctx, const int *peers, int n_peers, const ms_image *views, int nv12, const ms_gain_track_params *prm, void *scratch_dev, ms_stream stream)
+{
+    const char *who = "ms_dist_track_gains_views";
+    constexpr int MAX_PEERS = 4;      // = the buffers ms_track_gains_from_samples takes
+    MS_CHECK(d && ctx && peers && prm && scratch_dev, "%s: null argument", who);
+    MS_CHECK(!d->grouping, "%s: inside a group", who);
+    MS_CHECK(n_peers >= 1 && n_peers <= MAX_PEERS, "%s: %d peers, not in [1, %d]", who, n_peers, MAX_PEERS);
+    MS_CHECK(prm->struct_size == sizeof(ms_gain_track_params), "%s: ms_gain_track_params.struct_size is %u, this library expects %zu", who, prm->struct_size, sizeof(ms_gain_track_params));
+    MS_CHECK(prm->stride >= 1, "%s: stride %d < 1", who, prm->stride);
+    MS_CHECK(((uintptr_t)scratch_dev & 3u) == 0, "%s: scratch_dev is not 4-byte aligned", who);
+    int me = -1;
+    for (int k = 0; k < n_peers; ++k) {
+        if (int e = check_peer(d, peers[k], who)) return e;
+        for (int q = 0; q < k; ++q) MS_CHECK(peers[q] != peers[k], "%s: rank %d is listed twice", who, peers[k]);
+        if (peers[k] == d->rank) me = k;
+    }
+    MS_CHECK(me >= 0, "%s: rank %d is not one of the peers", who, d->rank);
+    // peer k = view shard k, and this rank's context is shard `me` of n_peers: anything else would size the slots for other blocks of views than the producer
+    // writes (the slots differ in size), so it is refused here, before the producer runs and before anything is posted
+    int vs = 0, vi = 0;
+    if (int e = ms_get_view_shard(ctx, &vs, &vi)) return e;
+    MS_CHECK(vs == n_peers, "%s: %d peers, but the context is one of %d view shard(s): a group has one rank per shard (ms_config.view_shards = n_peers)", who, n_peers, vs);
+    MS_CHECK(vi == me, "%s: the context is view shard %d, but rank %d is entry %d of peers: list the ranks in shard order", who, vi, d->rank, me);
+    // every context of the group holds the same cameras, so this rank sizes every peer's buffer (geometry and active set, the same on every rank)
+    size_t off[MAX_PEERS + 1] = {0};
+    for (int k = 0; k < n_peers; ++k) {
+        const size_t b = ms_gain_samples_bytes(ctx, prm->stride, n_peers == 1 ? -1 : k);
+        if (!b) return fail(MS_ERR_INVALID, "%s: no size for the sample buffer of shard %d: %s", who, k, std::string(ms_last_error()).c_str());
+        off[k + 1] = off[k] + b;
+    }
+    unsigned char *base = static_cast<unsigned char *>(scratch_dev);
+    // A rank whose samples are refused still takes part, with a zeroed buffer (no magic word): every rank of the group, this one included, rejects the update alike
+    // and none is left waiting.  (A failing memset is not fatal here: whatever the slot then holds is exchanged, and the error below is returned all the same.)
+    int bad = (nv12 ? ms_gain_samples_nv12 : ms_gain_samples)(ctx, views, prm->stride, base + off[me], stream);
+    std::string why;
+    if (bad) {
+        why = ms_last_error();
+        (void)hipMemsetAsync(base + off[me], 0, off[me + 1] - off[me], as_stream(stream));
+    }
+    if (n_peers > 1) {
+        if (int e = ms_dist_group_begin(d)) return e;
+        int err = MS_OK;
+        for (int k = 0; k < n_peers && !err; ++k) {
+            if (k == me) continue;
+            err = ms_dist_send(d, base + off[me], off[me + 1] - off[me], peers[k], MS_DIST_MEM_DEVICE, stream);
+            if (!err) err = ms_dist_recv(d, base + off[k], off[k + 1] - off[k], peers[k], MS_DIST_MEM_DEVICE, stream);
+        }
+        if (err) {                  // close the group without running it (as ms_dist_gather_slabs)
+            d->grouping = false;
+            d->ops.clear();
+            if (d->transport == MS_DIST_RCCL) (void)rccl().GroupEnd();
+            return err;
+        }
+        if (int e = ms_dist_group_end(d)) return e;
+    }
+    const void *ptrs[MAX_PEERS];
+    for (int k = 0; k < n_peers; ++k) ptrs[k] = base + off[k];
+    const int rc = ms_track_gains_from_samples(ctx, ptrs, n_peers, prm, stream);      // (with a zeroed buffer among them: counts the rejection here as on the peers)
+    if (bad) return fail(bad, "%s: this rank's samples were refused, the group rejects the update: %s", who, why.c_str());
+    return rc;
+}
+
 }  // extern "C"

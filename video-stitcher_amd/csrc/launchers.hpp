@@ -84,6 +84,45 @@ struct GainPartials { const unsigned long long *p[GAIN_MAX_PARTIALS]; int n; };
 inline size_t gain_partial_bytes(int n) { return sizeof(GainPartialHeader) + 2 * (size_t)n * n * sizeof(unsigned long long); }
 int launch_gain_partial_export(const GainTrackViews &V, const GainPartialHeader &H, GainTrackBuf *buf, void *partial, hipStream_t st);
 int launch_gain_update_partials(const GainTrackViews &V, const GainTrackTables &W, const GainPartialHeader &H, const GainPartials &P, GainTrackBuf *buf, double lambda, hipStream_t st);
+// Sample vectors (ms_gain_samples / ms_track_gains_from_samples): view shards.  What a pair needs of view a at a lattice sample is one integer, q_a or "not
+// seen"; the owner of a view stores it for every sample of the view's lattice rectangle R_v, the buffers travel, and every shard forms the pair sums from all of
+// them.  Layout of a buffer (ms_gain_samples_bytes; 32-bit words):
+//   [0] magic  [1] num_views  [2] active mask  [3] stride  [4..7] T.x, T.y, T.width, T.height  [8] mask of the views held  [9] total bytes  [10..15] 0
+//   [16 + v]   word offset of view v's data from the start of the buffer; 0 = not held
+//   data       per held view in view order, R_v row-major: 0 = not seen, else q + 1
+constexpr unsigned GAIN_SAMPLES_MAGIC = 0x56474d53u;               // "SMGV"
+constexpr int GAIN_SAMPLES_HEADER_WORDS = 16;
+constexpr int GAIN_MAX_SAMPLE_BUFS = 4;
+// R_v in lattice indices: the (sx, sy) with T.x + sx * stride in [roi.x, roi.x + roi.width) and the same in y; w or h may be 0.  off = the word offset of the
+// view in the buffer of a shard that holds `held`; computed on the host by gain_sample_rects alone, handed to producer and consumer by value.
+struct GainSampleRects { int x0[MS_MAX_VIEWS], y0[MS_MAX_VIEWS], w[MS_MAX_VIEWS], h[MS_MAX_VIEWS]; };
+struct GainSampleBufs { const unsigned *p[GAIN_MAX_SAMPLE_BUFS]; int n; };
+inline void gain_sample_rects(const GainTrackViews &V, GainSampleRects &R)
+{
+    auto first = [](int lo, int s) { return lo <= 0 ? 0 : (lo + s - 1) / s; };      // the smallest k >= 0 with k * s >= lo
+    for (int v = 0; v < V.n; ++v) {
+        const ms_rect r = V.roi[v];
+        const int x0 = first(r.x - V.T.x, V.stride), x1 = std::min(V.nsx, first(r.x + r.width - V.T.x, V.stride));
+        const int y0 = first(r.y - V.T.y, V.stride), y1 = std::min(V.nsy, first(r.y + r.height - V.T.y, V.stride));
+        R.x0[v] = x0; R.y0[v] = y0; R.w[v] = std::max(0, x1 - x0); R.h[v] = std::max(0, y1 - y0);
+    }
+}
+// word offsets of the views `held` in their buffer (0 elsewhere); returns the buffer's size in words
+inline size_t gain_sample_offsets(const GainTrackViews &V, const GainSampleRects &R, unsigned held, unsigned *off)
+{
+    size_t at = GAIN_SAMPLES_HEADER_WORDS + (size_t)V.n;
+    for (int v = 0; v < V.n; ++v) {
+        off[v] = 0;
+        if (!((held >> v) & 1u)) continue;
+        off[v] = (unsigned)at;
+        at += (size_t)R.w[v] * R.h[v];
+    }
+    return at;
+}
+int launch_gain_samples(const GainTrackViews &V, const GainSampleRects &R, unsigned held, bool nv12, void *samples, hipStream_t st);
+int launch_gain_stats_from_samples(const GainTrackViews &V, const GainSampleRects &R, const GainSampleBufs &P, GainTrackBuf *buf, hipStream_t st);
+int launch_gain_update_samples(const GainTrackViews &V, const GainTrackTables &W, const GainSampleRects &R, const GainSampleBufs &P, GainTrackBuf *buf, double lambda, hipStream_t st);
+int launch_gain_export_samples(const GainTrackViews &V, const GainSampleRects &R, const GainSampleBufs &P, GainTrackBuf *buf, hipStream_t st);
 void feather_weight_map(const uint8_t *mask, int rows, int cols, float sharpness, float *w);
 
 }  // namespace ms

@@ -15,7 +15,7 @@ MAX_RANKS = 16
 EXPORTS = [
     "ms_dist_unique_id", "ms_dist_create", "ms_dist_destroy", "ms_dist_get_info", "ms_dist_send", "ms_dist_recv", "ms_dist_group_begin",
     "ms_dist_group_end", "ms_dist_broadcast", "ms_dist_barrier", "ms_dist_gather_slabs", "ms_dist_mesh_exchange", "ms_dist_apply_meshes",
-    "ms_dist_set_rccl_library", "ms_dist_rccl_library_path", "ms_dist_track_gains",
+    "ms_dist_set_rccl_library", "ms_dist_rccl_library_path", "ms_dist_track_gains", "ms_dist_track_gains_views",
 ]
 
 
@@ -139,6 +139,25 @@ class Dist:
         arr = (C.c_int * len(peers))(*[int(r) for r in peers])
         views = comp._one_frame(frames)
         ms._chk(ms.load().ms_dist_track_gains(self._h, comp._ctx, arr, len(peers), views, int(bool(nv12)), C.byref(p), C.c_void_p(scratch.data_ptr()), ms._stream()))
+        return scratch
+
+    def track_gains_views(self, comp, peers, frames, scratch=None, nv12=False, stride=None, smoothing=None):
+        """ms_dist_track_gains_views: collective over the ranks `peers` of one view-shard group (shard order, the same list on every rank).  comp: this rank's
+        msstitch.Compositor (view shard peers.index(rank) of len(peers)); frames: one frame set (views outside comp.gain_sample_views() may be None); scratch:
+        int32 cuda tensor of sum(comp.gain_samples_bytes(stride, k)) bytes (allocated if None).  Returns the scratch tensor: it must stay alive until the stream
+        has passed the call."""
+        import torch
+        p = ms.gain_track_default_params()
+        if stride is not None:
+            p.stride = int(stride)
+        if smoothing is not None:
+            p.smoothing = float(smoothing)
+        if scratch is None:
+            total = sum(comp.gain_samples_bytes(p.stride, k if len(peers) > 1 else -1) for k in range(len(peers)))
+            scratch = torch.zeros(max(1, total // 4), dtype=torch.int32, device="cuda")
+        arr = (C.c_int * len(peers))(*[int(r) for r in peers])
+        views = comp._one_frame(frames)
+        ms._chk(ms.load().ms_dist_track_gains_views(self._h, comp._ctx, arr, len(peers), views, int(bool(nv12)), C.byref(p), C.c_void_p(scratch.data_ptr()), ms._stream()))
         return scratch
 
     def mesh_exchange(self, root, update, n_views, rows, cols):

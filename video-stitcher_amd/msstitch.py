@@ -117,6 +117,11 @@ def parse_gain_partial(partial, n):
     return hdr, body[:n * n].reshape(n, n).copy(), body[n * n:2 * n * n].reshape(n, n).copy()
 
 
+GAIN_SAMPLES_MAGIC = 0x56474d53
+GAIN_SAMPLES_HEADER_WORDS = 16      # magic, num_views, active mask, stride, T.x, T.y, T.width, T.height, held mask, total bytes, 6 x 0; num_views offsets follow
+GAIN_MAX_SAMPLE_BUFS = 4
+
+
 EXPORTS = [
     "ms_last_error", "ms_version", "ms_device_count", "ms_remap", "ms_resize_linear", "ms_convert_scale_8u", "ms_convert",
     "ms_copy_make_border", "ms_pyr_down", "ms_pyr_up", "ms_subtract_16s", "ms_add_16s", "ms_add_src_weight_32f",
@@ -133,6 +138,7 @@ EXPORTS = [
     "ms_gain_track_default_params", "ms_gain_stats", "ms_track_gains", "ms_get_gains",
     "ms_stitch_nv12_i420", "ms_gain_stats_nv12", "ms_track_gains_nv12", "ms_nv12_resize_linear_batch",
     "ms_gain_partial_bytes", "ms_get_gain_views", "ms_gain_stats_partial", "ms_gain_stats_partial_nv12", "ms_track_gains_from_partials", "ms_get_gain_track_counters",
+    "ms_gain_samples_bytes", "ms_get_view_shard", "ms_get_gain_sample_views", "ms_gain_samples", "ms_gain_samples_nv12", "ms_gain_stats_from_samples", "ms_track_gains_from_samples",
 ]
 
 _lib = None
@@ -986,6 +992,59 @@ class Compositor:
         st = _stream() if stream is None else C.c_void_p(getattr(stream, "cuda_stream", stream))
         arr = (C.c_void_p * len(partials))(*[t.data_ptr() for t in partials])
         _chk(load().ms_track_gains_from_partials(self._ctx, arr, len(partials), C.byref(p), st))
+
+    def gain_samples_bytes(self, stride, view_shard_index=-1):
+        """ms_gain_samples_bytes: size of the sample buffer of view shard `view_shard_index` (-1: this context's own) at this stride; 0 = refused."""
+        fn = load().ms_gain_samples_bytes
+        fn.restype = C.c_size_t
+        return int(fn(self._ctx, int(stride), int(view_shard_index)))
+
+    def view_shard(self):
+        """ms_get_view_shard: (view_shards, view_shard_index) of this context; (1, 0) without view sharding."""
+        a, b = C.c_int(0), C.c_int(0)
+        _chk(load().ms_get_view_shard(self._ctx, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def gain_sample_views(self):
+        """ms_get_gain_sample_views: bit mask of the views gain_samples reads (owned and active)."""
+        m = C.c_uint(0)
+        _chk(load().ms_get_gain_sample_views(self._ctx, C.byref(m)))
+        return m.value
+
+    def gain_samples(self, frames, stride, samples=None, nv12=False, stream=None):
+        """ms_gain_samples[_nv12]: the sample vectors of this context's own views into `samples` (a zeroed int32 cuda tensor of gain_samples_bytes(stride) if
+        None); enqueue-only.  Returns the buffer."""
+        if samples is None:
+            samples = _torch().zeros(self.gain_samples_bytes(stride) // 4, dtype=_torch().int32, device="cuda")
+        st = _stream() if stream is None else C.c_void_p(getattr(stream, "cuda_stream", stream))
+        views = self._one_frame(frames)
+        fn = load().ms_gain_samples_nv12 if nv12 else load().ms_gain_samples
+        _chk(fn(self._ctx, views, int(stride), C.c_void_p(samples.data_ptr()), st))
+        return samples
+
+    def gain_samples_nv12(self, frames_nv12, stride, samples=None, stream=None):
+        """ms_gain_samples_nv12: gain_samples from the cameras' NV12 planes."""
+        return self.gain_samples(frames_nv12, stride, samples=samples, nv12=True, stream=stream)
+
+    def gain_stats_from_samples(self, samples, stride):
+        """ms_gain_stats_from_samples: (N, S) as gain_stats reports them, formed from the shards' sample buffers (device tensors, any order).  Blocking."""
+        import numpy as np
+        N = np.zeros((self.n, self.n), dtype=np.int64)
+        S = np.zeros((self.n, self.n), dtype=np.int64)
+        arr = (C.c_void_p * len(samples))(*[t.data_ptr() for t in samples])
+        _chk(load().ms_gain_stats_from_samples(self._ctx, arr, len(samples), int(stride), N.ctypes.data_as(C.c_void_p), S.ctypes.data_as(C.c_void_p), _stream()))
+        return N, S
+
+    def track_gains_from_samples(self, samples, stride=None, smoothing=None, stream=None):
+        """ms_track_gains_from_samples: pair the shards' sample buffers (device tensors), solve, smooth and publish on the stream; enqueue-only."""
+        p = gain_track_default_params()
+        if stride is not None:
+            p.stride = int(stride)
+        if smoothing is not None:
+            p.smoothing = float(smoothing)
+        st = _stream() if stream is None else C.c_void_p(getattr(stream, "cuda_stream", stream))
+        arr = (C.c_void_p * len(samples))(*[t.data_ptr() for t in samples])
+        _chk(load().ms_track_gains_from_samples(self._ctx, arr, len(samples), C.byref(p), st))
 
     def gain_track_counters(self, stream=None):
         """ms_get_gain_track_counters: (solves_ok, solves_singular, updates_rejected); waits for the stream."""
