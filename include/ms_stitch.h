@@ -161,6 +161,24 @@ MS_API int ms_set_zero_masked_16sc3(ms_image *img, const ms_image *mask, ms_stre
 MS_API int ms_bitwise_and_8u(const ms_image *a, const ms_image *b, ms_image *dst, ms_stream stream);
 MS_API int ms_dilate3x3_8u(const ms_image *src, ms_image *dst, ms_stream stream);
 
+/* seam_finder->find(images_warped, corners, masks_warped) with the VoronoiSeamFinder (APP/calibration.cpp:134-135 -> VoronoiSeamFinder::find / findInPair,
+ * OCV/stitching/src/seam_finders.cpp:85-160): for every pair i < j whose ROIs overlap, in the reference's order, the overlap's pixels nearer (L1, strictly) to
+ * view i's own pixels are cleared from mask j, all others from mask i.  masks: n DEVICE 8UC1 images, masks[i] exactly rois[i].width x rois[i].height with
+ * contiguous rows (step == width), edited IN PLACE as the reference edits masks_warped: pair (0, 1)'s result is pair (0, 2)'s input.  Any non-zero value counts
+ * as set.  rois: HOST, corner + size of every view.  SYNCHRONOUS: allocates its distance planes and returns after `stream` has drained.
+ * MS_ERR_INVALID (checked before the device is touched): n outside [1, MS_MAX_VIEWS], a null pointer, an empty ROI, a mask of another type or size than its
+ * ROI, or rows that are not contiguous (nothing is staged: pass a packed copy). */
+MS_API int ms_voronoi_seams(int n, const ms_rect *rois, ms_image *masks, ms_stream stream);
+/* compensator->feed(corners, images_warped, masks_warped) with the GainCompensator (APP/calibration.cpp:122-132 -> GainCompensator::feed,
+ * OCV/stitching/src/exposure_compensate.cpp:71-145): per pair i <= j with overlapping ROIs, N = max(1, #pixels where both masks are 255) and the mean of
+ * sqrt(b^2 + g^2 + r^2) of either view over those pixels (double sums in raster order), the normal equations (alpha 0.01, beta 100) and cv::solve(DECOMP_LU).
+ * images: n DEVICE 8UC3 (step == 3 * width), masks: n DEVICE 8UC1 (step == width), each exactly its ROI's size; rois and gains_host (n doubles): HOST.
+ * N_host / I_host (HOST, n x n row-major, either may be NULL): the overlap counts and mean intensities the solve consumed, 0 where two ROIs do not meet.
+ * SYNCHRONOUS: allocates, and returns after `stream` has drained.  MS_ERR_INVALID as for ms_voronoi_seams (checked before the device is touched), and for a
+ * singular system (not reachable while every N[i][i] >= 1). */
+MS_API int ms_estimate_gains(int n, const ms_rect *rois, const ms_image *images, const ms_image *masks,
+                             double *gains_host, int *N_host, double *I_host, ms_stream stream);
+
 /* device::imgproc::buildWarp{Plane,Spherical,Cylindrical}Maps(tl_u, tl_v, map_x, map_y, k_rinv, r_kinv[, t], scale, stream)
  * OCV/stitching/src/warpers_cuda.cpp:51-67 -> cuda/build_warp_maps.cu:155-216.  k_rinv, r_kinv: 9 floats
  * (HOST), t: 3 floats (HOST, plane only, may be NULL). */

@@ -478,6 +478,121 @@ def voronoi_seams(corners, masks):
     return masks
 
 
+def gain_overlap_stats(corners, images, masks):
+    """GainCompensator::feed's overlap statistics (exposure_compensate.cpp:89-123): for every pair i <= j whose rectangles meet (overlapRoi, util.cpp:100-112),
+    over the pixels where BOTH masks equal 255 (:101; feed's level value, :66), N = max(1, their number) (:103) and I(i, j), I(j, i) = the sum of
+    sqrt(b^2 + g^2 + r^2) of view i, view j over them divided by N (:114-120).  The squares are summed as integers (sqr(int), util_inl.hpp:122) and the root is
+    taken in double; the sum runs pixel by pixel in raster order, which np.cumsum reproduces (np.sum adds pairwise and differs in the last bit).  Pairs that
+    do not meet stay 0 (:82-83).  Returns (N int64 n x n, I float64 n x n)."""
+    n = len(images)
+    N = np.zeros((n, n), np.int64)
+    I = np.zeros((n, n), np.float64)
+    for i in range(n):
+        for j in range(i, n):
+            (x1, y1), (x2, y2) = corners[i], corners[j]
+            (h1, w1), (h2, w2) = masks[i].shape, masks[j].shape
+            tlx, tly = max(x1, x2), max(y1, y2)
+            brx, bry = min(x1 + w1, x2 + w2), min(y1 + h1, y2 + h2)
+            if not (tlx < brx and tly < bry):
+                continue
+            sl1 = (slice(tly - y1, bry - y1), slice(tlx - x1, brx - x1))
+            sl2 = (slice(tly - y2, bry - y2), slice(tlx - x2, brx - x2))
+            both = (masks[i][sl1] == 255) & (masks[j][sl2] == 255)
+            N[i, j] = N[j, i] = max(1, int(both.sum()))
+            sums = []
+            for im, sl in ((images[i], sl1), (images[j], sl2)):
+                px = im[sl].astype(np.int64)
+                root = np.sqrt((px * px).sum(axis=2).astype(np.float64))[both]          # (boolean indexing keeps raster order)
+                sums.append(float(np.cumsum(root)[-1]) if root.size else 0.0)
+            I[i, j] = sums[0] / float(N[i, j])
+            I[j, i] = sums[1] / float(N[i, j])
+    return N, I
+
+
+def gain_normal_equations(N, I):
+    """The normal equations of GainCompensator::feed (exposure_compensate.cpp:125-140), alpha = 0.01, beta = 100, in the reference's accumulation order and
+    its left-to-right products, as Python floats (IEEE double, one rounding per operation).  Returns (A list of rows, b list)."""
+    n = len(N)
+    alpha, beta = 0.01, 100.0
+    A = [[0.0] * n for _ in range(n)]
+    b = [0.0] * n
+    for i in range(n):
+        for j in range(n):
+            Nij, Iij, Iji = float(int(N[i][j])), float(I[i][j]), float(I[j][i])
+            b[i] += beta * Nij
+            A[i][i] += beta * Nij
+            if j == i:
+                continue
+            A[i][i] += 2 * alpha * Iij * Iij * Nij
+            A[i][j] -= 2 * alpha * Iij * Iji * Nij
+    return A, b
+
+
+def solve_lu64(A, b):
+    """cv::solve(A, b, x, DECOMP_LU) on CV_64F with one right-hand side, in Python floats and the reference's operation order: the closed forms of
+    lapack.cpp:1107-1237 for n <= 3 (n = 2: :1141-1148 with det2, :748; n = 3: :1188-1209 with det3, :749-751; n = 1: :1229-1231), LUImpl
+    (matrix_decomp.cpp:52-107: partial pivoting, eps = 100 DBL_EPSILON, :127) above that.  A: list of rows, b: list; neither is modified.
+    Returns (x list or None when the reference reports a singular system, the number of row exchanges LUImpl made)."""
+    n = len(b)
+    A = [list(map(float, r)) for r in A]
+    b = list(map(float, b))
+    if n == 1:
+        return ([b[0] / A[0][0]] if A[0][0] != 0.0 else None), 0
+    if n == 2:
+        d = A[0][0] * A[1][1] - A[0][1] * A[1][0]
+        if d == 0.0:
+            return None, 0
+        d = 1.0 / d
+        return [(b[0] * A[1][1] - b[1] * A[0][1]) * d, (b[1] * A[0][0] - b[0] * A[1][0]) * d], 0
+    if n == 3:
+        d = (A[0][0] * (A[1][1] * A[2][2] - A[1][2] * A[2][1]) - A[0][1] * (A[1][0] * A[2][2] - A[1][2] * A[2][0]) +
+             A[0][2] * (A[1][0] * A[2][1] - A[1][1] * A[2][0]))
+        if d == 0.0:
+            return None, 0
+        d = 1.0 / d
+        t0 = ((A[1][1] * A[2][2] - A[1][2] * A[2][1]) * b[0] + (A[0][2] * A[2][1] - A[0][1] * A[2][2]) * b[1] + (A[0][1] * A[1][2] - A[0][2] * A[1][1]) * b[2]) * d
+        t1 = ((A[1][2] * A[2][0] - A[1][0] * A[2][2]) * b[0] + (A[0][0] * A[2][2] - A[0][2] * A[2][0]) * b[1] + (A[0][2] * A[1][0] - A[0][0] * A[1][2]) * b[2]) * d
+        t2 = ((A[1][0] * A[2][1] - A[1][1] * A[2][0]) * b[0] + (A[0][1] * A[2][0] - A[0][0] * A[2][1]) * b[1] + (A[0][0] * A[1][1] - A[0][1] * A[1][0]) * b[2]) * d
+        return [t0, t1, t2], 0
+    eps = 100 * 2.0 ** -52
+    swaps = 0
+    for i in range(n):
+        k = i
+        for j in range(i + 1, n):
+            if abs(A[j][i]) > abs(A[k][i]):
+                k = j
+        if abs(A[k][i]) < eps:
+            return None, swaps
+        if k != i:
+            for j in range(i, n):                       # (the reference exchanges columns i.. only: what lies left of them is never read again)
+                A[i][j], A[k][j] = A[k][j], A[i][j]
+            b[i], b[k] = b[k], b[i]
+            swaps += 1
+        d = -1 / A[i][i]
+        for j in range(i + 1, n):
+            al = A[j][i] * d
+            for q in range(i + 1, n):
+                A[j][q] += al * A[i][q]
+            b[j] += al * b[i]
+    for i in range(n - 1, -1, -1):
+        s = b[i]
+        for q in range(i + 1, n):
+            s -= A[i][q] * b[q]
+        b[i] = s / A[i][i]
+    return b, swaps
+
+
+def gain_compensator(corners, images, masks):
+    """GainCompensator::feed (exposure_compensate.cpp:71-145) -> (gains float64 (n,), N int64 (n, n), I float64 (n, n), row exchanges of the LU solve): the
+    three restatements above, one after the other.  A singular system (the reference's solve returns false and leaves the gains undefined) raises."""
+    N, I = gain_overlap_stats(corners, images, masks)
+    A, b = gain_normal_equations(N, I)
+    x, swaps = solve_lu64(A, b)
+    if x is None:
+        raise ValueError("singular gain system")
+    return np.array(x, np.float64), N, I, swaps
+
+
 def warp_maps_f64(proj, tl_u, tl_v, rows, cols, k_rinv, scale, t=(0, 0, 0)):
     """The backward maps of buildWarpMapsKernel (build_warp_maps.cu:67-152) in float64, from the same fp32 k_rinv, scale and t: the TRUE map
     the fp32 kernel approximates.  proj 0 plane, 1 cylindrical, 2 spherical (the ms_stitch.h / ORC_PROJ_* codes).  Returns (x, y, z) -- z is

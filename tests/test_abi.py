@@ -22,6 +22,9 @@ def test_header_symbols_are_exported(ms):
     for n in names:
         assert hasattr(lib, n), "libmsstitch.so does not export %s" % n
     assert sorted(ms.EXPORTS) == names, "msstitch.EXPORTS out of sync with include/ms_stitch.h"
+    for doc in ("README.md", "DESIGN.md"):      # the count both documents state is the header's
+        stated = re.findall(r"(\d+) entry points, each citing", open(os.path.join(ROOT, doc)).read())
+        assert stated == [str(len(names))], "%s states %s entry points, include/ms_stitch.h declares %d" % (doc, stated, len(names))
     # the multi-GPU layer (include/ms_dist.h) lives in the same library
     import msdist
     dist_names = declared_symbols("ms_dist.h")

@@ -9,6 +9,7 @@ import math
 import numpy as np
 import pytest
 
+import calib_cases
 import np_ref
 import synth
 
@@ -328,6 +329,102 @@ def test_voronoi_seams(oracle):
         for x, y in zip(a, b):
             assert np.array_equal(x, y)
         assert any(not np.array_equal(x, m) for x, m in zip(a, masks)), "the seams cut nothing: the case is vacuous"
+
+
+# ---- the per-op calibration tests' own inputs (tests/calib_cases.py): the two references agree on every case tests/test_calib_kernels_gpu.py runs -----------
+@pytest.mark.parametrize("name", calib_cases.VORONOI_CASES)
+def test_voronoi_seams_on_the_gpu_tests_inputs(oracle, name):
+    rois, masks = calib_cases.voronoi_case(name)
+    corners = [r[:2] for r in rois]
+    a = oracle.voronoi_seams(corners, [m.copy() for m in masks])
+    b = np_ref.voronoi_seams(corners, [m.copy() for m in masks])
+    for x, y in zip(a, b):
+        assert np.array_equal(x, y)
+    changed = any(not np.array_equal(x, m) for x, m in zip(a, masks))
+    assert changed == (name not in calib_cases.VORONOI_UNTOUCHED), "the case does not do what its name says"
+    if len(rois) == 2 and changed:                      # what is left of the overlap belongs to one view only
+        ox, oy, ow, oh = calib_cases.overlap(*rois)
+        s0, s1 = [m[oy - r[1]:oy - r[1] + oh, ox - r[0]:ox - r[0] + ow] for m, r in zip(a, rois)]
+        assert not ((s0 != 0) & (s1 != 0)).any()
+    if name == "nounique_both":                         # neither view has a pixel of its own: dist1 == dist2 everywhere, `<` is false, view i loses the overlap
+        assert not a[0].any() and np.array_equal(a[1], masks[1])
+    if name == "nounique_first":
+        assert not a[0].any() and np.array_equal(a[1], masks[1])
+    if name == "nounique_second":
+        assert not a[1].any() and np.array_equal(a[0], masks[0])
+    if name == "ties_columns":                          # overlap columns 25..39 of view 0: the middle one (32) is a tie and stays with view 1
+        assert a[0][:, :32].all() and not a[0][:, 32:].any() and not a[1][:, :7].any() and a[1][:, 7:].all()
+    if name == "ties_none_even":
+        assert a[0][:, :32].all() and not a[0][:, 32:].any() and not a[1][:, :8].any() and a[1][:, 8:].all()
+
+
+def test_voronoi_cases_cover_the_block_boundaries():
+    """rw + 2 gap and rh + 2 gap take 21, 63, 64, 65, 128 and 129 among the two-view cases: either side of the 64-lane blocks of k_vor_cols / k_vor_rows"""
+    seen_w, seen_h = set(), set()
+    for name in calib_cases.VORONOI_CASES:
+        rois, _ = calib_cases.voronoi_case(name)
+        if name.startswith("pair_"):
+            o = calib_cases.overlap(*rois)
+            seen_w.add(o[2] + 2 * calib_cases.GAP); seen_h.add(o[3] + 2 * calib_cases.GAP)
+            assert min(r[0] for r in rois) < 0 or min(r[1] for r in rois) < 0 or name == "pair_1x1"
+    assert seen_w >= {21, 63, 64, 65, 128, 129} and seen_h >= {21, 63, 64, 65, 128, 129}
+
+
+@pytest.mark.parametrize("name", calib_cases.GAIN_CASES)
+def test_gain_compensator_on_the_gpu_tests_inputs(oracle, name):
+    """oracle.gain_compensator == np_ref.gain_compensator, bit for bit, and np_ref's solve against numpy.linalg.solve as a sanity net under
+    rtol = 64 cond(A) 2^-52 (64: room for the growth of n <= 16 elimination steps) -- the bound does not pin anything, the equality does."""
+    rois, imgs, masks = calib_cases.gain_case(name)
+    corners = [r[:2] for r in rois]
+    g, N, I, swaps = np_ref.gain_compensator(corners, imgs, masks)
+    ref = np.array(oracle.gain_compensator(corners, imgs, masks), np.float64)
+    assert np.array_equal(g, ref), (name, g, ref)
+    A, b = np_ref.gain_normal_equations(N, I)
+    A, b = np.array(A), np.array(b)
+    rtol = 64 * np.linalg.cond(A) * 2.0 ** -52
+    np.testing.assert_allclose(g, np.linalg.solve(A, b), rtol=rtol, atol=0)
+    n = len(rois)
+    for i in range(n):
+        for j in range(n):
+            assert (N[i, j] == 0) == (calib_cases.overlap(rois[i], rois[j]) is None)
+    assert (swaps > 0) == (name in calib_cases.GAIN_ROW_SWAP_CASES), "row exchanges: %d" % swaps
+    if name == "no_common_255":
+        assert N[0, 1] == 1 and I[0, 1] == 0.0 and I[1, 0] == 0.0 and N[0, 2] > 100 and N[1, 2] > 100
+    if name == "views_1":
+        assert g[0] == 1.0
+    if n >= 2:
+        assert len(set(g.tolist())) == n, "the views' exposures differ: so must their gains"
+
+
+def test_gain_cases_cover_what_they_claim():
+    ns = set()
+    grey = 0
+    for name in calib_cases.GAIN_CASES:
+        rois, imgs, masks = calib_cases.gain_case(name)
+        ns.add(len(rois))
+        assert min(r[0] for r in rois) < 0 and min(r[1] for r in rois) < 0
+        assert all((im == 0).all(axis=2).any() and (im == 255).all(axis=2).any() for im in imgs) or name == "lu_row_exchange"
+        if len(rois) >= 2:              # sqrt(0) and sqrt(3 * 255^2) enter a pair sum: such pixels lie in an overlap, under 255 in both masks
+            black, white = calib_cases.counted_extremes(rois, imgs, masks)
+            assert black >= 10 and white >= 10, (name, black, white)
+        grey += sum(int(((m == 254) | (m == 128)).sum()) for m in masks)
+    assert ns >= {1, 2, 3, 4, 5, 8, 9, 16} and grey > 100
+
+
+def test_solve_lu64_branches():
+    """np_ref.solve_lu64 alone: every closed form against the LU path run on the same system (they differ in the last bits, not in the answer), the singular
+    exits, and a permutation matrix that needs n - 1 exchanges."""
+    rng = np.random.default_rng(5)
+    for n in (1, 2, 3):
+        A = rng.uniform(-1, 1, (n, n)) + 3 * np.eye(n)
+        b = rng.uniform(-1, 1, n)
+        x, swaps = np_ref.solve_lu64(A.tolist(), b.tolist())
+        np.testing.assert_allclose(x, np.linalg.solve(A, b), rtol=64 * np.linalg.cond(A) * 2.0 ** -52)
+        assert swaps == 0 and np_ref.solve_lu64(np.zeros((n, n)).tolist(), b.tolist())[0] is None
+    P = np.roll(np.eye(5), 1, axis=0) * 2.0
+    x, swaps = np_ref.solve_lu64(P.tolist(), [2.0, 4.0, 6.0, 8.0, 10.0])
+    assert swaps == 4 and x == [2.0, 3.0, 4.0, 5.0, 1.0]
+    assert np_ref.solve_lu64(np.ones((4, 4)).tolist(), [1.0] * 4)[0] is None
 
 
 # ---- warp maps (K18) against float64 truth ----------------------------------------------------------------------------------------------

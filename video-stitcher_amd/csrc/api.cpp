@@ -52,6 +52,26 @@ static int same_size(const ms_image *a, const ms_image *b, const char *what)
     return MS_OK;
 }
 
+// ms_voronoi_seams / ms_estimate_gains: the kernels of calib.hip assume of view i a device image of the given type, exactly its ROI's size, rows back to back.  Host checks only.
+static int check_calib_image(const char *fn, const char *what, int i, const ms_image &m, const ms_rect &r, int type, int channels)
+{
+    MS_CHECK(m.data, "%s: %s %d: null image", fn, what, i);
+    MS_CHECK(m.type == type, "%s: %s %d must be %s (type code %d, got %d)", fn, what, i, channels == 3 ? "8UC3" : "8UC1", type, m.type);
+    MS_CHECK(m.cols == r.width && m.rows == r.height, "%s: %s %d is %dx%d, its ROI %dx%d", fn, what, i, m.cols, m.rows, r.width, r.height);
+    MS_CHECK(m.step == (size_t)m.cols * channels, "%s: %s %d: rows must be contiguous (step %zu, %zu bytes per row): pass a packed copy", fn, what, i, m.step,
+             (size_t)m.cols * channels);
+    return MS_OK;
+}
+static int check_calib_rois(const char *fn, int n, const ms_rect *rois)
+{
+    MS_CHECK(n >= 1 && n <= MS_MAX_VIEWS, "%s: n = %d outside [1, %d]", fn, n, MS_MAX_VIEWS);
+    MS_CHECK(rois, "%s: null rois", fn);
+    for (int i = 0; i < n; ++i)
+        MS_CHECK(rois[i].width > 0 && rois[i].height > 0 && (long long)rois[i].x + rois[i].width <= 0x7fffffffLL && (long long)rois[i].y + rois[i].height <= 0x7fffffffLL,
+                 "%s: roi %d (%d, %d, %d x %d) is empty or leaves the int range", fn, i, rois[i].x, rois[i].y, rois[i].width, rois[i].height);
+    return MS_OK;
+}
+
 }  // namespace ms
 
 using namespace ms;
@@ -254,6 +274,34 @@ int ms_dilate3x3_8u(const ms_image *src, ms_image *dst, ms_stream s)
     PRE() IMG(src, "ms_dilate3x3_8u src") IMG(dst, "ms_dilate3x3_8u dst") SAME(src, dst, "ms_dilate3x3_8u")
     MS_CHECK(src->type == MS_8UC1 && dst->type == MS_8UC1 && src->data != dst->data, "ms_dilate3x3_8u: distinct 8UC1 images required");
     return launch_dilate3(*src, *dst, as_stream(s));
+}
+
+// the two calibration stages alone, on the caller's own ROIs, masks and images (kernels: calib.hip).  Every check is a host check and comes before the device.
+int ms_voronoi_seams(int n, const ms_rect *rois, ms_image *masks, ms_stream stream)
+{
+    if (int e = check_calib_rois("ms_voronoi_seams", n, rois)) return e;
+    MS_CHECK(masks, "ms_voronoi_seams: null masks");
+    uint8_t *ptr[MS_MAX_VIEWS];
+    for (int i = 0; i < n; ++i) {
+        if (int e = check_calib_image("ms_voronoi_seams", "mask", i, masks[i], rois[i], MS_8UC1, 1)) return e;
+        ptr[i] = (uint8_t *)masks[i].data;
+    }
+    if (int e = require_device()) return e;
+    return voronoi_seams_device(n, rois, ptr, as_stream(stream));
+}
+
+int ms_estimate_gains(int n, const ms_rect *rois, const ms_image *images, const ms_image *masks, double *gains_host, int *N_host, double *I_host, ms_stream stream)
+{
+    if (int e = check_calib_rois("ms_estimate_gains", n, rois)) return e;
+    MS_CHECK(images && masks && gains_host, "ms_estimate_gains: null images / masks / gains_host");
+    const uint8_t *ip[MS_MAX_VIEWS], *mp[MS_MAX_VIEWS];
+    for (int i = 0; i < n; ++i) {
+        if (int e = check_calib_image("ms_estimate_gains", "image", i, images[i], rois[i], MS_8UC3, 3)) return e;
+        if (int e = check_calib_image("ms_estimate_gains", "mask", i, masks[i], rois[i], MS_8UC1, 1)) return e;
+        ip[i] = (const uint8_t *)images[i].data; mp[i] = (const uint8_t *)masks[i].data;
+    }
+    if (int e = require_device()) return e;
+    return estimate_gains_device(n, rois, ip, mp, gains_host, as_stream(stream), N_host, I_host);
 }
 
 int ms_build_warp_maps(int projection, int tl_u, int tl_v, ms_image *mx, ms_image *my, const float *k_rinv, const float *r_kinv,

@@ -496,7 +496,7 @@ int voronoi_seams_device(int n, const ms_rect *rois, uint8_t *const *masks, hipS
 }
 
 // GainCompensator::feed over DEVICE images (8UC3, contiguous) and masks (8UC1, contiguous); gains come back to the host (n doubles)
-int estimate_gains_device(int n, const ms_rect *rois, const uint8_t *const *images, const uint8_t *const *masks, double *gains_host, hipStream_t st)
+int estimate_gains_device(int n, const ms_rect *rois, const uint8_t *const *images, const uint8_t *const *masks, double *gains_host, hipStream_t st, int *N_host, double *I_host)
 {
     if (n > MS_MAX_VIEWS) return fail(MS_ERR_INVALID, "estimate_gains_device: too many views");
     GainViews V{};
@@ -514,7 +514,9 @@ int estimate_gains_device(int n, const ms_rect *rois, const uint8_t *const *imag
         k_gain_solve<<<1, 1, 0, st>>>(n, Nm, Im, g, ok);
         int hok = 0;
         if (hipGetLastError() != hipSuccess || hipMemcpyAsync(gains_host, g, n * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipMemcpyAsync(&hok, ok, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+            hipMemcpyAsync(&hok, ok, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
+            (N_host && hipMemcpyAsync(N_host, Nm, nn * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess) ||
+            (I_host && hipMemcpyAsync(I_host, Im, nn * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess) || hipStreamSynchronize(st) != hipSuccess)
             rc = fail(MS_ERR_HIP, "estimate_gains_device: launch / copy failed");
         else if (!hok) rc = fail(MS_ERR_INVALID, "singular gain system");
     }

@@ -49,10 +49,11 @@ struct BlendGeom { int num_bands; ms_rect dst_roi_final, dst_roi; };
 struct ViewPad { int top, left, bottom, right, x_tl, y_tl, x_br, y_br; };
 BlendGeom blender_prepare(ms_rect dst_roi, int actual_num_bands);
 ViewPad blender_view_pad(const BlendGeom &g, int tl_x, int tl_y, int mask_cols, int mask_rows);
-// VoronoiSeamFinder over host masks (contiguous, h x w each), in place
-// VoronoiSeamFinder over device masks, in place
+// VoronoiSeamFinder over device masks (contiguous, roi-sized), in place
 int voronoi_seams_device(int n, const ms_rect *rois, uint8_t *const *masks_dev, hipStream_t st);                 // calib.hip
-int estimate_gains_device(int n, const ms_rect *rois, const uint8_t *const *images_dev, const uint8_t *const *masks_dev, double *gains_host, hipStream_t st);
+// N_host / I_host (n x n each, may be null): the overlap counts and mean intensities the solve consumed (ms_estimate_gains hands them out)
+int estimate_gains_device(int n, const ms_rect *rois, const uint8_t *const *images_dev, const uint8_t *const *masks_dev, double *gains_host, hipStream_t st,
+                          int *N_host = nullptr, double *I_host = nullptr);
 // exposure tracking (ms_gain_stats / ms_track_gains; kernels in calib.hip).  The sample lattice, the views' static maps and this call's frames, by value:
 struct ViewDesc;
 struct GainTrackViews {

@@ -139,6 +139,7 @@ EXPORTS = [
     "ms_stitch_nv12_i420", "ms_gain_stats_nv12", "ms_track_gains_nv12", "ms_nv12_resize_linear_batch",
     "ms_gain_partial_bytes", "ms_get_gain_views", "ms_gain_stats_partial", "ms_gain_stats_partial_nv12", "ms_track_gains_from_partials", "ms_get_gain_track_counters",
     "ms_gain_samples_bytes", "ms_get_view_shard", "ms_get_gain_sample_views", "ms_gain_samples", "ms_gain_samples_nv12", "ms_gain_stats_from_samples", "ms_track_gains_from_samples",
+    "ms_voronoi_seams", "ms_estimate_gains",
 ]
 
 _lib = None
@@ -382,6 +383,31 @@ def dilate3x3(src):
     dst = _new(src.shape, src.dtype)
     _chk(load().ms_dilate3x3_8u(C.byref(img(src)), C.byref(img(dst)), _stream()))
     return dst
+
+
+def _rects(rois):
+    return (Rect * len(rois))(*[Rect(*[int(v) for v in r]) for r in rois])
+
+
+def voronoi_seams(rois, masks_dev):
+    """VoronoiSeamFinder::find over device masks (uint8 (h, w) tensors, each exactly its ROI's size and contiguous), edited in place.  rois: (x, y, w, h) per view."""
+    n = len(masks_dev)
+    assert len(rois) == n
+    m = (Image * n)(*[img(t) for t in masks_dev])
+    _chk(load().ms_voronoi_seams(n, _rects(rois), m, _stream()))
+    return masks_dev
+
+
+def estimate_gains(rois, imgs_dev, masks_dev):
+    """GainCompensator::feed over device images (uint8 (h, w, 3)) and masks (uint8 (h, w)) -> (gains (n,) float64, N (n, n) int32, I (n, n) float64) on the host."""
+    import numpy as np
+    n = len(imgs_dev)
+    assert len(rois) == n and len(masks_dev) == n
+    a = (Image * n)(*[img(t) for t in imgs_dev]); m = (Image * n)(*[img(t) for t in masks_dev])
+    g, N, I = np.zeros(n, np.float64), np.zeros((n, n), np.int32), np.zeros((n, n), np.float64)
+    _chk(load().ms_estimate_gains(n, _rects(rois), a, m, g.ctypes.data_as(C.POINTER(C.c_double)), N.ctypes.data_as(C.POINTER(C.c_int)),
+                                  I.ctypes.data_as(C.POINTER(C.c_double)), _stream()))
+    return g, N, I
 
 
 def _fa(v, n):
