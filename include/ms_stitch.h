@@ -59,7 +59,8 @@ enum { MS_PROJ_PLANE = 0, MS_PROJ_CYLINDRICAL = 1, MS_PROJ_SPHERICAL = 2 };
 
 typedef struct ms_image {   /* PtrStepSz<T> field for field (OCV/core/include/opencv2/core/cuda_types.hpp:95-120), then the type code */
     void *data;
-    size_t step;            /* row pitch in bytes */
+    size_t step;            /* row pitch in bytes: any value >= the row's bytes (cols * element size) -- pitched allocations and ROIs of larger images as they are;
+                             * the images of ms_stitch* / ms_feed additionally need step < 2^24 (16 MiB) and rows * step < 2^32 (see ms_stitch) */
     int cols, rows;         /* PtrStepSz order: cols first */
     int type;
 } ms_image;
@@ -531,6 +532,11 @@ MS_API int ms_set_mesh_maps(ms_ctx *ctx, int view, const ms_image *x_mesh, const
  *   out8u[f]  8UC3 out_width x out_height equirect canvas (pano ROI placed at its spherical position;
  *             = consume()'s convertTo(CV_8U), timed.cpp:251) -- may be NULL;
  *   out16s[f] 16SC3 pano ROI (dst_roi_final sized) = blend()'s gpuOut (blenders.cpp:811) -- may be NULL.
+ * Layout of views, out8u and out16s (every frame its own; a GpuMat's data / step pass through unchanged): any row step from the row's bytes up to, not including,
+ * 2^24 bytes (16 MiB), with rows * step < 2^32 -- the kernels form row * step with a 24-bit multiply or in 32 bits; any base address for the 8U images; 2-byte
+ * alignment of base address and step for out16s.  Bytes between the end of a row and the next row, and canvas pixels outside the panorama ROI, are never written.
+ * Anything else is refused with MS_ERR_INVALID before a kernel is enqueued, in every entry point that takes these images (ms_stitch_nv12, ms_blend for the
+ * images ms_feed recorded, ms_stitch_partial / ms_stitch_finish, ms_stitch_timed).
  * No allocation, no host sync. */
 MS_API int ms_stitch(ms_ctx *ctx, int n_frames, const ms_image *views, ms_image *out8u, ms_image *out16s,
                      ms_stream stream);

@@ -3818,6 +3818,17 @@ struct KernelForm { int kernel, nf; bool al; size_t lds; };
 // one chunk of a call's frames, as the source-reading launches take it: its own source table, the per-frame buffers offset by its first frame
 struct Chunk { int f0, nf; SrcTable src; uint8_t *stage, *g0; };
 
+// the row-step rule of ms_image (include/ms_stitch.h): k_blend8 forms row * step with the 24-bit multiplier (mul24), the other writers and the warp kernels'
+// taps in 32 bits, so a step of 2^24 or an image of 2^32 bytes would be truncated silently; a step below the row's bytes overlaps rows
+static int check_step(const char *fn, const char *what, int idx, const ms_image &m, size_t px_bytes)
+{
+    const size_t row = (size_t)m.cols * px_bytes;
+    MS_CHECK(m.step >= row, "%s: %s[%d] has row step %zu, below the %zu bytes of its rows", fn, what, idx, m.step, row);
+    MS_CHECK(m.step < ((size_t)1 << 24), "%s: %s[%d] has row step %zu: the row step must be below 2^24 bytes (16 MiB)", fn, what, idx, m.step);
+    MS_CHECK((unsigned long long)m.rows * (unsigned long long)m.step < (1ull << 32), "%s: %s[%d] spans rows * step = %d * %zu bytes: must be below 2^32", fn, what, idx, m.rows, m.step);
+    return MS_OK;
+}
+
 static int check_call(ms_ctx *c, StitchCall &k, const ms_image *views, const ms_image *out8u, const ms_image *out16s, const ms_image *out_i420)
 {
     if (!c->blender_ready) return fail(MS_ERR_STATE, "ms_stitch: call ms_build_maps / masks / ms_init_blender first");
@@ -3840,6 +3851,7 @@ static int check_call(ms_ctx *c, StitchCall &k, const ms_image *views, const ms_
         else
         MS_CHECK(views[i].data && views[i].type == MS_8UC3 && views[i].rows == c->cfg.src_height && views[i].cols == c->cfg.src_width,
                  "ms_stitch: view %d must be 8UC3 %dx%d", i, c->cfg.src_width, c->cfg.src_height);
+        if (int e = check_step(k.nv12 ? "ms_stitch_nv12" : "ms_stitch", "view", i, views[i], k.nv12 ? 1 : 3)) return e;
         k.src.p[i] = (const uint8_t *)views[i].data;
         k.src.step[i] = (unsigned)views[i].step;
     }
@@ -3861,11 +3873,15 @@ static int check_call(ms_ctx *c, StitchCall &k, const ms_image *views, const ms_
         if (out8u && out8u[f].data) {
             MS_CHECK(out8u[f].type == MS_8UC3 && out8u[f].rows == P.out_h && out8u[f].cols == P.out_w,
                      "ms_stitch: out8u[%d] must be 8UC3 %dx%d", f, P.out_w, P.out_h);
+            if (int e = check_step("ms_stitch", "out8u", f, out8u[f], 3)) return e;
             k.out.p8[f] = (uint8_t *)out8u[f].data; k.out.step8[f] = (unsigned)out8u[f].step;
         }
         if (out16s && out16s[f].data) {
             MS_CHECK(out16s[f].type == MS_16SC3 && out16s[f].rows == P.fh && out16s[f].cols == P.fw,
                      "ms_stitch: out16s[%d] must be 16SC3 %dx%d", f, P.fw, P.fh);
+            if (int e = check_step("ms_stitch", "out16s", f, out16s[f], 6)) return e;
+            MS_CHECK((out16s[f].step & 1) == 0 && ((uintptr_t)out16s[f].data & 1) == 0,
+                     "ms_stitch: out16s[%d] needs 2-byte alignment: data %p, row step %zu", f, out16s[f].data, out16s[f].step);
             k.out.p16[f] = (int16_t *)out16s[f].data; k.out.step16[f] = (unsigned)out16s[f].step;
         }
         if (out_i420 && out_i420[f].data) {

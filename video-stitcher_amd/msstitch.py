@@ -880,9 +880,9 @@ class Compositor:
                 views[k] = img(t) if t is not None else Image(); k += 1      # None: a view this (column / view) shard never reads
         o8 = o16 = None
         if out8u is not None:
-            o8 = (Image * n_frames)(*[img(t) for t in out8u])
+            o8 = (Image * n_frames)(*[img(t) if t is not None else Image() for t in out8u])      # None: no 8U canvas for this frame (data == NULL)
         if out16s is not None:
-            o16 = (Image * n_frames)(*[img(t) for t in out16s])
+            o16 = (Image * n_frames)(*[img(t) if t is not None else Image() for t in out16s])
         return n_frames, views, o8, o16
 
     def stitch(self, frames, out8u=None, out16s=None):
