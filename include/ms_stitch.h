@@ -305,6 +305,32 @@ MS_API int ms_set_gain(ms_ctx *ctx, int view, double gain);
 /* warper->warpRoi + gpu_warper->buildMaps per view (APP/calibration.cpp:168-181,221) and
  * blender->prepare(corners, sizes) (calibration.cpp:196 -> blenders.cpp:82-85,237-295). */
 MS_API int ms_build_maps(ms_ctx *ctx, ms_stream stream);
+/* stitch_online's x_maps[i] / y_maps[i] as the caller's own (APP/timed.cpp:56, :84-90, :123-129) instead of gpu_warper->buildMaps' (calibration.cpp:221):
+ * the per-frame path of the reference remaps through whatever maps it is handed, so a rig with calibrated lens distortion, a fisheye model or any third-party
+ * calibration brings its own.  Replaces ms_build_maps and needs no ms_set_camera.
+ *   rois:  HOST, num_views rectangles: corner and size of each warped view in warper coordinates (what ms_view_geom.roi reports and blender->prepare(corners,
+ *          sizes) receives).
+ *   xmaps[i] / ymaps[i]: DEVICE 32FC1, exactly rois[i].width x rois[i].height; row step >= 4 * width and a multiple of 4, data 4-byte aligned.  The values are
+ *          cuda::remap's backward map -- source pixel coordinates -- and may be anything: outside the source, negative, NaN, +-inf (such pixels sample
+ *          BORDER_CONSTANT 0 like the reference's remap).
+ * The maps are COPIED into context storage (the caller may free or overwrite them when the call returns); resultRoi / prepare / the per-view padding and the
+ * canvas placement are those of ms_build_maps.  SYNCHRONOUS, calibration-time: drains `stream`, marks the maps built and invalidates masks and blender, so
+ * ms_build_masks or ms_set_mask, ms_set_gain and ms_init_blender / ms_init_feather follow as usual; not callable while another thread stitches.  Everything that
+ * depends on maps, ROIs and masks only works unchanged (every ms_stitch* form, CPW, ms_set_active_views, exposure tracking, column and view shards -- every shard
+ * is given the same maps --, the developer knobs; warp_lds_stage = 1 never stages).  What needs cameras is refused with MS_ERR_UNSUPPORTED: ms_calibrate_seam
+ * (it re-warps at seam scale) and ms_save_tables (the blob replays cameras).  A later ms_build_maps returns the context to the analytic maps.
+ * ms_get_maps returns the stored copies, ms_get_view_geom / ms_get_pano_geom the geometry derived from `rois`.
+ * MS_ERR_INVALID, before the device is touched: a null pointer; an image of another type or size than its ROI; a bad step or alignment; a ROI narrower than
+ * MS_MAPS_MIN_WIDTH, lower than MS_MAPS_MIN_HEIGHT or with a side above MS_MAPS_MAX_SIDE; a padded panorama (the ROIs' union) with a side above 32767.
+ *   MS_MAPS_MIN_WIDTH / _HEIGHT: the tiled kernels fetch a bilinear tap row as 8 bytes = 3 pixels clamped into the image and two rows at once; with CPW the
+ *          image sampled is the warped view itself, so a view has at least 3 columns and 2 rows (narrower contexts would fall back to the reference kernels).
+ *   MS_MAPS_MAX_SIDE: a work-list tile keeps its origin inside the PADDED view in 16 bits (<= 32767); the padding adds less than 8 * 2^num_bands <= 1024
+ *          columns / rows (num_bands <= 7: a gap of 3 * 2^num_bands either side, rounded out to multiples of 2^num_bands), hence 32768 - 1024. */
+enum { MS_MAPS_MIN_WIDTH = 3, MS_MAPS_MIN_HEIGHT = 2, MS_MAPS_MAX_SIDE = 31744 };
+MS_API int ms_set_maps(ms_ctx *ctx, const ms_rect *rois, const ms_image *xmaps, const ms_image *ymaps, ms_stream stream);
+/* where the context's maps come from: ms_build_maps (ANALYTIC, also before any maps are built) or ms_set_maps (CUSTOM) */
+enum { MS_MAPS_ANALYTIC = 0, MS_MAPS_CUSTOM = 1 };
+MS_API int ms_get_map_source(const ms_ctx *ctx, int *source);
 
 /* Compose-size blend masks (APP/calibration.cpp:224-237).  mode 0: warp(255, NEAREST) only;
  * mode 1: AND with Voronoi seams (VoronoiSeamFinder, seam_finders.cpp:85-160) computed at compose size

@@ -19,6 +19,7 @@
 // multiply/divide + truncation, and int16 accumulation wraps exactly like `short +=`.
 #include <algorithm>
 #include <atomic>
+#include <climits>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -1648,6 +1649,7 @@ struct ms_ctx {
     double gain[MAX_VIEWS];
     // stage flags
     bool maps_built = false, masks_built = false, blender_ready = false;
+    bool custom_maps = false;          // the maps are the caller's (ms_set_maps): no cameras, no 1-D projection tables -- the tiled warp kernels read xmap / ymap (PROJ_MAPS)
     // geometry
     ms_rect roi[MAX_VIEWS];
     BlendGeom bg{};
@@ -2007,7 +2009,7 @@ static int build_plan(ms_ctx *c)
                     if (any_in(Nd[v][0], V.pw, V.ph, x0, y0, WARP_TW, WARP_TH)) {
                         WarpTile t{};
                         t.view = (short)v; t.x0 = (short)x0; t.y0 = (short)y0;
-                        if (x0 >= V.left && x0 + WARP_TW <= V.left + V.aw && y0 >= V.top && y0 + WARP_TH <= V.top + V.ah) {
+                        if (!c->custom_maps && x0 >= V.left && x0 + WARP_TW <= V.left + V.aw && y0 >= V.top && y0 + WARP_TH <= V.top + V.ah) {      // (the caller's maps: no tables to index)
                             t.flags |= 4;         // interior tile: its table entries are known without the view descriptor
                             t.ctab = (int)(c->tab_off[v] + (size_t)(x0 - V.left));
                             t.rtab = (int)(c->tab_off[v] + (size_t)round_up(V.aw, 4) + (size_t)(y0 - V.top));
@@ -2324,8 +2326,78 @@ int ms_build_maps(ms_ctx *c, ms_stream stream)
     c->canvas_x = c->bg.dst_roi.x + c->cfg.out_width / 2;
     c->canvas_y = c->cfg.projection == MS_PROJ_SPHERICAL ? c->bg.dst_roi.y : c->bg.dst_roi.y + c->cfg.out_height / 2;
     MS_HIP(hipStreamSynchronize(st));
+    c->custom_maps = false;
     c->maps_built = true;
     c->masks_built = c->blender_ready = false;
+    return MS_OK;
+}
+
+// The caller's own backward maps (stitch_online's x_maps[i] / y_maps[i], timed.cpp:56, :84-90) instead of the warper's: copied into the storage ms_build_maps fills,
+// with the geometry ms_build_maps derives -- from the ROIs handed in instead of warpRoi.  No 1-D projection tables exist afterwards: the tiled warp kernels read the
+// dense maps (PROJ_MAPS).
+int ms_set_maps(ms_ctx *c, const ms_rect *rois, const ms_image *xmaps, const ms_image *ymaps, ms_stream stream)
+{
+    if (!c || !rois || !xmaps || !ymaps) return fail(MS_ERR_INVALID, "ms_set_maps: null argument");
+    const int N = c->N;
+    long long tlx = INT_MAX, tly = INT_MAX, brx = INT_MIN, bry = INT_MIN;
+    for (int i = 0; i < N; ++i) {
+        const ms_rect &r = rois[i];
+        MS_CHECK(r.width >= MS_MAPS_MIN_WIDTH && r.width <= MS_MAPS_MAX_SIDE && r.height >= MS_MAPS_MIN_HEIGHT && r.height <= MS_MAPS_MAX_SIDE,
+                 "ms_set_maps: ROI %d is %d x %d: the tiled kernels take views of %d..%d columns and %d..%d rows", i, r.width, r.height,
+                 (int)MS_MAPS_MIN_WIDTH, (int)MS_MAPS_MAX_SIDE, (int)MS_MAPS_MIN_HEIGHT, (int)MS_MAPS_MAX_SIDE);
+        for (int which = 0; which < 2; ++which) {
+            const ms_image &m = which ? ymaps[i] : xmaps[i];
+            const char *name = which ? "ymaps" : "xmaps";
+            MS_CHECK(m.data != nullptr, "ms_set_maps: %s[%d] has no data", name, i);
+            MS_CHECK(m.type == MS_32FC1 && m.cols == r.width && m.rows == r.height, "ms_set_maps: %s[%d] must be 32FC1 %d x %d like its ROI (it is type %d, %d x %d)",
+                     name, i, r.width, r.height, m.type, m.cols, m.rows);
+            MS_CHECK(m.step >= (size_t)r.width * sizeof(float) && (m.step & 3) == 0 && ((uintptr_t)m.data & 3) == 0,
+                     "ms_set_maps: %s[%d] needs a row step of at least %zu bytes that is a multiple of 4 and 4-byte aligned data (step %zu, data %p)",
+                     name, i, (size_t)r.width * sizeof(float), m.step, m.data);
+        }
+        tlx = std::min<long long>(tlx, r.x); tly = std::min<long long>(tly, r.y);
+        brx = std::max<long long>(brx, (long long)r.x + r.width); bry = std::max<long long>(bry, (long long)r.y + r.height);
+    }
+    {   // the padded panorama: band tiles keep their origin in 16 bits (blender_prepare rounds the union up to a multiple of 2^num_bands)
+        const long long m = 1ll << c->cfg.num_bands, pw = (brx - tlx + m - 1) / m * m, ph = (bry - tly + m - 1) / m * m;
+        MS_CHECK(pw <= 32767 && ph <= 32767, "ms_set_maps: the ROIs span a padded panorama of %lld x %lld: each side must be at most 32767", pw, ph);
+    }
+    hipStream_t st = as_stream(stream);
+    std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);
+    if (c->stitch_pending) MS_HIP(hipEventSynchronize(c->last_stitch));      // (a calibration-time call: no stitch still reads the maps replaced below)
+    c->maps_built = c->masks_built = c->blender_ready = false;
+    size_t total = 0;
+    for (int i = 0; i < N; ++i) {
+        c->roi[i] = rois[i];
+        c->map_pitch[i] = round_up(rois[i].width, 4);
+        c->map_off[i] = total;
+        total += (size_t)2 * rois[i].height * c->map_pitch[i];
+    }
+    if (int e = c->maps.alloc(total * sizeof(float))) return e;
+    MS_HIP(hipMemsetAsync(c->maps.p, 0, total * sizeof(float), st));      // (the up to 3 padding columns of a row are never read; zeroed all the same)
+    for (int i = 0; i < N; ++i) {
+        const ms_image mx = view_map_image(c, i, 0), my = view_map_image(c, i, 1);
+        MS_HIP(hipMemcpy2DAsync(mx.data, mx.step, xmaps[i].data, xmaps[i].step, (size_t)rois[i].width * sizeof(float), rois[i].height, hipMemcpyDeviceToDevice, st));
+        MS_HIP(hipMemcpy2DAsync(my.data, my.step, ymaps[i].data, ymaps[i].step, (size_t)rois[i].width * sizeof(float), rois[i].height, hipMemcpyDeviceToDevice, st));
+    }
+    c->tabs.release();      // no projection, no tables: nothing may follow a stale index into them
+    for (int i = 0; i < MAX_VIEWS; ++i) c->tab_off[i] = 0;
+    // blender->prepare(corners, sizes) and the canvas, as ms_build_maps
+    c->bg = blender_prepare(result_roi(N, c->roi), c->cfg.num_bands);
+    for (int i = 0; i < N; ++i)
+        c->pad[i] = blender_view_pad(c->bg, c->roi[i].x, c->roi[i].y, c->roi[i].width, c->roi[i].height);
+    c->canvas_x = c->bg.dst_roi.x + c->cfg.out_width / 2;
+    c->canvas_y = c->cfg.projection == MS_PROJ_SPHERICAL ? c->bg.dst_roi.y : c->bg.dst_roi.y + c->cfg.out_height / 2;
+    MS_HIP(hipStreamSynchronize(st));
+    c->custom_maps = true;
+    c->maps_built = true;
+    return MS_OK;
+}
+
+int ms_get_map_source(const ms_ctx *c, int *source)
+{
+    if (!c || !source) return fail(MS_ERR_INVALID, "ms_get_map_source: null argument");
+    *source = c->custom_maps ? MS_MAPS_CUSTOM : MS_MAPS_ANALYTIC;
     return MS_OK;
 }
 
@@ -2371,6 +2443,7 @@ int ms_calibrate_seam(ms_ctx *c, const ms_image *full_imgs, const float *K_seam,
 {
     if (!c || !full_imgs || !K_seam || !prm) return fail(MS_ERR_INVALID, "ms_calibrate_seam: null argument");
     if (!c->maps_built) return fail(MS_ERR_STATE, "ms_calibrate_seam: call ms_build_maps first");
+    if (c->custom_maps) return fail(MS_ERR_UNSUPPORTED, "ms_calibrate_seam: the context's maps are the caller's own (ms_set_maps): the seam-scale calibration re-warps from cameras it does not have");
     MS_CHECK(prm->seam_scale > 0 && prm->seam_scale <= 1.0 && prm->seam_warp_scale > 0, "ms_calibrate_seam: bad scales");
     hipStream_t st = as_stream(stream);
     const int N = c->N, W = c->cfg.src_width, H = c->cfg.src_height;
@@ -2502,10 +2575,13 @@ int ms_init_blender(ms_ctx *c, ms_stream stream)
         V.xmap = (const float *)c->maps.p + c->map_off[v];
         V.ymap = V.xmap + (size_t)V.ah * c->map_pitch[v];
         V.map_pitch = c->map_pitch[v];
-        V.coltab = (const float2 *)c->tabs.p + c->tab_off[v];
-        V.rowtab = V.coltab + round_up(V.aw, 4);
-        V.wp = c->wparams[v];
-        V.proj = c->cfg.projection;
+        if (c->custom_maps) V.proj = PROJ_MAPS;      // (no table storage exists: coltab / rowtab stay null, wp unset; the kernels read xmap / ymap)
+        else {
+            V.coltab = (const float2 *)c->tabs.p + c->tab_off[v];
+            V.rowtab = V.coltab + round_up(V.aw, 4);
+            V.wp = c->wparams[v];
+            V.proj = c->cfg.projection;
+        }
         V.s1_off = stage_total;
         V.s1_pitch = round_up(V.aw * 3, 4);
         stage_total += (long long)round_up(V.s1_pitch * V.ah + 8, 16);
@@ -3791,7 +3867,13 @@ static inline void with_value(T v, Fn &&f)
     else with_value<Vs...>(v, f);
 }
 template <class Fn>
-static inline void with_proj(const ms_ctx *c, Fn &&f) { with_value<(int)MS_PROJ_SPHERICAL, (int)MS_PROJ_CYLINDRICAL, (int)MS_PROJ_PLANE>(c->cfg.projection, f); }
+static inline void with_proj(const ms_ctx *c, Fn &&f)      // (PROJ_MAPS: the coordinate source of a context with the caller's own maps)
+{
+    with_value<(int)MS_PROJ_SPHERICAL, (int)MS_PROJ_CYLINDRICAL, (int)PROJ_MAPS, (int)MS_PROJ_PLANE>(c->custom_maps ? (int)PROJ_MAPS : c->cfg.projection, f);
+}
+// the kernels that never look at the projection's coordinate source (the mesh remap reads mesh maps) or have no dense-map form (k_warp_a: never chosen for the caller's maps)
+template <class Fn>
+static inline void with_cfg_proj(const ms_ctx *c, Fn &&f) { with_value<(int)MS_PROJ_SPHERICAL, (int)MS_PROJ_CYLINDRICAL, (int)MS_PROJ_PLANE>(c->cfg.projection, f); }
 
 // one ms_stitch* call: what check_call establishes before anything is enqueued, and what the enqueue stages share
 // the work lists a call runs: the context's (every view active) or those of the active subset (ms_set_active_views)
@@ -4069,7 +4151,7 @@ static KernelForm warp_form(const ms_ctx *c, const StitchCall &k, const Chunk &c
     // measured slower than the direct gathers on config 2 (353 vs 242 us per 16 frames: at its 1.6-2.1 x minification only 54 % of the tiles' source
     // boxes fit a staging buffer and 10 waves per CU cannot hide what 20 do; profiles/r02_warp_probes.txt)
     static const bool env_on = dev_knob("MS_WARP_ASYNC", 0) != 0;
-    bool staged = c->warp_lds_tiles > 0 && (c->cfg.warp_lds_stage == 1 || (env_on && c->cfg.warp_lds_stage != 2));
+    bool staged = c->warp_lds_tiles > 0 && !c->custom_maps && (c->cfg.warp_lds_stage == 1 || (env_on && c->cfg.warp_lds_stage != 2));      // (k_warp_a has no dense-map form: the caller's maps never stage)
     for (int i = 0; i < ch.nf * c->N; ++i) staged = staged && ((uintptr_t)ch.src.p[i] & 15) == 0;   // chunk copies start on 16-byte lines of the buffer
     if (staged) return {MS_WARP_KERNEL_LDS_STAGED, 1, false, 2 * WA_BUF_BYTES};
     // (with shared offsets the aligned form wins at every minification measured: config 5 -- 2.7 x, k_warp_t's unaligned territory -- 757 -> 730 / 738 -> 699 us per 16 frames;
@@ -4091,7 +4173,7 @@ static void launch_warp(const ms_ctx *c, const StitchCall &k, const Chunk &ch, c
     switch (f.kernel) {
     case MS_WARP_KERNEL_SHARED_ALIGNED:
         if (k.cpw)
-            with_proj(c, [&](auto P) { with_value<warp_nf(true), 1>(f.nf, [&](auto NF) {
+            with_cfg_proj(c, [&](auto P) { with_value<warp_nf(true), 1>(f.nf, [&](auto NF) {
                 k_warp_s<true, P, NF><<<g, b, f.lds, k.st>>>(tiles, k.vt, N, ch.src, H, W, k.mesh, ch.stage, c->stage_stride, ch.g0, c->g0_stride, tabs, ch.nf);
             }); });
         else
@@ -4118,7 +4200,7 @@ static void launch_warp(const ms_ctx *c, const StitchCall &k, const Chunk &ch, c
     case MS_WARP_KERNEL_LDS_STAGED: {
         const long long items = (long long)k.W.n_warp * ch.nf;
         const int grid = (int)std::min<long long>(items, (long long)c->n_cus * (160 * 1024 / (2 * WA_BUF_BYTES)));
-        with_proj(c, [&](auto P) {
+        with_cfg_proj(c, [&](auto P) {
             k_warp_a<P><<<dim3(grid), dim3(64), f.lds, k.st>>>(tiles, k.W.n_warp, k.vt, N, ch.src, H, W, ch.g0, c->g0_stride, tabs, ch.nf);
         });
         break;
@@ -4525,6 +4607,7 @@ int ms_save_tables(ms_ctx *c, void *buf, size_t cap, size_t *bytes_out)
     // a blob replays its context's configuration verbatim: one of a column / view shard would give EVERY loader that shard's window.  The unsharded
     // context is what "one blob for every rank" means; a rank that needs a shard creates it from the same K / R / gains / masks itself.
     if (c->cfg.col_shards > 1 || c->cfg.view_shards > 1) return fail(MS_ERR_UNSUPPORTED, "ms_save_tables: this context is a column / view shard; save the tables of an unsharded context");
+    if (c->custom_maps) return fail(MS_ERR_UNSUPPORTED, "ms_save_tables: the context's maps are the caller's own (ms_set_maps); a blob replays cameras, which this context does not have");
     size_t need = sizeof(TablesHeader);
     for (int v = 0; v < c->N; ++v) need += sizeof(TablesView) + (size_t)c->roi[v].width * c->roi[v].height;
     *bytes_out = need;

@@ -9,6 +9,10 @@ constexpr int MAX_VIEWS = 16;
 constexpr int MAX_SRC = 192;      // frames * views of ONE by-value source table (a launch of the kernels that read the callers' frames: the per-frame path sends them out in chunks)
 constexpr int MAX_FRAMES = 64;    // frames per ms_stitch call
 static_assert(MAX_SRC >= MAX_VIEWS, "a source table holds at least one frame of every view");
+// A fourth value of the tiled warp kernels' PROJ template argument, next to MS_PROJ_*: the coordinates are not rebuilt from the 1-D projection tables but READ from the
+// view's dense xmap / ymap -- a context whose maps the caller supplied (ms_set_maps) has no camera, hence no tables.  ViewDesc::proj carries it for such a context.
+constexpr int PROJ_MAPS = 3;
+static_assert(PROJ_MAPS != MS_PROJ_PLANE && PROJ_MAPS != MS_PROJ_CYLINDRICAL && PROJ_MAPS != MS_PROJ_SPHERICAL, "PROJ_MAPS must not name a projection");
 
 struct LevelDesc {
     int w, h, pitch;              // level size; pitch in elements
@@ -26,7 +30,7 @@ struct ViewDesc {
     int map_pitch;
     const float2 *coltab, *rowtab; // 1-D terms of the backward map (per ROI column / row); the fused path rebuilds
     WarpParams wp;                 // the coordinates from these (bit-identical to xmap/ymap) instead of reading 8 B/px
-    int proj;
+    int proj;                      // MS_PROJ_*, or PROJ_MAPS: no tables (coltab / rowtab are null, wp unset), the fused path reads xmap / ymap
     const uint8_t *wm0;           // padded 8-bit mask = level-0 weight before the 1/255 scale (static)
     int wm0_pitch;
     long long s1_off;             // byte offset of the CPW stage-1 image inside the per-frame stage buffer
@@ -78,7 +82,7 @@ struct OutTable { uint8_t *p8[MAX_FRAMES]; unsigned step8[MAX_FRAMES]; int16_t *
 // are never produced or read.  Skipping them is exact: a zero weight contributes trunc(L * 0) == 0.
 // out tile origin + source bbox (LDS-staged variant) + where the tile's projection tables start.  flags: bit 0 = bbox fits the LDS budget,
 // bit 1 = (CPW stage 1) reachable tile, bit 2 = every pixel of the tile lies inside the warped view in x and y (no reflect padding),
-// in which case ctab / rtab index the column / row terms of the tile's first column / row in the context's table buffer
+// in which case ctab / rtab index the column / row terms of the tile's first column / row in the context's table buffer (never set for PROJ_MAPS: there are no tables)
 struct WarpTile { short view, flags; short x0, y0; short sx0, sy0, sw, sh; int ctab, rtab; };
 struct DownTile { short view, pad; short x0, y0; };                              // output (level l+1) tile origin
 struct BlendTile { short x0, y0; unsigned view_mask; };                          // pano tile origin + contributing views

@@ -72,8 +72,11 @@ typedef unsigned ms_u32x3_a4 __attribute__((ext_vector_type(3), aligned(4)));
 #define MS_GLOBAL_AS __attribute__((address_space(1)))
 typedef float ms_f32x2_g __attribute__((ext_vector_type(2)));
 typedef float ms_f32x4_a8 __attribute__((ext_vector_type(4), aligned(8)));
+typedef float ms_f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
 __device__ __forceinline__ float2 gload_f2(const float2 *p) { const ms_f32x2_g v = *(const MS_GLOBAL_AS ms_f32x2_g *)(uintptr_t)p; return make_float2(v.x, v.y); }
 __device__ __forceinline__ float4 gload_f4(const float2 *p) { const ms_f32x4_a8 v = *(const MS_GLOBAL_AS ms_f32x4_a8 *)(uintptr_t)p; return make_float4(v.x, v.y, v.z, v.w); }   // two table entries, 8-byte aligned
+__device__ __forceinline__ float4 gload_f4(const float *p) { const ms_f32x4_a4 v = *(const MS_GLOBAL_AS ms_f32x4_a4 *)(uintptr_t)p; return make_float4(v.x, v.y, v.z, v.w); }     // four dense-map entries of a row, 4-byte aligned
+__device__ __forceinline__ float gload_f1(const float *p) { return *(const MS_GLOBAL_AS float *)(uintptr_t)p; }
 // The UNALIGNED 8-byte form stays a flat load: measured, config 5 (every tile takes this form): global_load_dwordx2 433-437 us per 8 frames, flat_load_dwordx2 392-395
 // (the commit before, whose scheduler order made unit 0 wait for all 16 reads: 402-408).  The aligned 12-byte form below gains from being global: config 2 218.9 -> 211.7 us per
 // 16 frames, the shipped configuration's stage 1 351 -> 324 (counted waits: unit 0 is blended while unit 1's reads are still in flight).
@@ -222,14 +225,30 @@ __device__ __forceinline__ void blend_taps2(const Taps ta, const Taps tb, const 
 
 // ---- Gaussian level 0 (remap + gain [or CPW stage 2] + reflect pad), 4 px per lane ---------------------
 // Source coordinates of the 4 pixels of a lane.  Non-CPW: rebuilt from the 1-D tables (same fp32 ops as the dense
-// x_map/y_map, which are therefore never read per frame); CPW stage 2: read from the dense mesh maps.
+// x_map/y_map, which are therefore never read per frame); CPW stage 2: read from the dense mesh maps; PROJ_MAPS (a context
+// with the caller's own maps, ms_set_maps: no tables): read from the view's dense x_map / y_map -- two 16-byte reads per lane
+// inside the view, eight 4-byte reads at reflected positions on its border, as the mesh-map form.
 template <bool CPW, int PROJ = -1>
 __device__ __forceinline__ void warp_coords4(const ViewDesc &V, const MeshTable &mesh, int v, int x, int y, float xc[4], float yc[4])
 {
     const int ay = reflect_fast(y - V.top, V.ah);
     const int i0 = x - V.left;
     const bool interior = i0 >= 0 && i0 + 3 < V.aw;
-    if (!CPW) {
+    if (!CPW && PROJ == PROJ_MAPS) {
+        const float *mxp = V.xmap + (size_t)ay * V.map_pitch, *myp = V.ymap + (size_t)ay * V.map_pitch;
+        if (interior) {
+            const float4 a = gload_f4(mxp + i0), b = gload_f4(myp + i0);
+            xc[0] = a.x; xc[1] = a.y; xc[2] = a.z; xc[3] = a.w;
+            yc[0] = b.x; yc[1] = b.y; yc[2] = b.z; yc[3] = b.w;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int ax = reflect_fast(i0 + k, V.aw);
+                xc[k] = gload_f1(mxp + ax);
+                yc[k] = gload_f1(myp + ax);
+            }
+        }
+    } else if (!CPW) {
         const float2 rt = gload_f2(V.rowtab + ay);
         float2 ct[4];
         if (interior) {
@@ -305,7 +324,8 @@ __global__ void __launch_bounds__(256) k_tile_bbox(WarpTile *__restrict__ tiles,
     if (stage1 ? (x - ox < V.aw && y - oy < V.ah) : (x < V.pw && y < V.ph)) {
         float xc[4], yc[4];
         MeshTable none{};
-        warp_coords4<false>(V, none, T.view, min(x, V.pw - 4), y, xc, yc);
+        if (V.proj == PROJ_MAPS) warp_coords4<false, PROJ_MAPS>(V, none, T.view, min(x, V.pw - 4), y, xc, yc);      // (the maps the warp kernels will read, not tables that do not exist)
+        else warp_coords4<false>(V, none, T.view, min(x, V.pw - 4), y, xc, yc);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const Taps t = make_taps(xc[k], yc[k], src_rows, src_cols);
@@ -380,8 +400,9 @@ __device__ __forceinline__ void warp_tile_direct(const WarpTile &T, int f0, int 
     unsigned sh1[2] = {0u, 0u}, sh2[2] = {0u, 0u};
     // the 1-D tables of the projection are read ONCE, up front (column terms of the lane's 4 pixels, row term of each row group):
     // building the coordinates of a group is then pure arithmetic, with no load between it and the tap reads
+    constexpr bool DENSE = CPW || PROJ == PROJ_MAPS;      // the coordinates are read (mesh maps / the view's own maps), not rebuilt from tables
     float2 ct[4], rt[NG];
-    if (!CPW) {
+    if (!DENSE) {
         if (T.flags & 4) {            // interior tile: table addresses come from the tile entry alone, so these loads do not wait for
                                       // the view descriptor (one round trip less on the wave's critical path)
             float4 a, b;
@@ -397,7 +418,7 @@ __device__ __forceinline__ void warp_tile_direct(const WarpTile &T, int f0, int 
             for (int g = 0; g < NG; ++g) rt[g] = gload_f2(V.rowtab + reflect_fast(min(ys[g], V.ph - 1) - V.top, V.ah));
         }
     }
-    if (CPW && NG <= 2) {        // the dense mesh maps of both row groups are read up front too (one round trip, not one per group)
+    if (DENSE && NG <= 2) {        // the dense mesh maps of both row groups are read up front too (one round trip, not one per group)
 #pragma unroll
         for (int g = 0; g < NG; ++g)
             if (active[g]) warp_coords4<CPW, PROJ>(V, mesh, v, x, ys[g], xc[g & 1], yc[g & 1]);
@@ -413,7 +434,7 @@ __device__ __forceinline__ void warp_tile_direct(const WarpTile &T, int f0, int 
             if (active[g]) { for (int k = 0; k < 4; ++k) { xc[cb][k] = 1.55f * (float)(x + k - V.left) + 20.3f; yc[cb][k] = 1.6f * (float)(ys[g] - V.top) + 10.7f; } }
 #else
             if (active[g]) {
-                if (CPW) {
+                if (DENSE) {
                     if (NG > 2) warp_coords4<CPW, PROJ>(V, mesh, v, x, ys[g], xc[cb], yc[cb]);      // (<= 2 groups: already read up front)
                 } else {
 #pragma unroll
@@ -602,8 +623,8 @@ __device__ __forceinline__ void warp_tile_shared(const WarpTile &T, int f0, int 
     const LevelDesc &L = V.lv[0];
     const size_t plane = (size_t)L.h * L.pitch;
     float xc[4], yc[4];
-    if (CPW) {
-        if (active) warp_coords4<true, PROJ>(V, mesh, v, x, y, xc, yc);
+    if (CPW || PROJ == PROJ_MAPS) {
+        if (active) warp_coords4<CPW, PROJ>(V, mesh, v, x, y, xc, yc);
     } else {
         float2 ct[4], rt;
         if (T.flags & 4) {            // interior tile: table addresses from the tile entry alone
@@ -815,7 +836,14 @@ __device__ __forceinline__ void nv12_tile(const WarpTile &T, int f0, int nf, int
     const LevelDesc &L = V.lv[0];
     const size_t plane = (size_t)L.h * L.pitch;
     float xc[4], yc[4];
-    {
+    if (PROJ == PROJ_MAPS) {      // the view's dense maps (S1: a view pixel is its padded position shifted by the border: identity reflect inside the view)
+        const MeshTable none{};
+        if (active) warp_coords4<false, PROJ>(V, none, v, S1 ? x + V.left : x, S1 ? y + V.top : y, xc, yc);
+        else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) xc[k] = yc[k] = -1.f;
+        }
+    } else {
         float2 ct[4], rt;
         if (S1) {
 #pragma unroll
@@ -1167,7 +1195,8 @@ __device__ __forceinline__ void stage1_tile(const WarpTile &T, int f0, int nf, c
         sp[fi] = src.p[f * n_views + v]; sstep[fi] = src.step[f * n_views + v];
     }
     float2 ct[4];
-    if (x + 3 < V.aw) {
+    if (PROJ == PROJ_MAPS) {      // (no tables: the maps are read below.  The table form around it is left statement for statement what it was, so the analytic instantiations compile to the same code)
+    } else if (x + 3 < V.aw) {
         float4 a, b;
         a = gload_f4(V.coltab + x);
         b = gload_f4(V.coltab + x + 2);
@@ -1176,10 +1205,15 @@ __device__ __forceinline__ void stage1_tile(const WarpTile &T, int f0, int nf, c
 #pragma unroll
         for (int k = 0; k < 4; ++k) ct[k] = gload_f2(V.coltab + min(x + k, V.aw - 1));
     }
-    const float2 rt = gload_f2(V.rowtab + y);
+    const float2 rt = PROJ == PROJ_MAPS ? make_float2(0.f, 0.f) : gload_f2(V.rowtab + y);
     float xc[4], yc[4];
+    if (PROJ == PROJ_MAPS) {      // the view's dense maps, through the padded position of the view pixel (identity reflect inside the view; columns past the view's last are not stored)
+        const MeshTable none{};
+        warp_coords4<false, PROJ>(V, none, v, x + V.left, y + V.top, xc, yc);
+    } else {
 #pragma unroll
-    for (int k = 0; k < 4; ++k) warp_combine(PROJ, ct[k], rt, V.wp, xc[k], yc[k]);
+        for (int k = 0; k < 4; ++k) warp_combine(PROJ, ct[k], rt, V.wp, xc[k], yc[k]);
+    }
     Px2 r1[2][4], r2[2][4];
     Px3 q1[AL ? 2 : 1][AL ? 4 : 1], q2[AL ? 2 : 1][AL ? 4 : 1];      // AL: aligned 12-byte tap reads, as in warp_tile_direct
     unsigned sh1[2] = {0u, 0u}, sh2[2] = {0u, 0u};
@@ -1275,7 +1309,8 @@ __device__ __forceinline__ void stage1_tile_shared(const WarpTile &T, int f0, in
     for (int fi = 0; fi < S1_NF; ++fi) base[fi] = (ms_gptr_u8)((uintptr_t)src.p[(f0 + (fi < nf ? fi : 0)) * n_views + v] & ~(uintptr_t)3);
     const unsigned lo2 = (unsigned)(uintptr_t)src.p[f0 * n_views + v] & 3u, st = src.step[f0 * n_views + v];
     float2 ct[4];
-    if (x + 3 < V.aw) {
+    if (PROJ == PROJ_MAPS) {      // (no tables: the maps are read below.  The table form around it is left statement for statement what it was, so the analytic instantiations compile to the same code)
+    } else if (x + 3 < V.aw) {
         float4 a, b;
         a = gload_f4(V.coltab + x);
         b = gload_f4(V.coltab + x + 2);
@@ -1284,10 +1319,15 @@ __device__ __forceinline__ void stage1_tile_shared(const WarpTile &T, int f0, in
 #pragma unroll
         for (int k = 0; k < 4; ++k) ct[k] = gload_f2(V.coltab + min(x + k, V.aw - 1));
     }
-    const float2 rt = gload_f2(V.rowtab + y);
+    const float2 rt = PROJ == PROJ_MAPS ? make_float2(0.f, 0.f) : gload_f2(V.rowtab + y);
     float xc[4], yc[4];
+    if (PROJ == PROJ_MAPS) {      // the view's dense maps, through the padded position of the view pixel (identity reflect inside the view; columns past the view's last are not stored)
+        const MeshTable none{};
+        warp_coords4<false, PROJ>(V, none, v, x + V.left, y + V.top, xc, yc);
+    } else {
 #pragma unroll
-    for (int k = 0; k < 4; ++k) warp_combine(PROJ, ct[k], rt, V.wp, xc[k], yc[k]);
+        for (int k = 0; k < 4; ++k) warp_combine(PROJ, ct[k], rt, V.wp, xc[k], yc[k]);
+    }
     unsigned va[4], vb[4], sh1 = 0u, sh2 = 0u;
     bool slow = false;
 #pragma unroll

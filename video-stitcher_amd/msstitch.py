@@ -18,6 +18,8 @@ BORDER_CONSTANT, BORDER_REFLECT = 0, 2
 INTER_NEAREST, INTER_LINEAR = 0, 1
 INTER_LINEAR_FIXPT = 0x101      # cv::remap's CPU arithmetic
 PROJ_PLANE, PROJ_CYLINDRICAL, PROJ_SPHERICAL = 0, 1, 2
+MAPS_ANALYTIC, MAPS_CUSTOM = 0, 1
+MAPS_MIN_WIDTH, MAPS_MIN_HEIGHT, MAPS_MAX_SIDE = 3, 2, 31744
 
 
 class MsError(RuntimeError):
@@ -140,6 +142,7 @@ EXPORTS = [
     "ms_gain_partial_bytes", "ms_get_gain_views", "ms_gain_stats_partial", "ms_gain_stats_partial_nv12", "ms_track_gains_from_partials", "ms_get_gain_track_counters",
     "ms_gain_samples_bytes", "ms_get_view_shard", "ms_get_gain_sample_views", "ms_gain_samples", "ms_gain_samples_nv12", "ms_gain_stats_from_samples", "ms_track_gains_from_samples",
     "ms_voronoi_seams", "ms_estimate_gains",
+    "ms_set_maps", "ms_get_map_source",
 ]
 
 _lib = None
@@ -692,11 +695,12 @@ class Compositor:
 
     def __init__(self, num_views, src_size, projection, warp_scale, num_bands=5, enable_cpw=False,
                  out_size=(0, 0), max_frames=1, simple_kernels=False, lds_stage=None, shards=1, shard_index=0, cv_remap=False,
-                 col_shards=1, col_shard_index=0, update_mask_margin=0):
+                 col_shards=1, col_shard_index=0, update_mask_margin=0, raster_order=False):
         cfg = Config(C.sizeof(Config), num_views, src_size[0], src_size[1], projection, warp_scale, num_bands, int(enable_cpw),
                      out_size[0], out_size[1], max_frames)
         cfg.debug_simple_kernels = 1 if simple_kernels else 0   # debug: force the one-pixel-per-lane reference kernels
         cfg.warp_lds_stage = 0 if lds_stage is None else (1 if lds_stage else 2)   # True: warp source tiles staged in LDS by LDS-DMA (opt-in, measured slower); False forces the direct gathers even under MS_WARP_ASYNC=1
+        cfg.raster_tile_order = 1 if raster_order else 0   # work lists in raster order instead of the XCD-aware order
         cfg.view_shards = shards; cfg.view_shard_index = shard_index   # view sharding
         cfg.col_shards = col_shards; cfg.col_shard_index = col_shard_index   # pano-column sharding
         cfg.self_check = 1 if os.environ.get("MS_CHECK_DIVIDE", "0") not in ("", "0") else 0   # (this binding is test / bench infrastructure: the LIBRARY reads no environment; tests/conftest.py sets the variable)
@@ -747,6 +751,21 @@ class Compositor:
 
     def build_maps(self):
         _chk(load().ms_build_maps(self._ctx, _stream()))
+
+    def set_maps(self, rois, xmaps, ymaps):
+        """ms_set_maps: the caller's own backward maps instead of build_maps() (no cameras needed).  rois: (x, y, width, height) per view; xmaps / ymaps: float32 cuda
+        tensors of height x width per view (row-strided views of larger tensors are fine).  The context keeps copies."""
+        assert len(rois) == self.n and len(xmaps) == self.n and len(ymaps) == self.n
+        r = (Rect * self.n)(*[Rect(*[int(v) for v in t]) for t in rois])
+        xs = (Image * self.n)(*[img(t) for t in xmaps])
+        ys = (Image * self.n)(*[img(t) for t in ymaps])
+        _chk(load().ms_set_maps(self._ctx, r, xs, ys, _stream()))
+
+    def map_source(self):
+        """ms_get_map_source: MAPS_ANALYTIC (build_maps) or MAPS_CUSTOM (set_maps)"""
+        v = C.c_int(-1)
+        _chk(load().ms_get_map_source(self._ctx, C.byref(v)))
+        return v.value
 
     def build_masks(self, mode=1):
         _chk(load().ms_build_masks(self._ctx, mode, _stream()))

@@ -102,6 +102,16 @@ public:
     void setCamera(int i, const float *K, const float *R) { check(ms_set_camera(ctx_, i, K, R)); }
     void setGain(int i, double g) { check(ms_set_gain(ctx_, i, g)); }                 // gc->gains()[i]
     void buildMaps(ms_stream s = nullptr) { check(ms_build_maps(ctx_, s)); }          // gpu_warper->buildMaps + blender->prepare
+    // ... or the caller's own x_maps / y_maps (what stitch_online receives, timed.cpp:56, :84-90) with the corners / sizes prepare() gets: any lens model or third-party
+    // calibration; no setCamera needed.  The maps are copied.  calibrate_seam / save_tables are refused on such a context (they need cameras).
+    template <class Mat> void setMaps(const std::vector<ms_rect> &rois, const std::vector<Mat> &x_maps, const std::vector<Mat> &y_maps, ms_stream s = nullptr)
+    {
+        if ((int)rois.size() != n_ || (int)x_maps.size() != n_ || (int)y_maps.size() != n_) throw Error(MS_ERR_INVALID, "setMaps: one ROI and one pair of maps per view");
+        std::vector<ms_image> x, y;
+        for (int i = 0; i < n_; ++i) { x.push_back(wrap(x_maps[i])); y.push_back(wrap(y_maps[i])); }
+        check(ms_set_maps(ctx_, rois.data(), x.data(), y.data(), s));
+    }
+    bool customMaps() const { int src = MS_MAPS_ANALYTIC; check(ms_get_map_source(ctx_, &src)); return src == MS_MAPS_CUSTOM; }
     void buildMasks(bool voronoi_seams = true, ms_stream s = nullptr) { check(ms_build_masks(ctx_, voronoi_seams ? 1 : 0, s)); }
     void setMask(int i, const uint8_t *host_mask, size_t step) { check(ms_set_mask(ctx_, i, host_mask, step)); }
     void init_gpu(ms_stream s = nullptr) { check(ms_init_blender(ctx_, s)); }         // mb->init_gpu for every view

@@ -21,6 +21,12 @@ int shim_compile_check()
         msshim::Calibration cal;
         std::unique_ptr<msshim::Compositor> calibrated = msshim::stitch_calib(frames, MS_PROJ_CYLINDRICAL, true, cal);      // stitch_calib
         (void)rig; (void)calibrated;
+        {   // a timed.cpp-style caller that owns x_maps / y_maps (and the corners / sizes prepare() got) hands them over instead of cameras
+            msshim::Compositor own(6, 1920, 1080, MS_PROJ_CYLINDRICAL, 611.f, 5, false, 3840, 1920);
+            std::vector<FakeGpuMat> x_maps(6), y_maps(6);
+            own.setMaps(std::vector<ms_rect>(6), x_maps, y_maps);
+            (void)own.customMaps();
+        }
         comp.stitch_one(frames, &a, (FakeGpuMat *)nullptr);
         comp.trackGains(frames, 4, 0.25);
         const std::vector<double> tracked = comp.gains();
