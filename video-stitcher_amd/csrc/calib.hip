@@ -3,6 +3,8 @@
 //       distanceTransform(DIST_L1, 3)   sources/modules/imgproc/src/distransform.cpp:70-137
 //   GainCompensator::feed               sources/modules/stitching/src/exposure_compensate.cpp:71-145 (overlap sums, normal equations, cv::solve)
 // so that ms_build_masks / ms_calibrate_seam move no pixels to the host: the only thing that comes back is the N gains.
+// Below them, exposure tracking from live frames (ms_gain_stats / ms_track_gains and their NV12, column-shard and view-shard forms): GainCompensator::feed's
+// statistics at compose scale on the caller's stream -- the kernels, and behind them the entry points that launch them (the context type comes from ctx.hpp).
 //
 // Exactness.  The reference's two-pass 3 x 3 chamfer with costs (1, 2) IS the city-block distance to the nearest zero pixel of the window
 // (a diagonal step costs two axis steps), in 16.16 fixed point; here the same integers come from two separable 1-D passes (columns, then
@@ -11,12 +13,68 @@
 // The gain sums are DOUBLE sums of square roots in raster order (exposure_compensate.cpp:103-117): order matters for the last bit, so one
 // thread per image pair walks its overlap in that order (the overlaps are seam-scale images: a few thousand pixels); the n x n solve follows
 // cv::solve's closed forms / LU (as the host version did) in a single thread.
-#include <vector>
 #include "common.hpp"
 #include "launchers.hpp"
 #include "descs.hpp"
+#include "ctx.hpp"
 
 namespace ms {
+// ---- exposure tracking: what its kernels take by value (the entry points below fill it).  The sample lattice, the views' static maps and this call's frames: -------
+struct GainTrackViews {
+    const float *xmap[MS_MAX_VIEWS]; int pitch[MS_MAX_VIEWS];      // projection maps (ymap follows xmap: roi.height rows further), pitch in elements
+    ms_rect roi[MS_MAX_VIEWS];
+    const uint8_t *src[MS_MAX_VIEWS]; unsigned step[MS_MAX_VIEWS]; // this call's 8UC3 frames, or their NV12 planes (active views only)
+    ms_rect T; int stride, nsx, nsy;                               // pano ROI, lattice step, samples per row / column
+    int n, src_w, src_h; unsigned active;
+};
+constexpr int GAIN_TRACK_MAX_TABLES = MS_MAX_VIEWS + 4;            // full set, its alternate copy, num_views + 1 cached subsets
+struct GainTrackTables { ViewDesc *tab[GAIN_TRACK_MAX_TABLES]; int n; };
+// Partial statistics (ms_gain_stats_partial / ms_track_gains_from_partials): the raw accumulators of one column window in a caller-owned device buffer, so that
+// the windows' integers add up on the device to the unsharded statistic.  Layout of a partial of an n-view context (ms_gain_partial_bytes):
+//   GainPartialHeader, cnt[n * n] (symmetric), S[n * n]  -- unsigned 64-bit each, before the max(1, cnt) rule
+constexpr unsigned GAIN_PARTIAL_MAGIC = 0x50474d53u;               // "SMGP"
+constexpr int GAIN_MAX_PARTIALS = 16;                              // = the largest ms_config.col_shards
+struct GainPartialHeader { unsigned magic, n, active, stride; int tx, ty, tw, th; };      // T = the pano ROI the lattice starts from (the same on every shard)
+struct GainPartials { const unsigned long long *p[GAIN_MAX_PARTIALS]; int n; };
+inline size_t gain_partial_bytes(int n) { return sizeof(GainPartialHeader) + 2 * (size_t)n * n * sizeof(unsigned long long); }
+// Sample vectors (ms_gain_samples / ms_track_gains_from_samples): view shards.  What a pair needs of view a at a lattice sample is one integer, q_a or "not
+// seen"; the owner of a view stores it for every sample of the view's lattice rectangle R_v, the buffers travel, and every shard forms the pair sums from all of
+// them.  Layout of a buffer (ms_gain_samples_bytes; 32-bit words):
+//   [0] magic  [1] num_views  [2] active mask  [3] stride  [4..7] T.x, T.y, T.width, T.height  [8] mask of the views held  [9] total bytes  [10..15] 0
+//   [16 + v]   word offset of view v's data from the start of the buffer; 0 = not held
+//   data       per held view in view order, R_v row-major: 0 = not seen, else q + 1
+constexpr unsigned GAIN_SAMPLES_MAGIC = 0x56474d53u;               // "SMGV"
+constexpr int GAIN_SAMPLES_HEADER_WORDS = 16;
+constexpr int GAIN_MAX_SAMPLE_BUFS = 4;
+// R_v in lattice indices: the (sx, sy) with T.x + sx * stride in [roi.x, roi.x + roi.width) and the same in y; w or h may be 0.  off = the word offset of the
+// view in the buffer of a shard that holds `held`; computed on the host by gain_sample_rects alone, handed to producer and consumer by value.
+struct GainSampleRects { int x0[MS_MAX_VIEWS], y0[MS_MAX_VIEWS], w[MS_MAX_VIEWS], h[MS_MAX_VIEWS]; };
+struct GainSampleBufs { const unsigned *p[GAIN_MAX_SAMPLE_BUFS]; int n; };
+inline GainSampleRects gain_sample_rects(const GainTrackViews &V)
+{
+    GainSampleRects R;
+    auto first = [](int lo, int s) { return lo <= 0 ? 0 : (lo + s - 1) / s; };      // the smallest k >= 0 with k * s >= lo
+    for (int v = 0; v < V.n; ++v) {
+        const ms_rect r = V.roi[v];
+        const int x0 = first(r.x - V.T.x, V.stride), x1 = std::min(V.nsx, first(r.x + r.width - V.T.x, V.stride));
+        const int y0 = first(r.y - V.T.y, V.stride), y1 = std::min(V.nsy, first(r.y + r.height - V.T.y, V.stride));
+        R.x0[v] = x0; R.y0[v] = y0; R.w[v] = std::max(0, x1 - x0); R.h[v] = std::max(0, y1 - y0);
+    }
+    return R;
+}
+// word offsets of the views `held` in their buffer (0 elsewhere); returns the buffer's size in words
+inline size_t gain_sample_offsets(const GainTrackViews &V, const GainSampleRects &R, unsigned held, unsigned *off)
+{
+    size_t at = GAIN_SAMPLES_HEADER_WORDS + (size_t)V.n;
+    for (int v = 0; v < V.n; ++v) {
+        off[v] = 0;
+        if (!((held >> v) & 1u)) continue;
+        off[v] = (unsigned)at;
+        at += (size_t)R.w[v] * R.h[v];
+    }
+    return at;
+}
+
 namespace {
 
 constexpr int VGAP = 10;                 // findInPair's `gap`
@@ -302,7 +360,7 @@ __global__ void __launch_bounds__(256) k_gain_update(GainTrackViews V, GainTrack
 }
 
 // ---- partial statistics: column shards (ms_gain_stats_partial / ms_track_gains_from_partials) ------------------------------------------------------
-// k_gain_stats over the lattice columns of this context's window IS the partial statistic: the launcher hands it a lattice whose origin is the window's first
+// k_gain_stats over the lattice columns of this context's window IS the partial statistic: ms_gain_stats_partial hands it a lattice whose origin is the window's first
 // sample column (V.T.x, V.nsx), so the kernel that reads the pixels is the one ms_track_gains runs.  k_gain_partial_export moves the raw accumulators into the
 // caller's buffer behind a header and clears them for the next call; plain vector stores.
 __global__ void __launch_bounds__(256) k_gain_partial_export(int n, GainPartialHeader H, unsigned long long *__restrict__ acc, unsigned *__restrict__ out)
@@ -346,7 +404,7 @@ __global__ void __launch_bounds__(256) k_gain_update_partials(GainTrackViews V, 
 
 // ---- sample vectors: view shards (ms_gain_samples / ms_track_gains_from_samples) -------------------------------------------------------------------------
 // A view shard holds the pixels of its own views only, so it cannot form a pair sum; it can store what a pair needs of each of its views, q or "not seen" at
-// every lattice sample of the view's rectangle R_v (launchers.hpp).  k_gain_samples: a lane owns one sample of one held view, lanes along sx, so a wave stores
+// every lattice sample of the view's rectangle R_v (GainSampleRects, above).  k_gain_samples: a lane owns one sample of one held view, lanes along sx, so a wave stores
 // one contiguous run of 4-byte words and reads the maps as k_gain_stats does.  The grid is the held views' own 64 x 4 tiles one after the other (first[i] = the
 // first workgroup of the i-th held view): no workgroup for a view of another shard, none beyond a small rectangle because another view's is large.  Workgroup 0
 // also stores header and offset table.
@@ -523,76 +581,475 @@ int estimate_gains_device(int n, const ms_rect *rois, const uint8_t *const *imag
     (void)hipFree(buf);
     return rc;
 }
+}  // namespace ms
 
-// ---- exposure tracking: the launches ms_gain_stats / ms_track_gains enqueue (compositor.hip owns the buffers and the ordering) --------------------
-int launch_gain_stats(const GainTrackViews &V, GainTrackBuf *buf, bool nv12, hipStream_t st)
+using namespace ms;
+
+// ---- exposure tracking: ms_gain_stats / ms_track_gains / ms_get_gains and their sharded forms, beside the kernels they launch ---------------------------------------
+static unsigned gain_window_reads(const ms_ctx *c, unsigned active)      // the active views whose warped ROI meets the window's columns
+{
+    const ms_rect T = c->bg.dst_roi_final;
+    const bool windowed = c->col_end > c->col_begin;
+    const int x0 = T.x + (windowed ? c->col_begin : 0), x1 = T.x + (windowed ? c->col_end : T.width);
+    unsigned m = 0;
+    for (int v = 0; v < c->N; ++v)
+        if (((active >> v) & 1u) && c->roi[v].x < x1 && c->roi[v].x + c->roi[v].width > x0) m |= 1u << v;
+    return m;
+}
+// the whole lattice of a stride, the views' ROIs and static maps, the active set -- without a call's checks (maps built, tables_mu held): what the sizes depend on
+static void gain_geometry_fill(const ms_ctx *c, int stride, GainTrackViews &V)
+{
+    V = GainTrackViews{};
+    V.n = c->N; V.src_w = c->cfg.src_width; V.src_h = c->cfg.src_height;
+    V.active = c->act ? c->act->views : all_views(c->N);
+    V.T = c->bg.dst_roi_final; V.stride = stride;
+    V.nsx = div_up(V.T.width, stride); V.nsy = div_up(V.T.height, stride);
+    for (int v = 0; v < c->N; ++v) {
+        V.xmap[v] = (const float *)c->maps.p + c->map_off[v]; V.pitch[v] = c->map_pitch[v];
+        V.roi[v] = c->roi[v];
+    }
+}
+// What every entry point checks on its context, and the by-value kernel argument without frames (taken under tables_mu: the active set and the geometry cannot
+// change meanwhile).  The caller states its sharding rule: view_shards / col_shards = a context sharded that way is served.  ms_gain_stats / ms_track_gains serve
+// neither (a shard does not hold every overlap); the partial calls serve column shards, the sample calls view shards.  frames: the call reads `views`, refused here
+// if null (gain_frames checks them one by one).  nv12: the views are the cameras' planes (8UC1, (src_height * 3 / 2) x src_width); the maps are all the statistic
+// needs, so the tiled warp is not required.
+static int gain_geometry(ms_ctx *c, const char *who, bool view_shards, bool col_shards, bool frames, const ms_image *views, int stride, bool nv12, GainTrackViews &V)
+{
+    if (!c->blender_ready) return fail(MS_ERR_STATE, "%s: call ms_init_blender first", who);
+    const bool by_view = sharded_ctx(c) || c->cfg.view_shards > 1, by_col = c->cfg.col_shards > 1;
+    if (!view_shards && !col_shards && (by_view || by_col))
+        return fail(MS_ERR_UNSUPPORTED, "%s: not for a view- or column-sharded context (a shard does not hold every overlap); column shards track with ms_gain_stats_partial / ms_track_gains_from_partials", who);
+    if (!col_shards && by_col) return fail(MS_ERR_UNSUPPORTED, "%s: not for a column-sharded context (column shards track with ms_gain_stats_partial / ms_track_gains_from_partials)", who);
+    if (!view_shards && by_view) return fail(MS_ERR_UNSUPPORTED, "%s: not for a view-sharded context (a pair statistic needs both views' pixels at one sample; a view shard holds only its own)", who);
+    if (c->feather_sharpness >= 0.f) return fail(MS_ERR_UNSUPPORTED, "%s: not for FeatherBlender contexts (ms_init_feather)", who);
+    if (frames) MS_CHECK(views, "%s: null views", who);
+    MS_CHECK(stride >= 1, "%s: stride %d < 1", who, stride);
+    if (nv12) MS_CHECK((c->cfg.src_width & 1) == 0 && (c->cfg.src_height & 1) == 0, "%s: NV12 frames have an even size, the context's source size is %dx%d", who, c->cfg.src_width, c->cfg.src_height);
+    gain_geometry_fill(c, stride, V);
+    return MS_OK;
+}
+// this call's frames of the views in `reads`: a view left out, one no sample of the window lies in, or another shard's, is never read and not looked at
+static int gain_frames(const char *who, const ms_image *views, unsigned reads, bool nv12, GainTrackViews &V)
+{
+    for (int v = 0; v < V.n; ++v) {
+        if (!((reads >> v) & 1u)) continue;
+        if (nv12)
+            MS_CHECK(views[v].data && views[v].type == MS_8UC1 && views[v].rows == V.src_h * 3 / 2 && views[v].cols == V.src_w && views[v].step >= (size_t)V.src_w,
+                     "%s: view %d must be the NV12 planes of a %dx%d frame (DEVICE 8UC1, %d rows)", who, v, V.src_w, V.src_h, V.src_h * 3 / 2);
+        else
+            MS_CHECK(views[v].data && views[v].type == MS_8UC3 && views[v].rows == V.src_h && views[v].cols == V.src_w && views[v].step >= (size_t)V.src_w * 3,
+                     "%s: view %d must be a DEVICE 8UC3 image of %dx%d", who, v, V.src_w, V.src_h);
+        V.src[v] = (const uint8_t *)views[v].data; V.step[v] = (unsigned)views[v].step;
+    }
+    return MS_OK;
+}
+// the header of a partial of V's rig, active set, stride and whole-ROI lattice (the same on every shard: before ms_gain_stats_partial narrows V to its window)
+static GainPartialHeader gain_partial_header(const GainTrackViews &V)
+{
+    return GainPartialHeader{GAIN_PARTIAL_MAGIC, (unsigned)V.n, V.active, (unsigned)V.stride, V.T.x, V.T.y, V.T.width, V.T.height};
+}
+// the one check of ms_gain_track_params (dist.cpp has its own: it refuses before anything moves between ranks)
+static int gain_params_check(const char *who, const ms_gain_track_params *prm)
+{
+    if (!prm) return fail(MS_ERR_INVALID, "%s: null params", who);
+    MS_CHECK(prm->struct_size == sizeof(ms_gain_track_params), "%s: ms_gain_track_params.struct_size is %u, this library expects %zu", who, prm->struct_size, sizeof(ms_gain_track_params));
+    MS_CHECK(prm->smoothing > 0.0 && prm->smoothing <= 1.0, "%s: smoothing %g outside (0, 1]", who, prm->smoothing);
+    return MS_OK;
+}
+// every view table a later stitch may read (tables_mu held): the full set, its enqueue-only-mask-update copy, the cached subsets
+static GainTrackTables gain_track_tables(ms_ctx *c)
+{
+    GainTrackTables W{};
+    W.tab[W.n++] = (ViewDesc *)c->view_tab.p;
+    if (c->alt.view_tab.p && (int)c->alt.h_views.size() == c->N) W.tab[W.n++] = (ViewDesc *)c->alt.view_tab.p;
+    for (auto &T : c->subsets)
+        if (T->view_tab.p && W.n < GAIN_TRACK_MAX_TABLES) W.tab[W.n++] = (ViewDesc *)T->view_tab.p;
+    return W;
+}
+// The one enqueue of every call that uses the accumulators (B).  The caller holds tables_mu (lock order: tables_mu, gain_mu, mesh_mu), so the geometry and the table
+// list it made stay valid until the kernels are in the stream; both locks are held for the enqueue only, never for a GPU wait.  `accumulate` adds this call's
+// statistics (or nothing: the partials are summed by the update itself), `finish` exports or solves and leaves the accumulators cleared.  A call that publishes
+// gains waits for the last stitch of another stream BETWEEN the two: the statistics overlap that stitch, only the update that rewrites its view tables runs behind it.
+// N_host, S_host: the tail of both statistics calls, the exported block to the host.  It cannot be overwritten before it is read back: the next call waits for
+// gain_ev, recorded behind the copies.  The caller synchronises once its locks are released.
+template <typename Accumulate, typename Finish>
+static int gain_enqueue(ms_ctx *c, hipStream_t st, bool publishes, Accumulate accumulate, Finish finish, long long *N_host = nullptr, long long *S_host = nullptr)
+{
+    GainTrackBuf *B = (GainTrackBuf *)c->gain_buf.p;
+    std::lock_guard<std::mutex> gk(c->gain_mu);
+    // the accumulators are shared by every call of the context: behind the last one, and behind whatever may still rewrite a view table
+    if (c->gain_ev_set) MS_HIP(hipStreamWaitEvent(st, c->gain_ev, 0));
+    if (c->subset_built_set) MS_HIP(hipStreamWaitEvent(st, c->subset_built, 0));
+    { std::lock_guard<std::mutex> mk(c->mesh_mu); if (c->tab_wait) MS_HIP(hipStreamWaitEvent(st, c->tab_ready, 0)); }
+    if (int e = accumulate(B)) return e;
+    // a call that publishes gains: behind every stitch that may still read the view tables, when that stitch runs on another stream
+    if (publishes && c->stitch_pending && c->last_stream_set && c->last_stream != st) MS_HIP(hipStreamWaitEvent(st, c->last_stitch, 0));
+    if (int e = finish(B)) return e;
+    if (N_host) {
+        const size_t nn = (size_t)c->N * c->N;
+        MS_HIP(hipMemcpyAsync(N_host, B->outN, nn * sizeof(long long), hipMemcpyDeviceToHost, st));
+        MS_HIP(hipMemcpyAsync(S_host, B->outS, nn * sizeof(long long), hipMemcpyDeviceToHost, st));
+    }
+    MS_HIP(hipEventRecord(c->gain_ev, st));
+    c->gain_ev_set = true;
+    if (publishes) {      // ... and now that gain_ev is recorded behind it, the next stitch on another stream waits for that event
+        c->gain_tracked = true;
+        c->gain_pub_stream = st; c->gain_pub_pending = true;
+    }
+    return MS_OK;
+}
+static int launch_checked() { MS_LAUNCH_CHECK(); return MS_OK; }
+// k_gain_stats over V's lattice, from 8UC3 frames or NV12 planes: what ms_gain_stats, ms_track_gains and ms_gain_stats_partial accumulate
+static int gain_accumulate(const GainTrackViews &V, GainTrackBuf *B, bool nv12, hipStream_t st)
 {
     if (V.nsx <= 0 || V.nsy <= 0) return MS_OK;
     const dim3 g(div_up(V.nsx, 64), div_up(V.nsy, 4)), b(64, 4);
-    if (nv12) k_gain_stats<true><<<g, b, 0, st>>>(V, buf->acc);
-    else k_gain_stats<false><<<g, b, 0, st>>>(V, buf->acc);
-    MS_LAUNCH_CHECK();
-    return MS_OK;
+    if (nv12) k_gain_stats<true><<<g, b, 0, st>>>(V, B->acc);
+    else k_gain_stats<false><<<g, b, 0, st>>>(V, B->acc);
+    return launch_checked();
 }
-int launch_gain_export(const GainTrackViews &V, GainTrackBuf *buf, hipStream_t st)
+// k_gain_stats' lattice walk from the shards' sample buffers: what ms_gain_stats_from_samples and ms_track_gains_from_samples accumulate
+static int gain_accumulate_samples(const GainTrackViews &V, const GainSampleRects &R, const GainSampleBufs &P, GainTrackBuf *B, hipStream_t st)
 {
-    k_gain_export<<<1, 256, 0, st>>>(V, buf->acc, buf->outN, buf->outS);
-    MS_LAUNCH_CHECK();
-    return MS_OK;
+    k_gain_stats_from_samples<<<dim3(div_up(V.nsx, 64), div_up(V.nsy, 4)), dim3(64, 4), 0, st>>>(V, R, P, B->acc);
+    return launch_checked();
 }
-int launch_gain_update(const GainTrackViews &V, const GainTrackTables &W, GainTrackBuf *buf, double lambda, hipStream_t st)
+
+extern "C" {
+
+int ms_gain_track_default_params(ms_gain_track_params *prm)
 {
-    k_gain_update<<<1, 256, 0, st>>>(V, W, buf->acc, buf->state, &buf->solves_ok, lambda);
-    MS_LAUNCH_CHECK();
-    return MS_OK;
-}
-int launch_gain_partial_export(const GainTrackViews &V, const GainPartialHeader &H, GainTrackBuf *buf, void *partial, hipStream_t st)
-{
-    k_gain_partial_export<<<1, 256, 0, st>>>(V.n, H, buf->acc, (unsigned *)partial);
-    MS_LAUNCH_CHECK();
-    return MS_OK;
-}
-int launch_gain_update_partials(const GainTrackViews &V, const GainTrackTables &W, const GainPartialHeader &H, const GainPartials &P, GainTrackBuf *buf, double lambda, hipStream_t st)
-{
-    k_gain_update_partials<<<1, 256, 0, st>>>(V, W, H, P, buf->state, &buf->solves_ok, lambda);
-    MS_LAUNCH_CHECK();
+    if (!prm) return fail(MS_ERR_INVALID, "ms_gain_track_default_params: null argument");
+    prm->struct_size = (unsigned)sizeof(ms_gain_track_params);
+    prm->stride = 4;
+    prm->smoothing = 0.25;
     return MS_OK;
 }
 
-int launch_gain_samples(const GainTrackViews &V, const GainSampleRects &R, unsigned held, bool nv12, void *samples, hipStream_t st)
+// ms_gain_stats / ms_gain_stats_nv12: only the kernel that reads the pixels differs
+static int gain_stats_impl(ms_ctx *c, const char *who, const ms_image *views, int stride, bool nv12, long long *N_host, long long *S_host, hipStream_t st)
 {
+    if (!c) return fail(MS_ERR_INVALID, "%s: null context", who);
+    if (!N_host || !S_host) return fail(MS_ERR_INVALID, "%s: null output", who);
+    {
+        std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);
+        GainTrackViews V;
+        if (int e = gain_geometry(c, who, false, false, true, views, stride, nv12, V)) return e;
+        if (int e = gain_frames(who, views, V.active, nv12, V)) return e;
+        auto accumulate = [&](GainTrackBuf *B) { return gain_accumulate(V, B, nv12, st); };
+        auto finish = [&](GainTrackBuf *B) {
+            k_gain_export<<<1, 256, 0, st>>>(V, B->acc, B->outN, B->outS);
+            return launch_checked();
+        };
+        if (int e = gain_enqueue(c, st, false, accumulate, finish, N_host, S_host)) return e;
+    }
+    MS_HIP(hipStreamSynchronize(st));
+    return MS_OK;
+}
+
+// ms_track_gains / ms_track_gains_nv12: the same accumulators, solve, smoothing and publication; calls of either form may alternate on one context
+static int track_gains_impl(ms_ctx *c, const char *who, const ms_image *views, const ms_gain_track_params *prm, bool nv12, hipStream_t st)
+{
+    if (!c) return fail(MS_ERR_INVALID, "%s: null context", who);
+    if (int e = gain_params_check(who, prm)) return e;
+    std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);
+    GainTrackViews V;
+    if (int e = gain_geometry(c, who, false, false, true, views, prm->stride, nv12, V)) return e;
+    if (int e = gain_frames(who, views, V.active, nv12, V)) return e;
+    const GainTrackTables W = gain_track_tables(c);
+    auto accumulate = [&](GainTrackBuf *B) { return gain_accumulate(V, B, nv12, st); };
+    auto finish = [&](GainTrackBuf *B) {
+        k_gain_update<<<1, 256, 0, st>>>(V, W, B->acc, B->state, &B->solves_ok, prm->smoothing);
+        return launch_checked();
+    };
+    return gain_enqueue(c, st, true, accumulate, finish);
+}
+
+int ms_gain_stats(ms_ctx *c, const ms_image *views, int stride, long long *N_host, long long *S_host, ms_stream stream)
+{
+    return gain_stats_impl(c, "ms_gain_stats", views, stride, false, N_host, S_host, as_stream(stream));
+}
+int ms_gain_stats_nv12(ms_ctx *c, const ms_image *views_nv12, int stride, long long *N_host, long long *S_host, ms_stream stream)
+{
+    return gain_stats_impl(c, "ms_gain_stats_nv12", views_nv12, stride, true, N_host, S_host, as_stream(stream));
+}
+int ms_track_gains(ms_ctx *c, const ms_image *views, const ms_gain_track_params *prm, ms_stream stream)
+{
+    return track_gains_impl(c, "ms_track_gains", views, prm, false, as_stream(stream));
+}
+int ms_track_gains_nv12(ms_ctx *c, const ms_image *views_nv12, const ms_gain_track_params *prm, ms_stream stream)
+{
+    return track_gains_impl(c, "ms_track_gains_nv12", views_nv12, prm, true, as_stream(stream));
+}
+
+int ms_get_gains(ms_ctx *c, double *gains_host, int *solves_ok, int *solves_singular, ms_stream stream)
+{
+    if (!c) return fail(MS_ERR_INVALID, "null context");
+    if (!gains_host) return fail(MS_ERR_INVALID, "ms_get_gains: null output");
+    if (!c->blender_ready || !c->gain_buf.p) return fail(MS_ERR_STATE, "ms_get_gains: call ms_init_blender first");
+    hipStream_t st = as_stream(stream);
+    bool wait;
+    { std::lock_guard<std::mutex> gk(c->gain_mu); wait = c->gain_ev_set; }
+    if (wait) MS_HIP(hipStreamWaitEvent(st, c->gain_ev, 0));      // (a track call on another stream)
+    GainTrackBuf *B = (GainTrackBuf *)c->gain_buf.p;
+    double g[MAX_VIEWS];
+    int cnt[2];
+    MS_HIP(hipMemcpyAsync(g, B->state, sizeof(g), hipMemcpyDeviceToHost, st));
+    MS_HIP(hipMemcpyAsync(cnt, &B->solves_ok, sizeof(cnt), hipMemcpyDeviceToHost, st));
+    MS_HIP(hipStreamSynchronize(st));
+    std::lock_guard<std::mutex> gk(c->gain_mu);
+    for (int v = 0; v < c->N; ++v) gains_host[v] = c->gain[v] = g[v];
+    if (solves_ok) *solves_ok = cnt[0];
+    if (solves_singular) *solves_singular = cnt[1];
+    return MS_OK;
+}
+
+// ---- exposure tracking on column shards: partial statistics in caller-owned device memory, summed and solved on the device ---------------------------------------
+size_t ms_gain_partial_bytes(const ms_ctx *c)
+{
+    if (!c) { (void)fail(MS_ERR_INVALID, "ms_gain_partial_bytes: null context"); return 0; }
+    return gain_partial_bytes(c->N);
+}
+
+int ms_get_gain_views(const ms_ctx *cc, unsigned *mask)
+{
+    if (!mask) return fail(MS_ERR_INVALID, "ms_get_gain_views: null output");
+    if (!cc) return fail(MS_ERR_INVALID, "ms_get_gain_views: null context");
+    ms_ctx *c = const_cast<ms_ctx *>(cc);
+    std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);
+    GainTrackViews V;
+    if (int e = gain_geometry(c, "ms_get_gain_views", false, true, false, nullptr, 1, false, V)) return e;
+    *mask = gain_window_reads(c, V.active) | (c->own_mask & c->needed_mask & V.active);
+    return MS_OK;
+}
+
+// ms_gain_stats_partial: the lattice columns of this context's column window (the whole ROI without column shards); only the views whose ROI meets those columns are checked and read
+static int gain_partial_impl(ms_ctx *c, const char *who, const ms_image *views, int stride, bool nv12, void *partial, hipStream_t st)
+{
+    // (what does not depend on the context first: these checks run, and are tested, without a device)
+    MS_CHECK(partial && ((uintptr_t)partial & 7u) == 0, "%s: the partial must be a DEVICE buffer of ms_gain_partial_bytes, 8-byte aligned", who);
+    MS_CHECK(views, "%s: null views", who);
+    MS_CHECK(stride >= 1, "%s: stride %d < 1", who, stride);
+    if (!c) return fail(MS_ERR_INVALID, "%s: null context", who);
+    std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);
+    GainTrackViews V;
+    if (int e = gain_geometry(c, who, false, true, true, views, stride, nv12, V)) return e;
+    if (int e = gain_frames(who, views, gain_window_reads(c, V.active), nv12, V)) return e;
+    const GainPartialHeader H = gain_partial_header(V);
+    if (c->col_end > c->col_begin) {      // the samples with col_begin <= u - T.x < col_end: the lattice starts at the window's first sample column
+        const int s0 = div_up(c->col_begin, stride), s1 = div_up(c->col_end, stride);
+        V.T.x += s0 * stride; V.nsx = s1 - s0;
+    }
+    auto accumulate = [&](GainTrackBuf *B) { return gain_accumulate(V, B, nv12, st); };
+    auto finish = [&](GainTrackBuf *B) {
+        k_gain_partial_export<<<1, 256, 0, st>>>(V.n, H, B->acc, (unsigned *)partial);
+        return launch_checked();
+    };
+    return gain_enqueue(c, st, false, accumulate, finish);
+}
+int ms_gain_stats_partial(ms_ctx *c, const ms_image *views, int stride, void *partial_dev, ms_stream stream)
+{
+    return gain_partial_impl(c, "ms_gain_stats_partial", views, stride, false, partial_dev, as_stream(stream));
+}
+int ms_gain_stats_partial_nv12(ms_ctx *c, const ms_image *views_nv12, int stride, void *partial_dev, ms_stream stream)
+{
+    return gain_partial_impl(c, "ms_gain_stats_partial_nv12", views_nv12, stride, true, partial_dev, as_stream(stream));
+}
+
+int ms_track_gains_from_partials(ms_ctx *c, const void *const *partials, int n_partials, const ms_gain_track_params *prm, ms_stream stream)
+{
+    const char *who = "ms_track_gains_from_partials";
+    if (int e = gain_params_check(who, prm)) return e;
+    MS_CHECK(partials, "%s: null partials", who);
+    MS_CHECK(n_partials >= 1 && n_partials <= GAIN_MAX_PARTIALS, "%s: %d partials, not in [1, %d]", who, n_partials, GAIN_MAX_PARTIALS);
+    GainPartials P{};
+    P.n = n_partials;
+    for (int k = 0; k < n_partials; ++k) {
+        MS_CHECK(partials[k] && ((uintptr_t)partials[k] & 7u) == 0, "%s: partial %d is null or not 8-byte aligned", who, k);
+        P.p[k] = (const unsigned long long *)partials[k];
+    }
+    MS_CHECK(prm->stride >= 1, "%s: stride %d < 1", who, prm->stride);
+    if (!c) return fail(MS_ERR_INVALID, "%s: null context", who);
+    hipStream_t st = as_stream(stream);
+    std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);
+    GainTrackViews V;
+    if (int e = gain_geometry(c, who, false, true, false, nullptr, prm->stride, false, V)) return e;
+    const GainPartialHeader H = gain_partial_header(V);
+    const GainTrackTables W = gain_track_tables(c);
+    // (the partials are the caller's: whatever wrote them is ordered before this call by the caller's stream)
+    auto accumulate = [](GainTrackBuf *) { return MS_OK; };      // (the update sums the partials itself)
+    auto finish = [&](GainTrackBuf *B) {
+        k_gain_update_partials<<<1, 256, 0, st>>>(V, W, H, P, B->state, &B->solves_ok, prm->smoothing);
+        return launch_checked();
+    };
+    return gain_enqueue(c, st, true, accumulate, finish);
+}
+
+// ---- exposure tracking on view shards: per-view sample vectors in caller-owned device memory, paired, summed and solved on the device -------------------------------
+static unsigned view_shard_mask(int N, int S, int k)      // the block of views of shard k of S (ms_create)
+{
+    unsigned m = 0;
+    for (int v = k * N / S; v < (k + 1) * N / S; ++v) m |= 1u << v;
+    return m;
+}
+size_t ms_gain_samples_bytes(const ms_ctx *c, int stride, int view_shard_index)
+{
+    const char *who = "ms_gain_samples_bytes";
+    if (!c) { (void)fail(MS_ERR_INVALID, "%s: null context", who); return 0; }
+    if (stride < 1) { (void)fail(MS_ERR_INVALID, "%s: stride %d < 1", who, stride); return 0; }
+    const int S = c->cfg.view_shards > 1 ? c->cfg.view_shards : 1;
+    if (view_shard_index < -1 || view_shard_index >= S) { (void)fail(MS_ERR_INVALID, "%s: view shard %d of %d", who, view_shard_index, S); return 0; }
+    if (!c->maps_built) { (void)fail(MS_ERR_STATE, "%s: call ms_build_maps first", who); return 0; }
+    if (c->cfg.col_shards > 1 || c->feather_sharpness >= 0.f) { (void)fail(MS_ERR_UNSUPPORTED, "%s: not for column-sharded or FeatherBlender contexts", who); return 0; }
+    std::lock_guard<std::recursive_mutex> tables_lk(const_cast<ms_ctx *>(c)->tables_mu);
+    const unsigned own = view_shard_index < 0 ? c->own_mask & all_views(c->N) : view_shard_mask(c->N, S, view_shard_index);
+    GainTrackViews V;
+    gain_geometry_fill(c, stride, V);
+    unsigned off[MS_MAX_VIEWS];
+    const size_t words = gain_sample_offsets(V, gain_sample_rects(V), own & V.active, off);
+    if (words > 0xffffffffu / 4u) { (void)fail(MS_ERR_INVALID, "%s: the buffer would exceed 4 GiB at stride %d; use a larger stride", who, stride); return 0; }
+    return words * 4;
+}
+
+int ms_get_view_shard(const ms_ctx *c, int *view_shards, int *view_shard_index)
+{
+    if (!view_shards || !view_shard_index) return fail(MS_ERR_INVALID, "ms_get_view_shard: null output");
+    if (!c) return fail(MS_ERR_INVALID, "ms_get_view_shard: null context");
+    const bool sharded = c->cfg.view_shards > 1;
+    *view_shards = sharded ? c->cfg.view_shards : 1;
+    *view_shard_index = sharded ? c->cfg.view_shard_index : 0;
+    return MS_OK;
+}
+
+int ms_get_gain_sample_views(const ms_ctx *cc, unsigned *mask)
+{
+    const char *who = "ms_get_gain_sample_views";
+    if (!mask) return fail(MS_ERR_INVALID, "%s: null output", who);
+    if (!cc) return fail(MS_ERR_INVALID, "%s: null context", who);
+    ms_ctx *c = const_cast<ms_ctx *>(cc);
+    std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);
+    GainTrackViews V;
+    if (int e = gain_geometry(c, who, true, false, false, nullptr, 1, false, V)) return e;
+    *mask = V.active & c->own_mask;
+    return MS_OK;
+}
+
+// ms_gain_samples: the whole lattice, the views this context owns.  The accumulators are not used: outside gain_enqueue, no gain_mu
+static int gain_samples_impl(ms_ctx *c, const char *who, const ms_image *views, int stride, bool nv12, void *samples, hipStream_t st)
+{
+    // (what does not depend on the context first: these checks run, and are tested, without a device)
+    MS_CHECK(samples && ((uintptr_t)samples & 3u) == 0, "%s: the samples must be a DEVICE buffer of ms_gain_samples_bytes, 4-byte aligned", who);
+    MS_CHECK(views, "%s: null views", who);
+    MS_CHECK(stride >= 1, "%s: stride %d < 1", who, stride);
+    if (!c) return fail(MS_ERR_INVALID, "%s: null context", who);
+    std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);      // for the enqueue only (as ms_track_gains)
+    GainTrackViews V;
+    if (int e = gain_geometry(c, who, true, false, true, views, stride, nv12, V)) return e;
+    const unsigned held = V.active & c->own_mask;
+    if (int e = gain_frames(who, views, held, nv12, V)) return e;
+    const GainSampleRects R = gain_sample_rects(V);
     GainSampleOut O{};
     O.held = held;
-    O.words = (unsigned)gain_sample_offsets(V, R, held, O.off);
+    const size_t words = gain_sample_offsets(V, R, held, O.off);
+    MS_CHECK(words <= 0xffffffffu / 4u, "%s: the buffer would exceed 4 GiB at stride %d; use a larger stride", who, stride);
+    O.words = (unsigned)words;
     for (int v = 0; v < V.n; ++v) {
         if (!((held >> v) & 1u) || R.w[v] == 0 || R.h[v] == 0) continue;
         O.view[O.nheld] = (unsigned char)v;
         O.first[O.nheld + 1] = O.first[O.nheld] + (unsigned)div_up(R.w[v], 64) * (unsigned)div_up(R.h[v], 4);
         ++O.nheld;
     }
-    dim3 b(64, 4), g(std::max(1u, O.first[O.nheld]));
+    const dim3 b(64, 4), g(std::max(1u, O.first[O.nheld]));
     if (nv12) k_gain_samples<true><<<g, b, 0, st>>>(V, R, O, (unsigned *)samples);
     else k_gain_samples<false><<<g, b, 0, st>>>(V, R, O, (unsigned *)samples);
-    MS_LAUNCH_CHECK();
-    return MS_OK;
+    return launch_checked();
 }
-int launch_gain_stats_from_samples(const GainTrackViews &V, const GainSampleRects &R, const GainSampleBufs &P, GainTrackBuf *buf, hipStream_t st)
+int ms_gain_samples(ms_ctx *c, const ms_image *views, int stride, void *samples_dev, ms_stream stream)
 {
-    dim3 b(64, 4), g(div_up(V.nsx, 64), div_up(V.nsy, 4));
-    k_gain_stats_from_samples<<<g, b, 0, st>>>(V, R, P, buf->acc);
-    MS_LAUNCH_CHECK();
-    return MS_OK;
+    return gain_samples_impl(c, "ms_gain_samples", views, stride, false, samples_dev, as_stream(stream));
 }
-int launch_gain_update_samples(const GainTrackViews &V, const GainTrackTables &W, const GainSampleRects &R, const GainSampleBufs &P, GainTrackBuf *buf, double lambda, hipStream_t st)
+int ms_gain_samples_nv12(ms_ctx *c, const ms_image *views_nv12, int stride, void *samples_dev, ms_stream stream)
 {
-    k_gain_update_samples<<<1, 256, 0, st>>>(V, W, R, P, buf->acc, buf->state, &buf->solves_ok, lambda);
-    MS_LAUNCH_CHECK();
-    return MS_OK;
+    return gain_samples_impl(c, "ms_gain_samples_nv12", views_nv12, stride, true, samples_dev, as_stream(stream));
 }
-int launch_gain_export_samples(const GainTrackViews &V, const GainSampleRects &R, const GainSampleBufs &P, GainTrackBuf *buf, hipStream_t st)
+
+// the checks both consumers share; everything that needs no context first
+static int gain_sample_bufs(const char *who, const void *const *samples, int n, int stride, GainSampleBufs &P)
 {
-    k_gain_export_samples<<<1, 256, 0, st>>>(V, R, P, buf->acc, buf->outN, buf->outS, &buf->solves_ok);
-    MS_LAUNCH_CHECK();
+    MS_CHECK(samples, "%s: null samples", who);
+    MS_CHECK(n >= 1 && n <= GAIN_MAX_SAMPLE_BUFS, "%s: %d sample buffers, not in [1, %d]", who, n, GAIN_MAX_SAMPLE_BUFS);
+    P = GainSampleBufs{};
+    P.n = n;
+    for (int k = 0; k < n; ++k) {
+        MS_CHECK(samples[k] && ((uintptr_t)samples[k] & 3u) == 0, "%s: sample buffer %d is null or not 4-byte aligned", who, k);
+        P.p[k] = (const unsigned *)samples[k];
+    }
+    MS_CHECK(stride >= 1, "%s: stride %d < 1", who, stride);
     return MS_OK;
 }
-}  // namespace ms
+
+int ms_gain_stats_from_samples(ms_ctx *c, const void *const *samples, int n, int stride, long long *N_host, long long *S_host, ms_stream stream)
+{
+    const char *who = "ms_gain_stats_from_samples";
+    if (!N_host || !S_host) return fail(MS_ERR_INVALID, "%s: null output", who);
+    GainSampleBufs P;
+    if (int e = gain_sample_bufs(who, samples, n, stride, P)) return e;
+    if (!c) return fail(MS_ERR_INVALID, "%s: null context", who);
+    hipStream_t st = as_stream(stream);
+    {   // (as ms_gain_stats)
+        std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);
+        GainTrackViews V;
+        if (int e = gain_geometry(c, who, true, false, false, nullptr, stride, false, V)) return e;
+        const GainSampleRects R = gain_sample_rects(V);
+        auto accumulate = [&](GainTrackBuf *B) { return gain_accumulate_samples(V, R, P, B, st); };
+        auto finish = [&](GainTrackBuf *B) {
+            k_gain_export_samples<<<1, 256, 0, st>>>(V, R, P, B->acc, B->outN, B->outS, &B->solves_ok);
+            return launch_checked();
+        };
+        if (int e = gain_enqueue(c, st, false, accumulate, finish, N_host, S_host)) return e;
+    }
+    MS_HIP(hipStreamSynchronize(st));
+    return MS_OK;
+}
+
+int ms_track_gains_from_samples(ms_ctx *c, const void *const *samples, int n, const ms_gain_track_params *prm, ms_stream stream)
+{
+    const char *who = "ms_track_gains_from_samples";
+    if (int e = gain_params_check(who, prm)) return e;
+    GainSampleBufs P;
+    if (int e = gain_sample_bufs(who, samples, n, prm->stride, P)) return e;
+    if (!c) return fail(MS_ERR_INVALID, "%s: null context", who);
+    hipStream_t st = as_stream(stream);
+    std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);
+    GainTrackViews V;
+    if (int e = gain_geometry(c, who, true, false, false, nullptr, prm->stride, false, V)) return e;
+    const GainSampleRects R = gain_sample_rects(V);
+    const GainTrackTables W = gain_track_tables(c);
+    // (the buffers are the caller's: whatever wrote them is ordered before this call by the caller's stream)
+    auto accumulate = [&](GainTrackBuf *B) { return gain_accumulate_samples(V, R, P, B, st); };
+    auto finish = [&](GainTrackBuf *B) {
+        k_gain_update_samples<<<1, 256, 0, st>>>(V, W, R, P, B->acc, B->state, &B->solves_ok, prm->smoothing);
+        return launch_checked();
+    };
+    return gain_enqueue(c, st, true, accumulate, finish);
+}
+
+int ms_get_gain_track_counters(ms_ctx *c, ms_gain_track_counters *out, ms_stream stream)
+{
+    if (!out) return fail(MS_ERR_INVALID, "ms_get_gain_track_counters: null output");
+    MS_CHECK(out->struct_size == sizeof(ms_gain_track_counters), "ms_get_gain_track_counters: ms_gain_track_counters.struct_size is %u, this library expects %zu", out->struct_size, sizeof(ms_gain_track_counters));
+    if (!c) return fail(MS_ERR_INVALID, "ms_get_gain_track_counters: null context");
+    if (!c->blender_ready || !c->gain_buf.p) return fail(MS_ERR_STATE, "ms_get_gain_track_counters: call ms_init_blender first");
+    hipStream_t st = as_stream(stream);
+    bool wait;
+    { std::lock_guard<std::mutex> gk(c->gain_mu); wait = c->gain_ev_set; }
+    if (wait) MS_HIP(hipStreamWaitEvent(st, c->gain_ev, 0));      // (a track call on another stream)
+    int cnt[3];
+    MS_HIP(hipMemcpyAsync(cnt, &((GainTrackBuf *)c->gain_buf.p)->solves_ok, sizeof(cnt), hipMemcpyDeviceToHost, st));
+    MS_HIP(hipStreamSynchronize(st));
+    out->solves_ok = cnt[0]; out->solves_singular = cnt[1]; out->updates_rejected = cnt[2];
+    return MS_OK;
+}
+
+}  // extern "C"

@@ -18,7 +18,6 @@
 // the 16S pyramids are evaluated in exact integer arithmetic, accumulate/normalise keep the fp32
 // multiply/divide + truncation, and int16 accumulation wraps exactly like `short +=`.
 #include <algorithm>
-#include <atomic>
 #include <climits>
 #include <memory>
 #include <mutex>
@@ -27,6 +26,7 @@
 #include "common.hpp"
 #include "launchers.hpp"
 #include "descs.hpp"
+#include "ctx.hpp"
 
 namespace ms {
 
@@ -1616,187 +1616,6 @@ __global__ void __launch_bounds__(256) k_mesh_mean_resize_all(MeshJobs T)
     mesh_mean_resize_blocks(T.j[blockIdx.y], (int)blockIdx.x, (int)gridDim.x);
 }
 
-// ------------------------------------------------------------------------------------------------
-// an owned device allocation: released with its owner (ms_ctx members, function-local scratch), never copied
-struct DevBuf {
-    void *p = nullptr; size_t bytes = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { release(); }
-    int alloc(size_t n)
-    {
-        release();
-        if (n == 0) n = 16;
-        MS_HIP(hipMalloc(&p, n));
-        bytes = n;
-        return MS_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
-};
-
-static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
-
-}  // namespace ms
-
-using namespace ms;
-
-struct ms_ctx {
-    ms_config cfg{};
-    int N = 0;
-    float K[MAX_VIEWS][9], R[MAX_VIEWS][9];
-    bool have_cam[MAX_VIEWS] = {};
-    double gain[MAX_VIEWS];
-    // stage flags
-    bool maps_built = false, masks_built = false, blender_ready = false;
-    bool custom_maps = false;          // the maps are the caller's (ms_set_maps): no cameras, no 1-D projection tables -- the tiled warp kernels read xmap / ymap (PROJ_MAPS)
-    // geometry
-    ms_rect roi[MAX_VIEWS];
-    BlendGeom bg{};
-    ViewPad pad[MAX_VIEWS];
-    // static device tables
-    DevBuf maps;                       // per view xmap | ymap
-    DevBuf tabs;                       // per view column table | row table (float2)
-    size_t tab_off[MAX_VIEWS] = {};
-    WarpParams wparams[MAX_VIEWS];
-    size_t map_off[MAX_VIEWS] = {};    // float offset of xmap; ymap follows at + ah*pitch
-    int map_pitch[MAX_VIEWS] = {};
-    DevBuf masks;                      // per view 8UC1 (aw x ah, pitch = aw)
-    size_t mask_off[MAX_VIEWS] = {};
-    DevBuf weights;                    // per view per level fp32
-    DevBuf wm0;                        // per view padded 8-bit mask (level-0 weights in 1 byte/px)
-    size_t wm0_off[MAX_VIEWS] = {};
-    size_t w_off[MAX_VIEWS][MAX_LEVELS] = {};
-    DevBuf den;                        // per level fp32 over the padded pano
-    size_t den_off[MAX_LEVELS] = {};
-    DevBuf result_mask;                // 8UC1 fw x fh
-    DevBuf view_tab;                   // ViewDesc[N]
-    std::vector<ViewDesc> h_views;
-    PanoDesc pano{};
-    // per-batch device buffers
-    DevBuf g0, gl, cl, stage;
-    long long g0_stride = 0, gl_stride = 0, cl_stride = 0, stage_stride = 0;
-    int max_pw = 0, max_ph = 0, max_aw = 0, max_ah = 0;
-    bool down_vec[MAX_LEVELS] = {};    // level l -> l+1 may use the vectorised kernel
-    bool blend_vec[MAX_LEVELS] = {};   // band l may use the 2x8 kernel
-    // work lists (tiles that are actually needed)
-    bool warp_tiled = false;
-    int tail_l0 = -1, tail_lds = 0, tail_strips = 1;
-    int tail_lds_b = 0, tail_strips_b = 1, tail_sw_b = 16;      // k_down_tail for batches (F > 2): wider strips
-    // the fused band kernel started one band finer: used for batches of 1-2 frames (live mode), where a launch costs more than the
-    // vectorised kernel saves
-    int btail2_t = -1, btail2_lds = 0, btail2_strips = 0;
-    int btail_t = -1, btail_lds = 0, btail_strips = 0;      // fused coarse band chain (k_blend_tail): finest band it produces, LDS bytes, strips    // fused coarse-level reduce (k_down_tail): first level it reads, LDS bytes; -1 = off
-    float feather_sharpness = -1.f;    // >= 0: single-band weights are FeatherBlender weight maps (ms_init_feather)
-    DevBuf warp_tiles, stage1_tiles, down_tiles[MAX_LEVELS], blend_tiles[MAX_LEVELS];
-    int n_stage1_tiles = 0, n_stage1_reachable = 0;
-    int last_warp_kernel = 0, last_stage1_kernel = 0;      // MS_WARP_KERNEL_* of the last ms_stitch (ms_get_stitch_kernels)
-    ms_image fed[MAX_VIEWS] = {};      // ms_feed: the views of the frame being assembled (borrowed until ms_blend)
-    unsigned fed_mask = 0;
-    DevBuf masks_eff;                  // ms_update_mask: masks re-warped through the CPW mesh (same layout as `masks`)
-    // Enqueue-only ms_update_mask (cfg.update_mask_margin > 0): a second copy of every table that depends on the masks.  `tab_active` says which
-    // copy ms_stitch reads (0: the members above / below, 1: alt); an update fills the other one on its own stream and swaps under mesh_mu.
-    struct AltTables { DevBuf weights, wm0, den, result_mask, pure_maps, view_tab; PanoDesc pano; std::vector<ViewDesc> h_views; } alt;
-    int tab_active = 0;
-    hipEvent_t tab_ready = nullptr;
-    bool tab_wait = false;
-    DevBuf mask_tmp, wm_scratch;       // re-warped mask / float weight map of the largest view
-    size_t w_total = 0, wm0_total = 0, den_total = 0, pure_total = 0, pure_off[MAX_LEVELS] = {};
-    std::atomic<bool> l0_integer_only{false};      // (atomic: launch_owner_maps clears it from the mask-update thread outside mesh_mu while ms_stitch reads it -- found by the ThreadSanitizer run of stitch_app --update-mask)
-                                                   // level 0 has an owner map without a single general cell (binary, exclusive seam masks): k_blend8's integer-only build (88 VGPRs) runs it;
-                                       // counted when build_plan makes the map, dropped by the first enqueue-only mask update (whose maps the host never sees)
-    bool use_eff[MAX_VIEWS] = {};
-    DevBuf pure_maps;                  // owner maps of the bands (PanoDesc::pure)
-    DevBuf disp_dev;                   // [view][mesh buffer]: max |mesh map - identity| as float bits, written by ms_set_mesh
-    int n_warp_tiles = 0, n_down_tiles[MAX_LEVELS] = {}, n_blend_tiles[MAX_LEVELS] = {};
-    int warp_lds_tiles = 0;            // tiles whose source bounding box fits a staging buffer of k_warp_a
-    bool warp_aligned = false;         // projection warp with the aligned 12-byte tap reads (k_warp_t<.., AL = true>): chosen from the tiles' minification
-    double warp_minification = 0;      // mean source columns per output column over the warp tiles
-    int n_cus = 256;
-    double plan_fraction = 1.0;        // needed level-0 pixels / padded pixels
-    // CPW mesh maps, double buffered
-    DevBuf mesh[2];
-    size_t mesh_off[MAX_VIEWS] = {};
-    int mesh_active[MAX_VIEWS] = {};   // which buffer ms_stitch reads for this view
-    bool mesh_set[MAX_VIEWS] = {};
-    DevBuf mesh_tmp;                   // scratch for convertMeshesToMap: vertex mesh x|y, two half-resolution accumulators ([count:24|sum_x:40], [sum_y]) used in turn
-    size_t mesh_small_cap = 0, mesh_half_cap = 0, mesh_dirty = 0;   // capacities (floats / cells); 64-bit words the previous update dirtied in its accumulator
-    int mesh_parity = 0;
-    DevBuf mesh_all;                   // scratch of ms_set_meshes (all views in one pair of launches): every view's vertex meshes, then per view two accumulator pairs used in turn
-    size_t mesh_all_small = 0;         // floats per vertex map the block was sized for
-    int mesh_all_parity = 0;
-    bool mesh_all_dirty = false;       // the accumulators of the other parity hold the previous call's sums (cleared by the next scatter launch)
-    std::mutex mesh_mu;                // guards the active indices / events shared with ms_stitch: held only across enqueues, never across a host wait
-    std::mutex mesh_update_mu;         // serialises mesh updates among themselves (shared scratch, staging slots); taken BEFORE mesh_mu
-    // Held by ms_stitch for the length of its enqueue and by everything that REBUILDS the static tables (ms_init_blender, and through it the synchronous
-    // ms_update_mask): a rebuild on the recalibration thread reallocates weights, sums and work lists, so it must neither overlap a stitch that is
-    // being enqueued (this lock) nor one that still runs on the GPU (the rebuild first waits for last_stitch under the lock).  Lock order:
-    // mesh_update_mu, tables_mu, mesh_mu.  The enqueue-only update paths (ms_set_mesh, ms_update_mask with a margin) never take it.
-    std::recursive_mutex tables_mu;
-    hipStream_t last_stream = nullptr; bool last_stream_set = false;
-    hipEvent_t last_stitch = nullptr;
-    std::atomic<bool> stitch_pending{false};
-    // asynchronous recalibration: a mesh update only enqueues work; `mesh_ready[v]` is recorded behind it and the next ms_stitch makes
-    // its stream wait for it; `mesh_chain` orders updates among themselves (they share the scratch and the staging buffers)
-    hipEvent_t mesh_ready[MAX_VIEWS] = {}, mesh_chain = nullptr;
-    bool mesh_wait[MAX_VIEWS] = {}, mesh_chain_set = false;
-    // ms_set_meshes updates every view behind ONE event: a view whose last update was part of such a call is ready when `mesh_chain` is (a later record of mesh_chain is a later
-    // point of the same chain of updates).  Twelve event records and as many stream waits per recalibration were 50 us of idle GPU between its kernels and the next stitch.
-    bool mesh_ready_via_chain[MAX_VIEWS] = {};
-    float *mesh_stage = nullptr;       // pinned host staging of the vertex meshes: a ring of MESH_STAGE_GENS generations of MAX_VIEWS slots + one generation of ms_set_mesh's own behind it (
-    size_t mesh_stage_floats = 0;      // ms_set_meshes walks the ring: the host waits for the COPY of the update a whole ring back -- `mesh_stage_ev` --, never for the update before this one)
-    static constexpr int MESH_STAGE_GENS = 8;
-    int mesh_stage_gen = 0;
-    hipEvent_t mesh_stage_ev[MESH_STAGE_GENS] = {};
-    bool mesh_stage_ev_set[MESH_STAGE_GENS] = {};
-    int canvas_x = 0, canvas_y = 0;
-    // view sharding (ms_config.view_shards = shard count S, view_shard_index = this shard's index): contiguous blocks of views per shard
-    unsigned own_mask = 0xffffffffu;
-    // pano-column sharding (ms_config.col_shards / col_shard_index): the window of pano-ROI columns this context composites and the views it reads for it
-    int col_begin = 0, col_end = 0;    // 0, 0 = whole panorama
-    unsigned needed_mask = 0xffffffffu;
-    long long pacc_stride = 0;         // elements per frame of a partial-accumulator buffer
-    // Camera dropout (ms_set_active_views).  The full-set tables above are never written by it: a subset has tables of its own, made on the device from the
-    // current full-set copy -- weight sums, result mask and owner maps of the active views, a view table whose inactive views have zero weights, and work
-    // lists without the inactive views.  The last few subsets stay cached (LRU), so a camera that drops out again costs a pointer swap.
-    struct SubsetTables {
-        unsigned views = 0, needed = 0;      // the active set; needed_mask & views
-        int gen = -1;                        // tables_gen the tables were made from
-        unsigned long long used = 0;         // LRU stamp
-        DevBuf den, result_mask, pure_maps, view_tab, warp_tiles, stage1_tiles, down_tiles[MAX_LEVELS], blend_tiles[MAX_LEVELS];
-        PanoDesc pano{};
-        int n_warp_tiles = 0, n_stage1_tiles = 0, n_down_tiles[MAX_LEVELS] = {};
-        bool l0_integer_only = false;
-        hipEvent_t ready = nullptr;          // recorded behind the rebuild; every stitch that reads these tables waits for it
-        ~SubsetTables() { if (ready) (void)hipEventDestroy(ready); }
-    };
-    std::vector<std::unique_ptr<SubsetTables>> subsets;
-    SubsetTables *act = nullptr;       // the tables ms_stitch reads: nullptr = all views (the full-set tables).  Written under tables_mu (and act_mu)
-    std::atomic<bool> subset_on{false};      // act != nullptr, for ms_update_mask (which does not take tables_mu on its enqueue-only path)
-    std::mutex act_mu;                 // serialises ms_set_active_views with ms_update_mask; taken BEFORE mesh_update_mu and tables_mu
-    int tables_gen = 0;                // bumped whenever the full-set tables change (ms_init_blender, ms_update_mask): cached subsets are rebuilt
-    unsigned long long subset_clock = 0;
-    DevBuf zero_w;                     // zeros as large as the largest view's level-0 weights (the weights of an inactive view)
-    hipEvent_t subset_built = nullptr; // behind the last subset rebuild: an enqueue-only mask update waits for it before it rewrites the copy the rebuild read
-    bool subset_built_set = false;
-    // tiles per view of the full-set lists: a subset's list sizes without reading the lists back
-    int warp_per_view[MAX_VIEWS] = {}, stage1_per_view[MAX_VIEWS] = {}, down_per_view[MAX_LEVELS][MAX_VIEWS] = {};
-    // Exposure tracking (ms_track_gains).  The gains live on the device as doubles (GainTrackBuf::state, seeded from `gain`); a track call's last kernel
-    // writes (float)state into every view table a stitch may read.  `gain` above is the host mirror: whoever uploads a view table from it, or saves it,
-    // calls pull_tracked_gains first, so that no path brings an older gain back.
-    DevBuf gain_buf;                   // one GainTrackBuf, allocated by ms_init_blender
-    hipEvent_t gain_ev = nullptr;      // behind the last ms_track_gains / ms_gain_stats: they share the accumulators, whatever their streams
-    bool gain_ev_set = false;
-    std::atomic<bool> gain_tracked{false};   // the device state may differ from `gain`
-    // A gain update publishes into view tables a stitch reads: on another stream than the stitches it runs behind the last stitch enqueued, and the next stitch waits for
-    // it (gain_ev), so a frame is composited with the gains before or after an update, never a mix.  Guarded by tables_mu, which both enqueues hold.
-    hipStream_t gain_pub_stream = nullptr;
-    bool gain_pub_pending = false;
-    std::mutex gain_mu;                // guards gain_ev_set, `gain` and the enqueues that use the accumulators; taken AFTER tables_mu, never held across a GPU wait by ms_track_gains
-};
-
-namespace ms {
-
 static int ctx_check_view(const ms_ctx *c, int v)
 {
     if (!c) return fail(MS_ERR_INVALID, "null context");
@@ -1815,6 +1634,7 @@ static ms_image view_map_image(const ms_ctx *c, int v, int which)
 
 }  // namespace ms
 
+using namespace ms;
 
 // ---- the plan: which tiles of which view/level are needed ------------------------------------------------
 // W_l = {w_{v,l} != 0};  N_l = pixels of Gaussian level l some consumer reads:
@@ -1901,8 +1721,6 @@ static void xcd_order(std::vector<T> &tiles, int chunk = 0)
     for (size_t i = 0; i < n; ++i) if (!used[i]) out.push_back(tiles[i]);
     tiles.swap(out);
 }
-
-static bool sharded_ctx(const ms_ctx *c) { return c->own_mask != ((c->N >= 32) ? 0xffffffffu : ((1u << c->N) - 1u)); }
 
 // k_owner_map for every band that has a map, into `pure` (laid out by build_plan), from the weights `vt` points at, of the views in `view_set`
 static int enqueue_owner_maps(const ms_ctx *c, const ViewDesc *vt, unsigned view_set, uint8_t *pure, hipStream_t st)
@@ -3347,7 +3165,7 @@ static int build_subset(ms_ctx *c, ms_ctx::SubsetTables &T, unsigned views, hipS
 int ms_set_active_views(ms_ctx *c, unsigned mask, ms_stream stream)
 {
     if (!c) return fail(MS_ERR_INVALID, "null context");
-    const unsigned all = (c->N >= 32) ? 0xffffffffu : ((1u << c->N) - 1u);
+    const unsigned all = all_views(c->N);
     if (mask == 0 || (mask & ~all)) return fail(MS_ERR_INVALID, "ms_set_active_views: mask 0x%x is empty or names a view >= %d", mask, c->N);
     std::lock_guard<std::mutex> alk(c->act_mu);
     std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);      // no stitch is being enqueued while the set changes (held for an enqueue, never for a GPU wait)
@@ -3377,463 +3195,9 @@ int ms_get_active_views(const ms_ctx *c, unsigned *mask)
 {
     if (!c || !mask) return fail(MS_ERR_INVALID, "ms_get_active_views: null argument");
     if (!c->blender_ready) return fail(MS_ERR_STATE, "ms_get_active_views: call ms_init_blender first");
-    const unsigned all = (c->N >= 32) ? 0xffffffffu : ((1u << c->N) - 1u);
+    const unsigned all = all_views(c->N);
     std::lock_guard<std::recursive_mutex> tables_lk(const_cast<ms_ctx *>(c)->tables_mu);
     *mask = c->act ? c->act->views : all;
-    return MS_OK;
-}
-
-// ---- exposure tracking: ms_gain_stats / ms_track_gains / ms_get_gains ---------------------------------------------------------------------------
-int ms_gain_track_default_params(ms_gain_track_params *prm)
-{
-    if (!prm) return fail(MS_ERR_INVALID, "ms_gain_track_default_params: null argument");
-    prm->struct_size = (unsigned)sizeof(ms_gain_track_params);
-    prm->stride = 4;
-    prm->smoothing = 0.25;
-    return MS_OK;
-}
-
-// what every entry point checks, and the by-value kernel argument (taken under tables_mu: the active set and the geometry cannot change meanwhile).
-// nv12: the views are the cameras' planes (8UC1, (src_height * 3 / 2) x src_width); the maps are all the statistic needs, so the tiled warp is not required.
-// mode GAIN_FULL: ms_gain_stats / ms_track_gains, the whole lattice, no shards.  GAIN_WINDOW: ms_gain_stats_partial, the lattice columns of this context's column
-// window (the whole ROI without column shards); only the views whose ROI meets those columns are checked and read.  GAIN_GEOM: ms_track_gains_from_partials, no frames.
-// GAIN_SAMPLES: ms_gain_samples, the whole lattice, the views this context owns (view shards allowed, column shards not); GAIN_SAMPLES_GEOM: the same without frames.
-enum { GAIN_FULL = 0, GAIN_WINDOW = 1, GAIN_GEOM = 2, GAIN_SAMPLES = 3, GAIN_SAMPLES_GEOM = 4 };
-static unsigned gain_window_reads(const ms_ctx *c, unsigned active)      // the active views whose warped ROI meets the window's columns
-{
-    const ms_rect T = c->bg.dst_roi_final;
-    const bool windowed = c->col_end > c->col_begin;
-    const int x0 = T.x + (windowed ? c->col_begin : 0), x1 = T.x + (windowed ? c->col_end : T.width);
-    unsigned m = 0;
-    for (int v = 0; v < c->N; ++v)
-        if (((active >> v) & 1u) && c->roi[v].x < x1 && c->roi[v].x + c->roi[v].width > x0) m |= 1u << v;
-    return m;
-}
-static int gain_track_args(ms_ctx *c, const char *who, const ms_image *views, int stride, bool nv12, GainTrackViews &V, int mode = GAIN_FULL, GainPartialHeader *H = nullptr)
-{
-    if (!c->blender_ready) return fail(MS_ERR_STATE, "%s: call ms_init_blender first", who);
-    if (mode == GAIN_FULL) {
-        if (sharded_ctx(c) || c->cfg.view_shards > 1 || c->cfg.col_shards > 1)
-            return fail(MS_ERR_UNSUPPORTED, "%s: not for a view- or column-sharded context (a shard does not hold every overlap); column shards track with ms_gain_stats_partial / ms_track_gains_from_partials", who);
-    } else if (mode == GAIN_SAMPLES || mode == GAIN_SAMPLES_GEOM) {
-        if (c->cfg.col_shards > 1) return fail(MS_ERR_UNSUPPORTED, "%s: not for a column-sharded context (column shards track with ms_gain_stats_partial / ms_track_gains_from_partials)", who);
-    } else if (sharded_ctx(c) || c->cfg.view_shards > 1)
-        return fail(MS_ERR_UNSUPPORTED, "%s: not for a view-sharded context (a pair statistic needs both views' pixels at one sample; a view shard holds only its own)", who);
-    if (c->feather_sharpness >= 0.f) return fail(MS_ERR_UNSUPPORTED, "%s: not for FeatherBlender contexts (ms_init_feather)", who);
-    const bool geom = mode == GAIN_GEOM || mode == GAIN_SAMPLES_GEOM;
-    if (!geom) MS_CHECK(views, "%s: null views", who);
-    MS_CHECK(stride >= 1, "%s: stride %d < 1", who, stride);
-    if (nv12) MS_CHECK((c->cfg.src_width & 1) == 0 && (c->cfg.src_height & 1) == 0, "%s: NV12 frames have an even size, the context's source size is %dx%d", who, c->cfg.src_width, c->cfg.src_height);
-    const int N = c->N;
-    const unsigned all = (N >= 32) ? 0xffffffffu : ((1u << N) - 1u);
-    V = GainTrackViews{};
-    V.n = N; V.src_w = c->cfg.src_width; V.src_h = c->cfg.src_height;
-    V.active = c->act ? c->act->views : all;
-    V.T = c->bg.dst_roi_final; V.stride = stride;
-    V.nsx = div_up(V.T.width, stride); V.nsy = div_up(V.T.height, stride);
-    if (H) *H = GainPartialHeader{GAIN_PARTIAL_MAGIC, (unsigned)N, V.active, (unsigned)stride, V.T.x, V.T.y, V.T.width, V.T.height};
-    unsigned reads = V.active;
-    if (mode == GAIN_SAMPLES) reads = V.active & c->own_mask;
-    if (mode == GAIN_WINDOW) {
-        reads = gain_window_reads(c, V.active);
-        if (c->col_end > c->col_begin) {      // the samples with col_begin <= u - T.x < col_end: the lattice starts at the window's first sample column
-            const int s0 = div_up(c->col_begin, stride), s1 = div_up(c->col_end, stride);
-            V.T.x += s0 * stride; V.nsx = s1 - s0;
-        }
-    }
-    for (int v = 0; v < N; ++v) {
-        V.xmap[v] = (const float *)c->maps.p + c->map_off[v]; V.pitch[v] = c->map_pitch[v];
-        V.roi[v] = c->roi[v];
-        if (geom || !((reads >> v) & 1u)) continue;      // a view left out, one no sample of the window lies in, or another shard's, is never read
-        if (nv12)
-            MS_CHECK(views[v].data && views[v].type == MS_8UC1 && views[v].rows == V.src_h * 3 / 2 && views[v].cols == V.src_w && views[v].step >= (size_t)V.src_w,
-                     "%s: view %d must be the NV12 planes of a %dx%d frame (DEVICE 8UC1, %d rows)", who, v, V.src_w, V.src_h, V.src_h * 3 / 2);
-        else
-            MS_CHECK(views[v].data && views[v].type == MS_8UC3 && views[v].rows == V.src_h && views[v].cols == V.src_w && views[v].step >= (size_t)V.src_w * 3,
-                     "%s: view %d must be a DEVICE 8UC3 image of %dx%d", who, v, V.src_w, V.src_h);
-        V.src[v] = (const uint8_t *)views[v].data; V.step[v] = (unsigned)views[v].step;
-    }
-    return MS_OK;
-}
-// every view table a later stitch may read (tables_mu held): the full set, its enqueue-only-mask-update copy, the cached subsets
-static GainTrackTables gain_track_tables(ms_ctx *c)
-{
-    GainTrackTables W{};
-    W.tab[W.n++] = (ViewDesc *)c->view_tab.p;
-    if (c->alt.view_tab.p && (int)c->alt.h_views.size() == c->N) W.tab[W.n++] = (ViewDesc *)c->alt.view_tab.p;
-    for (auto &T : c->subsets)
-        if (T->view_tab.p && W.n < GAIN_TRACK_MAX_TABLES) W.tab[W.n++] = (ViewDesc *)T->view_tab.p;
-    return W;
-}
-// the accumulators are shared by every call of the context: behind the last one, and behind whatever may still rewrite a view table (gain_mu held)
-static int gain_track_order(ms_ctx *c, hipStream_t st)
-{
-    if (c->gain_ev_set) MS_HIP(hipStreamWaitEvent(st, c->gain_ev, 0));
-    if (c->subset_built_set) MS_HIP(hipStreamWaitEvent(st, c->subset_built, 0));
-    std::lock_guard<std::mutex> mk(c->mesh_mu);
-    if (c->tab_wait) MS_HIP(hipStreamWaitEvent(st, c->tab_ready, 0));
-    return MS_OK;
-}
-
-// a call that publishes gains (tables_mu and gain_mu held): behind every stitch that may still read the view tables, when that stitch runs on another stream
-static int gain_publish_order(ms_ctx *c, hipStream_t st)
-{
-    if (c->stitch_pending && c->last_stream_set && c->last_stream != st) MS_HIP(hipStreamWaitEvent(st, c->last_stitch, 0));
-    return MS_OK;
-}
-// ... and once gain_ev is recorded behind it, the next stitch on another stream waits for that event
-static void gain_published(ms_ctx *c, hipStream_t st)
-{
-    c->gain_ev_set = true;
-    c->gain_tracked = true;
-    c->gain_pub_stream = st; c->gain_pub_pending = true;
-}
-
-// ms_gain_stats / ms_gain_stats_nv12: only the kernel that reads the pixels differs
-static int gain_stats_impl(ms_ctx *c, const char *who, const ms_image *views, int stride, bool nv12, long long *N_host, long long *S_host, ms_stream stream)
-{
-    if (!c) return fail(MS_ERR_INVALID, "%s: null context", who);
-    if (!N_host || !S_host) return fail(MS_ERR_INVALID, "%s: null output", who);
-    hipStream_t st = as_stream(stream);
-    const size_t nn = (size_t)c->N * c->N;
-    {   // both locks for the enqueue only; the exported block cannot be overwritten before it is read back: the next call waits for gain_ev, recorded behind the copies
-        std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);
-        std::lock_guard<std::mutex> gk(c->gain_mu);
-        GainTrackViews V;
-        if (int e = gain_track_args(c, who, views, stride, nv12, V)) return e;
-        GainTrackBuf *B = (GainTrackBuf *)c->gain_buf.p;
-        if (int e = gain_track_order(c, st)) return e;
-        if (int e = launch_gain_stats(V, B, nv12, st)) return e;
-        if (int e = launch_gain_export(V, B, st)) return e;
-        MS_HIP(hipMemcpyAsync(N_host, B->outN, nn * sizeof(long long), hipMemcpyDeviceToHost, st));
-        MS_HIP(hipMemcpyAsync(S_host, B->outS, nn * sizeof(long long), hipMemcpyDeviceToHost, st));
-        MS_HIP(hipEventRecord(c->gain_ev, st));
-        c->gain_ev_set = true;
-    }
-    MS_HIP(hipStreamSynchronize(st));
-    return MS_OK;
-}
-
-// ms_track_gains / ms_track_gains_nv12: the same accumulators, solve, smoothing and publication; calls of either form may alternate on one context
-static int track_gains_impl(ms_ctx *c, const char *who, const ms_image *views, const ms_gain_track_params *prm, bool nv12, ms_stream stream)
-{
-    if (!c) return fail(MS_ERR_INVALID, "%s: null context", who);
-    if (!prm) return fail(MS_ERR_INVALID, "%s: null params", who);
-    MS_CHECK(prm->struct_size == sizeof(ms_gain_track_params), "%s: ms_gain_track_params.struct_size is %u, this library expects %zu", who, prm->struct_size, sizeof(ms_gain_track_params));
-    MS_CHECK(prm->smoothing > 0.0 && prm->smoothing <= 1.0, "%s: smoothing %g outside (0, 1]", who, prm->smoothing);
-    hipStream_t st = as_stream(stream);
-    std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);      // held for the enqueue, never for a GPU wait: the table list below stays valid until the kernels are in the stream
-    GainTrackViews V;
-    if (int e = gain_track_args(c, who, views, prm->stride, nv12, V)) return e;
-    const GainTrackTables W = gain_track_tables(c);
-    GainTrackBuf *B = (GainTrackBuf *)c->gain_buf.p;
-    std::lock_guard<std::mutex> gk(c->gain_mu);
-    if (int e = gain_track_order(c, st)) return e;
-    if (int e = launch_gain_stats(V, B, nv12, st)) return e;
-    if (int e = gain_publish_order(c, st)) return e;
-    if (int e = launch_gain_update(V, W, B, prm->smoothing, st)) return e;
-    MS_HIP(hipEventRecord(c->gain_ev, st));
-    gain_published(c, st);
-    return MS_OK;
-}
-
-int ms_gain_stats(ms_ctx *c, const ms_image *views, int stride, long long *N_host, long long *S_host, ms_stream stream)
-{
-    return gain_stats_impl(c, "ms_gain_stats", views, stride, false, N_host, S_host, stream);
-}
-int ms_gain_stats_nv12(ms_ctx *c, const ms_image *views_nv12, int stride, long long *N_host, long long *S_host, ms_stream stream)
-{
-    return gain_stats_impl(c, "ms_gain_stats_nv12", views_nv12, stride, true, N_host, S_host, stream);
-}
-int ms_track_gains(ms_ctx *c, const ms_image *views, const ms_gain_track_params *prm, ms_stream stream)
-{
-    return track_gains_impl(c, "ms_track_gains", views, prm, false, stream);
-}
-int ms_track_gains_nv12(ms_ctx *c, const ms_image *views_nv12, const ms_gain_track_params *prm, ms_stream stream)
-{
-    return track_gains_impl(c, "ms_track_gains_nv12", views_nv12, prm, true, stream);
-}
-
-int ms_get_gains(ms_ctx *c, double *gains_host, int *solves_ok, int *solves_singular, ms_stream stream)
-{
-    if (!c) return fail(MS_ERR_INVALID, "null context");
-    if (!gains_host) return fail(MS_ERR_INVALID, "ms_get_gains: null output");
-    if (!c->blender_ready || !c->gain_buf.p) return fail(MS_ERR_STATE, "ms_get_gains: call ms_init_blender first");
-    hipStream_t st = as_stream(stream);
-    bool wait;
-    { std::lock_guard<std::mutex> gk(c->gain_mu); wait = c->gain_ev_set; }
-    if (wait) MS_HIP(hipStreamWaitEvent(st, c->gain_ev, 0));      // (a track call on another stream)
-    GainTrackBuf *B = (GainTrackBuf *)c->gain_buf.p;
-    double g[MAX_VIEWS];
-    int cnt[2];
-    MS_HIP(hipMemcpyAsync(g, B->state, sizeof(g), hipMemcpyDeviceToHost, st));
-    MS_HIP(hipMemcpyAsync(cnt, &B->solves_ok, sizeof(cnt), hipMemcpyDeviceToHost, st));
-    MS_HIP(hipStreamSynchronize(st));
-    std::lock_guard<std::mutex> gk(c->gain_mu);
-    for (int v = 0; v < c->N; ++v) gains_host[v] = c->gain[v] = g[v];
-    if (solves_ok) *solves_ok = cnt[0];
-    if (solves_singular) *solves_singular = cnt[1];
-    return MS_OK;
-}
-
-// ---- exposure tracking on column shards: partial statistics in caller-owned device memory, summed and solved on the device ---------------------------------------
-size_t ms_gain_partial_bytes(const ms_ctx *c)
-{
-    if (!c) { (void)fail(MS_ERR_INVALID, "ms_gain_partial_bytes: null context"); return 0; }
-    return gain_partial_bytes(c->N);
-}
-
-int ms_get_gain_views(const ms_ctx *cc, unsigned *mask)
-{
-    if (!mask) return fail(MS_ERR_INVALID, "ms_get_gain_views: null output");
-    if (!cc) return fail(MS_ERR_INVALID, "ms_get_gain_views: null context");
-    ms_ctx *c = const_cast<ms_ctx *>(cc);
-    std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);
-    GainTrackViews V;
-    if (int e = gain_track_args(c, "ms_get_gain_views", nullptr, 1, false, V, GAIN_GEOM)) return e;
-    *mask = gain_window_reads(c, V.active) | (c->own_mask & c->needed_mask & V.active);
-    return MS_OK;
-}
-
-static int gain_partial_impl(ms_ctx *c, const char *who, const ms_image *views, int stride, bool nv12, void *partial, ms_stream stream)
-{
-    // (what does not depend on the context first: these checks run, and are tested, without a device)
-    MS_CHECK(partial && ((uintptr_t)partial & 7u) == 0, "%s: the partial must be a DEVICE buffer of ms_gain_partial_bytes, 8-byte aligned", who);
-    MS_CHECK(views, "%s: null views", who);
-    MS_CHECK(stride >= 1, "%s: stride %d < 1", who, stride);
-    if (!c) return fail(MS_ERR_INVALID, "%s: null context", who);
-    hipStream_t st = as_stream(stream);
-    std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);      // both locks for the enqueue only (as ms_track_gains)
-    GainTrackViews V;
-    GainPartialHeader H;
-    if (int e = gain_track_args(c, who, views, stride, nv12, V, GAIN_WINDOW, &H)) return e;
-    GainTrackBuf *B = (GainTrackBuf *)c->gain_buf.p;
-    std::lock_guard<std::mutex> gk(c->gain_mu);
-    if (int e = gain_track_order(c, st)) return e;
-    if (int e = launch_gain_stats(V, B, nv12, st)) return e;
-    if (int e = launch_gain_partial_export(V, H, B, partial, st)) return e;
-    MS_HIP(hipEventRecord(c->gain_ev, st));
-    c->gain_ev_set = true;
-    return MS_OK;
-}
-int ms_gain_stats_partial(ms_ctx *c, const ms_image *views, int stride, void *partial_dev, ms_stream stream)
-{
-    return gain_partial_impl(c, "ms_gain_stats_partial", views, stride, false, partial_dev, stream);
-}
-int ms_gain_stats_partial_nv12(ms_ctx *c, const ms_image *views_nv12, int stride, void *partial_dev, ms_stream stream)
-{
-    return gain_partial_impl(c, "ms_gain_stats_partial_nv12", views_nv12, stride, true, partial_dev, stream);
-}
-
-int ms_track_gains_from_partials(ms_ctx *c, const void *const *partials, int n_partials, const ms_gain_track_params *prm, ms_stream stream)
-{
-    const char *who = "ms_track_gains_from_partials";
-    if (!prm) return fail(MS_ERR_INVALID, "%s: null params", who);
-    MS_CHECK(prm->struct_size == sizeof(ms_gain_track_params), "%s: ms_gain_track_params.struct_size is %u, this library expects %zu", who, prm->struct_size, sizeof(ms_gain_track_params));
-    MS_CHECK(prm->smoothing > 0.0 && prm->smoothing <= 1.0, "%s: smoothing %g outside (0, 1]", who, prm->smoothing);
-    MS_CHECK(partials, "%s: null partials", who);
-    MS_CHECK(n_partials >= 1 && n_partials <= GAIN_MAX_PARTIALS, "%s: %d partials, not in [1, %d]", who, n_partials, GAIN_MAX_PARTIALS);
-    GainPartials P{};
-    P.n = n_partials;
-    for (int k = 0; k < n_partials; ++k) {
-        MS_CHECK(partials[k] && ((uintptr_t)partials[k] & 7u) == 0, "%s: partial %d is null or not 8-byte aligned", who, k);
-        P.p[k] = (const unsigned long long *)partials[k];
-    }
-    MS_CHECK(prm->stride >= 1, "%s: stride %d < 1", who, prm->stride);
-    if (!c) return fail(MS_ERR_INVALID, "%s: null context", who);
-    hipStream_t st = as_stream(stream);
-    std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);      // held for the enqueue, never for a GPU wait (as ms_track_gains)
-    GainTrackViews V;
-    GainPartialHeader H;
-    if (int e = gain_track_args(c, who, nullptr, prm->stride, false, V, GAIN_GEOM, &H)) return e;
-    const GainTrackTables W = gain_track_tables(c);
-    GainTrackBuf *B = (GainTrackBuf *)c->gain_buf.p;
-    std::lock_guard<std::mutex> gk(c->gain_mu);
-    if (int e = gain_track_order(c, st)) return e;      // (the partials are the caller's: whatever wrote them is ordered before this call by the caller's stream)
-    if (int e = gain_publish_order(c, st)) return e;
-    if (int e = launch_gain_update_partials(V, W, H, P, B, prm->smoothing, st)) return e;
-    MS_HIP(hipEventRecord(c->gain_ev, st));
-    gain_published(c, st);
-    return MS_OK;
-}
-
-// ---- exposure tracking on view shards: per-view sample vectors in caller-owned device memory, paired, summed and solved on the device -------------------------------
-static unsigned view_shard_mask(int N, int S, int k)      // the block of views of shard k of S (ms_create)
-{
-    unsigned m = 0;
-    for (int v = k * N / S; v < (k + 1) * N / S; ++v) m |= 1u << v;
-    return m;
-}
-// the lattice geometry of a stride without a call's checks (maps built): what the sizes depend on
-static void gain_lattice(const ms_ctx *c, int stride, unsigned active, GainTrackViews &V)
-{
-    V = GainTrackViews{};
-    V.n = c->N; V.active = active;
-    V.T = c->bg.dst_roi_final; V.stride = stride;
-    V.nsx = div_up(V.T.width, stride); V.nsy = div_up(V.T.height, stride);
-    for (int v = 0; v < c->N; ++v) V.roi[v] = c->roi[v];
-}
-static size_t gain_samples_words(const GainTrackViews &V, unsigned held)
-{
-    GainSampleRects R;
-    unsigned off[MS_MAX_VIEWS];
-    gain_sample_rects(V, R);
-    return gain_sample_offsets(V, R, held, off);
-}
-size_t ms_gain_samples_bytes(const ms_ctx *c, int stride, int view_shard_index)
-{
-    const char *who = "ms_gain_samples_bytes";
-    if (!c) { (void)fail(MS_ERR_INVALID, "%s: null context", who); return 0; }
-    if (stride < 1) { (void)fail(MS_ERR_INVALID, "%s: stride %d < 1", who, stride); return 0; }
-    const int S = c->cfg.view_shards > 1 ? c->cfg.view_shards : 1;
-    if (view_shard_index < -1 || view_shard_index >= S) { (void)fail(MS_ERR_INVALID, "%s: view shard %d of %d", who, view_shard_index, S); return 0; }
-    if (!c->maps_built) { (void)fail(MS_ERR_STATE, "%s: call ms_build_maps first", who); return 0; }
-    if (c->cfg.col_shards > 1 || c->feather_sharpness >= 0.f) { (void)fail(MS_ERR_UNSUPPORTED, "%s: not for column-sharded or FeatherBlender contexts", who); return 0; }
-    std::lock_guard<std::recursive_mutex> tables_lk(const_cast<ms_ctx *>(c)->tables_mu);
-    const unsigned all = (c->N >= 32) ? 0xffffffffu : ((1u << c->N) - 1u);
-    const unsigned active = c->act ? c->act->views : all;
-    const unsigned own = view_shard_index < 0 ? c->own_mask & all : view_shard_mask(c->N, S, view_shard_index);
-    GainTrackViews V;
-    gain_lattice(c, stride, active, V);
-    const size_t words = gain_samples_words(V, own & active);
-    if (words > 0xffffffffu / 4u) { (void)fail(MS_ERR_INVALID, "%s: the buffer would exceed 4 GiB at stride %d; use a larger stride", who, stride); return 0; }
-    return words * 4;
-}
-
-int ms_get_view_shard(const ms_ctx *c, int *view_shards, int *view_shard_index)
-{
-    if (!view_shards || !view_shard_index) return fail(MS_ERR_INVALID, "ms_get_view_shard: null output");
-    if (!c) return fail(MS_ERR_INVALID, "ms_get_view_shard: null context");
-    const bool sharded = c->cfg.view_shards > 1;
-    *view_shards = sharded ? c->cfg.view_shards : 1;
-    *view_shard_index = sharded ? c->cfg.view_shard_index : 0;
-    return MS_OK;
-}
-
-int ms_get_gain_sample_views(const ms_ctx *cc, unsigned *mask)
-{
-    const char *who = "ms_get_gain_sample_views";
-    if (!mask) return fail(MS_ERR_INVALID, "%s: null output", who);
-    if (!cc) return fail(MS_ERR_INVALID, "%s: null context", who);
-    ms_ctx *c = const_cast<ms_ctx *>(cc);
-    std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);
-    GainTrackViews V;
-    if (int e = gain_track_args(c, who, nullptr, 1, false, V, GAIN_SAMPLES_GEOM)) return e;
-    *mask = V.active & c->own_mask;
-    return MS_OK;
-}
-
-static int gain_samples_impl(ms_ctx *c, const char *who, const ms_image *views, int stride, bool nv12, void *samples, ms_stream stream)
-{
-    // (what does not depend on the context first: these checks run, and are tested, without a device)
-    MS_CHECK(samples && ((uintptr_t)samples & 3u) == 0, "%s: the samples must be a DEVICE buffer of ms_gain_samples_bytes, 4-byte aligned", who);
-    MS_CHECK(views, "%s: null views", who);
-    MS_CHECK(stride >= 1, "%s: stride %d < 1", who, stride);
-    if (!c) return fail(MS_ERR_INVALID, "%s: null context", who);
-    hipStream_t st = as_stream(stream);
-    std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);      // for the enqueue only (as ms_track_gains); the accumulators are not used: no gain_mu
-    GainTrackViews V;
-    if (int e = gain_track_args(c, who, views, stride, nv12, V, GAIN_SAMPLES)) return e;
-    GainSampleRects R;
-    gain_sample_rects(V, R);
-    const unsigned held = V.active & c->own_mask;
-    MS_CHECK(gain_samples_words(V, held) <= 0xffffffffu / 4u, "%s: the buffer would exceed 4 GiB at stride %d; use a larger stride", who, stride);
-    return launch_gain_samples(V, R, held, nv12, samples, st);
-}
-int ms_gain_samples(ms_ctx *c, const ms_image *views, int stride, void *samples_dev, ms_stream stream)
-{
-    return gain_samples_impl(c, "ms_gain_samples", views, stride, false, samples_dev, stream);
-}
-int ms_gain_samples_nv12(ms_ctx *c, const ms_image *views_nv12, int stride, void *samples_dev, ms_stream stream)
-{
-    return gain_samples_impl(c, "ms_gain_samples_nv12", views_nv12, stride, true, samples_dev, stream);
-}
-
-// the checks both consumers share; everything that needs no context first
-static int gain_sample_bufs(const char *who, const void *const *samples, int n, int stride, GainSampleBufs &P)
-{
-    MS_CHECK(samples, "%s: null samples", who);
-    MS_CHECK(n >= 1 && n <= GAIN_MAX_SAMPLE_BUFS, "%s: %d sample buffers, not in [1, %d]", who, n, GAIN_MAX_SAMPLE_BUFS);
-    P = GainSampleBufs{};
-    P.n = n;
-    for (int k = 0; k < n; ++k) {
-        MS_CHECK(samples[k] && ((uintptr_t)samples[k] & 3u) == 0, "%s: sample buffer %d is null or not 4-byte aligned", who, k);
-        P.p[k] = (const unsigned *)samples[k];
-    }
-    MS_CHECK(stride >= 1, "%s: stride %d < 1", who, stride);
-    return MS_OK;
-}
-
-int ms_gain_stats_from_samples(ms_ctx *c, const void *const *samples, int n, int stride, long long *N_host, long long *S_host, ms_stream stream)
-{
-    const char *who = "ms_gain_stats_from_samples";
-    if (!N_host || !S_host) return fail(MS_ERR_INVALID, "%s: null output", who);
-    GainSampleBufs P;
-    if (int e = gain_sample_bufs(who, samples, n, stride, P)) return e;
-    if (!c) return fail(MS_ERR_INVALID, "%s: null context", who);
-    hipStream_t st = as_stream(stream);
-    const size_t nn = (size_t)c->N * c->N;
-    {   // (as ms_gain_stats)
-        std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);
-        std::lock_guard<std::mutex> gk(c->gain_mu);
-        GainTrackViews V;
-        if (int e = gain_track_args(c, who, nullptr, stride, false, V, GAIN_SAMPLES_GEOM)) return e;
-        GainSampleRects R;
-        gain_sample_rects(V, R);
-        GainTrackBuf *B = (GainTrackBuf *)c->gain_buf.p;
-        if (int e = gain_track_order(c, st)) return e;
-        if (int e = launch_gain_stats_from_samples(V, R, P, B, st)) return e;
-        if (int e = launch_gain_export_samples(V, R, P, B, st)) return e;
-        MS_HIP(hipMemcpyAsync(N_host, B->outN, nn * sizeof(long long), hipMemcpyDeviceToHost, st));
-        MS_HIP(hipMemcpyAsync(S_host, B->outS, nn * sizeof(long long), hipMemcpyDeviceToHost, st));
-        MS_HIP(hipEventRecord(c->gain_ev, st));
-        c->gain_ev_set = true;
-    }
-    MS_HIP(hipStreamSynchronize(st));
-    return MS_OK;
-}
-
-int ms_track_gains_from_samples(ms_ctx *c, const void *const *samples, int n, const ms_gain_track_params *prm, ms_stream stream)
-{
-    const char *who = "ms_track_gains_from_samples";
-    if (!prm) return fail(MS_ERR_INVALID, "%s: null params", who);
-    MS_CHECK(prm->struct_size == sizeof(ms_gain_track_params), "%s: ms_gain_track_params.struct_size is %u, this library expects %zu", who, prm->struct_size, sizeof(ms_gain_track_params));
-    MS_CHECK(prm->smoothing > 0.0 && prm->smoothing <= 1.0, "%s: smoothing %g outside (0, 1]", who, prm->smoothing);
-    GainSampleBufs P;
-    if (int e = gain_sample_bufs(who, samples, n, prm->stride, P)) return e;
-    if (!c) return fail(MS_ERR_INVALID, "%s: null context", who);
-    hipStream_t st = as_stream(stream);
-    std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);      // held for the enqueue, never for a GPU wait (as ms_track_gains)
-    GainTrackViews V;
-    if (int e = gain_track_args(c, who, nullptr, prm->stride, false, V, GAIN_SAMPLES_GEOM)) return e;
-    GainSampleRects R;
-    gain_sample_rects(V, R);
-    const GainTrackTables W = gain_track_tables(c);
-    GainTrackBuf *B = (GainTrackBuf *)c->gain_buf.p;
-    std::lock_guard<std::mutex> gk(c->gain_mu);
-    if (int e = gain_track_order(c, st)) return e;      // (the buffers are the caller's: whatever wrote them is ordered before this call by the caller's stream)
-    if (int e = launch_gain_stats_from_samples(V, R, P, B, st)) return e;
-    if (int e = gain_publish_order(c, st)) return e;
-    if (int e = launch_gain_update_samples(V, W, R, P, B, prm->smoothing, st)) return e;
-    MS_HIP(hipEventRecord(c->gain_ev, st));
-    gain_published(c, st);
-    return MS_OK;
-}
-
-int ms_get_gain_track_counters(ms_ctx *c, ms_gain_track_counters *out, ms_stream stream)
-{
-    if (!out) return fail(MS_ERR_INVALID, "ms_get_gain_track_counters: null output");
-    MS_CHECK(out->struct_size == sizeof(ms_gain_track_counters), "ms_get_gain_track_counters: ms_gain_track_counters.struct_size is %u, this library expects %zu", out->struct_size, sizeof(ms_gain_track_counters));
-    if (!c) return fail(MS_ERR_INVALID, "ms_get_gain_track_counters: null context");
-    if (!c->blender_ready || !c->gain_buf.p) return fail(MS_ERR_STATE, "ms_get_gain_track_counters: call ms_init_blender first");
-    hipStream_t st = as_stream(stream);
-    bool wait;
-    { std::lock_guard<std::mutex> gk(c->gain_mu); wait = c->gain_ev_set; }
-    if (wait) MS_HIP(hipStreamWaitEvent(st, c->gain_ev, 0));      // (a track call on another stream)
-    int cnt[3];
-    MS_HIP(hipMemcpyAsync(cnt, &((GainTrackBuf *)c->gain_buf.p)->solves_ok, sizeof(cnt), hipMemcpyDeviceToHost, st));
-    MS_HIP(hipStreamSynchronize(st));
-    out->solves_ok = cnt[0]; out->solves_singular = cnt[1]; out->updates_rejected = cnt[2];
     return MS_OK;
 }
 
@@ -3918,7 +3282,7 @@ static int check_call(ms_ctx *c, StitchCall &k, const ms_image *views, const ms_
     const int N = c->N, F = k.F_call;
     ShardArgs &S = k.S;
     const PanoDesc &P = c->pano;
-    const bool sharded = c->own_mask != ((N >= 32) ? 0xffffffffu : ((1u << N) - 1u));
+    const bool sharded = c->own_mask != all_views(N);
     if (S.mode == 0 && sharded) return fail(MS_ERR_STATE, "ms_stitch: this context owns a view shard; use ms_stitch_partial / ms_stitch_finish");
     S.own_mask = c->own_mask;
     S.pstride = c->pacc_stride;
@@ -4412,7 +3776,7 @@ int ms_get_needed_views(const ms_ctx *c, unsigned *mask)
 {
     if (!c || !mask) return fail(MS_ERR_INVALID, "ms_get_needed_views: null argument");
     if (!c->blender_ready) return fail(MS_ERR_STATE, "ms_get_needed_views: call ms_init_blender first");
-    const unsigned all = (c->N >= 32) ? 0xffffffffu : ((1u << c->N) - 1u);
+    const unsigned all = all_views(c->N);
     std::lock_guard<std::recursive_mutex> tables_lk(const_cast<ms_ctx *>(c)->tables_mu);
     *mask = c->own_mask & c->needed_mask & all & (c->act ? c->act->views : all);
     return MS_OK;
@@ -4453,7 +3817,7 @@ int ms_blend(ms_ctx *c, ms_image *out8u, ms_image *out16s, ms_stream stream)
 {
     if (!c) return fail(MS_ERR_INVALID, "null context");
     std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);      // (the active set cannot change between this check and the enqueue)
-    const unsigned all = (c->N >= 32) ? 0xffffffffu : ((1u << c->N) - 1u), need = c->act ? c->act->views : all;
+    const unsigned all = all_views(c->N), need = c->act ? c->act->views : all;
     if ((c->fed_mask & need) != need) return fail(MS_ERR_STATE, "ms_blend: only views 0x%x of 0x%x were fed since the last blend", c->fed_mask & all, need);
     c->fed_mask = 0;
     return stitch_impl(c, 1, c->fed, out8u, out16s, as_stream(stream), 0, nullptr, nullptr, nullptr);
