@@ -187,6 +187,48 @@ MS_API int ms_build_warp_maps(int projection, int tl_u, int tl_v, ms_image *map_
                               const float *k_rinv, const float *r_kinv, const float *t, float scale,
                               ms_stream stream);
 
+/* Lens distortion.  The warpers above assume an ideal pinhole (K * R^-1 alone); ms_lens puts a distortion model between R^-1 and K, so that a rig with calibrated
+ * Brown-Conrady coefficients or fisheye lenses gets its maps, ROIs and seam-scale calibration from the library (ms_set_lens + ms_build_maps) instead of bringing
+ * maps of its own (ms_set_maps).  For a ray (X, Y, Z) in camera coordinates (R^-1 times the warper's direction, R^-1 = R^T in double): rho = hypot(X, Y),
+ * theta = atan2(rho, Z); the view does not see the ray when theta > max_theta -- its map entry is (-1, -1), the reference's own "behind the camera" marker
+ * (stitching/src/cuda/build_warp_maps.cu:137-152).  Otherwise the distorted normalised coordinates (xd, yd) are
+ *   MS_LENS_BROWN (cvProjectPoints2, calib3d/src/calibration.cpp:760-790): x = X / Z, y = Y / Z, r2 = x^2 + y^2,
+ *       cdist = (1 + k1 r2 + k2 r2^2 + k3 r2^3) / (1 + k4 r2 + k5 r2^2 + k6 r2^3), xd = x cdist + 2 p1 x y + p2 (r2 + 2 x^2), yd = y cdist + p1 (r2 + 2 y^2) + 2 p2 x y;
+ *   MS_LENS_FISHEYE (cv::fisheye::projectPoints, calib3d/src/fisheye.cpp:130-150): theta_d = theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8),
+ *       (xd, yd) = (X, Y) theta_d / rho, (0, 0) at rho = 0.  The atan2 form equals OpenCV's atan(r) for Z > 0 and goes on past 90 degrees;
+ *   MS_LENS_NONE: xd = X / Z, yd = Y / Z, seen iff Z > 0;
+ * and the pixel is (K[0] xd + K[1] yd + K[2], K[4] yd + K[5]).  Everything is evaluated in double -- from (double)u / (double)(float)scale with double sin / cos -- and
+ * rounded to float once, at the store: calibration-time work, no fp32 evaluation order is part of the contract.  The library holds no inverse of the distortion. */
+enum { MS_LENS_NONE = 0, MS_LENS_BROWN = 1, MS_LENS_FISHEYE = 2 };
+typedef struct ms_lens {
+    unsigned struct_size;   /* as ms_config: mismatch = MS_ERR_INVALID */
+    int model;              /* MS_LENS_* */
+    double k[8];            /* BROWN: OpenCV distCoeffs order k1 k2 p1 p2 k3 k4 k5 k6; FISHEYE: k1..k4, k[4..7] must be 0 */
+    double max_theta_deg;   /* rays further than this from the optical axis are not seen.  BROWN: (0, 89]; FISHEYE: (0, 180]; 0 = default (BROWN 89, FISHEYE 180) */
+} ms_lens;
+/* Host only, no device needed.  MS_ERR_INVALID for: a null pointer, a struct_size mismatch, an unknown model, a non-finite coefficient, FISHEYE with non-zero k[4..7],
+ * max_theta_deg outside its range, and a radial profile that is not strictly increasing on [0, max_theta] -- r cdist(r) over r in [0, tan max_theta] for BROWN,
+ * theta_d(theta) for FISHEYE, sampled at 4096 uniform steps in double: a fold-back would put rays far outside the field of view back into the image (lower
+ * max_theta_deg to the range the calibration holds on).  BROWN's tangential terms p1, p2 are NOT part of the check.  MS_LENS_NONE passes whatever k holds. */
+MS_API int ms_lens_check(const ms_lens *lens);
+/* The model above on the host, for callers and tests: K 9 floats, ray = (X, Y, Z) in camera coordinates, px = the pixel, or (-1, -1) with *seen = 0.
+ * lens == NULL is MS_LENS_NONE; a lens ms_lens_check refuses is refused here. */
+MS_API int ms_lens_project(const float *K, const ms_lens *lens, const double ray[3], double px[2], int *seen);
+/* ms_build_warp_maps for a camera with a lens (buildWarp{Spherical,Cylindrical}Maps, stitching/src/cuda/build_warp_maps.cu:155-216, with the distortion between
+ * R^-1 and K, which is why K and R -- 9 floats each, HOST -- are passed separately).  map_x / map_y: 32FC1 of one size, any row step (pitched images, ROIs of
+ * larger ones).  lens == NULL is MS_LENS_NONE.  MS_PROJ_PLANE is MS_ERR_UNSUPPORTED. */
+MS_API int ms_build_warp_maps_lens(int projection, int tl_u, int tl_v, ms_image *map_x, ms_image *map_y, const float *K, const float *R, const ms_lens *lens,
+                                   float scale, ms_stream stream);
+/* RotationWarper::warpRoi (warpers_inl.hpp:136-146) for a camera with a lens, by forward evaluation on the device.  With s = (float)scale and U = llrint(pi s), the
+ * candidates are the integer warper coordinates u in [-U, U) and v in [0, U) (spherical) or v in [-V, V], V = ceil(s tan MS_LENS_CYL_MAX_ELEVATION_DEG) (cylindrical:
+ * the warper's v = tan(elevation) has no end, so views are cut at +-80 degrees).  A candidate is seen when its truncated float map coordinates lie in
+ * [0, src_w) x [0, src_h) -- the rule of the warp masks (remap of a white image, NEAREST, BORDER_CONSTANT: calibration.cpp:224-227) -- and the ROI is the bounding box
+ * of the seen candidates: every border row and column holds a seen pixel, a view that straddles +-pi or contains a pole comes out 2U wide (never wider than a canvas of
+ * out_width = 2 pi scale; the window is half-open for that reason).  SYNCHRONOUS.  MS_ERR_INVALID: a null pointer, an empty source, scale outside (0, 8192], a lens
+ * ms_lens_check refuses, no seen candidate ("sees nothing").  MS_PROJ_PLANE is MS_ERR_UNSUPPORTED. */
+enum { MS_LENS_CYL_MAX_ELEVATION_DEG = 80 };
+MS_API int ms_warp_roi_lens(int projection, const float *K, const float *R, const ms_lens *lens, float scale, int src_w, int src_h, ms_rect *roi, ms_stream stream);
+
 /* cvtColor(src, dst, CV_YUV2BGR_NV12): the capture-side conversion the reference runs on the CPU per camera frame
  * (APP/networking.cpp:45-47, 1920x1620 NV12 -> 1920x1080 BGR, defs.h:10-17) -> YUV420sp2RGB888Invoker<0,0>
  * (OCV/imgproc/src/color.cpp).  src 8UC1 of (rows*3/2) x cols (Y plane, then interleaved UV); dst 8UC3, even size. */
@@ -299,6 +341,18 @@ MS_API void ms_destroy(ms_ctx *ctx);
 
 /* cameras[i].K() / cameras[i].R as fp32 row-major 3x3 (APP/calibration.cpp:28-68,217-221) */
 MS_API int ms_set_camera(ms_ctx *ctx, int view, const float *K, const float *R);
+/* The view's lens (ms_lens above; cvProjectPoints2's distCoeffs / cv::fisheye::projectPoints' D beside cameras[i].K()): copied.  NULL or MS_LENS_NONE clears it.
+ * Like ms_set_camera it invalidates maps, masks and blender.  A context on which no view has a lens is bit for bit what it is without this call.  With a lens on
+ * at least one view, ms_build_maps sends EVERY view down the dense route (views without a lens as MS_LENS_NONE, in the same double arithmetic): ROIs from
+ * ms_warp_roi_lens' rule, maps from ms_build_warp_maps_lens' kernel into the storage ms_set_maps fills, no 1-D projection tables, the per-frame kernels of
+ * ms_set_maps, and its limits -- a view of at least MS_MAPS_MIN_WIDTH x MS_MAPS_MIN_HEIGHT with no side above MS_MAPS_MAX_SIDE, a padded panorama of at most 32767
+ * a side: MS_ERR_INVALID naming the view.  ms_get_map_source reports MS_MAPS_LENS.  Everything that reads maps, ROIs and masks works unchanged (every ms_stitch* form,
+ * CPW, ms_update_mask, ms_set_active_views, exposure tracking, column and view shards -- every shard is given the same cameras and lenses --, the developer knobs),
+ * and so does ms_calibrate_seam: distortion acts on normalised coordinates, so the same ms_lens serves at seam scale with K_seam.  Stated limits: MS_PROJ_PLANE
+ * contexts refuse a lens and ms_save_tables refuses a lens context (the blob format has no lens record), both MS_ERR_UNSUPPORTED.
+ * MS_ERR_INVALID: a bad view index, a lens ms_lens_check refuses (ms_get_lens: a null pointer). */
+MS_API int ms_set_lens(ms_ctx *ctx, int view, const ms_lens *lens);
+MS_API int ms_get_lens(const ms_ctx *ctx, int view, ms_lens *lens);
 /* GainCompensator::gains()[view]  (exposure_compensate.cpp:164-170, APP/timed.cpp:94) */
 MS_API int ms_set_gain(ms_ctx *ctx, int view, double gain);
 
@@ -318,7 +372,7 @@ MS_API int ms_build_maps(ms_ctx *ctx, ms_stream stream);
  * ms_build_masks or ms_set_mask, ms_set_gain and ms_init_blender / ms_init_feather follow as usual; not callable while another thread stitches.  Everything that
  * depends on maps, ROIs and masks only works unchanged (every ms_stitch* form, CPW, ms_set_active_views, exposure tracking, column and view shards -- every shard
  * is given the same maps --, the developer knobs; warp_lds_stage = 1 never stages).  What needs cameras is refused with MS_ERR_UNSUPPORTED: ms_calibrate_seam
- * (it re-warps at seam scale) and ms_save_tables (the blob replays cameras).  A later ms_build_maps returns the context to the analytic maps.
+ * (it re-warps at seam scale) and ms_save_tables (the blob replays cameras).  A later ms_build_maps returns the context to the analytic maps (with ms_set_lens: the lens maps).
  * ms_get_maps returns the stored copies, ms_get_view_geom / ms_get_pano_geom the geometry derived from `rois`.
  * MS_ERR_INVALID, before the device is touched: a null pointer; an image of another type or size than its ROI; a bad step or alignment; a ROI narrower than
  * MS_MAPS_MIN_WIDTH, lower than MS_MAPS_MIN_HEIGHT or with a side above MS_MAPS_MAX_SIDE; a padded panorama (the ROIs' union) with a side above 32767.
@@ -328,8 +382,8 @@ MS_API int ms_build_maps(ms_ctx *ctx, ms_stream stream);
  *          columns / rows (num_bands <= 7: a gap of 3 * 2^num_bands either side, rounded out to multiples of 2^num_bands), hence 32768 - 1024. */
 enum { MS_MAPS_MIN_WIDTH = 3, MS_MAPS_MIN_HEIGHT = 2, MS_MAPS_MAX_SIDE = 31744 };
 MS_API int ms_set_maps(ms_ctx *ctx, const ms_rect *rois, const ms_image *xmaps, const ms_image *ymaps, ms_stream stream);
-/* where the context's maps come from: ms_build_maps (ANALYTIC, also before any maps are built) or ms_set_maps (CUSTOM) */
-enum { MS_MAPS_ANALYTIC = 0, MS_MAPS_CUSTOM = 1 };
+/* where the context's maps come from: ms_build_maps (ANALYTIC, also before any maps are built; LENS when a view had a lens, ms_set_lens) or ms_set_maps (CUSTOM) */
+enum { MS_MAPS_ANALYTIC = 0, MS_MAPS_CUSTOM = 1, MS_MAPS_LENS = MS_MAPS_CUSTOM + 1 /* 2 */ };
 MS_API int ms_get_map_source(const ms_ctx *ctx, int *source);
 
 /* Compose-size blend masks (APP/calibration.cpp:224-237).  mode 0: warp(255, NEAREST) only;

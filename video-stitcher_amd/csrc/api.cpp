@@ -2,6 +2,7 @@
 // argument validation (the reference's CV_Assert / CV_Error become status codes), then the launcher.
 #include <cstdarg>
 #include "launchers.hpp"
+#include "lens.hpp"
 
 namespace ms {
 
@@ -311,6 +312,45 @@ int ms_build_warp_maps(int projection, int tl_u, int tl_v, ms_image *mx, ms_imag
     PRE() IMG(mx, "ms_build_warp_maps map_x") IMG(my, "ms_build_warp_maps map_y") SAME(mx, my, "ms_build_warp_maps")
     MS_CHECK(mx->type == MS_32FC1 && my->type == MS_32FC1 && k_rinv, "ms_build_warp_maps: 32FC1 maps and k_rinv required");
     return launch_build_warp_maps(projection, tl_u, tl_v, *mx, *my, k_rinv, t, scale, as_stream(s));
+}
+
+int ms_lens_check(const ms_lens *lens)
+{
+    MS_CHECK(lens, "ms_lens_check: null lens");
+    return lens_check("ms_lens_check", lens);
+}
+
+int ms_lens_project(const float *K, const ms_lens *lens, const double *ray, double *px, int *seen)
+{
+    MS_CHECK(K && ray && px && seen, "ms_lens_project: null argument");
+    if (lens) if (int e = lens_check("ms_lens_project", lens)) return e;
+    const LensCam cam = lens_cam(K, nullptr, lens);
+    double x = -1.0, y = -1.0;
+    *seen = lens_project(cam.model, cam, ray[0], ray[1], ray[2], x, y) ? 1 : 0;
+    px[0] = *seen ? x : -1.0; px[1] = *seen ? y : -1.0;
+    return MS_OK;
+}
+
+int ms_build_warp_maps_lens(int projection, int tl_u, int tl_v, ms_image *mx, ms_image *my, const float *K, const float *R, const ms_lens *lens, float scale, ms_stream s)
+{
+    MS_CHECK(K && R && scale > 0.f, "ms_build_warp_maps_lens: K, R and a positive scale required");
+    if (lens) if (int e = lens_check("ms_build_warp_maps_lens", lens)) return e;
+    if (projection == MS_PROJ_PLANE) return fail(MS_ERR_UNSUPPORTED, "ms_build_warp_maps_lens: the lens model is built for the spherical and cylindrical warpers, not MS_PROJ_PLANE");
+    PRE() IMG(mx, "ms_build_warp_maps_lens map_x") IMG(my, "ms_build_warp_maps_lens map_y") SAME(mx, my, "ms_build_warp_maps_lens")
+    MS_CHECK(mx->type == MS_32FC1 && my->type == MS_32FC1, "ms_build_warp_maps_lens: 32FC1 maps required");
+    return launch_lens_maps(projection, tl_u, tl_v, *mx, *my, K, R, lens, scale, as_stream(s));
+}
+
+int ms_warp_roi_lens(int projection, const float *K, const float *R, const ms_lens *lens, float scale, int src_w, int src_h, ms_rect *roi, ms_stream s)
+{
+    MS_CHECK(K && R && roi && src_w > 0 && src_h > 0, "ms_warp_roi_lens: bad argument");
+    if (lens) if (int e = lens_check("ms_warp_roi_lens", lens)) return e;
+    if (projection == MS_PROJ_PLANE) return fail(MS_ERR_UNSUPPORTED, "ms_warp_roi_lens: the lens model is built for the spherical and cylindrical warpers, not MS_PROJ_PLANE");
+    PRE()
+    bool seen = false;
+    if (int e = lens_roi_device(projection, K, R, lens, scale, src_w, src_h, roi, &seen, as_stream(s))) return e;
+    MS_CHECK(seen, "ms_warp_roi_lens: the view sees nothing: no warper coordinate of the candidate window maps into the %d x %d source", src_w, src_h);
+    return MS_OK;
 }
 
 int ms_nv12_to_bgr(const ms_image *src, ms_image *dst, ms_stream s)

@@ -2067,6 +2067,28 @@ int ms_set_camera(ms_ctx *c, int view, const float *K, const float *R)
     return MS_OK;
 }
 
+int ms_set_lens(ms_ctx *c, int view, const ms_lens *lens)
+{
+    if (int e = ctx_check_view(c, view)) return e;
+    if (lens) if (int e = lens_check("ms_set_lens", lens)) return e;
+    const bool on = lens && lens->model != MS_LENS_NONE;
+    if (on && c->cfg.projection == MS_PROJ_PLANE)
+        return fail(MS_ERR_UNSUPPORTED, "ms_set_lens: the lens model is built for the spherical and cylindrical warpers; this context is MS_PROJ_PLANE");
+    c->lens[view] = ms_lens{};
+    if (on) c->lens[view] = *lens;
+    c->maps_built = c->masks_built = c->blender_ready = false;
+    return MS_OK;
+}
+
+int ms_get_lens(const ms_ctx *c, int view, ms_lens *lens)
+{
+    if (int e = ctx_check_view(c, view)) return e;
+    MS_CHECK(lens, "ms_get_lens: null lens");
+    *lens = c->lens[view];
+    lens->struct_size = sizeof(ms_lens);
+    return MS_OK;
+}
+
 // The host mirror of the gains as the tracker left them (ms_track_gains): waits for the last track call and reads its state back.  For the synchronous
 // paths only -- whatever uploads a view table built from `gain`, saves it, or reports it.  A context that was never tracked is not touched.
 static int pull_tracked_gains(ms_ctx *c)
@@ -2104,12 +2126,90 @@ int ms_set_gain(ms_ctx *c, int view, double gain)
     return MS_OK;
 }
 
+// The limits of a context on dense maps (ms_set_maps, and ms_build_maps with a lens), MS_MAPS_*: the tiled kernels' smallest view, a tile's origin inside the padded
+// view in 16 bits, and the padded panorama (blender_prepare rounds the ROIs' union up to a multiple of 2^num_bands), whose band tiles keep their origin in 16 bits
+static int check_dense_rois(const ms_ctx *c, const char *who, const ms_rect *rois)
+{
+    long long tlx = INT_MAX, tly = INT_MAX, brx = INT_MIN, bry = INT_MIN;
+    for (int i = 0; i < c->N; ++i) {
+        const ms_rect &r = rois[i];
+        MS_CHECK(r.width >= MS_MAPS_MIN_WIDTH && r.width <= MS_MAPS_MAX_SIDE && r.height >= MS_MAPS_MIN_HEIGHT && r.height <= MS_MAPS_MAX_SIDE,
+                 "%s: ROI %d is %d x %d: the tiled kernels take views of %d..%d columns and %d..%d rows", who, i, r.width, r.height,
+                 (int)MS_MAPS_MIN_WIDTH, (int)MS_MAPS_MAX_SIDE, (int)MS_MAPS_MIN_HEIGHT, (int)MS_MAPS_MAX_SIDE);
+        tlx = std::min<long long>(tlx, r.x); tly = std::min<long long>(tly, r.y);
+        brx = std::max<long long>(brx, (long long)r.x + r.width); bry = std::max<long long>(bry, (long long)r.y + r.height);
+    }
+    const long long m = 1ll << c->cfg.num_bands, pw = (brx - tlx + m - 1) / m * m, ph = (bry - tly + m - 1) / m * m;
+    MS_CHECK(pw <= 32767 && ph <= 32767, "%s: the ROIs span a padded panorama of %lld x %lld: each side must be at most 32767", who, pw, ph);
+    return MS_OK;
+}
+
+// c->roi -> the layout of the dense-map storage (per view xmap | ymap, rows padded to 4 floats), allocated and zeroed; the 1-D projection tables are released
+static int alloc_dense_maps(ms_ctx *c, hipStream_t st)
+{
+    size_t total = 0;
+    for (int i = 0; i < c->N; ++i) {
+        c->map_pitch[i] = round_up(c->roi[i].width, 4);
+        c->map_off[i] = total;
+        total += (size_t)2 * c->roi[i].height * c->map_pitch[i];
+    }
+    if (int e = c->maps.alloc(total * sizeof(float))) return e;
+    MS_HIP(hipMemsetAsync(c->maps.p, 0, total * sizeof(float), st));      // (the up to 3 padding columns of a row are never read; zeroed all the same)
+    c->tabs.release();      // no projection, no tables: nothing may follow a stale index into them
+    for (int i = 0; i < MAX_VIEWS; ++i) c->tab_off[i] = 0;
+    return MS_OK;
+}
+
+// the view's lens for the lens launchers: nullptr (MS_LENS_NONE in the same double arithmetic) for a view without one
+static const ms_lens *view_lens(const ms_ctx *c, int v) { return c->lens[v].model != MS_LENS_NONE ? &c->lens[v] : nullptr; }
+
+// blender->prepare(corners, sizes), the per-view padding and the canvas placement from c->roi
+static void place_panorama(ms_ctx *c)
+{
+    c->bg = blender_prepare(result_roi(c->N, c->roi), c->cfg.num_bands);
+    for (int i = 0; i < c->N; ++i)
+        c->pad[i] = blender_view_pad(c->bg, c->roi[i].x, c->roi[i].y, c->roi[i].width, c->roi[i].height);
+    c->canvas_x = c->bg.dst_roi.x + c->cfg.out_width / 2;
+    c->canvas_y = c->cfg.projection == MS_PROJ_SPHERICAL ? c->bg.dst_roi.y : c->bg.dst_roi.y + c->cfg.out_height / 2;
+}
+
+// ms_build_maps of a rig with a lens on at least one view (ms_set_lens): every view goes the dense route -- ROIs by forward evaluation (k_lens_bbox), maps by
+// k_lens_maps into the storage ms_set_maps fills, under ms_set_maps' limits -- and the per-frame path reads them (PROJ_MAPS).  Everything behind the maps is the
+// analytic route's.
+static int build_maps_lens(ms_ctx *c, hipStream_t st)
+{
+    const int N = c->N, W = c->cfg.src_width, H = c->cfg.src_height;
+    ms_rect rois[MAX_VIEWS];
+    for (int i = 0; i < N; ++i) {
+        bool seen = false;
+        if (int e = lens_roi_device(c->cfg.projection, c->K[i], c->R[i], view_lens(c, i), c->cfg.warp_scale, W, H, &rois[i], &seen, st)) return e;
+        MS_CHECK(seen, "ms_build_maps: view %d sees nothing: no warper coordinate maps into its %d x %d source through its camera and lens", i, W, H);
+    }
+    if (int e = check_dense_rois(c, "ms_build_maps (with a lens: views as they warp through it)", rois)) return e;
+    std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);
+    if (c->stitch_pending) MS_HIP(hipEventSynchronize(c->last_stitch));      // (a calibration-time call: no stitch still reads the maps replaced below)
+    c->maps_built = c->masks_built = c->blender_ready = false;
+    for (int i = 0; i < N; ++i) c->roi[i] = rois[i];
+    if (int e = alloc_dense_maps(c, st)) return e;
+    for (int i = 0; i < N; ++i) {
+        ms_image mx = view_map_image(c, i, 0), my = view_map_image(c, i, 1);
+        if (int e = launch_lens_maps(c->cfg.projection, rois[i].x, rois[i].y, mx, my, c->K[i], c->R[i], view_lens(c, i), c->cfg.warp_scale, st)) return e;
+    }
+    place_panorama(c);
+    MS_HIP(hipStreamSynchronize(st));
+    c->custom_maps = c->lens_maps = true;
+    c->maps_built = true;
+    return MS_OK;
+}
+
 int ms_build_maps(ms_ctx *c, ms_stream stream)
 {
     if (!c) return fail(MS_ERR_INVALID, "null context");
     hipStream_t st = as_stream(stream);
     for (int i = 0; i < c->N; ++i)
         if (!c->have_cam[i]) return fail(MS_ERR_STATE, "ms_build_maps: camera %d not set", i);
+    for (int i = 0; i < c->N; ++i)
+        if (c->lens[i].model != MS_LENS_NONE) return build_maps_lens(c, st);
     const int W = c->cfg.src_width, H = c->cfg.src_height;
     size_t total = 0;
     for (int i = 0; i < c->N; ++i) {
@@ -2137,14 +2237,9 @@ int ms_build_maps(ms_ctx *c, ms_stream stream)
         k_warp_tabs<<<div_up(n, 256), 256, 0, st>>>(c->cfg.projection, c->roi[i].x, c->roi[i].y, c->roi[i].width, c->roi[i].height, ct, rt, W);
         MS_LAUNCH_CHECK();
     }
-    // blender->prepare(corners, sizes)
-    c->bg = blender_prepare(result_roi(c->N, c->roi), c->cfg.num_bands);
-    for (int i = 0; i < c->N; ++i)
-        c->pad[i] = blender_view_pad(c->bg, c->roi[i].x, c->roi[i].y, c->roi[i].width, c->roi[i].height);
-    c->canvas_x = c->bg.dst_roi.x + c->cfg.out_width / 2;
-    c->canvas_y = c->cfg.projection == MS_PROJ_SPHERICAL ? c->bg.dst_roi.y : c->bg.dst_roi.y + c->cfg.out_height / 2;
+    place_panorama(c);      // blender->prepare(corners, sizes)
     MS_HIP(hipStreamSynchronize(st));
-    c->custom_maps = false;
+    c->custom_maps = c->lens_maps = false;
     c->maps_built = true;
     c->masks_built = c->blender_ready = false;
     return MS_OK;
@@ -2157,12 +2252,9 @@ int ms_set_maps(ms_ctx *c, const ms_rect *rois, const ms_image *xmaps, const ms_
 {
     if (!c || !rois || !xmaps || !ymaps) return fail(MS_ERR_INVALID, "ms_set_maps: null argument");
     const int N = c->N;
-    long long tlx = INT_MAX, tly = INT_MAX, brx = INT_MIN, bry = INT_MIN;
+    if (int e = check_dense_rois(c, "ms_set_maps", rois)) return e;
     for (int i = 0; i < N; ++i) {
         const ms_rect &r = rois[i];
-        MS_CHECK(r.width >= MS_MAPS_MIN_WIDTH && r.width <= MS_MAPS_MAX_SIDE && r.height >= MS_MAPS_MIN_HEIGHT && r.height <= MS_MAPS_MAX_SIDE,
-                 "ms_set_maps: ROI %d is %d x %d: the tiled kernels take views of %d..%d columns and %d..%d rows", i, r.width, r.height,
-                 (int)MS_MAPS_MIN_WIDTH, (int)MS_MAPS_MAX_SIDE, (int)MS_MAPS_MIN_HEIGHT, (int)MS_MAPS_MAX_SIDE);
         for (int which = 0; which < 2; ++which) {
             const ms_image &m = which ? ymaps[i] : xmaps[i];
             const char *name = which ? "ymaps" : "xmaps";
@@ -2173,41 +2265,22 @@ int ms_set_maps(ms_ctx *c, const ms_rect *rois, const ms_image *xmaps, const ms_
                      "ms_set_maps: %s[%d] needs a row step of at least %zu bytes that is a multiple of 4 and 4-byte aligned data (step %zu, data %p)",
                      name, i, (size_t)r.width * sizeof(float), m.step, m.data);
         }
-        tlx = std::min<long long>(tlx, r.x); tly = std::min<long long>(tly, r.y);
-        brx = std::max<long long>(brx, (long long)r.x + r.width); bry = std::max<long long>(bry, (long long)r.y + r.height);
-    }
-    {   // the padded panorama: band tiles keep their origin in 16 bits (blender_prepare rounds the union up to a multiple of 2^num_bands)
-        const long long m = 1ll << c->cfg.num_bands, pw = (brx - tlx + m - 1) / m * m, ph = (bry - tly + m - 1) / m * m;
-        MS_CHECK(pw <= 32767 && ph <= 32767, "ms_set_maps: the ROIs span a padded panorama of %lld x %lld: each side must be at most 32767", pw, ph);
     }
     hipStream_t st = as_stream(stream);
     std::lock_guard<std::recursive_mutex> tables_lk(c->tables_mu);
     if (c->stitch_pending) MS_HIP(hipEventSynchronize(c->last_stitch));      // (a calibration-time call: no stitch still reads the maps replaced below)
     c->maps_built = c->masks_built = c->blender_ready = false;
-    size_t total = 0;
-    for (int i = 0; i < N; ++i) {
-        c->roi[i] = rois[i];
-        c->map_pitch[i] = round_up(rois[i].width, 4);
-        c->map_off[i] = total;
-        total += (size_t)2 * rois[i].height * c->map_pitch[i];
-    }
-    if (int e = c->maps.alloc(total * sizeof(float))) return e;
-    MS_HIP(hipMemsetAsync(c->maps.p, 0, total * sizeof(float), st));      // (the up to 3 padding columns of a row are never read; zeroed all the same)
+    for (int i = 0; i < N; ++i) c->roi[i] = rois[i];
+    if (int e = alloc_dense_maps(c, st)) return e;
     for (int i = 0; i < N; ++i) {
         const ms_image mx = view_map_image(c, i, 0), my = view_map_image(c, i, 1);
         MS_HIP(hipMemcpy2DAsync(mx.data, mx.step, xmaps[i].data, xmaps[i].step, (size_t)rois[i].width * sizeof(float), rois[i].height, hipMemcpyDeviceToDevice, st));
         MS_HIP(hipMemcpy2DAsync(my.data, my.step, ymaps[i].data, ymaps[i].step, (size_t)rois[i].width * sizeof(float), rois[i].height, hipMemcpyDeviceToDevice, st));
     }
-    c->tabs.release();      // no projection, no tables: nothing may follow a stale index into them
-    for (int i = 0; i < MAX_VIEWS; ++i) c->tab_off[i] = 0;
-    // blender->prepare(corners, sizes) and the canvas, as ms_build_maps
-    c->bg = blender_prepare(result_roi(N, c->roi), c->cfg.num_bands);
-    for (int i = 0; i < N; ++i)
-        c->pad[i] = blender_view_pad(c->bg, c->roi[i].x, c->roi[i].y, c->roi[i].width, c->roi[i].height);
-    c->canvas_x = c->bg.dst_roi.x + c->cfg.out_width / 2;
-    c->canvas_y = c->cfg.projection == MS_PROJ_SPHERICAL ? c->bg.dst_roi.y : c->bg.dst_roi.y + c->cfg.out_height / 2;
+    place_panorama(c);      // blender->prepare(corners, sizes) and the canvas, as ms_build_maps
     MS_HIP(hipStreamSynchronize(st));
     c->custom_maps = true;
+    c->lens_maps = false;
     c->maps_built = true;
     return MS_OK;
 }
@@ -2215,7 +2288,7 @@ int ms_set_maps(ms_ctx *c, const ms_rect *rois, const ms_image *xmaps, const ms_
 int ms_get_map_source(const ms_ctx *c, int *source)
 {
     if (!c || !source) return fail(MS_ERR_INVALID, "ms_get_map_source: null argument");
-    *source = c->custom_maps ? MS_MAPS_CUSTOM : MS_MAPS_ANALYTIC;
+    *source = c->lens_maps ? MS_MAPS_LENS : c->custom_maps ? MS_MAPS_CUSTOM : MS_MAPS_ANALYTIC;
     return MS_OK;
 }
 
@@ -2261,7 +2334,7 @@ int ms_calibrate_seam(ms_ctx *c, const ms_image *full_imgs, const float *K_seam,
 {
     if (!c || !full_imgs || !K_seam || !prm) return fail(MS_ERR_INVALID, "ms_calibrate_seam: null argument");
     if (!c->maps_built) return fail(MS_ERR_STATE, "ms_calibrate_seam: call ms_build_maps first");
-    if (c->custom_maps) return fail(MS_ERR_UNSUPPORTED, "ms_calibrate_seam: the context's maps are the caller's own (ms_set_maps): the seam-scale calibration re-warps from cameras it does not have");
+    if (c->custom_maps && !c->lens_maps) return fail(MS_ERR_UNSUPPORTED, "ms_calibrate_seam: the context's maps are the caller's own (ms_set_maps): the seam-scale calibration re-warps from cameras it does not have");
     MS_CHECK(prm->seam_scale > 0 && prm->seam_scale <= 1.0 && prm->seam_warp_scale > 0, "ms_calibrate_seam: bad scales");
     hipStream_t st = as_stream(stream);
     const int N = c->N, W = c->cfg.src_width, H = c->cfg.src_height;
@@ -2281,9 +2354,15 @@ int ms_calibrate_seam(ms_ctx *c, const ms_image *full_imgs, const float *K_seam,
         ms_image simg{seam.p, (size_t)ws * 3, ws, hs, MS_8UC3};
         if (int e = launch_resize_linear(full_imgs[i], simg, prm->seam_scale, prm->seam_scale, st)) return e;        // calibration.cpp:95
         const float *Ks = K_seam + 9 * i;
-        Projector P;
-        set_camera_params(P, Ks, c->R[i], nullptr, prm->seam_warp_scale);
-        rs[i] = warp_roi(c->cfg.projection, P, ws, hs);
+        if (c->lens_maps) {      // a rig with a lens: the ROI by forward evaluation.  Distortion acts on normalised coordinates, so the view's ms_lens serves K_seam as it is
+            bool seen = false;
+            if (int e = lens_roi_device(c->cfg.projection, Ks, c->R[i], view_lens(c, i), prm->seam_warp_scale, ws, hs, &rs[i], &seen, st)) return e;
+            MS_CHECK(seen, "ms_calibrate_seam: view %d sees nothing at seam scale", i);
+        } else {
+            Projector P;
+            set_camera_params(P, Ks, c->R[i], nullptr, prm->seam_warp_scale);
+            rs[i] = warp_roi(c->cfg.projection, P, ws, hs);
+        }
         MS_CHECK(rs[i].width > 0 && rs[i].height > 0 && (size_t)rs[i].width * rs[i].height < (1u << 28), "ms_calibrate_seam: bad seam ROI for view %d", i);
         const size_t npx = (size_t)rs[i].width * rs[i].height;
         if (int e = mapx.alloc(npx * 4)) return e;
@@ -2291,9 +2370,13 @@ int ms_calibrate_seam(ms_ctx *c, const ms_image *full_imgs, const float *K_seam,
         if (int e = wimg[i].alloc(npx * 3)) return e;
         if (int e = wmask[i].alloc(npx)) return e;
         ms_image mx{mapx.p, (size_t)rs[i].width * 4, rs[i].width, rs[i].height, MS_32FC1}, my{mapy.p, (size_t)rs[i].width * 4, rs[i].width, rs[i].height, MS_32FC1};
-        float k_rinv[9];
-        k_rinv_gemm(Ks, c->R[i], k_rinv);
-        if (int e = launch_build_warp_maps(c->cfg.projection, rs[i].x, rs[i].y, mx, my, k_rinv, nullptr, prm->seam_warp_scale, st)) return e;
+        if (c->lens_maps) {
+            if (int e = launch_lens_maps(c->cfg.projection, rs[i].x, rs[i].y, mx, my, Ks, c->R[i], view_lens(c, i), prm->seam_warp_scale, st)) return e;
+        } else {
+            float k_rinv[9];
+            k_rinv_gemm(Ks, c->R[i], k_rinv);
+            if (int e = launch_build_warp_maps(c->cfg.projection, rs[i].x, rs[i].y, mx, my, k_rinv, nullptr, prm->seam_warp_scale, st)) return e;
+        }
         ms_image wi{wimg[i].p, (size_t)rs[i].width * 3, rs[i].width, rs[i].height, MS_8UC3};
         if (int e = launch_remap(simg, mx, my, wi, MS_INTER_LINEAR, MS_BORDER_REFLECT, st)) return e;                   // calibration.cpp:118
         k_valid_mask<<<dim3(div_up(rs[i].width, 64), div_up(rs[i].height, 4)), dim3(64, 4), 0, st>>>(                // calibration.cpp:122
@@ -3971,6 +4054,7 @@ int ms_save_tables(ms_ctx *c, void *buf, size_t cap, size_t *bytes_out)
     // a blob replays its context's configuration verbatim: one of a column / view shard would give EVERY loader that shard's window.  The unsharded
     // context is what "one blob for every rank" means; a rank that needs a shard creates it from the same K / R / gains / masks itself.
     if (c->cfg.col_shards > 1 || c->cfg.view_shards > 1) return fail(MS_ERR_UNSUPPORTED, "ms_save_tables: this context is a column / view shard; save the tables of an unsharded context");
+    if (c->lens_maps) return fail(MS_ERR_UNSUPPORTED, "ms_save_tables: a view of this context has a lens (ms_set_lens); the blob format has no lens record, so it could not replay these maps");
     if (c->custom_maps) return fail(MS_ERR_UNSUPPORTED, "ms_save_tables: the context's maps are the caller's own (ms_set_maps); a blob replays cameras, which this context does not have");
     size_t need = sizeof(TablesHeader);
     for (int v = 0; v < c->N; ++v) need += sizeof(TablesView) + (size_t)c->roi[v].width * c->roi[v].height;

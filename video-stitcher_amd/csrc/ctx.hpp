@@ -46,10 +46,12 @@ struct ms_ctx {
     int N = 0;
     float K[ms::MAX_VIEWS][9], R[ms::MAX_VIEWS][9];
     bool have_cam[ms::MAX_VIEWS] = {};
+    ms_lens lens[ms::MAX_VIEWS] = {};      // model MS_LENS_NONE (0) = the view has none (ms_set_lens)
     double gain[ms::MAX_VIEWS];
     // stage flags
     bool maps_built = false, masks_built = false, blender_ready = false;
-    bool custom_maps = false;          // the maps are the caller's (ms_set_maps): no cameras, no 1-D projection tables -- the tiled warp kernels read xmap / ymap (PROJ_MAPS)
+    bool custom_maps = false;          // dense maps without 1-D projection tables -- the tiled warp kernels read xmap / ymap (PROJ_MAPS): the caller's (ms_set_maps, no cameras), or ...
+    bool lens_maps = false;            // ... ms_build_maps' own for a rig with a lens (ms_set_lens): custom_maps is set too, the cameras are known
     // geometry
     ms_rect roi[ms::MAX_VIEWS];
     ms::BlendGeom bg{};

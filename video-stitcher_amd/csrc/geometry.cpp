@@ -10,6 +10,7 @@
 #include <cmath>
 #include <vector>
 #include "launchers.hpp"
+#include "lens.hpp"
 
 namespace ms {
 
@@ -171,6 +172,35 @@ ms_rect result_roi(int n, const ms_rect *r)
         brx = std::max(brx, r[i].x + r[i].width); bry = std::max(bry, r[i].y + r[i].height);
     }
     return ms_rect{tlx, tly, brx - tlx, bry - tly};
+}
+
+// ms_lens_check: everything about an ms_lens that can be judged without a camera.  The radial profile -- r * cdist(r) over r in [0, tan max_theta] for BROWN,
+// theta_d(theta) over [0, max_theta] for FISHEYE -- must rise strictly over 4096 uniform steps: where it folds back, rays far outside the field of view land inside
+// the image again.  BROWN's tangential terms are not part of the profile.
+int lens_check(const char *who, const ms_lens *l)
+{
+    MS_CHECK(l->struct_size == sizeof(ms_lens), "%s: ms_lens.struct_size %u, this library's is %zu", who, l->struct_size, sizeof(ms_lens));
+    MS_CHECK(l->model == MS_LENS_NONE || l->model == MS_LENS_BROWN || l->model == MS_LENS_FISHEYE, "%s: unknown lens model %d", who, l->model);
+    if (l->model == MS_LENS_NONE) return MS_OK;
+    const bool fish = l->model == MS_LENS_FISHEYE;
+    for (int i = 0; i < 8; ++i) {
+        MS_CHECK(std::isfinite(l->k[i]), "%s: lens coefficient k[%d] is not finite", who, i);
+        MS_CHECK(!fish || i < 4 || l->k[i] == 0.0, "%s: MS_LENS_FISHEYE has four coefficients; k[%d] = %g must be 0", who, i, l->k[i]);
+    }
+    const double hi = fish ? 180.0 : 89.0;
+    MS_CHECK(l->max_theta_deg == 0.0 || (l->max_theta_deg > 0.0 && l->max_theta_deg <= hi), "%s: max_theta_deg %g outside (0, %g] (0 = the default, %g)", who,
+             l->max_theta_deg, hi, hi);
+    const double mt = lens_max_theta_deg(*l), end = fish ? mt * (LENS_PI / 180.0) : std::tan(mt * (LENS_PI / 180.0));
+    constexpr int STEPS = 4096;
+    double prev = 0.0;
+    for (int i = 1; i <= STEPS; ++i) {
+        const double a = end * i / STEPS, f = fish ? lens_fisheye_theta_d(l->k, a) : a * lens_brown_cdist(l->k, a * a);
+        if (!(f > prev) || !std::isfinite(f))
+            return fail(MS_ERR_INVALID, "%s: the radial profile of the lens is not strictly increasing up to max_theta_deg = %g (it folds back at %s = %g): lower max_theta_deg "
+                        "to the range the calibration holds on", who, mt, fish ? "theta" : "r", a);
+        prev = f;
+    }
+    return MS_OK;
 }
 
 BlendGeom blender_prepare(ms_rect roi, int actual_num_bands)

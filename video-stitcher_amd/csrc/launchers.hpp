@@ -29,6 +29,10 @@ int launch_normalize(const ms_image &w, ms_image &src, int width, int height, hi
 int launch_zero_masked(ms_image &img, const ms_image &mask, hipStream_t st);
 int launch_dilate3(const ms_image &src, ms_image &dst, hipStream_t st);
 int launch_build_warp_maps(int proj, int tl_u, int tl_v, ms_image &mx, ms_image &my, const float *k_rinv, const float *t, float scale, hipStream_t st);
+// lens.hip: the maps and the ROI of a camera with a lens (lens == nullptr: MS_LENS_NONE in the same double arithmetic).  lens_roi_device is synchronous;
+// *seen_any = false (roi untouched) when no candidate of the window hits the source.  `lens` has passed lens_check.
+int launch_lens_maps(int proj, int tl_u, int tl_v, ms_image &mx, ms_image &my, const float *K, const float *R, const ms_lens *lens, float scale, hipStream_t st);
+int lens_roi_device(int proj, const float *K, const float *R, const ms_lens *lens, float scale, int src_w, int src_h, ms_rect *roi, bool *seen_any, hipStream_t st);
 int launch_nv12_to_bgr(const ms_image &src, ms_image &dst, hipStream_t st);
 int launch_nv12_to_bgr_batch(const ms_image *src, ms_image *dst, int n, hipStream_t st);
 int launch_bgr_to_i420(const ms_image &src, ms_image &dst, hipStream_t st);
@@ -46,6 +50,7 @@ ms_rect warp_roi(int proj, const Projector &p, int src_w, int src_h);
 int calibrate_cameras(const ms_rig_params &q, ms_rig &r);
 void num_bands_rule(int pano_w, int pano_h, float blend_strength, float *blend_width, int *num_bands);
 ms_rect result_roi(int n, const ms_rect *rois);
+int lens_check(const char *who, const ms_lens *lens);      // ms_lens_check's rules; lens must not be null
 
 struct BlendGeom { int num_bands; ms_rect dst_roi_final, dst_roi; };
 struct ViewPad { int top, left, bottom, right, x_tl, y_tl, x_br, y_br; };

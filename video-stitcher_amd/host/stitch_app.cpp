@@ -19,6 +19,9 @@
 //                   [--i420] [--nv12 | --nv12-direct] [--dump pano.bin] [--no-upload] [--solve-mesh]
 //                   [--reference-calib [--work-megapix 0.6] [--seam-megapix 0.01] [--compose-megapix 1.4]]
 //                   [--drop-view V:F0:F1] [--dump-frames frames.bin] [--track-gains K] [--exposure-ramp V:F] [--dump-i420 planes.bin]
+//                   [--lens-brown k1,k2,p1,p2,k3 | --lens-fisheye k1,k2,k3,k4[,max_theta]]
+// --lens-brown / --lens-fisheye give EVERY camera that lens (ms_set_lens; coefficients as OpenCV's distCoeffs / fisheye D, max_theta in degrees): maps, ROIs and,
+// with --reference-calib, the seam-scale calibration come from the library's lens model, and the JSON line's "map_source" is 2 (MS_MAPS_LENS) instead of 0.
 // --nv12-direct keeps BGR copies of the cameras' frames off the device in every mode: the warp samples the planes (ms_stitch_nv12), --i420 makes the encoder's
 // planes in the same call (ms_stitch_nv12_i420: no 8U canvas is written; --dump, --dump-frames and --consume need the canvas and keep the two-step form
 // ms_stitch_nv12 + ms_bgr_to_i420), --track-gains reads the planes (ms_track_gains_nv12).  With a compose-scale resize (--reference-calib) the frames go
@@ -100,6 +103,7 @@ struct Options {
     int ramp_view = -1; double ramp_factor = 1.0;      // --exposure-ramp V:F
     std::string dump_i420;                      // --dump-i420 FILE
     bool fused_resize = false;                  // --fused-resize: with --nv12-direct and a compose-scale resize, planes -> small_imgs in one pass
+    ms_lens lens{sizeof(ms_lens), MS_LENS_NONE, {0, 0, 0, 0, 0, 0, 0, 0}, 0.0};      // --lens-brown / --lens-fisheye: every camera's lens
 };
 constexpr int CAMERA_TIMEOUT_MS = 100;               // --drop-view: how long the main loop waits for a camera's frame before it stitches without it
 
@@ -217,6 +221,15 @@ int main(int argc, char **argv)
         else if (k == "--track-gains") o.track_gains = atoi(next());
         else if (k == "--dump-i420") o.dump_i420 = next();
         else if (k == "--fused-resize") o.fused_resize = true;
+        else if (k == "--lens-brown") {      // k1,k2,p1,p2,k3 in distCoeffs order: k3 is k[4]
+            double *c = o.lens.k;
+            if (sscanf(next(), "%lf,%lf,%lf,%lf,%lf", &c[0], &c[1], &c[2], &c[3], &c[4]) != 5) { fprintf(stderr, "--lens-brown wants k1,k2,p1,p2,k3\n"); return 2; }
+            o.lens.model = MS_LENS_BROWN;
+        } else if (k == "--lens-fisheye") {
+            double *c = o.lens.k;
+            if (sscanf(next(), "%lf,%lf,%lf,%lf,%lf", &c[0], &c[1], &c[2], &c[3], &o.lens.max_theta_deg) < 4) { fprintf(stderr, "--lens-fisheye wants k1,k2,k3,k4[,max_theta]\n"); return 2; }
+            o.lens.model = MS_LENS_FISHEYE;
+        }
         else if (k == "--exposure-ramp") {
             if (sscanf(next(), "%d:%lf", &o.ramp_view, &o.ramp_factor) != 2 || o.ramp_view < 0 || o.ramp_factor < 0) { fprintf(stderr, "--exposure-ramp wants V:F\n"); return 2; }
         }
@@ -227,6 +240,7 @@ int main(int argc, char **argv)
     if (o.track_gains < 0) { fprintf(stderr, "--track-gains wants K >= 0\n"); return 2; }
     if (!o.dump_i420.empty() && !o.i420) { fprintf(stderr, "--dump-i420 needs --i420\n"); return 2; }
     if (o.fused_resize && !o.nv12_direct) { fprintf(stderr, "--fused-resize needs --nv12-direct\n"); return 2; }
+    if (ms_lens_check(&o.lens) != MS_OK) { fprintf(stderr, "stitch_app: %s\n", ms_last_error()); return 2; }
     FILE *frames_file = nullptr;       // --dump-frames (opened before any thread starts)
     if (!o.dump_frames.empty() && !(frames_file = fopen(o.dump_frames.c_str(), "wb"))) { fprintf(stderr, "cannot write %s\n", o.dump_frames.c_str()); return 2; }
     bool frames_file_ok = true;
@@ -237,6 +251,8 @@ int main(int argc, char **argv)
         // ---- stitch_calib ------------------------------------------------------------------------------------
         std::unique_ptr<msshim::Compositor> comp_owner;
         msshim::Calibration cal;
+        const bool with_lens = o.lens.model != MS_LENS_NONE;
+        const std::vector<ms_lens> lenses((size_t)o.views, o.lens);
         if (o.reference_calib) {
             // the reference's own calibration from the first frame of every camera (device 8UC3, full size)
             std::vector<DevMat> first(o.views);
@@ -246,7 +262,8 @@ int main(int argc, char **argv)
                 synth_frame(host.data(), o.w, o.h, i);
                 HIPCHECK(hipMemcpy2D(first[i].data, first[i].step, host.data(), (size_t)o.w * 3, (size_t)o.w * 3, o.h, hipMemcpyHostToDevice));
             }
-            comp_owner = msshim::stitch_calib(first, MS_PROJ_CYLINDRICAL, o.cpw, cal, o.hfov, o.work_mp, o.seam_mp, o.compose_mp, 5.f, -1, -1, 1, -1, nullptr, o.cpw ? o.update_mask : 0);
+            comp_owner = msshim::stitch_calib(first, MS_PROJ_CYLINDRICAL, o.cpw, cal, o.hfov, o.work_mp, o.seam_mp, o.compose_mp, 5.f, -1, -1, 1, -1, nullptr, o.cpw ? o.update_mask : 0,
+                                              with_lens ? lenses.data() : nullptr);
             for (auto &m : first) HIPCHECK(hipFree(m.data));
             const ms_pano_geom g = comp_owner->panoGeom();
             o.out_w = (2 * std::max(std::abs(cal.pano_roi.x), std::abs(cal.pano_roi.x + cal.pano_roi.width)) + 1) & ~1;
@@ -263,6 +280,7 @@ int main(int argc, char **argv)
             comp_owner.reset(new msshim::Compositor(o.views, o.w, o.h, MS_PROJ_SPHERICAL, (float)(o.out_w / (2.0 * M_PI)), o.bands, o.cpw, o.out_w, o.out_h, 1, o.cpw ? o.update_mask : 0));
             for (int i = 0; i < o.views; ++i) {
                 comp_owner->setCamera(i, cal.rig.K_compose[i], cal.rig.R[i]);
+                if (with_lens) comp_owner->setLens(i, &lenses[i]);
                 comp_owner->setGain(i, 1.0 + 0.02 * (i - (o.views - 1) / 2.0));
             }
             comp_owner->buildMaps();
@@ -634,10 +652,10 @@ int main(int argc, char **argv)
         }
         printf("{\"app\": \"stitch_app\", \"views\": %d, \"src\": \"%dx%d\", \"out\": \"%dx%d\", \"bands\": %d, \"cpw\": %s, \"i420\": %s, \"nv12\": %s, \"nv12_direct\": %s, \"upload\": %s, "
                "\"frames\": %lld, \"seconds\": %.4f, \"frames_per_s\": %.1f, \"recalibrations\": %d, \"mesh_solver_iterations\": %d, \"max_mesh_displacement_px\": %.2f, "
-               "\"orb_keypoints\": %lld, \"ratio_matches\": %lld, \"ransac_inliers\": %lld, \"update_mask_margin\": %d, \"update_mask_equals_sync_rebuild\": %s, \"consume_image_height\": %d, \"consume_checksum\": \"%016llx\", \"checksum\": \"%016llx\", \"degraded_frames\": %lld, \"i420_call\": \"%s\", \"fused_resize\": %s",
+               "\"orb_keypoints\": %lld, \"ratio_matches\": %lld, \"ransac_inliers\": %lld, \"update_mask_margin\": %d, \"update_mask_equals_sync_rebuild\": %s, \"consume_image_height\": %d, \"consume_checksum\": \"%016llx\", \"checksum\": \"%016llx\", \"degraded_frames\": %lld, \"i420_call\": \"%s\", \"fused_resize\": %s, \"map_source\": %d",
                o.views, o.w, o.h, o.out_w, o.out_h, pg.num_bands, o.cpw ? "true" : "false", o.i420 ? "true" : "false", o.nv12 ? "true" : "false", o.nv12_direct ? "true" : "false", o.upload ? "true" : "false",
                consumed, secs, consumed / secs, recalibrations.load(), solver_iterations.load(), (double)max_disp.load(),
-               total_keypoints.load(), total_matches.load(), total_inliers.load(), o.update_mask, selfcheck < 0 ? "null" : (selfcheck ? "true" : "false"), consume_image_height, consume_checksum, checksum, degraded_frames, i420_call, fused_resize ? "true" : "false");
+               total_keypoints.load(), total_matches.load(), total_inliers.load(), o.update_mask, selfcheck < 0 ? "null" : (selfcheck ? "true" : "false"), consume_image_height, consume_checksum, checksum, degraded_frames, i420_call, fused_resize ? "true" : "false", comp.mapSource());
         if (o.track_gains > 0) {
             std::vector<double> g((size_t)o.views);
             int ok = 0, singular = 0;

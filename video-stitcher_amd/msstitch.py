@@ -18,7 +18,9 @@ BORDER_CONSTANT, BORDER_REFLECT = 0, 2
 INTER_NEAREST, INTER_LINEAR = 0, 1
 INTER_LINEAR_FIXPT = 0x101      # cv::remap's CPU arithmetic
 PROJ_PLANE, PROJ_CYLINDRICAL, PROJ_SPHERICAL = 0, 1, 2
-MAPS_ANALYTIC, MAPS_CUSTOM = 0, 1
+MAPS_ANALYTIC, MAPS_CUSTOM, MAPS_LENS = 0, 1, 2
+LENS_NONE, LENS_BROWN, LENS_FISHEYE = 0, 1, 2
+LENS_CYL_MAX_ELEVATION_DEG = 80
 MAPS_MIN_WIDTH, MAPS_MIN_HEIGHT, MAPS_MAX_SIDE = 3, 2, 31744
 
 
@@ -44,6 +46,24 @@ class Config(C.Structure):
                 ("view_shards", C.c_int), ("view_shard_index", C.c_int), ("cpu_flavour_remap", C.c_int),
                 ("debug_simple_kernels", C.c_int), ("warp_lds_stage", C.c_int), ("raster_tile_order", C.c_int),
                 ("col_shards", C.c_int), ("col_shard_index", C.c_int), ("update_mask_margin", C.c_int), ("self_check", C.c_int)]
+
+
+class Lens(C.Structure):
+    """ms_lens.  Lens.brown(k1, k2, p1, p2, k3, k4, k5, k6) / Lens.fisheye(k1, k2, k3, k4) fill it; max_theta_deg = 0 is the model's default"""
+    _fields_ = [("struct_size", C.c_uint), ("model", C.c_int), ("k", C.c_double * 8), ("max_theta_deg", C.c_double)]
+
+    @classmethod
+    def make(cls, model, k=(), max_theta_deg=0.0):
+        k = [float(v) for v in k]
+        return cls(C.sizeof(cls), model, (C.c_double * 8)(*(k + [0.0] * (8 - len(k)))), float(max_theta_deg))
+
+    @classmethod
+    def brown(cls, *k, max_theta_deg=0.0):
+        return cls.make(LENS_BROWN, k, max_theta_deg)
+
+    @classmethod
+    def fisheye(cls, *k, max_theta_deg=0.0):
+        return cls.make(LENS_FISHEYE, k, max_theta_deg)
 
 
 class SeamParams(C.Structure):
@@ -143,6 +163,7 @@ EXPORTS = [
     "ms_gain_samples_bytes", "ms_get_view_shard", "ms_get_gain_sample_views", "ms_gain_samples", "ms_gain_samples_nv12", "ms_gain_stats_from_samples", "ms_track_gains_from_samples",
     "ms_voronoi_seams", "ms_estimate_gains",
     "ms_set_maps", "ms_get_map_source",
+    "ms_lens_check", "ms_lens_project", "ms_set_lens", "ms_get_lens", "ms_build_warp_maps_lens", "ms_warp_roi_lens",
 ]
 
 _lib = None
@@ -428,6 +449,41 @@ def build_warp_maps(projection, tl_u, tl_v, rows, cols, k_rinv, scale, t=None):
         ta, tp = _fa(t, 3)
     _chk(load().ms_build_warp_maps(projection, tl_u, tl_v, C.byref(img(mx)), C.byref(img(my)), kp, kp, tp, C.c_float(scale), _stream()))
     return mx, my
+
+
+def _lens_ptr(lens):
+    return C.byref(lens) if lens is not None else None
+
+
+def lens_check(lens):
+    """ms_lens_check (host only): raises MsError for a lens the library refuses"""
+    _chk(load().ms_lens_check(_lens_ptr(lens)))
+
+
+def lens_project(K, lens, ray):
+    """ms_lens_project (host only): the camera ray (X, Y, Z) -> ((px, py), seen); (-1, -1) when the lens does not see it"""
+    ka, kp = _fa(K, 9)
+    r = (C.c_double * 3)(*[float(v) for v in ray])
+    px = (C.c_double * 2)()
+    seen = C.c_int(-1)
+    _chk(load().ms_lens_project(kp, _lens_ptr(lens), r, px, C.byref(seen)))
+    return (px[0], px[1]), bool(seen.value)
+
+
+def build_warp_maps_lens(projection, tl_u, tl_v, rows, cols, K, R, lens, scale, out=None):
+    """ms_build_warp_maps_lens; out: (map_x, map_y) float32 cuda tensors to fill (views of larger tensors are fine) instead of new ones"""
+    torch = _torch()
+    mx, my = out if out is not None else (_new((rows, cols), torch.float32), _new((rows, cols), torch.float32))
+    ka, kp = _fa(K, 9); ra, rp = _fa(R, 9)
+    _chk(load().ms_build_warp_maps_lens(projection, tl_u, tl_v, C.byref(img(mx)), C.byref(img(my)), kp, rp, _lens_ptr(lens), C.c_float(scale), _stream()))
+    return mx, my
+
+
+def warp_roi_lens(projection, K, R, lens, scale, src_w, src_h):
+    ka, kp = _fa(K, 9); ra, rp = _fa(R, 9)
+    r = Rect()
+    _chk(load().ms_warp_roi_lens(projection, kp, rp, _lens_ptr(lens), C.c_float(scale), src_w, src_h, C.byref(r), _stream()))
+    return r.tuple()
 
 
 def nv12_to_bgr(src, dst=None):
@@ -746,6 +802,15 @@ class Compositor:
         ka, kp = _fa(K, 9); ra, rp = _fa(R, 9)
         _chk(load().ms_set_camera(self._ctx, view, kp, rp))
 
+    def set_lens(self, view, lens):
+        """ms_set_lens: a Lens, or None to clear the view's"""
+        _chk(load().ms_set_lens(self._ctx, view, _lens_ptr(lens)))
+
+    def get_lens(self, view):
+        lens = Lens()
+        _chk(load().ms_get_lens(self._ctx, view, C.byref(lens)))
+        return lens
+
     def set_gain(self, view, gain):
         _chk(load().ms_set_gain(self._ctx, view, C.c_double(gain)))
 
@@ -762,7 +827,7 @@ class Compositor:
         _chk(load().ms_set_maps(self._ctx, r, xs, ys, _stream()))
 
     def map_source(self):
-        """ms_get_map_source: MAPS_ANALYTIC (build_maps) or MAPS_CUSTOM (set_maps)"""
+        """ms_get_map_source: MAPS_ANALYTIC (build_maps), MAPS_LENS (build_maps with a lens on some view) or MAPS_CUSTOM (set_maps)"""
         v = C.c_int(-1)
         _chk(load().ms_get_map_source(self._ctx, C.byref(v)))
         return v.value

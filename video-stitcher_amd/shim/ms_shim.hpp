@@ -101,6 +101,8 @@ public:
     // calibrateCameras + warpImages (calibration.cpp:28-248): K, R are the 3x3 CV_32F matrices of cameras[i]
     void setCamera(int i, const float *K, const float *R) { check(ms_set_camera(ctx_, i, K, R)); }
     void setGain(int i, double g) { check(ms_set_gain(ctx_, i, g)); }                 // gc->gains()[i]
+    // cameras[i]'s distortion (cvProjectPoints2's distCoeffs / cv::fisheye::projectPoints' D): with a lens on any view buildMaps / calibrateSeam go through the lens model
+    void setLens(int i, const ms_lens *lens) { check(ms_set_lens(ctx_, i, lens)); }   // nullptr clears it
     void buildMaps(ms_stream s = nullptr) { check(ms_build_maps(ctx_, s)); }          // gpu_warper->buildMaps + blender->prepare
     // ... or the caller's own x_maps / y_maps (what stitch_online receives, timed.cpp:56, :84-90) with the corners / sizes prepare() gets: any lens model or third-party
     // calibration; no setCamera needed.  The maps are copied.  calibrate_seam / save_tables are refused on such a context (they need cameras).
@@ -112,6 +114,7 @@ public:
         check(ms_set_maps(ctx_, rois.data(), x.data(), y.data(), s));
     }
     bool customMaps() const { int src = MS_MAPS_ANALYTIC; check(ms_get_map_source(ctx_, &src)); return src == MS_MAPS_CUSTOM; }
+    int mapSource() const { int src = MS_MAPS_ANALYTIC; check(ms_get_map_source(ctx_, &src)); return src; }      // MS_MAPS_ANALYTIC / _CUSTOM / _LENS
     void buildMasks(bool voronoi_seams = true, ms_stream s = nullptr) { check(ms_build_masks(ctx_, voronoi_seams ? 1 : 0, s)); }
     void setMask(int i, const uint8_t *host_mask, size_t step) { check(ms_set_mask(ctx_, i, host_mask, step)); }
     void init_gpu(ms_stream s = nullptr) { check(ms_init_blender(ctx_, s)); }         // mb->init_gpu for every view
@@ -245,11 +248,13 @@ struct Calibration {
 // projection: the app ships MS_PROJ_CYLINDRICAL (calibration.cpp:100,156); out_w / out_h: canvas for the 8U output, 0 = none.
 // update_mask_margin > 0 (CPW only): update_mask() on the returned compositor only enqueues, so the recalibration thread may call it after every
 // mesh swap while frames flow; with 0 it is the synchronous rebuild, which makes a concurrent stitch_one wait (never race) for its ~50 ms.
+// lenses: nullptr, or one ms_lens per view (model MS_LENS_NONE = that view has none): handed to ms_set_lens, so that the ROIs, the maps and the seam-scale
+// pipeline go through the lens model (spherical and cylindrical projections).
 template <class Mat>
 std::unique_ptr<Compositor> stitch_calib(const std::vector<Mat> &full_imgs, int projection, bool enable_local, Calibration &cal,
                                          double hfov_deg = 90.0, double work_megapix = 0.6, double seam_megapix = 0.01, double compose_megapix = 1.4,
                                          float blend_strength = 5.f, int out_w = 0, int out_h = 0, int frames_in_flight = 1,
-                                         int num_bands_override = -1, ms_stream s = nullptr, int update_mask_margin = 0)
+                                         int num_bands_override = -1, ms_stream s = nullptr, int update_mask_margin = 0, const ms_lens *lenses = nullptr)
 {
     const int n = (int)full_imgs.size();
     if (n < 1) throw Error(MS_ERR_INVALID, "stitch_calib: no images");
@@ -257,7 +262,8 @@ std::unique_ptr<Compositor> stitch_calib(const std::vector<Mat> &full_imgs, int 
     const ms_rig &rig = cal.rig;
     std::vector<ms_rect> rois(n);
     for (int i = 0; i < n; ++i)            // warper->warpRoi(sz, K, R) at compose scale :163-181
-        check(ms_warp_roi(projection, rig.K_compose[i], rig.R[i], rig.compose_warp_scale, rig.compose_width, rig.compose_height, &rois[i]));
+        check(lenses ? ms_warp_roi_lens(projection, rig.K_compose[i], rig.R[i], &lenses[i], rig.compose_warp_scale, rig.compose_width, rig.compose_height, &rois[i], s)
+                     : ms_warp_roi(projection, rig.K_compose[i], rig.R[i], rig.compose_warp_scale, rig.compose_width, rig.compose_height, &rois[i]));
     check(ms_result_roi(n, rois.data(), &cal.pano_roi));
     check(ms_num_bands_rule(cal.pano_roi.width, cal.pano_roi.height, blend_strength, &cal.blend_width, &cal.num_bands));       // :183-194
     if (num_bands_override >= 0) cal.num_bands = num_bands_override;
@@ -269,6 +275,7 @@ std::unique_ptr<Compositor> stitch_calib(const std::vector<Mat> &full_imgs, int 
     std::unique_ptr<Compositor> comp(new Compositor(n, rig.compose_width, rig.compose_height, projection, rig.compose_warp_scale, cal.num_bands,
                                                     enable_local, out_w, out_h, frames_in_flight, enable_local ? update_mask_margin : 0));
     for (int i = 0; i < n; ++i) comp->setCamera(i, rig.K_compose[i], rig.R[i]);
+    if (lenses) for (int i = 0; i < n; ++i) comp->setLens(i, &lenses[i]);
     comp->buildMaps(s);                                                                                          // :196, :221
     ms_seam_params sp{rig.seam_scale, rig.seam_warp_scale, enable_local ? 1 : 0, 1};
     cal.gains.assign(n, 1.0);
