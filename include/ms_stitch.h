@@ -780,6 +780,76 @@ MS_API int ms_feature_mask(const ms_image *warped_view, int a_x0, int a_width, i
 MS_API int ms_find_homography_ransac(const float *src_xy, const float *dst_xy, int n, double reproj_threshold, int max_iters, double confidence,
                                      double *H, uint8_t *inlier_mask, int *n_inliers, ms_stream stream);
 
+/* ---- Rig rotation refinement: ray bundle adjustment from feature matches ---------------------------------------------------------------------
+ * detail::BundleAdjusterRay (OCV/stitching/src/motion_estimators.cpp:514-700) with the focals held: the stage between the feature front end above and
+ * ms_set_camera / ms_build_maps that the reference app leaves out because it hard-codes the ring of ms_calibrate_cameras.  A warped pixel (u, v) of view i shows
+ * the source pixel whose camera ray is R_i^-1 d(u, v), d the warper's backward direction -- on the analytic route and on the lens route alike -- so matches in
+ * warped-view pixels carry the camera rays and the refinement needs neither K nor an inverse of the distortion.
+ * The arithmetic contract, all of it in double:
+ *   A match k on the view pair (i, j) holds two unit camera rays of one scene point, a_k seen by view i and b_k by view j.  The unknowns are the rotations R_v
+ *   (camera to rig, the R of ms_set_camera) of every view but the anchor, whose rotation is held (the gauge).  Pairs are taken as i < j (a and b swapped where a
+ *   match lists (j, i)); a pair with fewer than min_pair_matches matches is ignored and counted; after that every view must be connected to the anchor.
+ *   Residual (BundleAdjusterRay::calcError, motion_estimators.cpp:556-627; with the focals held its sqrt(f1 f2) factor drops out): with p = R_i a, q = R_j b
+ *   (row r: R[3r] a0 + R[3r+1] a1 + R[3r+2] a2, summed left to right), r = p - q, s = sqrt(r0 r0 + r1 r1 + r2 r2).  Huber threshold h in radians: w = 1 and
+ *   rho = s^2 when h = 0 or s <= h, otherwise w = h / s and rho = (2 h) s - h h.  cost = sum rho.
+ *   Linearisation about the update R_v <- Exp(delta_v) R_v (Exp = Rodrigues): J_i = -[p]x, J_j = +[q]x,
+ *     g_i = sum w J_i^T r = sum w (p x r),            g_j = sum w J_j^T r = sum -(w (q x r)),
+ *     H_ii = sum w J_i^T J_i = sum w [p]x^T [p]x       (diagonal w (p1 p1 + p2 p2), ..; off-diagonal -(w (p0 p1)), ..), H_jj likewise with q,
+ *     H_ij = sum w J_i^T J_j = sum w (q p^T - (p.q) I) (row r, column c: w (q_r p_c); diagonal -(w (p1 q1 + p2 q2)), ..), H_ji = H_ij^T.
+ *   Every product and sum of a term is one IEEE operation in the order written (no fused multiply-add): implementations differ by the order of the sums only.
+ *   Levenberg-Marquardt: lambda = 1e-3; solve (H + lambda diag H) delta = -g over the non-anchor views (at most 45 unknowns) by Cholesky -- a pivot that is not
+ *   positive counts as a rejected step; form the trial rotations and accept iff cost_trial <= cost.  Accept: lambda <- max(lambda / 10, 1e-12), stop as
+ *   CONVERGED when max |delta| < step_tol.  Reject: lambda <- 10 lambda, stop as STALLED when lambda > 1e12.  Every judged trial (and every refused pivot) is one
+ *   iteration; stop as ITERATION_LIMIT at max_iters.  All three return MS_OK with the last ACCEPTED rotations: cost_final <= cost_initial always. */
+enum { MS_RIG_CONVERGED = 0, MS_RIG_STALLED = 1, MS_RIG_ITERATION_LIMIT = 2 };
+typedef struct ms_rig_match {
+    int view_a, view_b;
+    double a[3], b[3];             /* unit camera rays of one scene point: a in view_a's camera, b in view_b's */
+} ms_rig_match;
+typedef struct ms_rig_refine_params {
+    unsigned struct_size;          /* as ms_config: mismatch = MS_ERR_INVALID */
+    int anchor_view;               /* 0: the view whose rotation is held */
+    double huber_rad;              /* 0 = plain least squares; otherwise the Huber threshold on |r| in radians */
+    int max_iters;                 /* 50; [1, 1000] */
+    double step_tol;               /* 1e-10 */
+    int min_pair_matches;          /* 4: pairs with fewer matches are ignored */
+} ms_rig_refine_params;
+typedef struct ms_rig_refine_info {
+    int iterations, stop_reason;   /* MS_RIG_* */
+    double cost_initial, cost_final;
+    int matches_used, pairs_used, pairs_ignored;
+    int outliers;                  /* matches with s > huber_rad at the returned rotations (0 without Huber) */
+    double max_rotation_rad;       /* the largest angle between a view's input and output rotation */
+} ms_rig_refine_info;
+/* RotationWarper::warpBackward's direction (Plane / Spherical / CylindricalProjector::mapBackward, stitching/include/opencv2/stitching/detail/warpers_inl.hpp:229-307)
+ * as a camera ray.  Host only, needs no device.  uv: n absolute warper coordinates (ROI corner + view pixel); rays: n unit camera rays R^T d(u, v) / |R^T d(u, v)| with,
+ * in double from u' = (double)u / (double)scale, v' likewise: spherical d = (sin(pi - v') sin u', cos(pi - v'), sin(pi - v') cos u'), cylindrical d = (sin u', v', cos u'),
+ * plane d = (u' - t0, v' - t1, 1 - t2) (t: 3 floats, NULL = zero; ignored by the other two).  R: 9 doubles row-major. */
+MS_API int ms_warper_rays(int projection, float scale, const float *t, const double *R, int n, const float *uv, double *rays);
+/* BundleAdjusterRay's defaults in this contract's terms (motion_estimators.cpp:514-555): anchor 0, no Huber, 50 iterations, step_tol 1e-10, 4 matches a pair */
+MS_API int ms_rig_refine_default_params(ms_rig_refine_params *prm);
+/* BundleAdjusterRay::calcError + calcJacobian (motion_estimators.cpp:556-700) as the normal equations, per op: cost, H (3 n_views x 3 n_views row-major, the anchor
+ * included -- no view is held here) and g (3 n_views) at the rotations R (n_views x 9 doubles), every pair used whatever its size.  All pointers HOST.  Synchronises. */
+MS_API int ms_rig_accumulate(int n_views, const double *R, const ms_rig_match *matches, int n, double huber_rad, double *cost, double *H, double *g, ms_stream stream);
+/* BundleAdjusterBase::estimate (motion_estimators.cpp:223-324: CvLevMarq over calcError / calcJacobian) for the contract above, the whole loop on the device: matches
+ * are grouped by pair on the host (stably: input order is kept inside a pair) and uploaded once, max_iters + 1 rounds of two kernels are enqueued with no host step
+ * in between -- they return at once after the stop flag is set --, the result comes back in one copy and `stream` is synchronised once, at the end.  No
+ * floating-point atomics: two calls on the same inputs return the same bits.  R_in is used as given (n_views x 9 doubles, HOST); R_out likewise, the anchor's
+ * bit-equal to its R_in; info may be NULL.
+ * MS_ERR_INVALID, before the device is touched: a null pointer; n_views outside [2, MS_MAX_VIEWS]; a view index out of range or view_a == view_b; a ray (or
+ * rotation) that is not finite or whose length is off 1 by more than 1e-6; n outside [1, 2^20]; a bad anchor; a struct_size mismatch; max_iters outside [1, 1000],
+ * a negative huber_rad or step_tol, min_pair_matches < 1; a view not connected to the anchor (the message names the first). */
+MS_API int ms_refine_rig_rotations(int n_views, const double *R_in, const ms_rig_match *matches, int n, const ms_rig_refine_params *prm, double *R_out,
+                                   ms_rig_refine_info *info, ms_stream stream);
+/* The context form (Stitcher::estimateCameraParams' bundle adjustment, stitching/src/stitcher.cpp:573-574, on the matches featurefinder::matchFeatures selects):
+ * the per-view lists in ms_create_mesh's layout -- x1, y1 in the list's own view, x2, y2 in view dst, pixels of the projection-warped views before any CPW mesh --
+ * are turned into rays with the context's projection, warp_scale, view ROI corners and CURRENT cameras by ms_warper_rays' arithmetic (corner + pixel added in
+ * double), then refined as above from the current rotations.  R_out: num_views x 9 floats for ms_set_camera; nothing is applied -- the caller runs the usual
+ * chain (ms_set_camera, ms_build_maps, masks, ms_init_blender).  Lens contexts work unchanged.  MS_ERR_STATE before ms_build_maps; MS_ERR_UNSUPPORTED for
+ * MS_MAPS_CUSTOM contexts (no cameras); MS_ERR_INVALID as above and for a list that names its own view or a view out of range. */
+MS_API int ms_refine_rig(ms_ctx *ctx, const ms_mesh_match *matches, const int *match_count, const ms_rig_refine_params *prm, float *R_out,
+                         ms_rig_refine_info *info, ms_stream stream);
+
 /* device-resident static tables, for parity tests: x_maps[i]/y_maps[i] (32FC1), masks (8UC1),
  * weight pyramid level (32FC1). Borrowed pointers owned by ctx. */
 MS_API int ms_get_maps(const ms_ctx *ctx, int view, ms_image *xmap, ms_image *ymap);

@@ -1,5 +1,5 @@
 // ctx.hpp -- the context type behind the C ABI's opaque ms_ctx, for the units that define its entry points: compositor.hip (life cycle, tables, the per-frame
-// path) and calib.hip (exposure tracking).  Internal; nothing else includes it.
+// path), calib.hip (exposure tracking) and rig.hip (ms_refine_rig).  Internal; nothing else includes it.
 #pragma once
 #include <atomic>
 #include <memory>

@@ -20,6 +20,12 @@
 //                   [--reference-calib [--work-megapix 0.6] [--seam-megapix 0.01] [--compose-megapix 1.4]]
 //                   [--drop-view V:F0:F1] [--dump-frames frames.bin] [--track-gains K] [--exposure-ramp V:F] [--dump-i420 planes.bin]
 //                   [--lens-brown k1,k2,p1,p2,k3 | --lens-fisheye k1,k2,k3,k4[,max_theta]]
+//                   [--rig-error V:YAW:PITCH:ROLL] [--refine-rig]
+// --rig-error (degrees) renders camera V's scene frames (synth_scene_frame: --solve-mesh's frames and --refine-rig's) through a rig that is really rotated by
+// R_y(yaw) R_x(pitch) R_z(roll) in the camera's own frame, while calibration assumes the ideal ring.  --refine-rig runs, after the first calibration, the device
+// front end between neighbouring views on the projection-warped scene frames (as --solve-mesh does every round), then ms_refine_rig with a Huber threshold of two
+// warped pixels; it applies the rotations (ms_set_camera), calibrates again and prints one line "rig_refine: {...}" with the refinement's info and every view's
+// angle to the rendered truth before and after, in the anchor's gauge.
 // --lens-brown / --lens-fisheye give EVERY camera that lens (ms_set_lens; coefficients as OpenCV's distCoeffs / fisheye D, max_theta in degrees): maps, ROIs and,
 // with --reference-calib, the seam-scale calibration come from the library's lens model, and the JSON line's "map_source" is 2 (MS_MAPS_LENS) instead of 0.
 // --nv12-direct keeps BGR copies of the cameras' frames off the device in every mode: the warp samples the planes (ms_stitch_nv12), --i420 makes the encoder's
@@ -104,6 +110,8 @@ struct Options {
     std::string dump_i420;                      // --dump-i420 FILE
     bool fused_resize = false;                  // --fused-resize: with --nv12-direct and a compose-scale resize, planes -> small_imgs in one pass
     ms_lens lens{sizeof(ms_lens), MS_LENS_NONE, {0, 0, 0, 0, 0, 0, 0, 0}, 0.0};      // --lens-brown / --lens-fisheye: every camera's lens
+    int rig_err_view = -1; double rig_err_deg[3] = {0, 0, 0};    // --rig-error V:YAW:PITCH:ROLL
+    bool refine_rig = false;                    // --refine-rig
 };
 constexpr int CAMERA_TIMEOUT_MS = 100;               // --drop-view: how long the main loop waits for a camera's frame before it stitches without it
 
@@ -127,7 +135,8 @@ static void synth_frame(unsigned char *dst, int w, int h, int view)
 // structure for the descriptors) seen through the pinhole camera `view` of the rig, so that neighbouring warped views show the SAME content where they
 // overlap and the device front-end finds real correspondences.  `shift_px` moves this camera's view of the scene by that many panorama pixels
 // (a stand-in for parallax): it is what the mesh optimiser then has to absorb.
-static void synth_scene_frame(unsigned char *dst, int w, int h, int view, int n_views, double hfov_deg, double pano_scale, double shift_px)
+// `E` (3 x 3 row-major, may be null): the camera's real orientation inside its nominal one -- the ray of a pixel is E * (dx, dy, 1) in the ring camera's frame (--rig-error).
+static void synth_scene_frame(unsigned char *dst, int w, int h, int view, int n_views, double hfov_deg, double pano_scale, double shift_px, const double *E = nullptr)
 {
     const float rot = (float)(2.0 * M_PI * (double)(float)view / n_views);
     const double c = std::cos((double)rot), s = std::sin((double)rot);
@@ -135,7 +144,11 @@ static void synth_scene_frame(unsigned char *dst, int w, int h, int view, int n_
     const double cell = 32.0 / pano_scale;                          // blocks of 32 panorama pixels
     for (int y = 0; y < h; ++y)
         for (int x = 0; x < w; ++x) {
-            const double dx = (x - w / 2.0) / f, dy = (y - h / 2.0) / f, dz = 1.0;
+            double dx = (x - w / 2.0) / f, dy = (y - h / 2.0) / f, dz = 1.0;
+            if (E) {
+                const double ex = E[0] * dx + E[1] * dy + E[2], ey = E[3] * dx + E[4] * dy + E[5], ez = E[6] * dx + E[7] * dy + E[8];
+                dx = ex; dy = ey; dz = ez;
+            }
             const double X = c * dx + s * dz, Y = dy, Z = -s * dx + c * dz;           // world = R_y(rot) * camera
             const double u = std::atan2(X, Z) + shift_px / pano_scale, v = M_PI - std::acos(Y / std::sqrt(X * X + Y * Y + Z * Z));
             const long long cu = (long long)std::floor(u / cell), cv = (long long)std::floor(v / cell);
@@ -171,6 +184,29 @@ static void synth_nv12(unsigned char *dst, int w, int h, int view)
 }
 
 // a smooth synthetic CPW mesh (the optimiser that produces real ones is out of scope): identity + amp sin(2 pi u + phase) sin(pi v)
+// 3 x 3 row-major helpers of --rig-error / --refine-rig
+static void mat3_mul(const double *A, const double *B, double *C)
+{
+    double T[9];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) T[r * 3 + c] = A[r * 3] * B[c] + A[r * 3 + 1] * B[3 + c] + A[r * 3 + 2] * B[6 + c];
+    memcpy(C, T, sizeof(T));
+}
+static void mat3_t(const double *A, double *C) { double T[9]; for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) T[r * 3 + c] = A[c * 3 + r]; memcpy(C, T, sizeof(T)); }
+static void rot_axis(int axis, double t, double *R)       // 0: R_x, 1: R_y (the ring's convention), 2: R_z
+{
+    const double c = std::cos(t), s = std::sin(t);
+    const double Rx[9] = {1, 0, 0, 0, c, -s, 0, s, c}, Ry[9] = {c, 0, s, 0, 1, 0, -s, 0, c}, Rz[9] = {c, -s, 0, s, c, 0, 0, 0, 1};
+    memcpy(R, axis == 0 ? Rx : (axis == 1 ? Ry : Rz), sizeof(Rx));
+}
+static double mat3_angle(const double *A, const double *B)      // the angle of A B^T
+{
+    double Bt[9], M[9];
+    mat3_t(B, Bt); mat3_mul(A, Bt, M);
+    const double x = M[7] - M[5], y = M[2] - M[6], z = M[3] - M[1];
+    return std::atan2(0.5 * std::sqrt(x * x + y * y + z * z), 0.5 * (M[0] + M[4] + M[8] - 1.0));
+}
+
 static void make_mesh(int aw, int ah, int N, int M, double phase, double amp, std::vector<float> &mx, std::vector<float> &my)
 {
     mx.resize((size_t)N * M); my.resize((size_t)N * M);
@@ -230,6 +266,10 @@ int main(int argc, char **argv)
             if (sscanf(next(), "%lf,%lf,%lf,%lf,%lf", &c[0], &c[1], &c[2], &c[3], &o.lens.max_theta_deg) < 4) { fprintf(stderr, "--lens-fisheye wants k1,k2,k3,k4[,max_theta]\n"); return 2; }
             o.lens.model = MS_LENS_FISHEYE;
         }
+        else if (k == "--refine-rig") o.refine_rig = true;
+        else if (k == "--rig-error") {
+            if (sscanf(next(), "%d:%lf:%lf:%lf", &o.rig_err_view, &o.rig_err_deg[0], &o.rig_err_deg[1], &o.rig_err_deg[2]) != 4 || o.rig_err_view < 0) { fprintf(stderr, "--rig-error wants V:YAW:PITCH:ROLL\n"); return 2; }
+        }
         else if (k == "--exposure-ramp") {
             if (sscanf(next(), "%d:%lf", &o.ramp_view, &o.ramp_factor) != 2 || o.ramp_view < 0 || o.ramp_factor < 0) { fprintf(stderr, "--exposure-ramp wants V:F\n"); return 2; }
         }
@@ -237,6 +277,8 @@ int main(int argc, char **argv)
     }
     if (o.drop_view >= o.views) { fprintf(stderr, "--drop-view: view %d of %d\n", o.drop_view, o.views); return 2; }
     if (o.ramp_view >= o.views) { fprintf(stderr, "--exposure-ramp: view %d of %d\n", o.ramp_view, o.views); return 2; }
+    if (o.rig_err_view >= o.views) { fprintf(stderr, "--rig-error: view %d of %d\n", o.rig_err_view, o.views); return 2; }
+    if (o.refine_rig && (o.reference_calib || o.nv12)) { fprintf(stderr, "stitch_app: --refine-rig is wired up for the BASELINE rig with BGR cameras (no --reference-calib, no --nv12)\n"); return 2; }
     if (o.track_gains < 0) { fprintf(stderr, "--track-gains wants K >= 0\n"); return 2; }
     if (!o.dump_i420.empty() && !o.i420) { fprintf(stderr, "--dump-i420 needs --i420\n"); return 2; }
     if (o.fused_resize && !o.nv12_direct) { fprintf(stderr, "--fused-resize needs --nv12-direct\n"); return 2; }
@@ -299,6 +341,78 @@ int main(int argc, char **argv)
         hipStream_t stitch_stream, recal_stream;
         HIPCHECK(hipStreamCreateWithFlags(&stitch_stream, hipStreamNonBlocking));
         HIPCHECK(hipStreamCreateWithFlags(&recal_stream, hipStreamNonBlocking));
+        // the scene frames' geometry: camera i really sits at R_y(shift_i / scale) R_ring_i E_i (the shift is --solve-mesh's stand-in for parallax, E --rig-error's rotation)
+        std::vector<double> rig_E((size_t)9 * o.views, 0.0);
+        for (int i = 0; i < o.views; ++i) {
+            double *E = &rig_E[9 * (size_t)i];
+            E[0] = E[4] = E[8] = 1.0;
+            if (i == o.rig_err_view) {
+                double Ry[9], Rx[9], Rz[9];
+                rot_axis(1, o.rig_err_deg[0] * M_PI / 180.0, Ry); rot_axis(0, o.rig_err_deg[1] * M_PI / 180.0, Rx); rot_axis(2, o.rig_err_deg[2] * M_PI / 180.0, Rz);
+                mat3_mul(Rx, Rz, E); mat3_mul(Ry, E, E);
+            }
+        }
+        auto scene_shift = [&](int i) { return o.solve_mesh ? (i % 2 ? 1.0 : -1.0) * std::max(1.5, warp_scale / 200.0) : 0.0; };   // odd / even cameras see the scene +-3 px apart
+        if (o.refine_rig) {
+            // Stitcher::estimateCameraParams' bundle adjustment (stitching/src/stitcher.cpp:573-574) in the place the reference app leaves empty: warp the scene frames
+            // with the ring's maps, createMesh's front end between neighbours (meshwarper.cpp:82-119), ms_refine_rig, and the calibration chain again
+            namespace ff = msshim::featurefinder;
+            std::vector<DevMat> full(o.views), images(o.views);
+            std::vector<unsigned char> host((size_t)o.w * o.h * 3);
+            for (int i = 0; i < o.views; ++i) {
+                const ms_view_geom g = comp.viewGeom(i);
+                full[i].create(o.h, o.w, MS_8UC3, 3);
+                images[i].create(g.roi.height, g.roi.width, MS_8UC3, 3);
+                synth_scene_frame(host.data(), o.w, o.h, i, o.views, o.hfov, warp_scale, scene_shift(i), i == o.rig_err_view ? &rig_E[9 * (size_t)i] : nullptr);
+                HIPCHECK(hipMemcpy2D(full[i].data, full[i].step, host.data(), (size_t)o.w * 3, (size_t)o.w * 3, o.h, hipMemcpyHostToDevice));
+                ms_image xm, ym;
+                msshim::check(ms_get_maps(comp.raw(), i, &xm, &ym));
+                ms_image src = msshim::wrap(full[i]), dst = msshim::wrap(images[i]);
+                msshim::check(ms_remap(&src, &xm, &ym, &dst, MS_INTER_LINEAR_FIXPT, MS_BORDER_CONSTANT, (ms_stream)recal_stream));
+            }
+            std::vector<DevMat> fmasks;
+            ff::featureMasks(images, fmasks, std::min(400, std::max(16, o.out_w / 10)), (ms_stream)recal_stream);
+            std::vector<ff::ImageFeatures<DevMat>> feats;
+            ff::findFeatures(images, fmasks, feats, (ms_stream)recal_stream);
+            std::vector<ff::MatchesInfo> pairwise(o.views);
+            ff::matchFeatures(feats, pairwise, (ms_stream)recal_stream);
+            ms_rig_refine_params prm;
+            msshim::check(ms_rig_refine_default_params(&prm));
+            prm.huber_rad = 2.0 / warp_scale;
+            std::vector<float> R_new;
+            const ms_rig_refine_info info = msshim::refineRig(comp, msshim::inlierLists(feats, pairwise), R_new, &prm, (ms_stream)recal_stream);
+            for (auto *v : {&full, &images, &fmasks}) for (auto &m : *v) if (m.data) HIPCHECK(hipFree(m.data));
+            for (auto &f : feats) if (f.descriptors.data) HIPCHECK(hipFree(f.descriptors.data));
+            // every view's angle to the rendered truth in the gauge of the held anchor: R_ring_0 R_true_0^T R_true_i
+            std::vector<double> truth((size_t)9 * o.views), ring((size_t)9 * o.views);
+            for (int i = 0; i < o.views; ++i) {
+                double Rs[9];
+                for (int k = 0; k < 9; ++k) ring[9 * (size_t)i + k] = (double)cal.rig.R[i][k];
+                rot_axis(1, scene_shift(i) / warp_scale, Rs);
+                mat3_mul(&ring[9 * (size_t)i], &rig_E[9 * (size_t)i], &truth[9 * (size_t)i]);
+                mat3_mul(Rs, &truth[9 * (size_t)i], &truth[9 * (size_t)i]);
+            }
+            double G[9];
+            mat3_t(&truth[0], G); mat3_mul(&ring[0], G, G);
+            printf("rig_refine: {\"iterations\": %d, \"stop_reason\": %d, \"cost_initial\": %.9g, \"cost_final\": %.9g, \"matches_used\": %d, \"pairs_used\": %d, \"pairs_ignored\": %d, "
+                   "\"outliers\": %d, \"max_rotation_rad\": %.9g, \"warp_scale\": %.9g", info.iterations, info.stop_reason, info.cost_initial, info.cost_final, info.matches_used,
+                   info.pairs_used, info.pairs_ignored, info.outliers, info.max_rotation_rad, (double)warp_scale);
+            for (int pass = 0; pass < 2; ++pass) {
+                printf(", \"%s\": [", pass ? "angle_to_truth_rad" : "angle_before_rad");
+                for (int i = 0; i < o.views; ++i) {
+                    double want[9], got[9];
+                    mat3_mul(G, &truth[9 * (size_t)i], want);
+                    for (int k = 0; k < 9; ++k) got[k] = pass ? (double)R_new[9 * (size_t)i + k] : ring[9 * (size_t)i + k];
+                    printf("%s%.6g", i ? ", " : "", mat3_angle(got, want));
+                }
+                printf("]");
+            }
+            printf("}\n");
+            for (int i = 0; i < o.views; ++i) comp.setCamera(i, cal.rig.K_compose[i], &R_new[9 * (size_t)i]);
+            comp.buildMaps();
+            comp.buildMasks(true);
+            comp.init_gpu();
+        }
         if (o.cpw)
             for (int i = 0; i < o.views; ++i) {
                 const ms_view_geom g = comp.viewGeom(i);
@@ -320,7 +434,7 @@ int main(int argc, char **argv)
             f.w = o.w; f.h = o.h;
             f.p = host_slab + (size_t)i * host_frame_bytes;
             if (o.nv12) synth_nv12(f.p, o.w, o.h, i);          // (h * 3/2 rows of w bytes)
-            else if (o.solve_mesh) synth_scene_frame(f.p, o.w, o.h, i, o.views, o.hfov, warp_scale, (i % 2 ? 1.0 : -1.0) * std::max(1.5, warp_scale / 200.0));   // odd / even cameras see the scene +-3 px apart
+            else if (o.solve_mesh) synth_scene_frame(f.p, o.w, o.h, i, o.views, o.hfov, warp_scale, scene_shift(i), i == o.rig_err_view ? &rig_E[9 * (size_t)i] : nullptr);
             else synth_frame(f.p, o.w, o.h, i);
             f.seq = 0;
         }

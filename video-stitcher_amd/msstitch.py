@@ -110,6 +110,23 @@ class MeshInfo(C.Structure):
     _fields_ = [("rows", C.c_int), ("cols", C.c_int), ("nnz", C.c_int), ("iterations", C.c_int), ("error", C.c_double)]
 
 
+class RigMatch(C.Structure):
+    _fields_ = [("view_a", C.c_int), ("view_b", C.c_int), ("a", C.c_double * 3), ("b", C.c_double * 3)]
+
+
+class RigRefineParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("anchor_view", C.c_int), ("huber_rad", C.c_double), ("max_iters", C.c_int), ("step_tol", C.c_double),
+                ("min_pair_matches", C.c_int)]
+
+
+class RigRefineInfo(C.Structure):
+    _fields_ = [("iterations", C.c_int), ("stop_reason", C.c_int), ("cost_initial", C.c_double), ("cost_final", C.c_double), ("matches_used", C.c_int),
+                ("pairs_used", C.c_int), ("pairs_ignored", C.c_int), ("outliers", C.c_int), ("max_rotation_rad", C.c_double)]
+
+
+RIG_CONVERGED, RIG_STALLED, RIG_ITERATION_LIMIT = 0, 1, 2
+
+
 class GainTrackParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint), ("stride", C.c_int), ("smoothing", C.c_double)]
 
@@ -164,6 +181,7 @@ EXPORTS = [
     "ms_voronoi_seams", "ms_estimate_gains",
     "ms_set_maps", "ms_get_map_source",
     "ms_lens_check", "ms_lens_project", "ms_set_lens", "ms_get_lens", "ms_build_warp_maps_lens", "ms_warp_roi_lens",
+    "ms_warper_rays", "ms_rig_refine_default_params", "ms_rig_accumulate", "ms_refine_rig_rotations", "ms_refine_rig",
 ]
 
 _lib = None
@@ -484,6 +502,68 @@ def warp_roi_lens(projection, K, R, lens, scale, src_w, src_h):
     r = Rect()
     _chk(load().ms_warp_roi_lens(projection, kp, rp, _lens_ptr(lens), C.c_float(scale), src_w, src_h, C.byref(r), _stream()))
     return r.tuple()
+
+
+def warper_rays(projection, scale, R, uv, t=None):
+    """ms_warper_rays (host only): absolute warper coordinates uv (n, 2) -> unit camera rays (n, 3) float64 of a camera with rotation R (3 x 3 float64)"""
+    import numpy as np
+    uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+    Ra = np.ascontiguousarray(R, np.float64).reshape(9)
+    out = np.empty((len(uv), 3), np.float64)
+    tp = None
+    if t is not None:
+        ta, tp = _fa(t, 3)
+    dp = C.POINTER(C.c_double)
+    _chk(load().ms_warper_rays(projection, C.c_float(scale), tp, Ra.ctypes.data_as(dp), len(uv), uv.ctypes.data_as(C.POINTER(C.c_float)), out.ctypes.data_as(dp)))
+    return out
+
+
+def rig_refine_default_params(**kw):
+    """ms_rig_refine_default_params; keyword arguments override fields"""
+    p = RigRefineParams()
+    _chk(load().ms_rig_refine_default_params(C.byref(p)))
+    for k, v in kw.items():
+        assert hasattr(p, k), k
+        setattr(p, k, v)
+    return p
+
+
+def rig_matches(matches):
+    """[(view_a, view_b, a (3,), b (3,)), ...] -> a RigMatch array"""
+    arr = (RigMatch * max(1, len(matches)))()
+    for k, (va, vb, a, b) in enumerate(matches):
+        arr[k] = RigMatch(int(va), int(vb), (C.c_double * 3)(*[float(x) for x in a]), (C.c_double * 3)(*[float(x) for x in b]))
+    return arr
+
+
+def _rig_info(info):
+    return {k: getattr(info, k) for k, _ in RigRefineInfo._fields_}
+
+
+def rig_accumulate(R, matches, huber_rad=0.0):
+    """ms_rig_accumulate: R (n, 3, 3) float64, matches as rig_matches takes them -> (cost, H (3n, 3n), g (3n,)) at R"""
+    import numpy as np
+    Ra = np.ascontiguousarray(R, np.float64)
+    n = len(Ra)
+    H = np.empty((3 * n, 3 * n), np.float64); g = np.empty(3 * n, np.float64)
+    cost = C.c_double(0)
+    dp = C.POINTER(C.c_double)
+    _chk(load().ms_rig_accumulate(n, Ra.ctypes.data_as(dp), rig_matches(matches), len(matches), C.c_double(huber_rad), C.byref(cost), H.ctypes.data_as(dp),
+                                  g.ctypes.data_as(dp), _stream()))
+    return cost.value, H, g
+
+
+def refine_rig_rotations(R, matches, params=None):
+    """ms_refine_rig_rotations: R (n, 3, 3) float64, matches as rig_matches takes them -> (refined R (n, 3, 3) float64, info dict)"""
+    import numpy as np
+    Ra = np.ascontiguousarray(R, np.float64)
+    n = len(Ra)
+    out = np.empty((n, 3, 3), np.float64)
+    prm = params if params is not None else rig_refine_default_params()
+    info = RigRefineInfo()
+    dp = C.POINTER(C.c_double)
+    _chk(load().ms_refine_rig_rotations(n, Ra.ctypes.data_as(dp), rig_matches(matches), len(matches), C.byref(prm), out.ctypes.data_as(dp), C.byref(info), _stream()))
+    return out, _rig_info(info)
 
 
 def nv12_to_bgr(src, dst=None):
@@ -813,6 +893,17 @@ class Compositor:
 
     def set_gain(self, view, gain):
         _chk(load().ms_set_gain(self._ctx, view, C.c_double(gain)))
+
+    def refine_rig(self, matches, params=None):
+        """ms_refine_rig: matches[v] = list of (x1, y1, x2, y2, dst) in projection-warped view pixels (create_mesh's layout) -> (R (n, 3, 3) float32 for
+        set_camera, info dict).  Nothing is applied to the context."""
+        import numpy as np
+        marr, mcnt = _match_array(matches)
+        prm = params if params is not None else rig_refine_default_params()
+        out = np.empty((self.n, 3, 3), np.float32)
+        info = RigRefineInfo()
+        _chk(load().ms_refine_rig(self._ctx, marr, mcnt, C.byref(prm), out.ctypes.data_as(C.POINTER(C.c_float)), C.byref(info), _stream()))
+        return out, _rig_info(info)
 
     def build_maps(self):
         _chk(load().ms_build_maps(self._ctx, _stream()))

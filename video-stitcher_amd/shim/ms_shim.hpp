@@ -540,4 +540,35 @@ private:
     std::vector<char> have_old_;                             // !old_features.at(idx).empty()
 };
 
+// ---- rig rotations from the same matches: detail::BundleAdjusterRay (stitching/src/motion_estimators.cpp:514-700) with the focals held ---------
+// Every RANSAC inlier of every pair, as the per-view lists ms_refine_rig takes (ms_create_mesh's layout: x1, y1 in view src, x2, y2 in view dst).
+template <class Features, class Matches>
+std::vector<std::vector<ms_mesh_match>> inlierLists(const std::vector<Features> &features, const std::vector<Matches> &pairwise_matches)
+{
+    std::vector<std::vector<ms_mesh_match>> lists(features.size());
+    for (const Matches &pw : pairwise_matches)
+        for (size_t i = 0; i < pw.inliers_mask.size(); ++i) {
+            if (!pw.inliers_mask[i]) continue;
+            const auto &p1 = features[pw.src_img_idx].keypoints[pw.matches[i].queryIdx].pt;
+            const auto &p2 = features[pw.dst_img_idx].keypoints[pw.matches[i].trainIdx].pt;
+            lists[pw.src_img_idx].push_back(ms_mesh_match{p1.x, p1.y, p2.x, p2.y, pw.dst_img_idx});
+        }
+    return lists;
+}
+// (*bundle_adjuster_)(features_, pairwise_matches_, cameras_) (stitching/src/stitcher.cpp:573-574) for the rotations of a calibrated compositor: R_out receives
+// num_views x 9 floats for setCamera; nothing is applied -- setCamera, buildMaps, the masks and init_gpu follow as in the first calibration.  prm == nullptr: the defaults
+inline ms_rig_refine_info refineRig(Compositor &comp, const std::vector<std::vector<ms_mesh_match>> &lists, std::vector<float> &R_out, const ms_rig_refine_params *prm = nullptr,
+                                    ms_stream s = nullptr)
+{
+    ms_rig_refine_params dflt;
+    check(ms_rig_refine_default_params(&dflt));
+    std::vector<ms_mesh_match> flat;
+    std::vector<int> count;
+    for (const auto &l : lists) { flat.insert(flat.end(), l.begin(), l.end()); count.push_back((int)l.size()); }
+    R_out.assign(9 * lists.size(), 0.f);
+    ms_rig_refine_info info{};
+    check(ms_refine_rig(comp.raw(), flat.data(), count.data(), prm ? prm : &dflt, R_out.data(), &info, s));
+    return info;
+}
+
 }  // namespace msshim
