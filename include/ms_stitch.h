@@ -179,6 +179,28 @@ MS_API int ms_voronoi_seams(int n, const ms_rect *rois, ms_image *masks, ms_stre
  * singular system (not reachable while every N[i][i] >= 1). */
 MS_API int ms_estimate_gains(int n, const ms_rect *rois, const ms_image *images, const ms_image *masks,
                              double *gains_host, int *N_host, double *I_host, ms_stream stream);
+/* Content-aware seams: seam_finder->find(images_warped, corners, masks_warped) (APP/calibration.cpp:134-135) with a minimum-cost path through every overlap instead
+ * of the VoronoiSeamFinder, which never looks at a pixel (the reference's own comment, calibration.cpp:207: "Better solution might be needed").  In the spirit of
+ * detail::DpSeamFinder (OCV/stitching/src/seam_finders.cpp) but NOT a restatement of it: the contract is the one below, all of it integer arithmetic, so results
+ * are bit-exact and two calls return the same bytes (tests/dp_seam_ref.py is its numpy statement).
+ * Arguments as for ms_estimate_gains / ms_voronoi_seams: images n DEVICE 8UC3 (step == 3 * width), masks n DEVICE 8UC1 (step == width), each exactly its ROI's
+ * size; rois HOST; a set mask pixel is != 0; masks are edited IN PLACE, pairs i < j with overlapping ROIs in the reference's order (PairwiseSeamFinder::run), so
+ * pair (0, 1)'s result is pair (0, 2)'s input.  SYNCHRONOUS: allocates its scratch and returns after `stream` has drained.
+ * One pair, with the overlap rectangle O of w x h pixels:
+ *   Orientation and sides.  Per view: its set pixels inside O grown by 10 on every side (ms_voronoi_seams' gap) and clipped to the view's ROI, coordinates
+ *     relative to (O.x - 10, O.y - 10); n, Sx, Sy their count and coordinate sums (int64).  dx = Sx_j n_i - Sx_i n_j, dy likewise: the sign of the difference of
+ *     the two centroids.  The seam is VERTICAL (one column per row) if |dx| >= |dy|, else HORIZONTAL (one row per column): the same algorithm on the transpose.
+ *     The first side -- the columns <= the seam's -- belongs to view i if the chosen d >= 0, else to view j.  Pixels decide, not ROI centres: the view that
+ *     straddles +-pi has a full-width ROI.
+ *   Cost.  B = the pixels of O set in both masks.  c = |db| + |dg| + |dr| (0 .. 765) on B, 1024 elsewhere in O.
+ *   DP.  M(0, x) = c(0, x); M(y, x) = c(y, x) + min M(y - 1, x') over x' in {x - 1, x, x + 1} within [0, w), ties preferring x, then x - 1, then x + 1.  The
+ *     seam ends at the argmin of the last row, ties preferring the smallest |2 x - (w - 1)|, then the smaller x, and is traced back from there.  M < 2^23.
+ *   Edit.  Only pixels of B change: on the first side the other view's mask is cleared, beyond the seam the first side's owner's.  Behind a pair no pixel of its
+ *     overlap is set in both masks.
+ * MS_ERR_INVALID, all checked on the host before the device is touched: as for ms_estimate_gains (n outside [1, MS_MAX_VIEWS], a null pointer, an empty ROI, an
+ * image or mask of another type or size than its ROI, rows that are not contiguous), and an overlap with a side above MS_DP_MAX_SIDE, naming the pair. */
+enum { MS_DP_MAX_SIDE = 4096 };
+MS_API int ms_dp_seams(int n, const ms_rect *rois, const ms_image *images, ms_image *masks, ms_stream stream);
 
 /* device::imgproc::buildWarp{Plane,Spherical,Cylindrical}Maps(tl_u, tl_v, map_x, map_y, k_rinv, r_kinv[, t], scale, stream)
  * OCV/stitching/src/warpers_cuda.cpp:51-67 -> cuda/build_warp_maps.cu:155-216.  k_rinv, r_kinv: 9 floats
@@ -388,12 +410,19 @@ MS_API int ms_get_map_source(const ms_ctx *ctx, int *source);
 
 /* Compose-size blend masks (APP/calibration.cpp:224-237).  mode 0: warp(255, NEAREST) only;
  * mode 1: AND with Voronoi seams (VoronoiSeamFinder, seam_finders.cpp:85-160) computed at compose size
- * (the app computes them at seam scale and resizes up: stated simplification). */
+ * (the app computes them at seam scale and resizes up: stated simplification).
+ * The call has no images: mode 1 is Voronoi whatever ms_set_seam_finder says. */
 MS_API int ms_build_masks(ms_ctx *ctx, int mode, ms_stream stream);
+/* Which seam finder ms_calibrate_seam cuts with (seam_finder->find, calibration.cpp:134-135): MS_SEAM_VORONOI, ms_voronoi_seams' (the default: a context that
+ * never calls the setter behaves bit for bit as before), or MS_SEAM_DP, ms_dp_seams' on the warped seam-scale images.  Calibration state like the masks it
+ * shapes: ms_save_tables does not store it, ms_create and ms_load_tables contexts start at Voronoi.  MS_ERR_INVALID: a null pointer, another value. */
+enum { MS_SEAM_VORONOI = 0, MS_SEAM_DP = 1 };
+MS_API int ms_set_seam_finder(ms_ctx *ctx, int finder);
+MS_API int ms_get_seam_finder(const ms_ctx *ctx, int *finder);
 /* The reference's own calibration at seam scale (APP/calibration.cpp:92-135, 224-237): resize the N full frames (DEVICE 8UC3) by
  * seam_scale, warp image (LINEAR/REFLECT) and a 255-mask (NEAREST/CONSTANT) with the per-view seam intrinsics K_seam (HOST, N x 9,
  * = K at work scale times seam_work_aspect, calibration.cpp:110-116) and seam_warp_scale, estimate the exposure gains
- * (GainCompensator::feed, exposure_compensate.cpp:71-145), cut Voronoi seams, optionally dilate, resize the seam masks to the compose
+ * (GainCompensator::feed, exposure_compensate.cpp:71-145), cut Voronoi seams (or ms_dp_seams': ms_set_seam_finder), optionally dilate, resize the seam masks to the compose
  * mask size and AND them with warp(255) at compose scale.  Leaves the masks ready for ms_init_blender; gains_out (HOST, N) may be NULL.
  * The full frames may be larger than the context's source size (compose_scale < 1: the context composites the resized frames, the seam
  * images are still cut from the full ones, calibration.cpp:95); all N must have one size. */

@@ -305,6 +305,29 @@ int ms_estimate_gains(int n, const ms_rect *rois, const ms_image *images, const 
     return estimate_gains_device(n, rois, ip, mp, gains_host, as_stream(stream), N_host, I_host);
 }
 
+// kernels: seam_dp.hip.  The overlap sides are checked here too: a refusal must not need a device
+int ms_dp_seams(int n, const ms_rect *rois, const ms_image *images, ms_image *masks, ms_stream stream)
+{
+    if (int e = check_calib_rois("ms_dp_seams", n, rois)) return e;
+    MS_CHECK(images && masks, "ms_dp_seams: null images / masks");
+    const uint8_t *ip[MS_MAX_VIEWS];
+    uint8_t *mp[MS_MAX_VIEWS];
+    for (int i = 0; i < n; ++i) {
+        if (int e = check_calib_image("ms_dp_seams", "image", i, images[i], rois[i], MS_8UC3, 3)) return e;
+        if (int e = check_calib_image("ms_dp_seams", "mask", i, masks[i], rois[i], MS_8UC1, 1)) return e;
+        ip[i] = (const uint8_t *)images[i].data; mp[i] = (uint8_t *)masks[i].data;
+    }
+    for (int i = 0; i + 1 < n; ++i)
+        for (int j = i + 1; j < n; ++j) {
+            const int w = std::min(rois[i].x + rois[i].width, rois[j].x + rois[j].width) - std::max(rois[i].x, rois[j].x);
+            const int h = std::min(rois[i].y + rois[i].height, rois[j].y + rois[j].height) - std::max(rois[i].y, rois[j].y);
+            MS_CHECK(!(w > 0 && h > 0) || (w <= MS_DP_MAX_SIDE && h <= MS_DP_MAX_SIDE), "ms_dp_seams: the overlap of views %d and %d is %dx%d: a side above MS_DP_MAX_SIDE = %d",
+                     i, j, w, h, MS_DP_MAX_SIDE);
+        }
+    if (int e = require_device()) return e;
+    return dp_seams_device(n, rois, ip, mp, as_stream(stream));
+}
+
 int ms_build_warp_maps(int projection, int tl_u, int tl_v, ms_image *mx, ms_image *my, const float *k_rinv, const float *r_kinv,
                        const float *t, float scale, ms_stream s)
 {

@@ -2292,6 +2292,20 @@ int ms_get_map_source(const ms_ctx *c, int *source)
     return MS_OK;
 }
 
+int ms_set_seam_finder(ms_ctx *c, int finder)
+{
+    MS_CHECK(finder == MS_SEAM_VORONOI || finder == MS_SEAM_DP, "ms_set_seam_finder: finder %d is neither MS_SEAM_VORONOI (0) nor MS_SEAM_DP (1)", finder);
+    if (!c) return fail(MS_ERR_INVALID, "ms_set_seam_finder: null context");
+    c->seam_finder = finder;
+    return MS_OK;
+}
+int ms_get_seam_finder(const ms_ctx *c, int *finder)
+{
+    if (!c || !finder) return fail(MS_ERR_INVALID, "ms_get_seam_finder: null argument");
+    *finder = c->seam_finder;
+    return MS_OK;
+}
+
 static int alloc_masks(ms_ctx *c)
 {
     size_t total = 0;
@@ -2395,7 +2409,8 @@ int ms_calibrate_seam(ms_ctx *c, const ms_image *full_imgs, const float *K_seam,
             if (prm->estimate_gains) if (int e = ms_set_gain(c, i, g[i])) return e;
         }
     }
-    if (int e = voronoi_seams_device(N, rs.data(), mpw.data(), st)) return e;                                         // calibration.cpp:134-135, on the device
+    if (c->seam_finder == MS_SEAM_DP) { if (int e = dp_seams_device(N, rs.data(), ip.data(), mpw.data(), st)) return e; }  // ms_set_seam_finder: ms_dp_seams' cut (seam_dp.hip)
+    else if (int e = voronoi_seams_device(N, rs.data(), mpw.data(), st)) return e;                                    // calibration.cpp:134-135, on the device
     DevBuf dil, big;
     for (int i = 0; i < N; ++i) {
         const size_t npx = (size_t)rs[i].width * rs[i].height;

@@ -195,6 +195,7 @@ struct ms_ctx {
     hipStream_t gain_pub_stream = nullptr;
     bool gain_pub_pending = false;
     std::mutex gain_mu;                // guards gain_ev_set, `gain` and the enqueues that use the accumulators; taken AFTER tables_mu, never held across a GPU wait by ms_track_gains
+    int seam_finder = MS_SEAM_VORONOI; // ms_set_seam_finder: what ms_calibrate_seam cuts with.  Calibration state: not in the table blob
 };
 
 namespace ms {

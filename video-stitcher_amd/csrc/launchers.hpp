@@ -61,6 +61,8 @@ int voronoi_seams_device(int n, const ms_rect *rois, uint8_t *const *masks_dev, 
 // N_host / I_host (n x n each, may be null): the overlap counts and mean intensities the solve consumed (ms_estimate_gains hands them out)
 int estimate_gains_device(int n, const ms_rect *rois, const uint8_t *const *images_dev, const uint8_t *const *masks_dev, double *gains_host, hipStream_t st,
                           int *N_host = nullptr, double *I_host = nullptr);
+// minimum-cost DP seams over device images (8UC3) and masks, contiguous and roi-sized, masks in place; refuses an overlap side above MS_DP_MAX_SIDE
+int dp_seams_device(int n, const ms_rect *rois, const uint8_t *const *images_dev, uint8_t *const *masks_dev, hipStream_t st);                            // seam_dp.hip
 void feather_weight_map(const uint8_t *mask, int rows, int cols, float sharpness, float *w);
 
 }  // namespace ms

@@ -17,7 +17,7 @@
 //
 // Usage: stitch_app [--views 6] [--size 1920x1080] [--out 3840x1920] [--hfov 90] [--bands 5] [--frames 300] [--cpw]
 //                   [--i420] [--nv12 | --nv12-direct] [--dump pano.bin] [--no-upload] [--solve-mesh]
-//                   [--reference-calib [--work-megapix 0.6] [--seam-megapix 0.01] [--compose-megapix 1.4]]
+//                   [--reference-calib [--work-megapix 0.6] [--seam-megapix 0.01] [--compose-megapix 1.4] [--seam-finder voronoi|dp]]
 //                   [--drop-view V:F0:F1] [--dump-frames frames.bin] [--track-gains K] [--exposure-ramp V:F] [--dump-i420 planes.bin]
 //                   [--lens-brown k1,k2,p1,p2,k3 | --lens-fisheye k1,k2,k3,k4[,max_theta]]
 //                   [--rig-error V:YAW:PITCH:ROLL] [--refine-rig]
@@ -112,6 +112,7 @@ struct Options {
     ms_lens lens{sizeof(ms_lens), MS_LENS_NONE, {0, 0, 0, 0, 0, 0, 0, 0}, 0.0};      // --lens-brown / --lens-fisheye: every camera's lens
     int rig_err_view = -1; double rig_err_deg[3] = {0, 0, 0};    // --rig-error V:YAW:PITCH:ROLL
     bool refine_rig = false;                    // --refine-rig
+    int seam_finder = MS_SEAM_VORONOI;          // --seam-finder voronoi | dp (with --reference-calib: what the seam-scale calibration cuts with)
 };
 constexpr int CAMERA_TIMEOUT_MS = 100;               // --drop-view: how long the main loop waits for a camera's frame before it stitches without it
 
@@ -267,6 +268,12 @@ int main(int argc, char **argv)
             o.lens.model = MS_LENS_FISHEYE;
         }
         else if (k == "--refine-rig") o.refine_rig = true;
+        else if (k == "--seam-finder") {
+            const std::string v = next();
+            if (v == "voronoi") o.seam_finder = MS_SEAM_VORONOI;
+            else if (v == "dp") o.seam_finder = MS_SEAM_DP;
+            else { fprintf(stderr, "--seam-finder wants voronoi or dp\n"); return 2; }
+        }
         else if (k == "--rig-error") {
             if (sscanf(next(), "%d:%lf:%lf:%lf", &o.rig_err_view, &o.rig_err_deg[0], &o.rig_err_deg[1], &o.rig_err_deg[2]) != 4 || o.rig_err_view < 0) { fprintf(stderr, "--rig-error wants V:YAW:PITCH:ROLL\n"); return 2; }
         }
@@ -279,6 +286,7 @@ int main(int argc, char **argv)
     if (o.ramp_view >= o.views) { fprintf(stderr, "--exposure-ramp: view %d of %d\n", o.ramp_view, o.views); return 2; }
     if (o.rig_err_view >= o.views) { fprintf(stderr, "--rig-error: view %d of %d\n", o.rig_err_view, o.views); return 2; }
     if (o.refine_rig && (o.reference_calib || o.nv12)) { fprintf(stderr, "stitch_app: --refine-rig is wired up for the BASELINE rig with BGR cameras (no --reference-calib, no --nv12)\n"); return 2; }
+    if (o.seam_finder != MS_SEAM_VORONOI && !o.reference_calib) { fprintf(stderr, "stitch_app: --seam-finder dp needs --reference-calib (the seam-scale calibration has the images; ms_build_masks has none)\n"); return 2; }
     if (o.track_gains < 0) { fprintf(stderr, "--track-gains wants K >= 0\n"); return 2; }
     if (!o.dump_i420.empty() && !o.i420) { fprintf(stderr, "--dump-i420 needs --i420\n"); return 2; }
     if (o.fused_resize && !o.nv12_direct) { fprintf(stderr, "--fused-resize needs --nv12-direct\n"); return 2; }
@@ -305,7 +313,7 @@ int main(int argc, char **argv)
                 HIPCHECK(hipMemcpy2D(first[i].data, first[i].step, host.data(), (size_t)o.w * 3, (size_t)o.w * 3, o.h, hipMemcpyHostToDevice));
             }
             comp_owner = msshim::stitch_calib(first, MS_PROJ_CYLINDRICAL, o.cpw, cal, o.hfov, o.work_mp, o.seam_mp, o.compose_mp, 5.f, -1, -1, 1, -1, nullptr, o.cpw ? o.update_mask : 0,
-                                              with_lens ? lenses.data() : nullptr);
+                                              with_lens ? lenses.data() : nullptr, o.seam_finder);
             for (auto &m : first) HIPCHECK(hipFree(m.data));
             const ms_pano_geom g = comp_owner->panoGeom();
             o.out_w = (2 * std::max(std::abs(cal.pano_roi.x), std::abs(cal.pano_roi.x + cal.pano_roi.width)) + 1) & ~1;
@@ -766,10 +774,10 @@ int main(int argc, char **argv)
         }
         printf("{\"app\": \"stitch_app\", \"views\": %d, \"src\": \"%dx%d\", \"out\": \"%dx%d\", \"bands\": %d, \"cpw\": %s, \"i420\": %s, \"nv12\": %s, \"nv12_direct\": %s, \"upload\": %s, "
                "\"frames\": %lld, \"seconds\": %.4f, \"frames_per_s\": %.1f, \"recalibrations\": %d, \"mesh_solver_iterations\": %d, \"max_mesh_displacement_px\": %.2f, "
-               "\"orb_keypoints\": %lld, \"ratio_matches\": %lld, \"ransac_inliers\": %lld, \"update_mask_margin\": %d, \"update_mask_equals_sync_rebuild\": %s, \"consume_image_height\": %d, \"consume_checksum\": \"%016llx\", \"checksum\": \"%016llx\", \"degraded_frames\": %lld, \"i420_call\": \"%s\", \"fused_resize\": %s, \"map_source\": %d",
+               "\"orb_keypoints\": %lld, \"ratio_matches\": %lld, \"ransac_inliers\": %lld, \"update_mask_margin\": %d, \"update_mask_equals_sync_rebuild\": %s, \"consume_image_height\": %d, \"consume_checksum\": \"%016llx\", \"checksum\": \"%016llx\", \"degraded_frames\": %lld, \"i420_call\": \"%s\", \"fused_resize\": %s, \"map_source\": %d, \"seam_finder\": \"%s\"",
                o.views, o.w, o.h, o.out_w, o.out_h, pg.num_bands, o.cpw ? "true" : "false", o.i420 ? "true" : "false", o.nv12 ? "true" : "false", o.nv12_direct ? "true" : "false", o.upload ? "true" : "false",
                consumed, secs, consumed / secs, recalibrations.load(), solver_iterations.load(), (double)max_disp.load(),
-               total_keypoints.load(), total_matches.load(), total_inliers.load(), o.update_mask, selfcheck < 0 ? "null" : (selfcheck ? "true" : "false"), consume_image_height, consume_checksum, checksum, degraded_frames, i420_call, fused_resize ? "true" : "false", comp.mapSource());
+               total_keypoints.load(), total_matches.load(), total_inliers.load(), o.update_mask, selfcheck < 0 ? "null" : (selfcheck ? "true" : "false"), consume_image_height, consume_checksum, checksum, degraded_frames, i420_call, fused_resize ? "true" : "false", comp.mapSource(), comp.seamFinder() == MS_SEAM_DP ? "dp" : "voronoi");
         if (o.track_gains > 0) {
             std::vector<double> g((size_t)o.views);
             int ok = 0, singular = 0;

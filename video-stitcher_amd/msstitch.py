@@ -19,6 +19,8 @@ INTER_NEAREST, INTER_LINEAR = 0, 1
 INTER_LINEAR_FIXPT = 0x101      # cv::remap's CPU arithmetic
 PROJ_PLANE, PROJ_CYLINDRICAL, PROJ_SPHERICAL = 0, 1, 2
 MAPS_ANALYTIC, MAPS_CUSTOM, MAPS_LENS = 0, 1, 2
+SEAM_VORONOI, SEAM_DP = 0, 1          # ms_set_seam_finder
+DP_MAX_SIDE = 4096                    # MS_DP_MAX_SIDE: the largest overlap side ms_dp_seams takes
 LENS_NONE, LENS_BROWN, LENS_FISHEYE = 0, 1, 2
 LENS_CYL_MAX_ELEVATION_DEG = 80
 MAPS_MIN_WIDTH, MAPS_MIN_HEIGHT, MAPS_MAX_SIDE = 3, 2, 31744
@@ -182,6 +184,7 @@ EXPORTS = [
     "ms_set_maps", "ms_get_map_source",
     "ms_lens_check", "ms_lens_project", "ms_set_lens", "ms_get_lens", "ms_build_warp_maps_lens", "ms_warp_roi_lens",
     "ms_warper_rays", "ms_rig_refine_default_params", "ms_rig_accumulate", "ms_refine_rig_rotations", "ms_refine_rig",
+    "ms_dp_seams", "ms_set_seam_finder", "ms_get_seam_finder",
 ]
 
 _lib = None
@@ -437,6 +440,16 @@ def voronoi_seams(rois, masks_dev):
     assert len(rois) == n
     m = (Image * n)(*[img(t) for t in masks_dev])
     _chk(load().ms_voronoi_seams(n, _rects(rois), m, _stream()))
+    return masks_dev
+
+
+def dp_seams(rois, imgs_dev, masks_dev):
+    """ms_dp_seams: a minimum-cost seam through every overlap, over device images (uint8 (h, w, 3)) and masks (uint8 (h, w)), each exactly its ROI's size and
+    contiguous; the masks are edited in place.  rois: (x, y, w, h) per view."""
+    n = len(masks_dev)
+    assert len(rois) == n and len(imgs_dev) == n
+    a = (Image * n)(*[img(t) for t in imgs_dev]); m = (Image * n)(*[img(t) for t in masks_dev])
+    _chk(load().ms_dp_seams(n, _rects(rois), a, m, _stream()))
     return masks_dev
 
 
@@ -925,6 +938,15 @@ class Compositor:
 
     def build_masks(self, mode=1):
         _chk(load().ms_build_masks(self._ctx, mode, _stream()))
+
+    def set_seam_finder(self, finder):
+        """ms_set_seam_finder: SEAM_VORONOI (the default) or SEAM_DP -- what calibrate_seam cuts with.  build_masks(1) has no images and stays Voronoi."""
+        _chk(load().ms_set_seam_finder(self._ctx, int(finder)))
+
+    def seam_finder(self):
+        v = C.c_int(-1)
+        _chk(load().ms_get_seam_finder(self._ctx, C.byref(v)))
+        return v.value
 
     def calibrate_seam(self, full_imgs, K_seam, seam_scale, seam_warp_scale, dilate=False, estimate_gains=True):
         """stitch_calib's seam-scale pipeline; returns the estimated gains."""

@@ -116,6 +116,9 @@ public:
     bool customMaps() const { int src = MS_MAPS_ANALYTIC; check(ms_get_map_source(ctx_, &src)); return src == MS_MAPS_CUSTOM; }
     int mapSource() const { int src = MS_MAPS_ANALYTIC; check(ms_get_map_source(ctx_, &src)); return src; }      // MS_MAPS_ANALYTIC / _CUSTOM / _LENS
     void buildMasks(bool voronoi_seams = true, ms_stream s = nullptr) { check(ms_build_masks(ctx_, voronoi_seams ? 1 : 0, s)); }
+    // what calibrateSeam cuts with (seam_finder->find, calibration.cpp:134-135): MS_SEAM_VORONOI as the reference, or MS_SEAM_DP, a minimum-cost seam through the warped images
+    void setSeamFinder(int finder) { check(ms_set_seam_finder(ctx_, finder)); }
+    int seamFinder() const { int f = MS_SEAM_VORONOI; check(ms_get_seam_finder(ctx_, &f)); return f; }
     void setMask(int i, const uint8_t *host_mask, size_t step) { check(ms_set_mask(ctx_, i, host_mask, step)); }
     void init_gpu(ms_stream s = nullptr) { check(ms_init_blender(ctx_, s)); }         // mb->init_gpu for every view
     void update_mask(int img_num, ms_stream s = nullptr) { check(ms_update_mask(ctx_, img_num, s)); }   // mb->update_mask(idx, x_mesh, y_mesh): uses the view's active mesh
@@ -250,11 +253,13 @@ struct Calibration {
 // mesh swap while frames flow; with 0 it is the synchronous rebuild, which makes a concurrent stitch_one wait (never race) for its ~50 ms.
 // lenses: nullptr, or one ms_lens per view (model MS_LENS_NONE = that view has none): handed to ms_set_lens, so that the ROIs, the maps and the seam-scale
 // pipeline go through the lens model (spherical and cylindrical projections).
+// seam_finder: MS_SEAM_VORONOI (calibration.cpp:134) or MS_SEAM_DP (Compositor::setSeamFinder).
 template <class Mat>
 std::unique_ptr<Compositor> stitch_calib(const std::vector<Mat> &full_imgs, int projection, bool enable_local, Calibration &cal,
                                          double hfov_deg = 90.0, double work_megapix = 0.6, double seam_megapix = 0.01, double compose_megapix = 1.4,
                                          float blend_strength = 5.f, int out_w = 0, int out_h = 0, int frames_in_flight = 1,
-                                         int num_bands_override = -1, ms_stream s = nullptr, int update_mask_margin = 0, const ms_lens *lenses = nullptr)
+                                         int num_bands_override = -1, ms_stream s = nullptr, int update_mask_margin = 0, const ms_lens *lenses = nullptr,
+                                         int seam_finder = MS_SEAM_VORONOI)
 {
     const int n = (int)full_imgs.size();
     if (n < 1) throw Error(MS_ERR_INVALID, "stitch_calib: no images");
@@ -277,6 +282,7 @@ std::unique_ptr<Compositor> stitch_calib(const std::vector<Mat> &full_imgs, int 
     for (int i = 0; i < n; ++i) comp->setCamera(i, rig.K_compose[i], rig.R[i]);
     if (lenses) for (int i = 0; i < n; ++i) comp->setLens(i, &lenses[i]);
     comp->buildMaps(s);                                                                                          // :196, :221
+    if (seam_finder != MS_SEAM_VORONOI) comp->setSeamFinder(seam_finder);
     ms_seam_params sp{rig.seam_scale, rig.seam_warp_scale, enable_local ? 1 : 0, 1};
     cal.gains.assign(n, 1.0);
     comp->calibrateSeam(full_imgs, &rig.K_seam[0][0], sp, cal.gains.data(), s);                                  // :92-135, :224-237
