@@ -879,6 +879,108 @@ MS_API int ms_refine_rig_rotations(int n_views, const double *R_in, const ms_rig
 MS_API int ms_refine_rig(ms_ctx *ctx, const ms_mesh_match *matches, const int *match_count, const ms_rig_refine_params *prm, float *R_out,
                          ms_rig_refine_info *info, ms_stream stream);
 
+/* ---- Self-calibrating rigs: focals and rotations from feature matches ----------------------------------------------------------------------------
+ * The three steps of OpenCV's stitching pipeline that produce and correct the one rig parameter the section above holds fixed, the focal length:
+ * detail::focalsFromHomography (OCV/stitching/src/autocalib.cpp:63-91), detail::HomographyBasedEstimator (motion_estimators.cpp:127-193: estimateFocal, the maximum
+ * spanning tree, CalcRotation) and detail::BundleAdjusterRay over focal AND rotation (motion_estimators.cpp:514-700).  The first two are a few dozen operations on
+ * the host; the bundle adjustment runs on the device with the whole Levenberg-Marquardt loop resident there, as the rotation refinement above does.
+ * The arithmetic contract of the bundle adjustment, all of it in double:
+ *   A match k on the view pair (i, j) holds two CENTRED source pixels of one scene point, (xa, ya) in view i and (xb, yb) in view j: pixels measured from the
+ *   principal point, y already divided by the aspect ratio K[4] / K[0].  Pairs are taken as i < j (the two pixels swapped where a match lists (j, i)); a pair with
+ *   fewer than min_pair_matches matches is ignored and counted; after that every view must be connected to the anchor.
+ *   Unknowns per view v: the rotation R_v (camera to rig), updated R_v <- Exp(delta_v) R_v, the anchor's held; and the log-focal s_v = ln f_v, updated
+ *   f_v <- f_v exp(d_v) (a focal never turns non-positive).  The anchor's focal is free.  shared_focal != 0: one s for the whole rig.  At most 3 * 15 + 16 = 61.
+ *   Rays: na = sqrt(xa xa + ya ya + f_i f_i), a = (xa / na, ya / na, f_i / na); nb and b likewise with f_j.  p = R_i a, q = R_j b (row r: R[3r] a0 + R[3r+1] a1 +
+ *   R[3r+2] a2, summed left to right).
+ *   Residual (calcError's `mult`): m = sqrt(f_i f_j), r_k = m (p_k - q_k): pixels.  (Without m, f -> infinity sends every ray to the axis and the cost to 0.)
+ *   s = sqrt(r0 r0 + r1 r1 + r2 r2).  Huber threshold h = huber_px: w = 1 and rho = s^2 when h = 0 or s <= h, otherwise w = h / s and rho = (2 h) s - h h.
+ *   Jacobian, analytic (OpenCV differentiates numerically), with u_k = m p_k, v_k = m q_k, ma = m a2, mb = m b2:
+ *     dr/d delta_i = -[u]x,   dr/d s_i = ci,  ci_k = 0.5 r_k + ma (R_i[3k+2] - a2 p_k)        (d a / d s_i = a2 (e_z - a2 a), d m / d s_i = m / 2)
+ *     dr/d delta_j = +[v]x,   dr/d s_j = cj,  cj_k = 0.5 r_k - mb (R_j[3k+2] - b2 q_k)
+ *   The 46 sums of a pair, 4 unknowns a view in the order (delta_0, delta_1, delta_2, s); x is the cross product, (x)_k its component k:
+ *     cost  sum rho
+ *     g_i   sum w (u x r)_k, k = 0 1 2: w (u1 r2 - u2 r1), w (u2 r0 - u0 r2), w (u0 r1 - u1 r0);   then sum w (ci0 r0 + ci1 r1 + ci2 r2)
+ *     g_j   sum -(w (v x r)_k);                                                                     then sum w (cj0 r0 + cj1 r1 + cj2 r2)
+ *     H_ii  symmetric, stored (00 01 02 03 11 12 13 22 23 33): w (u1 u1 + u2 u2), -(w (u0 u1)), -(w (u0 u2)), w (u x ci)_0, w (u0 u0 + u2 u2), -(w (u1 u2)),
+ *           w (u x ci)_1, w (u0 u0 + u1 u1), w (u x ci)_2, w (ci0 ci0 + ci1 ci1 + ci2 ci2)
+ *     H_jj  the same with v and cj, its three rotation-focal entries negated: -(w (v x cj)_k)
+ *     H_ij  4 x 4 row-major (rows: view i): rotation rows r, rotation columns c: w (v_r u_c) off the diagonal, -(w (u1 v1 + u2 v2)), -(w (u0 v0 + u2 v2)),
+ *           -(w (u0 v0 + u1 v1)) on it; column 3: w (u x cj)_r; row 3: -(w (v x ci)_c), then w (ci0 cj0 + ci1 cj1 + ci2 cj2).  H_ji = H_ij^T.
+ *     outliers  the number of matches with s > h
+ *   Every product, sum, division and sqrt above is one IEEE operation in the order written (no fused multiply-add), sums of three left to right: two
+ *   implementations differ by the order of the per-match sums only.  With a shared focal the focal rows and columns of all views are added into one.
+ *   Levenberg-Marquardt: exactly the rule of the section above (lambda = 1e-3, Cholesky of H + lambda diag H with a non-positive pivot a rejected step, accept iff
+ *   cost_trial <= cost, lambda / 10 floored at 1e-12 or * 10, the MS_RIG_* stop reasons); step_tol is tested on max |.| over the rotation AND log-focal
+ *   components of the step.  The call returns the last ACCEPTED state: cost_final <= cost_initial always. */
+typedef struct ms_pair_homography {
+    int view_a, view_b;
+    double H[9];                   /* row-major; maps centred pixels of view_a to centred pixels of view_b */
+    int weight;                    /* the pair's inlier count: the edge weight of the spanning tree */
+} ms_pair_homography;
+typedef struct ms_rig_estimate_info {
+    int focal_estimates;           /* pairs whose homography gave both focals */
+    int tree_parent[MS_MAX_VIEWS]; /* the view each view's rotation was chained from; -1 for the anchor */
+} ms_rig_estimate_info;
+typedef struct ms_rig_px_match {
+    int view_a, view_b;
+    double a[2], b[2];             /* centred source pixels of one scene point: a in view_a, b in view_b */
+} ms_rig_px_match;
+typedef struct ms_rig_focal_params {
+    unsigned struct_size;          /* as ms_config: mismatch = MS_ERR_INVALID */
+    int anchor_view;               /* 0: the view whose rotation is held */
+    int shared_focal;              /* 1: one focal for the whole rig (identical cameras); 0: one a view */
+    int max_iters;                 /* 50; [1, 1000] */
+    double huber_px;               /* 0 = plain least squares; otherwise the Huber threshold on |r| in pixels */
+    double step_tol;               /* 1e-10 */
+    int min_pair_matches;          /* 4: pairs with fewer matches are ignored */
+} ms_rig_focal_params;
+typedef struct ms_rig_focal_info {
+    int iterations, stop_reason;   /* MS_RIG_* */
+    double cost_initial, cost_final;
+    int matches_used, pairs_used, pairs_ignored;
+    int outliers;                  /* matches with s > huber_px at the returned cameras (0 without Huber) */
+    double max_rotation_rad;       /* the largest angle between a view's input and output rotation */
+    double max_focal_ratio;        /* the largest of f_out / f_in and f_in / f_out over the views (>= 1) */
+} ms_rig_focal_info;
+/* detail::focalsFromHomography (autocalib.cpp:63-91) on a homography between CENTRED pixel coordinates: *f0 the focal of the source view, *f1 of the destination,
+ * each written only where its flag comes back 1 (a rotation about the optical axis alone, the identity among them, determines neither).  Host only, no device. */
+MS_API int ms_focals_from_homography(const double H[9], double *f0, double *f1, int *f0_ok, int *f1_ok);
+/* detail::HomographyBasedEstimator (motion_estimators.cpp:127-193) on centred pixels, aspect 1.  Host only, no device.  Focal: the median of sqrt(f0 f1) over the pairs
+ * whose homography gives both (an even count: the mean of the middle two), for every view; none valid: every focal is width + height and the call returns 1
+ * (estimateFocal's fallback, autocalib.cpp:129-137).  Rotations: a maximum spanning tree over `weight` (Kruskal, ties to the earlier pair), walked breadth-first
+ * from `anchor`, whose rotation is the identity; along an edge a -> b with H mapping a to b, R_b = R_a K_a^-1 H^-1 K_b (H itself where the pair is listed (b, a)),
+ * K = diag(f, f, 1); every product is then projected onto SO(3) as U V^T of its singular value decomposition (a one-sided Jacobi SVD; the column of U of the smallest
+ * singular value negated where det U V^T < 0), which also removes H's free scale.  focals: n_views doubles, R: n_views x 9 doubles row-major, info may be NULL.
+ * MS_ERR_INVALID: a null pointer, n_views outside [2, MS_MAX_VIEWS], n_pairs outside [1, MS_MAX_VIEWS^2], a bad anchor or view index, a pair of a view with itself, a negative weight, a
+ * non-finite or singular H, width or height < 1, a view the pairs do not connect to the anchor (the message names it). */
+MS_API int ms_estimate_rig(int n_views, const ms_pair_homography *pairs, int n_pairs, int anchor, int width, int height, double *focals, double *R,
+                           ms_rig_estimate_info *info);
+/* anchor 0, per-view focals, 50 iterations, no Huber, step_tol 1e-10, 4 matches a pair */
+MS_API int ms_rig_focal_default_params(ms_rig_focal_params *prm);
+/* The normal equations of the contract above, per op: cost, H (4 n_views x 4 n_views row-major, view v at rows 4v .. 4v + 3, one focal a view, no view held) and g
+ * (4 n_views) at the focals f (n_views) and rotations R (n_views x 9), every pair used whatever its size.  All pointers HOST.  Synchronises. */
+MS_API int ms_rig_focal_accumulate(int n_views, const double *f, const double *R, const ms_rig_px_match *matches, int n, double huber_px, double *cost, double *H,
+                                   double *g, ms_stream stream);
+/* BundleAdjusterBase::estimate over focals and rotations, the whole loop on the device exactly as ms_refine_rig_rotations runs it: matches grouped by pair on the host
+ * (stably), one pinned upload, max_iters + 1 rounds of two kernels with no host step in between, one copy back, one synchronise.  No floating-point atomics: two calls
+ * on the same inputs return the same bits.  f_in / f_out: n_views doubles, R_in / R_out: n_views x 9 doubles, HOST; the anchor's R_out is bit-equal to its R_in; with
+ * shared_focal every f_out is the same double; info may be NULL.
+ * MS_ERR_INVALID, before the device is touched: a null pointer; n_views outside [2, MS_MAX_VIEWS]; n outside [1, 2^20]; a focal that is not finite or not positive;
+ * with shared_focal, f_in that are not all equal; a rotation that is not finite or whose R R^T is off the identity by more than 1e-6 in an entry; a view index out
+ * of range or view_a == view_b; a pixel that is not finite; a bad anchor; a struct_size mismatch; max_iters outside [1, 1000]; a negative or non-finite huber_px or
+ * step_tol; min_pair_matches < 1; a view not connected to the anchor (the message names the first). */
+MS_API int ms_refine_rig_cameras(int n_views, const double *f_in, const double *R_in, const ms_rig_px_match *matches, int n, const ms_rig_focal_params *prm,
+                                 double *f_out, double *R_out, ms_rig_focal_info *info, ms_stream stream);
+/* The context form, ms_refine_rig's with the focals free: the same per-view lists of projection-warped view pixels become camera rays by ms_warper_rays' arithmetic
+ * with the context's CURRENT cameras, and a ray (x, y, z) becomes the centred pixel f_cur (x / z, y / z), f_cur = (double)K[0] of its view.  focal_out: num_views
+ * doubles; R_out: num_views x 9 floats.  Nothing is applied: the caller sets K[0] = f and K[4] = f (old K[4] / K[0]) and runs the usual chain (ms_set_camera,
+ * ms_build_maps, masks, ms_init_blender).  MS_ERR_STATE before ms_build_maps; MS_ERR_UNSUPPORTED for MS_MAPS_CUSTOM contexts (no cameras) and for lens contexts: a
+ * warped pixel of a lens context carries the camera ray but not the source pixel, and the ray's pixel at ANOTHER focal lies at another distorted radius -- refining
+ * a focal under a lens needs the inverse distortion, which the library does not have.  MS_ERR_INVALID as above, for a list that names its own view or a view out of
+ * range, and for a ray with z <= 0 (behind the camera: it has no pixel), naming the match. */
+MS_API int ms_refine_rig_focals(ms_ctx *ctx, const ms_mesh_match *matches, const int *match_count, const ms_rig_focal_params *prm, double *focal_out, float *R_out,
+                                ms_rig_focal_info *info, ms_stream stream);
+
 /* device-resident static tables, for parity tests: x_maps[i]/y_maps[i] (32FC1), masks (8UC1),
  * weight pyramid level (32FC1). Borrowed pointers owned by ctx. */
 MS_API int ms_get_maps(const ms_ctx *ctx, int view, ms_image *xmap, ms_image *ymap);

@@ -129,6 +129,28 @@ class RigRefineInfo(C.Structure):
 RIG_CONVERGED, RIG_STALLED, RIG_ITERATION_LIMIT = 0, 1, 2
 
 
+class PairHomography(C.Structure):
+    _fields_ = [("view_a", C.c_int), ("view_b", C.c_int), ("H", C.c_double * 9), ("weight", C.c_int)]
+
+
+class RigEstimateInfo(C.Structure):
+    _fields_ = [("focal_estimates", C.c_int), ("tree_parent", C.c_int * 16)]
+
+
+class RigPxMatch(C.Structure):
+    _fields_ = [("view_a", C.c_int), ("view_b", C.c_int), ("a", C.c_double * 2), ("b", C.c_double * 2)]
+
+
+class RigFocalParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("anchor_view", C.c_int), ("shared_focal", C.c_int), ("max_iters", C.c_int), ("huber_px", C.c_double),
+                ("step_tol", C.c_double), ("min_pair_matches", C.c_int)]
+
+
+class RigFocalInfo(C.Structure):
+    _fields_ = [("iterations", C.c_int), ("stop_reason", C.c_int), ("cost_initial", C.c_double), ("cost_final", C.c_double), ("matches_used", C.c_int),
+                ("pairs_used", C.c_int), ("pairs_ignored", C.c_int), ("outliers", C.c_int), ("max_rotation_rad", C.c_double), ("max_focal_ratio", C.c_double)]
+
+
 class GainTrackParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint), ("stride", C.c_int), ("smoothing", C.c_double)]
 
@@ -185,6 +207,7 @@ EXPORTS = [
     "ms_lens_check", "ms_lens_project", "ms_set_lens", "ms_get_lens", "ms_build_warp_maps_lens", "ms_warp_roi_lens",
     "ms_warper_rays", "ms_rig_refine_default_params", "ms_rig_accumulate", "ms_refine_rig_rotations", "ms_refine_rig",
     "ms_dp_seams", "ms_set_seam_finder", "ms_get_seam_finder",
+    "ms_focals_from_homography", "ms_estimate_rig", "ms_rig_focal_default_params", "ms_rig_focal_accumulate", "ms_refine_rig_cameras", "ms_refine_rig_focals",
 ]
 
 _lib = None
@@ -579,6 +602,84 @@ def refine_rig_rotations(R, matches, params=None):
     return out, _rig_info(info)
 
 
+def focals_from_homography(H):
+    """ms_focals_from_homography (host only): H (3 x 3) between centred pixels -> (f0 or None, f1 or None), the focals of the source and the destination view"""
+    import numpy as np
+    Ha = np.ascontiguousarray(H, np.float64).reshape(9)
+    f0, f1, ok0, ok1 = C.c_double(0), C.c_double(0), C.c_int(0), C.c_int(0)
+    _chk(load().ms_focals_from_homography(Ha.ctypes.data_as(C.POINTER(C.c_double)), C.byref(f0), C.byref(f1), C.byref(ok0), C.byref(ok1)))
+    return (f0.value if ok0.value else None), (f1.value if ok1.value else None)
+
+
+def pair_homographies(pairs):
+    """[(view_a, view_b, H (3 x 3), weight), ...] -> a PairHomography array"""
+    arr = (PairHomography * max(1, len(pairs)))()
+    for k, (va, vb, H, w) in enumerate(pairs):
+        arr[k] = PairHomography(int(va), int(vb), (C.c_double * 9)(*[float(x) for row in H for x in row]), int(w))
+    return arr
+
+
+def estimate_rig(n_views, pairs, size, anchor=0):
+    """ms_estimate_rig (host only): pairs as pair_homographies takes them, size = (width, height) of a source image -> (focals (n,), R (n, 3, 3) float64, info dict);
+    info["status"] is 1 where no homography gave a focal and width + height stands in"""
+    import numpy as np
+    f = np.empty(n_views, np.float64); R = np.empty((n_views, 3, 3), np.float64)
+    info = RigEstimateInfo()
+    dp = C.POINTER(C.c_double)
+    rc = _chk(load().ms_estimate_rig(n_views, pair_homographies(pairs), len(pairs), int(anchor), int(size[0]), int(size[1]), f.ctypes.data_as(dp), R.ctypes.data_as(dp),
+                                     C.byref(info)))
+    return f, R, {"status": rc, "focal_estimates": info.focal_estimates, "tree_parent": list(info.tree_parent)[:n_views]}
+
+
+def rig_focal_default_params(**kw):
+    """ms_rig_focal_default_params; keyword arguments override fields"""
+    p = RigFocalParams()
+    _chk(load().ms_rig_focal_default_params(C.byref(p)))
+    for k, v in kw.items():
+        assert hasattr(p, k), k
+        setattr(p, k, v)
+    return p
+
+
+def rig_px_matches(matches):
+    """[(view_a, view_b, a (2,), b (2,)), ...] -> a RigPxMatch array"""
+    arr = (RigPxMatch * max(1, len(matches)))()
+    for k, (va, vb, a, b) in enumerate(matches):
+        arr[k] = RigPxMatch(int(va), int(vb), (C.c_double * 2)(float(a[0]), float(a[1])), (C.c_double * 2)(float(b[0]), float(b[1])))
+    return arr
+
+
+def _rig_focal_info(info):
+    return {k: getattr(info, k) for k, _ in RigFocalInfo._fields_}
+
+
+def rig_focal_accumulate(f, R, matches, huber_px=0.0):
+    """ms_rig_focal_accumulate: f (n,), R (n, 3, 3) float64, matches as rig_px_matches takes them -> (cost, H (4n, 4n), g (4n,)) at these cameras"""
+    import numpy as np
+    fa = np.ascontiguousarray(f, np.float64); Ra = np.ascontiguousarray(R, np.float64)
+    n = len(Ra)
+    H = np.empty((4 * n, 4 * n), np.float64); g = np.empty(4 * n, np.float64)
+    cost = C.c_double(0)
+    dp = C.POINTER(C.c_double)
+    _chk(load().ms_rig_focal_accumulate(n, fa.ctypes.data_as(dp), Ra.ctypes.data_as(dp), rig_px_matches(matches), len(matches), C.c_double(huber_px), C.byref(cost),
+                                        H.ctypes.data_as(dp), g.ctypes.data_as(dp), _stream()))
+    return cost.value, H, g
+
+
+def refine_rig_cameras(f, R, matches, params=None):
+    """ms_refine_rig_cameras: f (n,), R (n, 3, 3) float64, matches as rig_px_matches takes them -> (refined f (n,), refined R (n, 3, 3), info dict)"""
+    import numpy as np
+    fa = np.ascontiguousarray(f, np.float64); Ra = np.ascontiguousarray(R, np.float64)
+    n = len(Ra)
+    fo = np.empty(n, np.float64); out = np.empty((n, 3, 3), np.float64)
+    prm = params if params is not None else rig_focal_default_params()
+    info = RigFocalInfo()
+    dp = C.POINTER(C.c_double)
+    _chk(load().ms_refine_rig_cameras(n, fa.ctypes.data_as(dp), Ra.ctypes.data_as(dp), rig_px_matches(matches), len(matches), C.byref(prm), fo.ctypes.data_as(dp),
+                                      out.ctypes.data_as(dp), C.byref(info), _stream()))
+    return fo, out, _rig_focal_info(info)
+
+
 def nv12_to_bgr(src, dst=None):
     if dst is None:
         dst = _new((src.shape[0] * 2 // 3, src.shape[1], 3), _torch().uint8)
@@ -917,6 +1018,17 @@ class Compositor:
         info = RigRefineInfo()
         _chk(load().ms_refine_rig(self._ctx, marr, mcnt, C.byref(prm), out.ctypes.data_as(C.POINTER(C.c_float)), C.byref(info), _stream()))
         return out, _rig_info(info)
+
+    def refine_rig_focals(self, matches, params=None):
+        """ms_refine_rig_focals: matches as refine_rig takes them -> (focals (n,) float64, R (n, 3, 3) float32, info dict).  Nothing is applied to the context."""
+        import numpy as np
+        marr, mcnt = _match_array(matches)
+        prm = params if params is not None else rig_focal_default_params()
+        f = np.empty(self.n, np.float64); out = np.empty((self.n, 3, 3), np.float32)
+        info = RigFocalInfo()
+        _chk(load().ms_refine_rig_focals(self._ctx, marr, mcnt, C.byref(prm), f.ctypes.data_as(C.POINTER(C.c_double)), out.ctypes.data_as(C.POINTER(C.c_float)),
+                                         C.byref(info), _stream()))
+        return f, out, _rig_focal_info(info)
 
     def build_maps(self):
         _chk(load().ms_build_maps(self._ctx, _stream()))
