@@ -86,7 +86,7 @@ def recovery_case(name):
 
 @pytest.mark.parametrize("name", ["pair2", "ring6", "ring6-shared", "chords16", "chords16-shared"])
 def test_exact_recovery(ms, cuda, name):
-    """exact matches have the true cameras as a zero of the cost; chords16 is the 61-unknown system, k_rigf_step's LDS limit.  Bounds: the reference ends within
+    """exact matches have the true cameras as a zero of the cost; chords16 is the 61-unknown system, k_rig_step<4>'s LDS limit.  Bounds: the reference ends within
     6e-16 of the true focal ratio and 3e-16 rad; 1e-12 leaves the conditioning of the largest system three orders."""
     f0, R0, ft, Rt, pairs, M = recovery_case(name)
     n, shared = len(f0), name.endswith("shared")

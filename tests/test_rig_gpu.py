@@ -41,11 +41,12 @@ def max_angle(A, B):
 
 
 # ---- 1. accumulate, per op --------------------------------------------------------------------------------------
-@pytest.mark.parametrize("m", [1, 63, 64, 65, 257, 1025])
+@pytest.mark.parametrize("m", [1, 4, 63, 64, 65, 255, 256, 257, 1000, 1025])
 def test_accumulate_per_op(ms, cuda, m):
     """3 views, pair (0, 1) with m matches, pair (1, 2) with 5, pair (0, 2) with none, listed in shuffled order with a third of them as (j, i).  The terms of the
     two implementations are the same bits (the contract fixes their arithmetic); only the order of the sums differs, and for two orders of n rounded terms the
-    results differ by at most (n - 1) 2^-52 S, S the sum of the terms' absolute values: the bound below, (m + 8) 2^-52 S, covers the m + 5 terms of any entry."""
+    results differ by at most (n - 1) 2^-52 S, S the sum of the terms' absolute values: the bound below, (m + 8) 2^-52 S, covers the m + 5 terms of any entry.
+    The sizes are those of tests/test_rig_focal_gpu.py and 1025: the two tests run one reduction body (csrc/rig_lm.hpp) through its two instances."""
     rng = np.random.default_rng(100 + m)
     R = rr.perturbed(rr.ring(3), rng, 5.0)
     M = rr.make_matches(rr.perturbed(rr.ring(3), rng, 5.0), [(0, 1), (1, 2)], [m, 5], rng, noise=2e-3)

@@ -1,5 +1,5 @@
 // ctx.hpp -- the context type behind the C ABI's opaque ms_ctx, for the units that define its entry points: compositor.hip (life cycle, tables, the per-frame
-// path), calib.hip (exposure tracking), rig.hip (ms_refine_rig) and rig_focal.hip (ms_refine_rig_focals).  Internal; nothing else includes it.
+// path), calib.hip (exposure tracking), and through rig_lm.hpp rig.hip (ms_refine_rig) and rig_focal.hip (ms_refine_rig_focals).  Internal; nothing else includes it.
 #pragma once
 #include <atomic>
 #include <memory>
