@@ -981,6 +981,79 @@ MS_API int ms_refine_rig_cameras(int n_views, const double *f_in, const double *
 MS_API int ms_refine_rig_focals(ms_ctx *ctx, const ms_mesh_match *matches, const int *match_count, const ms_rig_focal_params *prm, double *focal_out, float *R_out,
                                 ms_rig_focal_info *info, ms_stream stream);
 
+/* ---- Pairwise matching: every view pair of a rig in one call ---------------------------------------------------------------------------------------
+ * detail::BestOf2NearestMatcher / BestOf2NearestRangeMatcher (OCV/stitching/src/matchers.cpp:248-297 the two-direction 2-NN match with ratio test and
+ * cross-check, :692-770 the per-pair homography and confidence, :784-808 the candidate pairs), the stage of Stitcher::estimateCameraParams between
+ * ms_orb_detect_and_compute and ms_estimate_rig; then leaveBiggestComponent (motion_estimators.cpp:1041-1097) and waveCorrect (:892-970), the two host
+ * steps that turn its output into a connected, level rig.
+ * Candidate pairs: every (i, j), i < j, with j < i + range_width where range_width > 0 and pair_mask[i * n_views + j] != 0 where pair_mask is given, in
+ * lexicographic order; pairs_out lists them all.  A pair with an empty view is listed with count 0, no H and confidence 0 (the reference skips it and
+ * leaves the default MatchesInfo).
+ * The device stage, integers only but for one float compare, exact: for a pair (a, b) the two nearest rows of b for every row of a and of a for every
+ * row of b, by ms_knn_match_hamming2's rule ((distance, index) order); a query whose train side has fewer than two rows yields nothing.  Ratio test:
+ * t = 1.f - match_conf (one float subtraction); query q with nearest (j0, d0) and second (j1, d1) passes iff (float)d0 < t * (float)d1 (one float
+ * multiply).  The pair's list: every passing row q of a, ascending, as (q, j0, d0) -- n_forward of them --, then every passing row q of b, ascending, as
+ * (j0, q, d0) unless (j0, q) is already there, i.e. unless row j0 of a passed and its nearest row is q.  The order is part of the contract (the fixed
+ * RANSAC subset sequence indexes into it).  Two launches whatever the number of pairs: the 2-NN of every row of every directed pair (a workgroup stages
+ * tiles of train rows in LDS and scores 64 queries against each), then one workgroup a pair for ratio test, cross-check and an ordered prefix-scan
+ * compaction (no atomics: two calls return the same bits); one upload, one copy back, one synchronise.
+ * The host stage, per pair with count >= num_matches_thresh1, BestOf2NearestMatcher::match line for line: the matches' keypoints as centred floats
+ * (x - width * 0.5f, y - height * 0.5f) go to ms_find_homography_ransac in list order (inlier flags, num_inliers, H; no model: have_H = 0);
+ * |det H| < DBL_EPSILON: have_H stays 1, num_inliers = 0, confidence 0; otherwise confidence = num_inliers / (8 + 0.3 * count) in double, a value above 3
+ * becomes 0 (two views of the same image), and with num_inliers >= num_matches_thresh2 a second ms_find_homography_ransac on the inliers alone replaces H
+ * (no model: have_H = 0; flags, count and confidence stay).  Below thresh1: have_H = 0, num_inliers = 0, confidence 0, every inlier flag 0.
+ * Descriptors: 8UC1, the same length in every view, a multiple of 4 up to 64 bytes, data and step multiples of 4 (32 bytes is the specialised kernel);
+ * these are checked on the views that have keypoints.
+ * MS_ERR_INVALID before the device is touched: a null pointer; n_views outside [2, MS_MAX_VIEWS]; a struct_size mismatch; match_conf not finite or outside
+ * [0, 1); a negative threshold or range_width; a descriptor type, length, step or alignment off the rule above or lengths that differ; n_keypoints negative,
+ * above descriptors.rows or above MS_MATCH_MAX_KEYPOINTS; null keypoints or descriptors where n_keypoints > 0; keypoint_stride < 2; width or height < 1;
+ * pairs_cap below the number of candidate pairs.  After the device stage: matches_cap below the total, with the needed total in *n_matches (and the
+ * candidate count in *n_pairs), as ms_orb_detect_and_compute treats a short buffer. */
+#define MS_MATCH_MAX_KEYPOINTS 32768
+typedef struct ms_view_features {
+    ms_image descriptors;          /* DEVICE 8UC1, rows >= n_keypoints (ORB hands back `cap` rows), cols = descriptor bytes */
+    const float *keypoints;        /* HOST; row k starts at keypoints + k * keypoint_stride, x then y (ms_orb_detect_and_compute rows: stride 6) */
+    int keypoint_stride, n_keypoints;
+    int width, height;             /* ImageFeatures::img_size */
+} ms_view_features;
+typedef struct ms_pair_match_params {
+    unsigned struct_size;          /* as ms_config: mismatch = MS_ERR_INVALID */
+    float match_conf;              /* 0.3f (the ORB value of stitching_detailed) */
+    int num_matches_thresh1;       /* 6 */
+    int num_matches_thresh2;       /* 6 */
+    int range_width;               /* 0: every pair i < j; k > 0: j < i + k (BestOf2NearestRangeMatcher) */
+    const unsigned char *pair_mask;/* NULL or n_views x n_views, row-major, entry (i, j), i < j, non-zero = try the pair */
+    double ransac_reproj_threshold; int ransac_max_iters; double ransac_confidence;   /* 0 = ms_find_homography_ransac's defaults */
+} ms_pair_match_params;
+typedef struct ms_feature_match { int query, train, distance, inlier; } ms_feature_match;   /* query in view_a, train in view_b */
+typedef struct ms_pair_matches {
+    int view_a, view_b;            /* view_a < view_b */
+    int first, count;              /* this pair's slice of matches_out */
+    int n_forward;                 /* how many of them came from the a -> b direction (they come first) */
+    int num_inliers, have_H;
+    double H[9];                   /* centred pixels of view_a -> centred pixels of view_b: ms_pair_homography's convention */
+    double confidence;
+} ms_pair_matches;
+/* match_conf 0.3f, thresholds 6 and 6 (BestOf2NearestMatcher's defaults with the ORB match_conf of stitching_detailed), every pair, RANSAC defaults */
+MS_API int ms_pair_match_default_params(ms_pair_match_params *prm);
+MS_API int ms_match_pairs(int n_views, const ms_view_features *views, const ms_pair_match_params *prm,
+                          ms_pair_matches *pairs_out, int pairs_cap, int *n_pairs,
+                          ms_feature_match *matches_out, int matches_cap, int *n_matches, ms_stream stream);
+/* leaveBiggestComponent (motion_estimators.cpp:1041-1097).  Host only, no device.  The views are joined over the pairs with confidence >= conf_threshold;
+ * keep receives the views of the largest component in ascending order (room for n_views), *n_keep their number.  Among components of equal size the one
+ * that holds the lowest view index wins.  n_views in [1, MS_MAX_VIEWS]; pairs may be NULL where n_pairs is 0 (then keep is view 0 alone).
+ * MS_ERR_INVALID: a null pointer, a negative n_pairs, a view index out of range, view_a == view_b, a conf_threshold that is not a number. */
+MS_API int ms_biggest_component(int n_views, const ms_pair_matches *pairs, int n_pairs, double conf_threshold, int *keep, int *n_keep);
+/* waveCorrect (motion_estimators.cpp:892-970) in double (the reference works in float).  Host only, no device.  R_in / R_out: n_views x 9 doubles row-major,
+ * camera to rig; they may be the same array.  moment = sum over the views of x x^T, x a rotation's first column; its eigenvectors by cyclic Jacobi rotations,
+ * eigenvalues in descending order as cv::eigen gives them; rg1 = the eigenvector of the smallest eigenvalue for MS_WAVE_HORIZ, of the largest for MS_WAVE_VERT;
+ * rg0 = rg1 x (sum of the third columns), normalised; rg2 = rg0 x rg1; HORIZ: sum of rg0 . x < 0, VERT: sum of rg1 . x > 0 negates rg0 and rg1 (lines 936-956:
+ * the result does not depend on the eigenvector's sign); R_out[v] = [rg0; rg1; rg2] R_in[v].  Returns 1 with R_out = R_in where |rg0| <= DBL_MIN or
+ * n_views <= 1 (the reference returns without touching the rotations).  MS_ERR_INVALID: a null pointer, n_views outside [1, MS_MAX_VIEWS], another kind,
+ * a rotation entry that is not finite. */
+enum { MS_WAVE_HORIZ = 0, MS_WAVE_VERT = 1 };
+MS_API int ms_wave_correct(int n_views, const double *R_in, int kind, double *R_out);
+
 /* device-resident static tables, for parity tests: x_maps[i]/y_maps[i] (32FC1), masks (8UC1),
  * weight pyramid level (32FC1). Borrowed pointers owned by ctx. */
 MS_API int ms_get_maps(const ms_ctx *ctx, int view, ms_image *xmap, ms_image *ymap);

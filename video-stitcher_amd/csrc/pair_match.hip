@@ -1,0 +1,425 @@
+// pair_match.hip -- every view pair of a rig matched in one call (gfx950): detail::BestOf2NearestMatcher / BestOf2NearestRangeMatcher
+// (OCV/stitching/src/matchers.cpp:248-297 two-direction 2-NN + ratio test + cross-check, :692-770 homography and confidence, :784-808 candidate pairs),
+// then the two host steps that follow it in Stitcher::estimateCameraParams: leaveBiggestComponent (motion_estimators.cpp:1041-1097) and waveCorrect (:892-970).
+//
+// Two launches whatever the number of pairs.  k_pair_knn2: the grid is laid over a table of (directed pair, first query) entries; a workgroup scores 64
+// queries (one a lane, the descriptor in registers) against tiles of 256 train rows staged in LDS -- a train row comes from L2 once per workgroup and tile,
+// every LDS read is a broadcast --, its four waves take a quarter of the tile each and merge their (distance, index)-ordered best pairs at the end.
+// k_pair_select: one workgroup a pair applies the ratio test and the cross-check and compacts with a ballot / prefix scan, so the list order is exact and
+// no atomic assigns a position.  Integer work but for the one float compare of the ratio test (-ffp-contract=off: one multiply, one compare).
+#include <cfloat>
+#include <climits>
+#include <cmath>
+#include <vector>
+#include "common.hpp"
+
+namespace ms {
+namespace {
+
+constexpr int PM_QUERIES = 64;         // queries a workgroup: one a lane
+constexpr int PM_TILE = 256;           // train rows a tile: 8 KiB of LDS at 32 bytes a row, 16 KiB at 64
+constexpr int PM_THREADS = 256;
+
+struct PmView { const uint8_t *desc; size_t step; int n, pad; };
+struct PmSeg { int qview, tview; unsigned knn_off, pad; };             // a directed pair: the rows of qview against the rows of tview (>= 2 of them)
+struct PmBlock { int seg, q0; };
+struct PmPair { int na, nb; unsigned knn_ab, knn_ba, slot_off, pad; };   // a pair with both views non-empty; its list has room for na + nb slots
+
+// ms_knn_match_hamming2's order, as matcher.hip states it (that unit is left as it is: its object file stays byte-identical)
+struct Best2 { int d0, j0, d1, j1; };
+
+__device__ __forceinline__ bool before(int da, int ja, int db, int jb) { return da < db || (da == db && ja < jb); }
+
+__device__ __forceinline__ void insert(Best2 &b, int d, int j)
+{
+    if (before(d, j, b.d0, b.j0)) { b.d1 = b.d0; b.j1 = b.j0; b.d0 = d; b.j0 = j; }
+    else if (before(d, j, b.d1, b.j1)) { b.d1 = d; b.j1 = j; }
+}
+
+// knn[seg.knn_off + q] = (j0, d0, j1, d1): ms_knn_match_hamming2's rule.  Only directed pairs whose train side has two rows or more are in the table.
+template <int WORDS>
+__global__ void __launch_bounds__(PM_THREADS) k_pair_knn2(const PmView *__restrict__ views, const PmSeg *__restrict__ segs, const PmBlock *__restrict__ blocks, int words,
+                                                          int4 *__restrict__ knn)
+{
+    constexpr int MAXW = WORDS ? WORDS : 16;
+    __shared__ __attribute__((aligned(16))) unsigned tile[PM_TILE * MAXW];
+    __shared__ int4 part[PM_THREADS / 64 - 1][64];
+    const PmBlock blk = blocks[blockIdx.x];
+    const PmSeg seg = segs[blk.seg];
+    const PmView qv = views[seg.qview], tv = views[seg.tview];
+    const int W = WORDS ? WORDS : words;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int q = blk.q0 + lane;
+    const bool live = q < qv.n;
+    unsigned qw[MAXW];
+    const unsigned *qp = (const unsigned *)(qv.desc + (size_t)(live ? q : blk.q0) * qv.step);      // (blk.q0 < qv.n: the table holds no empty block)
+#pragma unroll
+    for (int k = 0; k < MAXW; ++k) qw[k] = k < W ? qp[k] : 0u;
+    Best2 b{INT_MAX, INT_MAX, INT_MAX, INT_MAX};          // index INT_MAX = "none": sorts after every real row
+    for (int t0 = 0; t0 < tv.n; t0 += PM_TILE) {
+        const int rows = min(PM_TILE, tv.n - t0);
+        __syncthreads();                                  // the previous tile has been scored by every wave
+        for (int i = threadIdx.x; i < rows * W; i += PM_THREADS) {
+            const int r = i / W, k = i - r * W;
+            tile[i] = ((const unsigned *)(tv.desc + (size_t)(t0 + r) * tv.step))[k];
+        }
+        __syncthreads();
+        const int r1 = min(rows, wave * 64 + 64);
+#pragma unroll 4
+        for (int r = wave * 64; r < r1; ++r) {
+            const unsigned *tp = tile + r * W;
+            int d = 0;
+#pragma unroll
+            for (int k = 0; k < MAXW; ++k)
+                if (k < W) d += __popc(qw[k] ^ tp[k]);
+            insert(b, d, t0 + r);
+        }
+    }
+    if (wave) part[wave - 1][lane] = make_int4(b.d0, b.j0, b.d1, b.j1);
+    __syncthreads();
+    if (wave == 0 && live) {
+        for (int w = 0; w < PM_THREADS / 64 - 1; ++w) {
+            const int4 o = part[w][lane];
+            insert(b, o.x, o.y);
+            insert(b, o.z, o.w);
+        }
+        knn[seg.knn_off + q] = make_int4(b.j0, b.d0, b.j1, b.d1);
+    }
+}
+
+// the position of a passing thread among the passing threads of the workgroup, in thread order; total = how many pass.  Called by every thread.
+__device__ __forceinline__ int block_rank(bool pass, int *wsum, int &total)
+{
+    const unsigned long long m = __ballot(pass);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __syncthreads();                                      // the previous round's sums have been read
+    if (lane == 0) wsum[wave] = __popcll(m);
+    __syncthreads();
+    int off = 0;
+    total = 0;
+#pragma unroll
+    for (int w = 0; w < PM_THREADS / 64; ++w) { const int c = wsum[w]; off += w < wave ? c : 0; total += c; }
+    return off + __popcll(m & ((1ull << lane) - 1ull));
+}
+
+__device__ __forceinline__ bool ratio_pass(const int4 e, float t) { return (float)e.y < t * (float)e.w; }
+
+// slots[p.slot_off ..]: the pair's list, query | train << 16 (both below 2^15) and the distance; hdr[pair] = (count, n_forward)
+__global__ void __launch_bounds__(PM_THREADS) k_pair_select(const PmPair *__restrict__ pairs, const int4 *__restrict__ knn, float t, int2 *__restrict__ hdr,
+                                                            uint2 *__restrict__ slots)
+{
+    __shared__ int wsum[PM_THREADS / 64];
+    const PmPair p = pairs[blockIdx.x];
+    uint2 *out = slots + p.slot_off;
+    int base = 0, total;
+    if (p.nb >= 2)
+        for (int q0 = 0; q0 < p.na; q0 += PM_THREADS) {
+            const int q = q0 + (int)threadIdx.x;
+            int4 e = make_int4(0, 0, 0, 0);
+            bool pass = false;
+            if (q < p.na) { e = knn[p.knn_ab + q]; pass = ratio_pass(e, t); }
+            const int pos = block_rank(pass, wsum, total);
+            if (pass) out[base + pos] = make_uint2((unsigned)q | ((unsigned)e.x << 16), (unsigned)e.y);
+            base += total;
+        }
+    const int n_forward = base;
+    if (p.na >= 2)
+        for (int q0 = 0; q0 < p.nb; q0 += PM_THREADS) {
+            const int q = q0 + (int)threadIdx.x;
+            int4 e = make_int4(0, 0, 0, 0);
+            bool pass = false;
+            if (q < p.nb) { e = knn[p.knn_ba + q]; pass = ratio_pass(e, t); }
+            if (pass && p.nb >= 2) {                      // (j0, q) already listed: row j0 of a passed and its nearest row is q
+                const int4 f = knn[p.knn_ab + e.x];
+                if (f.x == q && ratio_pass(f, t)) pass = false;
+            }
+            const int pos = block_rank(pass, wsum, total);
+            if (pass) out[base + pos] = make_uint2((unsigned)e.x | ((unsigned)q << 16), (unsigned)e.y);
+            base += total;
+        }
+    if (threadIdx.x == 0) hdr[blockIdx.x] = make_int2(base, n_forward);
+}
+
+size_t pm_align(size_t n) { return (n + 255) & ~(size_t)255; }
+
+double pm_det3(const double *H)
+{
+    return H[0] * (H[4] * H[8] - H[5] * H[7]) - H[1] * (H[3] * H[8] - H[5] * H[6]) + H[2] * (H[3] * H[7] - H[4] * H[6]);
+}
+
+// cyclic Jacobi on a symmetric 3 x 3: A -> eigenvalues on the diagonal, V's columns the eigenvectors
+void pm_jacobi3(double A[3][3], double V[3][3])
+{
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) V[i][j] = i == j ? 1.0 : 0.0;
+    for (int sweep = 0; sweep < 64; ++sweep) {
+        const double off = std::fabs(A[0][1]) + std::fabs(A[0][2]) + std::fabs(A[1][2]);
+        if (off == 0.0) break;
+        for (int p = 0; p < 2; ++p)
+            for (int q = p + 1; q < 3; ++q) {
+                if (A[p][q] == 0.0) continue;
+                const double theta = (A[q][q] - A[p][p]) / (2.0 * A[p][q]);
+                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+                const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+                for (int k = 0; k < 3; ++k) { const double akp = A[k][p], akq = A[k][q]; A[k][p] = c * akp - s * akq; A[k][q] = s * akp + c * akq; }
+                for (int k = 0; k < 3; ++k) { const double apk = A[p][k], aqk = A[q][k]; A[p][k] = c * apk - s * aqk; A[q][k] = s * apk + c * aqk; }
+                A[p][q] = A[q][p] = 0.0;                  // (what the rotation makes of it, up to rounding)
+                for (int k = 0; k < 3; ++k) { const double vkp = V[k][p], vkq = V[k][q]; V[k][p] = c * vkp - s * vkq; V[k][q] = s * vkp + c * vkq; }
+            }
+    }
+}
+
+void pm_cross(const double a[3], const double b[3], double o[3])
+{
+    o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+}  // namespace
+}  // namespace ms
+
+using namespace ms;
+
+extern "C" {
+
+int ms_pair_match_default_params(ms_pair_match_params *prm)
+{
+    MS_CHECK(prm, "ms_pair_match_default_params: null params");
+    *prm = ms_pair_match_params{};
+    prm->struct_size = (unsigned)sizeof(ms_pair_match_params);
+    prm->match_conf = 0.3f; prm->num_matches_thresh1 = 6; prm->num_matches_thresh2 = 6; prm->range_width = 0; prm->pair_mask = nullptr;
+    prm->ransac_reproj_threshold = 0.0; prm->ransac_max_iters = 0; prm->ransac_confidence = 0.0;
+    return MS_OK;
+}
+
+int ms_match_pairs(int n_views, const ms_view_features *views, const ms_pair_match_params *prm, ms_pair_matches *pairs_out, int pairs_cap, int *n_pairs,
+                   ms_feature_match *matches_out, int matches_cap, int *n_matches, ms_stream stream)
+{
+    const char *fn = "ms_match_pairs";
+    MS_CHECK(views && prm && pairs_out && n_pairs && matches_out && n_matches, "%s: null argument", fn);
+    MS_CHECK(n_views >= 2 && n_views <= MS_MAX_VIEWS, "%s: n_views = %d outside [2, %d]", fn, n_views, MS_MAX_VIEWS);
+    MS_CHECK(prm->struct_size == sizeof(ms_pair_match_params), "%s: params struct_size %u, this library's is %zu", fn, prm->struct_size, sizeof(ms_pair_match_params));
+    MS_CHECK(std::isfinite(prm->match_conf) && prm->match_conf >= 0.f && prm->match_conf < 1.f, "%s: match_conf %g outside [0, 1)", fn, (double)prm->match_conf);
+    MS_CHECK(prm->num_matches_thresh1 >= 0 && prm->num_matches_thresh2 >= 0, "%s: num_matches_thresh1 / num_matches_thresh2 = %d / %d must not be negative", fn,
+             prm->num_matches_thresh1, prm->num_matches_thresh2);
+    MS_CHECK(prm->range_width >= 0, "%s: range_width %d must not be negative", fn, prm->range_width);
+    MS_CHECK(std::isfinite(prm->ransac_reproj_threshold) && prm->ransac_reproj_threshold >= 0.0 && prm->ransac_max_iters >= 0 && std::isfinite(prm->ransac_confidence) &&
+                 prm->ransac_confidence >= 0.0 && prm->ransac_confidence < 1.0,
+             "%s: ransac_reproj_threshold / ransac_max_iters / ransac_confidence = %g / %d / %g (0 = the default; confidence below 1)", fn, prm->ransac_reproj_threshold,
+             prm->ransac_max_iters, prm->ransac_confidence);
+    MS_CHECK(pairs_cap >= 0 && matches_cap >= 0, "%s: pairs_cap / matches_cap = %d / %d must not be negative", fn, pairs_cap, matches_cap);
+    int bytes = 0;
+    for (int v = 0; v < n_views; ++v) {
+        const ms_view_features &f = views[v];
+        MS_CHECK(f.n_keypoints >= 0 && f.n_keypoints <= MS_MATCH_MAX_KEYPOINTS, "%s: view %d: n_keypoints %d outside [0, %d]", fn, v, f.n_keypoints, MS_MATCH_MAX_KEYPOINTS);
+        MS_CHECK(f.n_keypoints <= f.descriptors.rows, "%s: view %d: n_keypoints %d above descriptors.rows %d", fn, v, f.n_keypoints, f.descriptors.rows);
+        MS_CHECK(f.keypoint_stride >= 2, "%s: view %d: keypoint_stride %d below 2", fn, v, f.keypoint_stride);
+        MS_CHECK(f.width >= 1 && f.height >= 1, "%s: view %d: image size (width, height) %d x %d", fn, v, f.width, f.height);
+        if (f.n_keypoints == 0) continue;
+        MS_CHECK(f.keypoints, "%s: view %d: null keypoints", fn, v);
+        MS_CHECK(f.descriptors.data, "%s: view %d: null descriptors", fn, v);
+        MS_CHECK(f.descriptors.type == MS_8UC1, "%s: view %d: descriptors type %d (need 8UC1)", fn, v, f.descriptors.type);
+        MS_CHECK(f.descriptors.cols > 0 && f.descriptors.cols % 4 == 0 && f.descriptors.cols <= 64, "%s: view %d: descriptor length %d (need a multiple of 4 up to 64 bytes)", fn, v,
+                 f.descriptors.cols);
+        MS_CHECK(f.descriptors.step % 4 == 0 && f.descriptors.step >= (size_t)f.descriptors.cols && (uintptr_t)f.descriptors.data % 4 == 0,
+                 "%s: view %d: descriptors step %zu / data must be 4-byte aligned and the step not below the row", fn, v, f.descriptors.step);
+        MS_CHECK(bytes == 0 || bytes == f.descriptors.cols, "%s: view %d: descriptor length %d differs from %d of an earlier view", fn, v, f.descriptors.cols, bytes);
+        bytes = f.descriptors.cols;
+    }
+    // the candidate pairs (matchers.cpp:794-798)
+    std::vector<int> cand;
+    for (int i = 0; i < n_views - 1; ++i)
+        for (int j = i + 1; j < n_views; ++j) {
+            if (prm->range_width > 0 && j >= i + prm->range_width) continue;
+            if (prm->pair_mask && !prm->pair_mask[i * n_views + j]) continue;
+            cand.push_back(i * n_views + j);
+        }
+    const int np = (int)cand.size();
+    MS_CHECK(pairs_cap >= np, "%s: pairs_cap %d below the %d candidate pairs", fn, pairs_cap, np);
+    if (int e = require_device()) return e;
+    hipStream_t st = as_stream(stream);
+
+    // tables: views, directed pairs, (directed pair, first query) blocks, active pairs
+    std::vector<PmView> hv(n_views);
+    for (int v = 0; v < n_views; ++v) hv[v] = PmView{(const uint8_t *)views[v].descriptors.data, views[v].descriptors.step, views[v].n_keypoints, 0};
+    std::vector<PmSeg> segs;
+    std::vector<PmBlock> blocks;
+    std::vector<PmPair> active;
+    std::vector<int> active_of(np, -1);
+    size_t knn_n = 0, slot_n = 0;
+    for (int k = 0; k < np; ++k) {
+        const int a = cand[k] / n_views, b = cand[k] % n_views, na = hv[a].n, nb = hv[b].n;
+        if (na == 0 || nb == 0) continue;
+        PmPair p{na, nb, 0u, 0u, (unsigned)slot_n, 0u};
+        for (int dir = 0; dir < 2; ++dir) {
+            const int qv = dir ? b : a, tv = dir ? a : b;
+            if (hv[tv].n < 2) continue;
+            (dir ? p.knn_ba : p.knn_ab) = (unsigned)knn_n;
+            for (int q0 = 0; q0 < hv[qv].n; q0 += PM_QUERIES) blocks.push_back(PmBlock{(int)segs.size(), q0});
+            segs.push_back(PmSeg{qv, tv, (unsigned)knn_n, 0u});
+            knn_n += (size_t)hv[qv].n;
+        }
+        active_of[k] = (int)active.size();
+        active.push_back(p);
+        slot_n += (size_t)(na + nb);
+    }
+    const int n_active = (int)active.size();
+    std::vector<int2> hdr(n_active);
+    std::vector<uint2> slots;
+    if (n_active) {
+        const size_t o_views = 0, o_segs = o_views + pm_align(hv.size() * sizeof(PmView)), o_blocks = o_segs + pm_align(segs.size() * sizeof(PmSeg)),
+                     o_pairs = o_blocks + pm_align(blocks.size() * sizeof(PmBlock)), up_bytes = o_pairs + pm_align(active.size() * sizeof(PmPair));
+        const size_t o_knn = up_bytes, o_out = o_knn + pm_align(knn_n * sizeof(int4)), o_slots = pm_align((size_t)n_active * sizeof(int2)),
+                     out_bytes = o_slots + slot_n * sizeof(uint2);
+        char *dev = (char *)device_scratch().get(o_out + out_bytes);         // per-thread grow-only block: see DeviceScratch (common.hpp)
+        if (!dev) return fail(MS_ERR_NOMEM, "%s: cannot allocate %zu bytes of device scratch", fn, o_out + out_bytes);
+        char *pin = (char *)pinned_scratch().get(up_bytes + out_bytes);
+        if (!pin) return fail(MS_ERR_NOMEM, "%s: cannot allocate pinned staging memory", fn);
+        memcpy(pin + o_views, hv.data(), hv.size() * sizeof(PmView));
+        if (!segs.empty()) memcpy(pin + o_segs, segs.data(), segs.size() * sizeof(PmSeg));
+        if (!blocks.empty()) memcpy(pin + o_blocks, blocks.data(), blocks.size() * sizeof(PmBlock));
+        memcpy(pin + o_pairs, active.data(), active.size() * sizeof(PmPair));
+        hipError_t e = hipMemcpyAsync(dev, pin, up_bytes, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && !blocks.empty()) {
+            const PmView *dv = (const PmView *)(dev + o_views); const PmSeg *ds = (const PmSeg *)(dev + o_segs); const PmBlock *db = (const PmBlock *)(dev + o_blocks);
+            if (bytes == 32) k_pair_knn2<8><<<(unsigned)blocks.size(), PM_THREADS, 0, st>>>(dv, ds, db, 8, (int4 *)(dev + o_knn));
+            else k_pair_knn2<0><<<(unsigned)blocks.size(), PM_THREADS, 0, st>>>(dv, ds, db, bytes / 4, (int4 *)(dev + o_knn));
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) {
+            k_pair_select<<<n_active, PM_THREADS, 0, st>>>((const PmPair *)(dev + o_pairs), (const int4 *)(dev + o_knn), 1.f - prm->match_conf, (int2 *)(dev + o_out),
+                                                           (uint2 *)(dev + o_out + o_slots));
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(pin + up_bytes, dev + o_out, out_bytes, hipMemcpyDeviceToHost, st);
+        const hipError_t se = hipStreamSynchronize(st);      // also after a failed enqueue: nothing of this call stays in flight over the scratch blocks
+        MS_HIP(e);
+        MS_HIP(se);
+        memcpy(hdr.data(), pin + up_bytes, (size_t)n_active * sizeof(int2));
+        slots.resize(slot_n);
+        if (slot_n) memcpy(slots.data(), pin + up_bytes + o_slots, slot_n * sizeof(uint2));      // (ms_find_homography_ransac below stages through the same pinned block)
+    }
+    long long total = 0;
+    for (int k = 0; k < n_active; ++k) {
+        if (hdr[k].x < 0 || hdr[k].x > active[k].na + active[k].nb || hdr[k].y < 0 || hdr[k].y > hdr[k].x)
+            return fail(MS_ERR_HIP, "%s: the device returned an impossible match count (%d, %d) for an active pair", fn, hdr[k].x, hdr[k].y);
+        total += hdr[k].x;
+    }
+    *n_pairs = np;
+    *n_matches = (int)total;
+    MS_CHECK(total <= matches_cap, "%s: matches_cap %d below the %lld matches found (*n_matches holds the number)", fn, matches_cap, total);
+
+    int first = 0;
+    std::vector<float> src, dst, src_in, dst_in;
+    std::vector<uint8_t> mask;
+    for (int k = 0; k < np; ++k) {
+        ms_pair_matches &pm = pairs_out[k];
+        pm = ms_pair_matches{};
+        const int a = cand[k] / n_views, b = cand[k] % n_views;
+        pm.view_a = a; pm.view_b = b; pm.first = first;
+        if (active_of[k] < 0) continue;
+        const int count = hdr[active_of[k]].x;
+        pm.count = count; pm.n_forward = hdr[active_of[k]].y;
+        const uint2 *sl = slots.data() + active[active_of[k]].slot_off;
+        ms_feature_match *m = matches_out + first;
+        for (int i = 0; i < count; ++i) m[i] = ms_feature_match{(int)(sl[i].x & 0xffffu), (int)(sl[i].x >> 16), (int)sl[i].y, 0};
+        first += count;
+        if (count < prm->num_matches_thresh1) continue;
+        // BestOf2NearestMatcher::match (matchers.cpp:699-770)
+        const ms_view_features &fa = views[a], &fb = views[b];
+        src.resize(2 * (size_t)count); dst.resize(2 * (size_t)count); mask.assign((size_t)count + 1, 0);
+        for (int i = 0; i < count; ++i) {
+            const float *pa = fa.keypoints + (size_t)m[i].query * fa.keypoint_stride, *pb = fb.keypoints + (size_t)m[i].train * fb.keypoint_stride;
+            src[2 * i] = pa[0] - fa.width * 0.5f; src[2 * i + 1] = pa[1] - fa.height * 0.5f;
+            dst[2 * i] = pb[0] - fb.width * 0.5f; dst[2 * i + 1] = pb[1] - fb.height * 0.5f;
+        }
+        int ninl = 0;
+        int rc = ms_find_homography_ransac(src.data(), dst.data(), count, prm->ransac_reproj_threshold, prm->ransac_max_iters, prm->ransac_confidence, pm.H, mask.data(), &ninl,
+                                           stream);
+        if (rc < 0) return rc;
+        if (rc == 1) continue;                            // no model: have_H = 0
+        pm.have_H = 1;
+        if (std::fabs(pm_det3(pm.H)) < DBL_EPSILON) continue;
+        pm.num_inliers = 0;
+        for (int i = 0; i < count; ++i) { m[i].inlier = mask[i] ? 1 : 0; pm.num_inliers += m[i].inlier; }
+        pm.confidence = pm.num_inliers / (8 + 0.3 * count);
+        if (pm.confidence > 3.) pm.confidence = 0.;
+        if (pm.num_inliers < prm->num_matches_thresh2) continue;
+        src_in.clear(); dst_in.clear();
+        for (int i = 0; i < count; ++i)
+            if (m[i].inlier) { src_in.push_back(src[2 * i]); src_in.push_back(src[2 * i + 1]); dst_in.push_back(dst[2 * i]); dst_in.push_back(dst[2 * i + 1]); }
+        rc = ms_find_homography_ransac(src_in.data(), dst_in.data(), pm.num_inliers, prm->ransac_reproj_threshold, prm->ransac_max_iters, prm->ransac_confidence, pm.H, nullptr,
+                                       nullptr, stream);
+        if (rc < 0) return rc;
+        if (rc == 1) pm.have_H = 0;
+    }
+    return MS_OK;
+}
+
+int ms_biggest_component(int n_views, const ms_pair_matches *pairs, int n_pairs, double conf_threshold, int *keep, int *n_keep)
+{
+    const char *fn = "ms_biggest_component";
+    MS_CHECK(keep && n_keep && (pairs || n_pairs == 0), "%s: null argument", fn);
+    MS_CHECK(n_views >= 1 && n_views <= MS_MAX_VIEWS, "%s: n_views = %d outside [1, %d]", fn, n_views, MS_MAX_VIEWS);
+    MS_CHECK(n_pairs >= 0, "%s: n_pairs = %d must not be negative", fn, n_pairs);
+    MS_CHECK(!std::isnan(conf_threshold), "%s: conf_threshold is not a number", fn);
+    int comp[MS_MAX_VIEWS], size[MS_MAX_VIEWS] = {0};
+    for (int v = 0; v < n_views; ++v) comp[v] = v;        // a component is named by its lowest view
+    for (int k = 0; k < n_pairs; ++k) {
+        const int a = pairs[k].view_a, b = pairs[k].view_b;
+        MS_CHECK(a >= 0 && a < n_views && b >= 0 && b < n_views, "%s: pair %d names views %d, %d outside [0, %d)", fn, k, a, b, n_views);
+        MS_CHECK(a != b, "%s: pair %d pairs view %d with itself", fn, k, a);
+        if (!(pairs[k].confidence >= conf_threshold)) continue;
+        const int lo = comp[a] < comp[b] ? comp[a] : comp[b], hi = comp[a] < comp[b] ? comp[b] : comp[a];
+        for (int v = 0; v < n_views; ++v) if (comp[v] == hi) comp[v] = lo;
+    }
+    for (int v = 0; v < n_views; ++v) ++size[comp[v]];
+    int best = 0;
+    for (int v = 1; v < n_views; ++v) if (size[v] > size[best]) best = v;      // ties: the component with the lowest view
+    int n = 0;
+    for (int v = 0; v < n_views; ++v) if (comp[v] == best) keep[n++] = v;
+    *n_keep = n;
+    return MS_OK;
+}
+
+int ms_wave_correct(int n_views, const double *R_in, int kind, double *R_out)
+{
+    const char *fn = "ms_wave_correct";
+    MS_CHECK(R_in && R_out, "%s: null argument", fn);
+    MS_CHECK(n_views >= 1 && n_views <= MS_MAX_VIEWS, "%s: n_views = %d outside [1, %d]", fn, n_views, MS_MAX_VIEWS);
+    MS_CHECK(kind == MS_WAVE_HORIZ || kind == MS_WAVE_VERT, "%s: kind %d (MS_WAVE_HORIZ = 0, MS_WAVE_VERT = 1)", fn, kind);
+    for (int k = 0; k < 9 * n_views; ++k) MS_CHECK(std::isfinite(R_in[k]), "%s: view %d: rotation entry %d is not finite", fn, k / 9, k % 9);
+    double Rc[MS_MAX_VIEWS * 9];
+    memcpy(Rc, R_in, sizeof(double) * 9 * (size_t)n_views);                     // R_out may be R_in
+    memcpy(R_out, Rc, sizeof(double) * 9 * (size_t)n_views);
+    if (n_views <= 1) return 1;
+    double A[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, V[3][3], img_k[3] = {0, 0, 0};
+    for (int v = 0; v < n_views; ++v) {
+        const double *R = Rc + 9 * v, x[3] = {R[0], R[3], R[6]};
+        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) A[i][j] += x[i] * x[j];
+        img_k[0] += R[2]; img_k[1] += R[5]; img_k[2] += R[8];
+    }
+    pm_jacobi3(A, V);
+    int order[3] = {0, 1, 2};                             // descending eigenvalues, the earlier first among equals
+    for (int i = 0; i < 2; ++i) for (int j = 0; j < 2 - i; ++j) if (A[order[j]][order[j]] < A[order[j + 1]][order[j + 1]]) { const int t = order[j]; order[j] = order[j + 1]; order[j + 1] = t; }
+    const int col = kind == MS_WAVE_HORIZ ? order[2] : order[0];
+    double rg1[3] = {V[0][col], V[1][col], V[2][col]}, rg0[3], rg2[3];
+    pm_cross(rg1, img_k, rg0);
+    const double norm = std::sqrt(rg0[0] * rg0[0] + rg0[1] * rg0[1] + rg0[2] * rg0[2]);
+    if (norm <= DBL_MIN) return 1;
+    for (int i = 0; i < 3; ++i) rg0[i] /= norm;
+    pm_cross(rg0, rg1, rg2);
+    double conf = 0.0;
+    for (int v = 0; v < n_views; ++v) {
+        const double *R = Rc + 9 * v;
+        if (kind == MS_WAVE_HORIZ) conf += rg0[0] * R[0] + rg0[1] * R[3] + rg0[2] * R[6];
+        else conf -= rg1[0] * R[0] + rg1[1] * R[3] + rg1[2] * R[6];
+    }
+    if (conf < 0) for (int i = 0; i < 3; ++i) { rg0[i] = -rg0[i]; rg1[i] = -rg1[i]; }
+    const double *G[3] = {rg0, rg1, rg2};
+    for (int v = 0; v < n_views; ++v)
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c)
+                R_out[9 * v + 3 * r + c] = G[r][0] * Rc[9 * v + c] + G[r][1] * Rc[9 * v + 3 + c] + G[r][2] * Rc[9 * v + 6 + c];
+    return MS_OK;
+}
+
+}  // extern "C"

@@ -151,6 +151,29 @@ class RigFocalInfo(C.Structure):
                 ("pairs_used", C.c_int), ("pairs_ignored", C.c_int), ("outliers", C.c_int), ("max_rotation_rad", C.c_double), ("max_focal_ratio", C.c_double)]
 
 
+MATCH_MAX_KEYPOINTS = 32768         # MS_MATCH_MAX_KEYPOINTS
+WAVE_HORIZ, WAVE_VERT = 0, 1        # ms_wave_correct
+
+
+class ViewFeatures(C.Structure):
+    _fields_ = [("descriptors", Image), ("keypoints", C.POINTER(C.c_float)), ("keypoint_stride", C.c_int), ("n_keypoints", C.c_int), ("width", C.c_int),
+                ("height", C.c_int)]
+
+
+class PairMatchParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("match_conf", C.c_float), ("num_matches_thresh1", C.c_int), ("num_matches_thresh2", C.c_int), ("range_width", C.c_int),
+                ("pair_mask", C.POINTER(C.c_ubyte)), ("ransac_reproj_threshold", C.c_double), ("ransac_max_iters", C.c_int), ("ransac_confidence", C.c_double)]
+
+
+class FeatureMatch(C.Structure):
+    _fields_ = [("query", C.c_int), ("train", C.c_int), ("distance", C.c_int), ("inlier", C.c_int)]
+
+
+class PairMatches(C.Structure):
+    _fields_ = [("view_a", C.c_int), ("view_b", C.c_int), ("first", C.c_int), ("count", C.c_int), ("n_forward", C.c_int), ("num_inliers", C.c_int), ("have_H", C.c_int),
+                ("H", C.c_double * 9), ("confidence", C.c_double)]
+
+
 class GainTrackParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint), ("stride", C.c_int), ("smoothing", C.c_double)]
 
@@ -208,6 +231,7 @@ EXPORTS = [
     "ms_warper_rays", "ms_rig_refine_default_params", "ms_rig_accumulate", "ms_refine_rig_rotations", "ms_refine_rig",
     "ms_dp_seams", "ms_set_seam_finder", "ms_get_seam_finder",
     "ms_focals_from_homography", "ms_estimate_rig", "ms_rig_focal_default_params", "ms_rig_focal_accumulate", "ms_refine_rig_cameras", "ms_refine_rig_focals",
+    "ms_pair_match_default_params", "ms_match_pairs", "ms_biggest_component", "ms_wave_correct",
 ]
 
 _lib = None
@@ -678,6 +702,94 @@ def refine_rig_cameras(f, R, matches, params=None):
     _chk(load().ms_refine_rig_cameras(n, fa.ctypes.data_as(dp), Ra.ctypes.data_as(dp), rig_px_matches(matches), len(matches), C.byref(prm), fo.ctypes.data_as(dp),
                                       out.ctypes.data_as(dp), C.byref(info), _stream()))
     return fo, out, _rig_focal_info(info)
+
+
+def pair_match_default_params(**kw):
+    """ms_pair_match_default_params; keyword arguments override fields (pair_mask: see match_pairs)"""
+    p = PairMatchParams()
+    _chk(load().ms_pair_match_default_params(C.byref(p)))
+    for k, v in kw.items():
+        assert hasattr(p, k), k
+        setattr(p, k, v)
+    return p
+
+
+def view_features(features):
+    """[(keypoints (n, >= 2) float32 numpy -- x, y first, ms.orb_detect_and_compute's rows as they are --, descriptors torch uint8 (rows >= n, bytes) on the device or
+    None for an empty view, (width, height)), ...] -> (a ViewFeatures array, the objects it borrows from: keep them alive as long as the array)"""
+    import numpy as np
+    arr = (ViewFeatures * max(1, len(features)))()
+    keep = []
+    for v, (kp, desc, size) in enumerate(features):
+        kp = np.ascontiguousarray(kp, np.float32)
+        if kp.ndim != 2:
+            kp = kp.reshape(-1, 2)
+        keep.append((kp, desc))
+        arr[v] = ViewFeatures(Image() if desc is None else img(desc), kp.ctypes.data_as(C.POINTER(C.c_float)), max(2, kp.shape[1]), kp.shape[0], int(size[0]), int(size[1]))
+    return arr, keep
+
+
+def match_pairs(features, matches_cap=None, params=None, pair_mask=None, **kw):
+    """ms_match_pairs (detail::BestOf2NearestMatcher over every candidate pair): features as view_features takes them; keyword arguments override fields of
+    ms_pair_match_params (match_conf, num_matches_thresh1, num_matches_thresh2, range_width, ransac_*); pair_mask: (n, n) uint8 or None.
+    Returns a list with one dict per candidate pair: view_a, view_b, first, count, n_forward, num_inliers, have_H, H (3 x 3 float64, None without a model),
+    confidence, and matches, a (count, 4) int32 array of (query in view_a, train in view_b, distance, inlier)."""
+    import numpy as np
+    n = len(features)
+    prm = params if params is not None else pair_match_default_params(**kw)
+    mask = None
+    if pair_mask is not None:
+        mask = np.ascontiguousarray(pair_mask, np.uint8)
+        assert mask.shape == (n, n)
+        prm.pair_mask = mask.ctypes.data_as(C.POINTER(C.c_ubyte))
+    views, keep = view_features(features)
+    pairs_cap = max(1, n * (n - 1) // 2)
+    if matches_cap is None:         # a pair's list never holds more than one match per row of either view
+        matches_cap = sum(max(views[i].n_keypoints, 0) for i in range(n)) * max(n - 1, 1)
+    pairs = (PairMatches * pairs_cap)()
+    out = np.zeros((max(1, matches_cap), 4), np.int32)
+    n_pairs, n_matches = C.c_int(0), C.c_int(0)
+    _chk(load().ms_match_pairs(n, views, C.byref(prm), pairs, pairs_cap, C.byref(n_pairs), out.ctypes.data_as(C.POINTER(FeatureMatch)), int(matches_cap), C.byref(n_matches),
+                               _stream()))
+    del keep, mask
+    res = []
+    for k in range(n_pairs.value):
+        p = pairs[k]
+        res.append({"view_a": p.view_a, "view_b": p.view_b, "first": p.first, "count": p.count, "n_forward": p.n_forward, "num_inliers": p.num_inliers, "have_H": p.have_H,
+                    "H": np.array(p.H[:], np.float64).reshape(3, 3) if p.have_H else None, "confidence": p.confidence, "matches": out[p.first:p.first + p.count].copy()})
+    return res
+
+
+def pair_matches(pairs):
+    """match_pairs' records (view_a, view_b, confidence are read) -> a PairMatches array, for biggest_component"""
+    arr = (PairMatches * max(1, len(pairs)))()
+    for k, p in enumerate(pairs):
+        arr[k].view_a, arr[k].view_b, arr[k].confidence = int(p["view_a"]), int(p["view_b"]), float(p["confidence"])
+    return arr
+
+
+def pairs_for_estimate_rig(pairs):
+    """match_pairs' records with a homography -> what estimate_rig takes: (view_a, view_b, H, weight = num_inliers)"""
+    return [(p["view_a"], p["view_b"], p["H"], p["num_inliers"]) for p in pairs if p["have_H"]]
+
+
+def biggest_component(n_views, pairs, conf_threshold=1.0):
+    """ms_biggest_component (leaveBiggestComponent; host only): pairs as match_pairs returns them -> the ascending views of the largest component over the pairs
+    with confidence >= conf_threshold (ties: the component with the lowest view)"""
+    keep = (C.c_int * max(1, n_views))()
+    n_keep = C.c_int(0)
+    _chk(load().ms_biggest_component(int(n_views), pair_matches(pairs) if len(pairs) else None, len(pairs), C.c_double(conf_threshold), keep, C.byref(n_keep)))
+    return list(keep[:n_keep.value])
+
+
+def wave_correct(R, kind=WAVE_HORIZ):
+    """ms_wave_correct (waveCorrect in double; host only): R (n, 3, 3) camera to rig -> (corrected R (n, 3, 3) float64, status: 1 where the input came back unchanged)"""
+    import numpy as np
+    Ra = np.ascontiguousarray(R, np.float64)
+    out = np.empty_like(Ra)
+    dp = C.POINTER(C.c_double)
+    rc = _chk(load().ms_wave_correct(len(Ra), Ra.ctypes.data_as(dp), int(kind), out.ctypes.data_as(dp)))
+    return out, rc
 
 
 def nv12_to_bgr(src, dst=None):

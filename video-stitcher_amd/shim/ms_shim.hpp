@@ -415,6 +415,53 @@ template <class Mat> void matchFeaturesTemporal(const std::vector<ImageFeatures<
         matchPair(features[i], prev_features[i], pairwise_matches[i], s);
     }
 }
+
+// detail::BestOf2NearestMatcher / BestOf2NearestRangeMatcher::operator() (OCV/stitching/src/matchers.cpp:784-808 -> MatchPairsBody, :65-111) over ms_match_pairs:
+// every candidate pair in one call, pairwise_matches the reference's n x n table -- entry (i, j), i < j, as ms_match_pairs returns it, entry (j, i) its dual with
+// queryIdx / trainIdx swapped and H inverted (:88-99).  params: ms_pair_match_default_params with the caller's edits, or nullptr for the defaults.
+template <class Mat> void matchPairs(const std::vector<ImageFeatures<Mat>> &features, std::vector<MatchesInfo> &pairwise_matches, const ms_pair_match_params *params = nullptr,
+                                     ms_stream s = nullptr)
+{
+    static_assert(sizeof(KeyPoint) == 6 * sizeof(float), "KeyPoint rows are read as 6 floats, x and y first");
+    const int n = (int)features.size();
+    ms_pair_match_params prm;
+    check(ms_pair_match_default_params(&prm));
+    if (params) prm = *params;
+    std::vector<ms_view_features> views(n);
+    size_t cap = 0;
+    for (int i = 0; i < n; ++i) {
+        const ImageFeatures<Mat> &f = features[i];
+        views[i] = ms_view_features{wrap(f.descriptors), f.keypoints.empty() ? nullptr : &f.keypoints[0].pt.x, 6, (int)f.keypoints.size(), f.img_size.width, f.img_size.height};
+        cap += f.keypoints.size() * (size_t)(n - 1);         // a pair's list holds at most one match per row of either view
+    }
+    std::vector<ms_pair_matches> pairs((size_t)n * n);
+    std::vector<ms_feature_match> matches(cap + 1);
+    int n_pairs = 0, n_matches = 0;
+    check(ms_match_pairs(n, views.data(), &prm, pairs.data(), n * n, &n_pairs, matches.data(), (int)cap, &n_matches, s));
+    pairwise_matches.assign((size_t)n * n, MatchesInfo());
+    for (int k = 0; k < n_pairs; ++k) {
+        const ms_pair_matches &p = pairs[k];
+        MatchesInfo &m = pairwise_matches[(size_t)p.view_a * n + p.view_b], &dual = pairwise_matches[(size_t)p.view_b * n + p.view_a];
+        m.src_img_idx = p.view_a; m.dst_img_idx = p.view_b;
+        for (int i = 0; i < p.count; ++i) {
+            const ms_feature_match &fm = matches[p.first + i];
+            m.matches.push_back(DMatch{fm.query, fm.train, (float)fm.distance});
+            m.inliers_mask.push_back((unsigned char)fm.inlier);
+        }
+        m.num_inliers = p.num_inliers; m.have_H = p.have_H != 0; m.confidence = p.confidence;
+        for (int e = 0; e < 9; ++e) m.H[e] = p.H[e];
+        dual = m;
+        dual.src_img_idx = p.view_b; dual.dst_img_idx = p.view_a;
+        for (DMatch &d : dual.matches) { const int q = d.queryIdx; d.queryIdx = d.trainIdx; d.trainIdx = q; }
+        if (m.have_H) {                                      // H.inv(): the adjugate over the determinant; a singular H inverts to zeros as cv::Mat::inv(DECOMP_LU) does
+            const double *h = m.H;
+            const double det = h[0] * (h[4] * h[8] - h[5] * h[7]) - h[1] * (h[3] * h[8] - h[5] * h[6]) + h[2] * (h[3] * h[7] - h[4] * h[6]);
+            const double adj[9] = {h[4] * h[8] - h[5] * h[7], h[2] * h[7] - h[1] * h[8], h[1] * h[5] - h[2] * h[4], h[5] * h[6] - h[3] * h[8], h[0] * h[8] - h[2] * h[6],
+                                   h[2] * h[3] - h[0] * h[5], h[3] * h[7] - h[4] * h[6], h[1] * h[6] - h[0] * h[7], h[0] * h[4] - h[1] * h[3]};
+            for (int e = 0; e < 9; ++e) dual.H[e] = det != 0.0 ? adj[e] / det : 0.0;
+        }
+    }
+}
 }  // namespace featurefinder
 
 // ---- MeshWarper: createMesh's host logic around ms_create_mesh (360_stitcher/meshwarper.cpp:158-335) --------------------------

@@ -54,6 +54,9 @@ int shim_compile_check()
         std::vector<msshim::featurefinder::MatchesInfo> fpair(6);
         msshim::featurefinder::matchFeatures(ffeats, fpair);
         msshim::featurefinder::matchFeaturesTemporal(ffeats, ffeats, fpair);
+        // detail::BestOf2NearestMatcher over every pair: the n x n table Stitcher::estimateCameraParams reads
+        std::vector<msshim::featurefinder::MatchesInfo> fall;
+        msshim::featurefinder::matchPairs(ffeats, fall);
         msshim::MeshWarper mw(6, 10, 10, 600.f, 1.0, 0.5);
         mw.calibrateMeshWarp(comp, frames, ffeats, fpair);
         mw.calibrateMeshWarp(comp, frames, feats, pairwise);
