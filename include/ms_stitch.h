@@ -803,11 +803,29 @@ MS_API int ms_feature_mask(const ms_image *warped_view, int a_x0, int a_width, i
 /* cv::findHomography(src, dst, mask, RANSAC) of featurefinder::matchFeatures (featurefinder.cpp:68-90 -> calib3d/src/fundam.cpp:319-402,
  * ptsetreg.cpp:53-290, levmarq.cpp:76-214): src_xy / dst_xy HOST, n points (x, y) each.  reproj_threshold <= 0 -> 3, max_iters <= 0 -> 2000,
  * confidence outside (0, 1) -> 0.995 (the reference's defaults).  Same cv::RNG subset sequence, subset checks, acceptance rule and adaptive
- * iteration count as the reference; all candidate 4-point models are fitted and scored on the device in one launch, the final N-point fit and the
- * 10-iteration Levenberg-Marquardt polish of the winner run on the host.  H: 9 doubles row-major (H[8] = 1); inlier_mask: n bytes (may be NULL).
- * Returns MS_OK, 1 if no model was found (H zeroed; the reference returns an empty Mat), or a negative status. */
+ * iteration count as the reference; all candidate 4-point models are fitted and scored on the device (the batch of one of the call below), the final
+ * N-point fit and the 10-iteration Levenberg-Marquardt polish of the winner run on the host.  H: 9 doubles row-major (H[8] = 1); inlier_mask: n bytes
+ * (may be NULL).  Returns MS_OK, 1 if no model was found (H zeroed; the reference returns an empty Mat), or a negative status. */
 MS_API int ms_find_homography_ransac(const float *src_xy, const float *dst_xy, int n, double reproj_threshold, int max_iters, double confidence,
                                      double *H, uint8_t *inlier_mask, int *n_inliers, ms_stream stream);
+/* The same for n_problems independent point sets in one device pass: what BestOf2NearestMatcher::match (OCV/stitching/src/matchers.cpp:699-770) driven over all
+ * pairs asks of cv::findHomography (calib3d/src/fundam.cpp:319-402) pair after pair.  Problem p holds the points offsets[p] .. offsets[p + 1] - 1 of src_xy / dst_xy
+ * (HOST, (x, y) each; offsets: n_problems + 1 ints, ascending, offsets[0] = 0; empty problems are allowed) and gets exactly what
+ * ms_find_homography_ransac(src_xy + 2 * offsets[p], dst_xy + 2 * offsets[p], offsets[p + 1] - offsets[p], ...) returns, bit for bit: H + 9 * p (zeroed without a
+ * model), inlier_mask + offsets[p] (may be NULL), n_inliers[p] (may be NULL) and status[p] = 0 (a model) or 1 (none).  A problem's result depends neither on
+ * its neighbours nor on its place in the batch.  The three RANSAC parameters are shared and follow the same defaults rule.
+ * Per problem on the host, as in the single call: the cv::RNG subset sequence (seeded per problem), the subset checks, the sequential first-strictly-better scan
+ * with the adaptive iteration count, the final N-point fit and the polish; problems with fewer than 5 points or no drawable subset never reach the device.  On the
+ * device, for all problems at once: one lane per hypothesis fits its 4-point model (k_ransac_fit); one workgroup per (problem, 64 hypotheses) counts inliers, the
+ * problem's points staged through LDS in chunks of 512 and split over the workgroup's 4 waves, 128 points of a chunk each (k_ransac_score; the counts are
+ * integers, so the split changes nothing); after the host's scans a third launch gathers the winners' models.  Per batch, whatever n_problems is: at most
+ * 3 launches, 4 copies (upload; counts back; winners' numbers up; their models back) and 2 synchronisations over the calling thread's grow-only staging
+ * blocks, no allocation once they have grown; none of it where no problem needs the device or (the last launch and its two copies) where none has a winner.
+ * Returns MS_OK (also when every problem ends without a model) or a negative status.  MS_ERR_INVALID before the device is touched: n_problems < 0; null offsets,
+ * H or status; offsets[0] != 0 or a descending pair; null src_xy or dst_xy with offsets[n_problems] > 0; a reproj_threshold or confidence that is not finite.
+ * n_problems == 0 is MS_OK and touches nothing.  Synchronises. */
+MS_API int ms_find_homography_ransac_batch(int n_problems, const int *offsets, const float *src_xy, const float *dst_xy, double reproj_threshold, int max_iters,
+                                           double confidence, double *H, uint8_t *inlier_mask, int *n_inliers, int *status, ms_stream stream);
 
 /* ---- Rig rotation refinement: ray bundle adjustment from feature matches ---------------------------------------------------------------------
  * detail::BundleAdjusterRay (OCV/stitching/src/motion_estimators.cpp:514-700) with the focals held: the stage between the feature front end above and
@@ -997,11 +1015,13 @@ MS_API int ms_refine_rig_focals(ms_ctx *ctx, const ms_mesh_match *matches, const
  * RANSAC subset sequence indexes into it).  Two launches whatever the number of pairs: the 2-NN of every row of every directed pair (a workgroup stages
  * tiles of train rows in LDS and scores 64 queries against each), then one workgroup a pair for ratio test, cross-check and an ordered prefix-scan
  * compaction (no atomics: two calls return the same bits); one upload, one copy back, one synchronise.
- * The host stage, per pair with count >= num_matches_thresh1, BestOf2NearestMatcher::match line for line: the matches' keypoints as centred floats
- * (x - width * 0.5f, y - height * 0.5f) go to ms_find_homography_ransac in list order (inlier flags, num_inliers, H; no model: have_H = 0);
- * |det H| < DBL_EPSILON: have_H stays 1, num_inliers = 0, confidence 0; otherwise confidence = num_inliers / (8 + 0.3 * count) in double, a value above 3
- * becomes 0 (two views of the same image), and with num_inliers >= num_matches_thresh2 a second ms_find_homography_ransac on the inliers alone replaces H
- * (no model: have_H = 0; flags, count and confidence stay).  Below thresh1: have_H = 0, num_inliers = 0, confidence 0, every inlier flag 0.
+ * The host stage, two batched rounds of ms_find_homography_ransac_batch instead of up to two RANSAC calls a pair; per pair the rule is
+ * BestOf2NearestMatcher::match line for line, and every field is what a ms_find_homography_ransac call on that pair alone gives.  Round 1 holds every pair with
+ * count >= num_matches_thresh1: the matches' keypoints as centred floats (x - width * 0.5f, y - height * 0.5f) in list order (inlier flags, num_inliers, H;
+ * no model: have_H = 0); |det H| < DBL_EPSILON: have_H stays 1, num_inliers = 0, confidence 0; otherwise confidence = num_inliers / (8 + 0.3 * count) in double,
+ * a value above 3 becomes 0 (two views of the same image).  Round 2 holds every pair that passed the determinant test with num_inliers >= num_matches_thresh2:
+ * a second RANSAC on the inliers alone replaces H (no model: have_H = 0; flags, count and confidence stay).  Below thresh1: have_H = 0, num_inliers = 0,
+ * confidence 0, every inlier flag 0.  A round without a pair costs nothing.
  * Descriptors: 8UC1, the same length in every view, a multiple of 4 up to 64 bytes, data and step multiples of 4 (32 bytes is the specialised kernel);
  * these are checked on the views that have keypoints.
  * MS_ERR_INVALID before the device is touched: a null pointer; n_views outside [2, MS_MAX_VIEWS]; a struct_size mismatch; match_conf not finite or outside

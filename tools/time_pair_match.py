@@ -55,7 +55,8 @@ def random_views(n, rng):
 class Caller:
     """ms_match_pairs with its arrays built beforehand"""
 
-    def __init__(self, feats, **kw):
+    def __init__(self, feats, lib=None, **kw):
+        self.lib = lib if lib is not None else ms.load()      # (another build of the same ABI: tools/time_ransac_batch.py)
         self.n = len(feats)
         self.views, self.keep = ms.view_features(feats)
         self.prm = ms.pair_match_default_params(**kw)
@@ -65,9 +66,9 @@ class Caller:
         self.n_pairs, self.n_matches = C.c_int(0), C.c_int(0)
 
     def __call__(self):
-        rc = ms.load().ms_match_pairs(self.n, self.views, C.byref(self.prm), self.pairs, self.n * self.n, C.byref(self.n_pairs), self.out.ctypes.data_as(C.POINTER(ms.FeatureMatch)),
-                                      self.cap, C.byref(self.n_matches), None)
-        assert rc == 0, ms.load().ms_last_error()
+        rc = self.lib.ms_match_pairs(self.n, self.views, C.byref(self.prm), self.pairs, self.n * self.n, C.byref(self.n_pairs), self.out.ctypes.data_as(C.POINTER(ms.FeatureMatch)),
+                                     self.cap, C.byref(self.n_matches), None)
+        assert rc == 0, self.lib.ms_last_error()
 
     def lists(self):
         return [(self.pairs[k].view_a, self.pairs[k].view_b, self.pairs[k].n_forward, self.out[self.pairs[k].first:self.pairs[k].first + self.pairs[k].count, :3].copy())
@@ -129,8 +130,11 @@ def views_row(name, once=False):
             "speedup": statistics.median(rb) / statistics.median(ra), "lists_equal": True}
 
 
-def planted_row():
-    n, shared = 6, 400
+PLANTED_VIEWS, PLANTED_SHARED = 6, 400
+
+
+def planted_features():
+    n, shared = PLANTED_VIEWS, PLANTED_SHARED
     rng = np.random.default_rng(7)
     W, H = 640, 480
     c = np.array([W / 2, H / 2])
@@ -148,7 +152,12 @@ def planted_row():
         for r in range(shared):
             flips[r, rng.choice(256, size=int(rng.integers(0, 31)), replace=False)] = 1
         descs[v + 1][dst] = descs[v][src] ^ np.packbits(flips, axis=1)
-    feats = [(kps[v], torch.from_numpy(descs[v]).cuda(), (W, H)) for v in range(n)]
+    return [(kps[v], torch.from_numpy(descs[v]).cuda(), (W, H)) for v in range(n)]
+
+
+def planted_row():
+    n, shared = PLANTED_VIEWS, PLANTED_SHARED
+    feats = planted_features()
     full, off = Caller(feats), Caller(feats, num_matches_thresh1=NEVER)
     full(); off()
     rf, ro = timed([full, off])

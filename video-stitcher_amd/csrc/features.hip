@@ -7,8 +7,9 @@
 //       calib3d/src/fundam.cpp:46-260, 319-402; ptsetreg.cpp:53-290; levmarq.cpp:76-214
 //
 // What is on the device: every per-pixel and per-keypoint stage of ORB (image / mask pyramids, FAST scores, non-max suppression and
-// ordered compaction, Harris responses, angles, descriptors) and RANSAC's hypothesis generation-and-scoring (one thread per 4-point
-// model, all `maxIters` models at once).  What stays on the host, as in the reference: the keypoint COUNTS between stages (the reference
+// ordered compaction, Harris responses, angles, descriptors) and RANSAC's hypothesis fitting and scoring (all `maxIters` 4-point models of
+// every problem of a batch at once: one lane per model fits it, one workgroup per 64 models counts their inliers; ms_find_homography_ransac
+// is the batch of one).  What stays on the host, as in the reference: the keypoint COUNTS between stages (the reference
 // reads them back too: fast.cu:338-341, :379-382), the two culls (tiny stable sorts; the reference sorts on the device with an unstable
 // thrust sort, so its keypoint order is not defined -- ours is: raster order, stable culls), RANSAC's sequential subset draw and best-model
 // scan, and the final N-point fit + Levenberg-Marquardt polish of ONE model.
@@ -16,6 +17,7 @@
 // correctly rounded float of the double function.
 #include <algorithm>
 #include <cfloat>
+#include <climits>
 #include <cmath>
 #include <cstring>
 #include <numeric>
@@ -214,27 +216,45 @@ __global__ void __launch_bounds__(256) k_orb_desc(const uint8_t *__restrict__ im
     desc[(size_t)p * dstep + b] = (uint8_t)v;
 }
 
-// ---- RANSAC: one thread per 4-point hypothesis -- HomographyEstimatorCallback::runKernel (fundam.cpp:80-142) then the inlier count of
-// RANSACPointSetRegistrator::findInliers with computeError's float arithmetic (fundam.cpp:144-166, ptsetreg.cpp:85-104)
+// ---- RANSAC: per 4-point hypothesis HomographyEstimatorCallback::runKernel (fundam.cpp:80-142, k_ransac_fit: one lane a hypothesis), then the inlier count
+// of RANSACPointSetRegistrator::findInliers with computeError's float arithmetic (fundam.cpp:144-166, ptsetreg.cpp:85-104; k_ransac_score)
+// Every loop over matrix entries is unrolled in full, so that on the device the two 9 x 9 matrices live in registers under constant indices and not in scratch
+// memory under computed ones; the operations and their order are untouched (no contraction, no reassociation: the same bits, host and device).
 __host__ __device__ inline void jacobi_eig9(double A[9][9], double V[9][9], double w[9])
 {
-    for (int i = 0; i < 9; ++i) { for (int j = 0; j < 9; ++j) V[i][j] = 0; V[i][i] = 1; }
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+#pragma unroll
+        for (int j = 0; j < 9; ++j) V[i][j] = 0;
+        V[i][i] = 1;
+    }
     for (int sweep = 0; sweep < 60; ++sweep) {
         double off = 0;
-        for (int i = 0; i < 9; ++i) for (int j = i + 1; j < 9; ++j) off += A[i][j] * A[i][j];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) {
+#pragma unroll
+            for (int j = i + 1; j < 9; ++j) off += A[i][j] * A[i][j];
+        }
         if (off < 1e-300) break;
-        for (int p = 0; p < 8; ++p)
+#pragma unroll
+        for (int p = 0; p < 8; ++p) {
+#pragma unroll
             for (int q = p + 1; q < 9; ++q) {
                 const double apq = A[p][q];
                 if (fabs(apq) < 1e-300) continue;
                 const double theta = (A[q][q] - A[p][p]) / (2 * apq);
                 const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1));
                 const double c = 1 / sqrt(t * t + 1), s = t * c;
+#pragma unroll
                 for (int k = 0; k < 9; ++k) { const double akp = A[k][p], akq = A[k][q]; A[k][p] = c * akp - s * akq; A[k][q] = s * akp + c * akq; }
+#pragma unroll
                 for (int k = 0; k < 9; ++k) { const double apk = A[p][k], aqk = A[q][k]; A[p][k] = c * apk - s * aqk; A[q][k] = s * apk + c * aqk; }
+#pragma unroll
                 for (int k = 0; k < 9; ++k) { const double vkp = V[k][p], vkq = V[k][q]; V[k][p] = c * vkp - s * vkq; V[k][q] = s * vkp + c * vkq; }
             }
+        }
     }
+#pragma unroll
     for (int i = 0; i < 9; ++i) w[i] = A[i][i];
 }
 }  // namespace
@@ -249,18 +269,36 @@ __host__ __device__ static bool homography_dlt(const float *Mx, const float *My,
     if (fabs(smx) < DBL_EPSILON || fabs(smy) < DBL_EPSILON || fabs(sMx) < DBL_EPSILON || fabs(sMy) < DBL_EPSILON) return false;
     smx = count / smx; smy = count / smy; sMx = count / sMx; sMy = count / sMy;
     double L[9][9], V[9][9], w[9];
-    for (int j = 0; j < 9; ++j) for (int k = 0; k < 9; ++k) L[j][k] = 0;
+#pragma unroll
+    for (int j = 0; j < 9; ++j) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) L[j][k] = 0;
+    }
     for (int i = 0; i < count; ++i) {
         const double x = (mx[i] - cmx) * smx, y = (my[i] - cmy) * smy, X = (Mx[i] - cMx) * sMx, Y = (My[i] - cMy) * sMy;
         const double Lx[9] = {X, Y, 1, 0, 0, 0, -x * X, -x * Y, -x}, Ly[9] = {0, 0, 0, X, Y, 1, -y * X, -y * Y, -y};
-        for (int j = 0; j < 9; ++j) for (int k = j; k < 9; ++k) L[j][k] += Lx[j] * Lx[k] + Ly[j] * Ly[k];
+#pragma unroll
+        for (int j = 0; j < 9; ++j) {
+#pragma unroll
+            for (int k = j; k < 9; ++k) L[j][k] += Lx[j] * Lx[k] + Ly[j] * Ly[k];
+        }
     }
-    for (int j = 0; j < 9; ++j) for (int k = 0; k < j; ++k) L[j][k] = L[k][j];
+#pragma unroll
+    for (int j = 0; j < 9; ++j) {
+#pragma unroll
+        for (int k = 0; k < j; ++k) L[j][k] = L[k][j];
+    }
     jacobi_eig9(L, V, w);
-    int best = 0;
-    for (int i = 1; i < 9; ++i) if (w[i] < w[best]) best = i;               // cv::eigen sorts descending and the reference takes the last row
-    double h0[9];
-    for (int i = 0; i < 9; ++i) h0[i] = V[i][best];
+    double wbest = w[0], h0[9];                                             // cv::eigen sorts descending and the reference takes the last row: the FIRST smallest
+#pragma unroll
+    for (int i = 0; i < 9; ++i) h0[i] = V[i][0];
+#pragma unroll
+    for (int c = 1; c < 9; ++c) {
+        const bool lower = w[c] < wbest;
+        wbest = lower ? w[c] : wbest;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) h0[i] = lower ? V[i][c] : h0[i];
+    }
     const double inv[9] = {1. / smx, 0, cmx, 0, 1. / smy, cmy, 0, 0, 1}, nrm[9] = {sMx, 0, -cMx * sMx, 0, sMy, -cMy * sMy, 0, 0, 1};
     double t[9];
     for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) t[3 * r + c] = inv[3 * r] * h0[c] + inv[3 * r + 1] * h0[3 + c] + inv[3 * r + 2] * h0[6 + c];
@@ -269,11 +307,14 @@ __host__ __device__ static bool homography_dlt(const float *Mx, const float *My,
     for (int i = 0; i < 9; ++i) H[i] *= s;
     return true;
 }
-__host__ __device__ static inline int homography_inliers(const double H[9], const float *Mx, const float *My, const float *mx, const float *my, int n, float t, uint8_t *mask)
+// (host and device) computeError + the threshold compare of findInliers over the points [i0, i1): the model's first 8 entries as floats, every point
+// the same float operations in the same order whoever calls it -- the score kernel on its wave's share of a chunk in LDS, the host for the winner's mask
+__host__ __device__ static inline int homography_inliers_range(const float h[8], const float *Mx, const float *My, const float *mx, const float *my, int i0, int i1, float t,
+                                                               uint8_t *mask)
 {
-    const float h0 = (float)H[0], h1 = (float)H[1], h2 = (float)H[2], h3 = (float)H[3], h4 = (float)H[4], h5 = (float)H[5], h6 = (float)H[6], h7 = (float)H[7];
+    const float h0 = h[0], h1 = h[1], h2 = h[2], h3 = h[3], h4 = h[4], h5 = h[5], h6 = h[6], h7 = h[7];
     int good = 0;
-    for (int i = 0; i < n; ++i) {
+    for (int i = i0; i < i1; ++i) {
         const float ww = 1.f / (h6 * Mx[i] + h7 * My[i] + 1.f);
         const float dx = (h0 * Mx[i] + h1 * My[i] + h2) * ww - mx[i], dy = (h3 * Mx[i] + h4 * My[i] + h5) * ww - my[i];
         const int f = dx * dx + dy * dy <= t;
@@ -282,21 +323,84 @@ __host__ __device__ static inline int homography_inliers(const double H[9], cons
     }
     return good;
 }
+__host__ __device__ static inline int homography_inliers(const double H[9], const float *Mx, const float *My, const float *mx, const float *my, int n, float t, uint8_t *mask)
+{
+    float h[8];
+    for (int k = 0; k < 8; ++k) h[k] = (float)H[k];
+    return homography_inliers_range(h, Mx, My, mx, my, 0, n, t, mask);
+}
 
 namespace {
-__global__ void __launch_bounds__(64) k_ransac_score(const float *__restrict__ Mx, const float *__restrict__ My, const float *__restrict__ mx, const float *__restrict__ my, int n,
-                                                     const int *__restrict__ subsets, int n_hyp, float thresh_sq, double *__restrict__ models, int *__restrict__ good)
+// ---- batched RANSAC: the hypotheses of every problem of a batch in two launches.  The fit (a 9 x 9 double eigen-solve a lane) and the scoring (a float loop over
+// the problem's points) are separate kernels: the fit's register and scratch state does not sit on the scoring loop, and the scoring spreads a problem's points
+// over the waves of a workgroup instead of walking them all in one lane.
+constexpr int RS_LANES = 64;                                    // hypotheses a score workgroup takes: one a lane, the same in each of its waves
+constexpr int RS_WAVES = 4;                                     // waves of a score workgroup
+constexpr int RS_WAVE_POINTS = 128;                             // W: the points one wave takes of a chunk
+constexpr int RS_CHUNK = RS_WAVES * RS_WAVE_POINTS;             // C = 512: the points staged in LDS at a time (4 float planes: 8 KiB)
+struct RsProb { int pt_off, n, hyp_off, n_hyp; };               // a problem's slice of the point planes and of the hypothesis arrays
+struct RsBlock { int prob, hyp0; };                             // a score workgroup: hypotheses [hyp0, hyp0 + 64) of problem prob
+struct RsHyp { int prob, i0, i1, i2, i3; };                     // a hypothesis: its problem and its four points (indices into the problem's slice)
+
+// pts: four planes of n_pts floats (Mx, My, mx, my), every problem's points at its pt_off
+__global__ void __launch_bounds__(64) k_ransac_fit(const float *__restrict__ pts, size_t n_pts, const RsProb *__restrict__ probs, const RsHyp *__restrict__ hyps, int n_hyp,
+                                                   double *__restrict__ models, int *__restrict__ valid)
 {
-    const int h = blockIdx.x * 64 + threadIdx.x;
-    if (h >= n_hyp) return;
+    const int g = blockIdx.x * 64 + threadIdx.x;
+    if (g >= n_hyp) return;
+    const RsHyp r = hyps[g];
+    const float *Mx = pts + probs[r.prob].pt_off, *My = Mx + n_pts, *mx = My + n_pts, *my = mx + n_pts;
+    const int idx[4] = {r.i0, r.i1, r.i2, r.i3};
     float sMx[4], sMy[4], smx[4], smy[4];
-    for (int k = 0; k < 4; ++k) { const int i = subsets[4 * h + k]; sMx[k] = Mx[i]; sMy[k] = My[i]; smx[k] = mx[i]; smy[k] = my[i]; }
+    for (int k = 0; k < 4; ++k) { const int i = idx[k]; sMx[k] = Mx[i]; sMy[k] = My[i]; smx[k] = mx[i]; smy[k] = my[i]; }
     double H[9];
-    int g = -1;
-    if (homography_dlt(sMx, sMy, smx, smy, 4, H)) g = homography_inliers(H, Mx, My, mx, my, n, thresh_sq, nullptr);
-    else for (int i = 0; i < 9; ++i) H[i] = 0;
-    good[h] = g;
-    for (int i = 0; i < 9; ++i) models[9 * h + i] = H[i];
+    const bool ok = homography_dlt(sMx, sMy, smx, smy, 4, H);
+    if (!ok) for (int i = 0; i < 9; ++i) H[i] = 0;
+    valid[g] = ok ? 1 : 0;
+    for (int i = 0; i < 9; ++i) models[9 * (size_t)g + i] = H[i];
+}
+
+// One workgroup per (problem, 64 hypotheses).  Lane l of EVERY wave holds hypothesis hyp0 + l; the problem's points pass through LDS in chunks of RS_CHUNK, and wave w
+// counts the inliers among points [w * RS_WAVE_POINTS, (w + 1) * RS_WAVE_POINTS) of each chunk.  All lanes of a wave read the same LDS address (a broadcast, no bank
+// conflict).  The counts are integers, so the split changes nothing; the waves' counts are added through LDS at the end.  good = -1: the hypothesis has no model.
+__global__ void __launch_bounds__(RS_LANES * RS_WAVES) k_ransac_score(const float *__restrict__ pts, size_t n_pts, const RsProb *__restrict__ probs,
+                                                                       const RsBlock *__restrict__ blocks, const double *__restrict__ models,
+                                                                       const int *__restrict__ valid, float thresh_sq, int *__restrict__ good)
+{
+    __shared__ float s_pts[4][RS_CHUNK];
+    __shared__ int s_cnt[RS_WAVES][RS_LANES];
+    const RsBlock b = blocks[blockIdx.x];
+    const RsProb p = probs[b.prob];
+    const int lane = threadIdx.x & (RS_LANES - 1), wave = threadIdx.x / RS_LANES;
+    const bool live = b.hyp0 + lane < p.n_hyp;
+    const size_t g = (size_t)p.hyp_off + (size_t)(b.hyp0 + lane);
+    const bool has = live && valid[g] != 0;
+    float h[8];
+    for (int k = 0; k < 8; ++k) h[k] = has ? (float)models[9 * g + k] : 0.f;
+    int cnt = 0;
+    for (int c0 = 0; c0 < p.n; c0 += RS_CHUNK) {
+        const int m = min(RS_CHUNK, p.n - c0);
+        __syncthreads();                                        // the chunk before is counted
+        for (int i = threadIdx.x; i < m; i += RS_LANES * RS_WAVES)
+            for (int pl = 0; pl < 4; ++pl) s_pts[pl][i] = pts[pl * n_pts + (size_t)(p.pt_off + c0 + i)];
+        __syncthreads();
+        const int i0 = wave * RS_WAVE_POINTS, i1 = min(m, i0 + RS_WAVE_POINTS);
+        if (has && i0 < i1) cnt += homography_inliers_range(h, s_pts[0], s_pts[1], s_pts[2], s_pts[3], i0, i1, thresh_sq, nullptr);
+    }
+    s_cnt[wave][lane] = cnt;
+    __syncthreads();
+    if (wave == 0 && live) {
+        int sum = 0;
+        for (int w = 0; w < RS_WAVES; ++w) sum += s_cnt[w][lane];
+        good[g] = has ? sum : -1;
+    }
+}
+
+// the winners' models out of the model array: 9 doubles per listed hypothesis
+__global__ void __launch_bounds__(64) k_ransac_gather(const double *__restrict__ models, const int *__restrict__ win, int n_win, double *__restrict__ out)
+{
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t < 9 * n_win) out[t] = models[9 * (size_t)win[t / 9] + t % 9];
 }
 
 // cv::RNG (core/include/opencv2/core/operations.hpp: multiply-with-carry, CV_RNG_COEFF 4164903690)
@@ -421,6 +525,193 @@ void lm_refine(const float *Mx, const float *My, const float *mx, const float *m
         if (!(iter < 10 && nd >= FLT_EPSILON && nr >= FLT_EPSILON)) break;
     }
     memcpy(h, x, sizeof(x));
+}
+
+static inline size_t rs_align(size_t n) { return (n + 255) & ~(size_t)255; }
+
+// One problem of a batch on the host: its points as planes, what the device is asked about it and what comes back
+struct RsProblem {
+    int n = 0;
+    std::vector<float> Mx, My, mx, my;
+    std::vector<uint8_t> mask;
+    double H[9] = {0};
+    bool ok = false;
+    int dev = -1;                   // index among the problems that go to the device, -1: settled on the host
+    int drawn = 0;                  // hypotheses drawn
+    size_t sub_off = 0;             // its first hypothesis in the batch's subset list
+};
+
+// cv::findHomography(RANSAC) on every problem of a batch; the arguments are checked and a device is present.  Per problem the steps of the reference in their order;
+// the device work of ALL problems goes out in one pass: 1 upload, k_ransac_fit, k_ransac_score, 1 copy back (the counts), 1 synchronise; then the sequential scans
+// on the host and, where a problem has a winner, 1 upload (the winners' hypothesis numbers), k_ransac_gather, 1 copy back (their models), 1 synchronise:
+// 3 launches, 4 copies, 2 synchronisations at most, whatever n_problems is; none where no problem reaches the device.
+int ransac_batch(const char *fn, int n_problems, const int *offsets, const float *src_xy, const float *dst_xy, double reproj_threshold, int max_iters, double confidence,
+                 double *H_out, uint8_t *inlier_mask, int *n_inliers, int *status, ms_stream stream)
+{
+    if (reproj_threshold <= 0) reproj_threshold = 3;                       // defaultRANSACReprojThreshold (fundam.cpp:325, :351)
+    if (max_iters <= 0) max_iters = 2000;
+    if (!(confidence > 0 && confidence < 1)) confidence = 0.995;
+    const float t = (float)(reproj_threshold * reproj_threshold);
+    const int total_pts = offsets[n_problems];
+    for (int p = 0; p < n_problems; ++p) { status[p] = 1; if (n_inliers) n_inliers[p] = 0; }
+    for (size_t i = 0; i < 9 * (size_t)n_problems; ++i) H_out[i] = 0;
+    if (inlier_mask && total_pts > 0) memset(inlier_mask, 0, (size_t)total_pts);
+
+    std::vector<RsProblem> P(n_problems);
+    std::vector<int> subsets;                                              // 4 point indices per hypothesis, the device problems one after another
+    int n_dev = 0;
+    size_t dev_pts = 0, n_blocks = 0;
+    for (int p = 0; p < n_problems; ++p) {
+        RsProblem &q = P[p];
+        const int n = q.n = offsets[p + 1] - offsets[p];
+        if (n < 4) continue;                                               // (the reference returns an empty Mat)
+        const float *s = src_xy + 2 * (size_t)offsets[p], *d = dst_xy + 2 * (size_t)offsets[p];
+        q.Mx.resize(n); q.My.resize(n); q.mx.resize(n); q.my.resize(n); q.mask.assign(n, 0);
+        for (int i = 0; i < n; ++i) { q.Mx[i] = s[2 * i]; q.My[i] = s[2 * i + 1]; q.mx[i] = d[2 * i]; q.my[i] = d[2 * i + 1]; }
+        if (n == 4) {                                                      // method == 0 || npoints == 4 (fundam.cpp:356-360)
+            q.ok = homography_dlt(q.Mx.data(), q.My.data(), q.mx.data(), q.my.data(), 4, q.H);
+            std::fill(q.mask.begin(), q.mask.end(), (uint8_t)1);
+            continue;
+        }
+        // every subset the sequential loop COULD draw, in its order (ptsetreg.cpp:106-173): the draw does not depend on the models found
+        CvRng rng((unsigned long long)-1);
+        q.sub_off = subsets.size() / 4;
+        int drawn = 0;
+        for (; drawn < max_iters; ++drawn) {
+            int idx[4];
+            bool found = false;
+            for (int iters = 0; iters < 10000; ++iters) {
+                for (int i = 0; i < 4; ++i) {
+                    for (;;) { idx[i] = rng.uniform(0, n); int j = 0; for (; j < i; ++j) if (idx[i] == idx[j]) break; if (j == i) break; }
+                }
+                float sx[4], sy[4], dx[4], dy[4];
+                for (int i = 0; i < 4; ++i) { sx[i] = q.Mx[idx[i]]; sy[i] = q.My[idx[i]]; dx[i] = q.mx[idx[i]]; dy[i] = q.my[idx[i]]; }
+                if (check_subset4(sx, sy, dx, dy)) { found = true; break; }
+            }
+            if (!found) break;
+            subsets.insert(subsets.end(), idx, idx + 4);
+        }
+        if (drawn == 0) continue;
+        q.drawn = drawn; q.dev = n_dev++;
+        dev_pts += (size_t)n;
+        n_blocks += (size_t)div_up(drawn, RS_LANES);
+    }
+
+    if (n_dev) {
+        const size_t n_hyp = subsets.size() / 4;
+        if (n_hyp > (size_t)INT_MAX / 16 || dev_pts > (size_t)INT_MAX / 16)
+            return fail(MS_ERR_INVALID, "%s: %zu hypotheses over %zu points are more than one batch holds", fn, n_hyp, dev_pts);
+        hipStream_t st = as_stream(stream);
+        // the upload, packed: point planes, problems, score workgroups, hypotheses; behind it on the device the models, flags and counts, the winners' list and models
+        const size_t o_pts = 0, o_probs = o_pts + rs_align(4 * dev_pts * sizeof(float)), o_blocks = o_probs + rs_align((size_t)n_dev * sizeof(RsProb)),
+                     o_hyps = o_blocks + rs_align(n_blocks * sizeof(RsBlock)), up_bytes = o_hyps + rs_align(n_hyp * sizeof(RsHyp));
+        const size_t o_models = up_bytes, o_valid = o_models + rs_align(9 * n_hyp * sizeof(double)), o_good = o_valid + rs_align(n_hyp * sizeof(int)),
+                     o_win = o_good + rs_align(n_hyp * sizeof(int)), o_winH = o_win + rs_align((size_t)n_dev * sizeof(int)),
+                     dev_bytes = o_winH + rs_align(9 * (size_t)n_dev * sizeof(double));
+        const size_t h_good = up_bytes, h_win = h_good + rs_align(n_hyp * sizeof(int)), h_winH = h_win + rs_align((size_t)n_dev * sizeof(int)),
+                     pin_bytes = h_winH + rs_align(9 * (size_t)n_dev * sizeof(double));
+        char *dev = (char *)device_scratch().get(dev_bytes);                // per-thread grow-only block: see DeviceScratch (common.hpp)
+        if (!dev) return fail(MS_ERR_NOMEM, "%s: cannot allocate %zu bytes of device scratch", fn, dev_bytes);
+        char *pin = (char *)pinned_scratch().get(pin_bytes);
+        if (!pin) return fail(MS_ERR_NOMEM, "%s: cannot allocate pinned staging memory", fn);
+        float *hp = (float *)(pin + o_pts);
+        RsProb *hprob = (RsProb *)(pin + o_probs);
+        RsBlock *hblk = (RsBlock *)(pin + o_blocks);
+        RsHyp *hhyp = (RsHyp *)(pin + o_hyps);
+        size_t pt = 0, blk = 0;
+        for (int p = 0; p < n_problems; ++p) {
+            const RsProblem &q = P[p];
+            if (q.dev < 0) continue;
+            memcpy(hp + pt, q.Mx.data(), sizeof(float) * q.n); memcpy(hp + dev_pts + pt, q.My.data(), sizeof(float) * q.n);
+            memcpy(hp + 2 * dev_pts + pt, q.mx.data(), sizeof(float) * q.n); memcpy(hp + 3 * dev_pts + pt, q.my.data(), sizeof(float) * q.n);
+            hprob[q.dev] = RsProb{(int)pt, q.n, (int)q.sub_off, q.drawn};
+            for (int h0 = 0; h0 < q.drawn; h0 += RS_LANES) hblk[blk++] = RsBlock{q.dev, h0};
+            for (int h = 0; h < q.drawn; ++h) {
+                const int *s = &subsets[4 * (q.sub_off + h)];
+                hhyp[q.sub_off + h] = RsHyp{q.dev, s[0], s[1], s[2], s[3]};
+            }
+            pt += (size_t)q.n;
+        }
+        const float *d_pts = (const float *)(dev + o_pts);
+        const RsProb *d_probs = (const RsProb *)(dev + o_probs);
+        double *d_models = (double *)(dev + o_models);
+        int *d_valid = (int *)(dev + o_valid), *d_good = (int *)(dev + o_good);
+        hipError_t e = hipMemcpyAsync(dev, pin, up_bytes, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) {
+            k_ransac_fit<<<(unsigned)div_up((int)n_hyp, 64), 64, 0, st>>>(d_pts, dev_pts, d_probs, (const RsHyp *)(dev + o_hyps), (int)n_hyp, d_models, d_valid);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) {
+            k_ransac_score<<<(unsigned)n_blocks, RS_LANES * RS_WAVES, 0, st>>>(d_pts, dev_pts, d_probs, (const RsBlock *)(dev + o_blocks), d_models, d_valid, t, d_good);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(pin + h_good, d_good, n_hyp * sizeof(int), hipMemcpyDeviceToHost, st);
+        hipError_t se = hipStreamSynchronize(st);          // also after a failed enqueue: nothing of this call stays in flight over the scratch blocks
+        MS_HIP(e);
+        MS_HIP(se);
+        // the sequential scan of RANSACPointSetRegistrator::run (ptsetreg.cpp:208-240) per problem: first strictly better model wins, the iteration budget shrinks as it goes
+        const int *good = (const int *)(pin + h_good);
+        int *win = (int *)(pin + h_win);
+        std::vector<int> win_prob;
+        for (int p = 0; p < n_problems; ++p) {
+            const RsProblem &q = P[p];
+            if (q.dev < 0) continue;
+            const int *g = good + q.sub_off;
+            int niters = std::max(max_iters, 1), max_good = 0, best = -1;
+            for (int iter = 0; iter < niters && iter < q.drawn; ++iter) {
+                if (g[iter] < 0) continue;                                 // runKernel returned no model
+                if (g[iter] > q.n) return fail(MS_ERR_HIP, "%s: the device returned an impossible inlier count (%d of %d points)", fn, g[iter], q.n);
+                if (g[iter] > std::max(max_good, 3)) {
+                    best = iter; max_good = g[iter];
+                    niters = ransac_update_iters(confidence, (double)(q.n - max_good) / q.n, 4, niters);
+                }
+            }
+            if (best >= 0) { win[win_prob.size()] = (int)(q.sub_off + best); win_prob.push_back(p); }
+        }
+        if (!win_prob.empty()) {
+            const int n_win = (int)win_prob.size();
+            e = hipMemcpyAsync(dev + o_win, pin + h_win, (size_t)n_win * sizeof(int), hipMemcpyHostToDevice, st);
+            if (e == hipSuccess) {
+                k_ransac_gather<<<(unsigned)div_up(9 * n_win, 64), 64, 0, st>>>(d_models, (const int *)(dev + o_win), n_win, (double *)(dev + o_winH));
+                e = hipGetLastError();
+            }
+            if (e == hipSuccess) e = hipMemcpyAsync(pin + h_winH, dev + o_winH, 9 * (size_t)n_win * sizeof(double), hipMemcpyDeviceToHost, st);
+            se = hipStreamSynchronize(st);
+            MS_HIP(e);
+            MS_HIP(se);
+            for (int k = 0; k < n_win; ++k) {
+                RsProblem &q = P[win_prob[k]];
+                memcpy(q.H, pin + h_winH + 72 * (size_t)k, sizeof(q.H));
+                homography_inliers(q.H, q.Mx.data(), q.My.data(), q.mx.data(), q.my.data(), q.n, t, q.mask.data());
+                q.ok = true;
+            }
+        }
+    }
+
+    std::vector<float> iMx, iMy, imx, imy;
+    for (int p = 0; p < n_problems; ++p) {
+        RsProblem &q = P[p];
+        if (!q.ok) continue;
+        const int n = q.n;
+        // compressElems + runKernel on the inliers + Levenberg-Marquardt polish (fundam.cpp:370-385)
+        if (n > 4) {
+            iMx.clear(); iMy.clear(); imx.clear(); imy.clear();
+            for (int i = 0; i < n; ++i) if (q.mask[i]) { iMx.push_back(q.Mx[i]); iMy.push_back(q.My[i]); imx.push_back(q.mx[i]); imy.push_back(q.my[i]); }
+            const int m = (int)iMx.size();
+            if (m > 0) {
+                double H2[9];
+                if (homography_dlt(iMx.data(), iMy.data(), imx.data(), imy.data(), m, H2)) memcpy(q.H, H2, sizeof(q.H));
+                lm_refine(iMx.data(), iMy.data(), imx.data(), imy.data(), m, q.H);      // the 8 free parameters; H[8] stays 1
+            }
+        }
+        memcpy(H_out + 9 * (size_t)p, q.H, sizeof(q.H));
+        int cnt = 0;
+        uint8_t *mk = inlier_mask ? inlier_mask + offsets[p] : nullptr;
+        for (int i = 0; i < n; ++i) { if (mk) mk[i] = q.mask[i]; cnt += q.mask[i]; }
+        if (n_inliers) n_inliers[p] = cnt;
+        status[p] = 0;
+    }
+    return MS_OK;
 }
 
 }  // namespace
@@ -623,96 +914,31 @@ int ms_find_homography_ransac(const float *src_xy, const float *dst_xy, int n, d
 {
     if (int e = require_device()) return e;
     MS_CHECK(src_xy && dst_xy && H_out && n >= 0, "ms_find_homography_ransac: bad argument");
-    if (reproj_threshold <= 0) reproj_threshold = 3;                       // defaultRANSACReprojThreshold (fundam.cpp:325, :351)
-    if (max_iters <= 0) max_iters = 2000;
-    if (!(confidence > 0 && confidence < 1)) confidence = 0.995;
-    if (n_inliers) *n_inliers = 0;
-    if (inlier_mask) memset(inlier_mask, 0, (size_t)n);
-    for (int i = 0; i < 9; ++i) H_out[i] = 0;
-    if (n < 4) return 1;                                                   // (the reference returns an empty Mat)
-    std::vector<float> Mx(n), My(n), mx(n), my(n);
-    for (int i = 0; i < n; ++i) { Mx[i] = src_xy[2 * i]; My[i] = src_xy[2 * i + 1]; mx[i] = dst_xy[2 * i]; my[i] = dst_xy[2 * i + 1]; }
-    std::vector<uint8_t> best_mask(n, 0);
-    double H[9];
-    bool ok = false;
-    if (n == 4) {                                                          // method == 0 || npoints == 4 (fundam.cpp:356-360)
-        ok = homography_dlt(Mx.data(), My.data(), mx.data(), my.data(), 4, H);
-        std::fill(best_mask.begin(), best_mask.end(), (uint8_t)1);
-    } else {
-        // every subset the sequential loop COULD draw, in its order (ptsetreg.cpp:106-173): the draw does not depend on the models found
-        CvRng rng((unsigned long long)-1);
-        std::vector<int> subsets;
-        subsets.reserve(4 * (size_t)max_iters);
-        int drawn = 0;
-        for (; drawn < max_iters; ++drawn) {
-            int idx[4];
-            bool found = false;
-            for (int iters = 0; iters < 10000; ++iters) {
-                for (int i = 0; i < 4; ++i) {
-                    for (;;) { idx[i] = rng.uniform(0, n); int j = 0; for (; j < i; ++j) if (idx[i] == idx[j]) break; if (j == i) break; }
-                }
-                float sx[4], sy[4], dx[4], dy[4];
-                for (int i = 0; i < 4; ++i) { sx[i] = Mx[idx[i]]; sy[i] = My[idx[i]]; dx[i] = mx[idx[i]]; dy[i] = my[idx[i]]; }
-                if (check_subset4(sx, sy, dx, dy)) { found = true; break; }
-            }
-            if (!found) break;
-            subsets.insert(subsets.end(), idx, idx + 4);
-        }
-        if (drawn == 0) return 1;
-        // all hypotheses scored at once on the device
-        hipStream_t st = as_stream(stream);
-        struct Dev { void *p = nullptr; ~Dev() { if (p) (void)hipFree(p); } };
-        Dev d_pts, d_sub, d_models, d_good;
-        MS_HIP(hipMalloc(&d_pts.p, sizeof(float) * 4 * (size_t)n));
-        MS_HIP(hipMalloc(&d_sub.p, sizeof(int) * subsets.size()));
-        MS_HIP(hipMalloc(&d_models.p, sizeof(double) * 9 * (size_t)drawn));
-        MS_HIP(hipMalloc(&d_good.p, sizeof(int) * (size_t)drawn));
-        float *dp = (float *)d_pts.p;
-        MS_HIP(hipMemcpyAsync(dp, Mx.data(), sizeof(float) * n, hipMemcpyHostToDevice, st));
-        MS_HIP(hipMemcpyAsync(dp + n, My.data(), sizeof(float) * n, hipMemcpyHostToDevice, st));
-        MS_HIP(hipMemcpyAsync(dp + 2 * (size_t)n, mx.data(), sizeof(float) * n, hipMemcpyHostToDevice, st));
-        MS_HIP(hipMemcpyAsync(dp + 3 * (size_t)n, my.data(), sizeof(float) * n, hipMemcpyHostToDevice, st));
-        MS_HIP(hipMemcpyAsync(d_sub.p, subsets.data(), sizeof(int) * subsets.size(), hipMemcpyHostToDevice, st));
-        const float t = (float)(reproj_threshold * reproj_threshold);
-        k_ransac_score<<<div_up(drawn, 64), 64, 0, st>>>(dp, dp + n, dp + 2 * (size_t)n, dp + 3 * (size_t)n, n, (const int *)d_sub.p, drawn, t, (double *)d_models.p, (int *)d_good.p);
-        MS_LAUNCH_CHECK();
-        std::vector<int> good(drawn);
-        std::vector<double> models(9 * (size_t)drawn);
-        MS_HIP(hipMemcpyAsync(good.data(), d_good.p, sizeof(int) * (size_t)drawn, hipMemcpyDeviceToHost, st));
-        MS_HIP(hipMemcpyAsync(models.data(), d_models.p, sizeof(double) * 9 * (size_t)drawn, hipMemcpyDeviceToHost, st));
-        MS_HIP(hipStreamSynchronize(st));
-        // the sequential scan of RANSACPointSetRegistrator::run (ptsetreg.cpp:208-240): first strictly better model wins, the iteration budget shrinks as it goes
-        int niters = std::max(max_iters, 1), max_good = 0, best = -1;
-        for (int iter = 0; iter < niters && iter < drawn; ++iter) {
-            if (good[iter] < 0) continue;                                  // runKernel returned no model
-            if (good[iter] > std::max(max_good, 3)) {
-                best = iter; max_good = good[iter];
-                niters = ransac_update_iters(confidence, (double)(n - max_good) / n, 4, niters);
-            }
-        }
-        if (best >= 0) {
-            memcpy(H, &models[9 * (size_t)best], sizeof(H));
-            homography_inliers(H, Mx.data(), My.data(), mx.data(), my.data(), n, t, best_mask.data());
-            ok = true;
-        }
-    }
-    if (!ok) return 1;
-    // compressElems + runKernel on the inliers + Levenberg-Marquardt polish (fundam.cpp:370-385)
-    if (n > 4) {
-        std::vector<float> iMx, iMy, imx, imy;
-        for (int i = 0; i < n; ++i) if (best_mask[i]) { iMx.push_back(Mx[i]); iMy.push_back(My[i]); imx.push_back(mx[i]); imy.push_back(my[i]); }
-        const int m = (int)iMx.size();
-        if (m > 0) {
-            double H2[9];
-            if (homography_dlt(iMx.data(), iMy.data(), imx.data(), imy.data(), m, H2)) memcpy(H, H2, sizeof(H));
-            lm_refine(iMx.data(), iMy.data(), imx.data(), imy.data(), m, H);      // the 8 free parameters; H[8] stays 1
-        }
-    }
-    memcpy(H_out, H, sizeof(H));
-    int cnt = 0;
-    for (int i = 0; i < n; ++i) { if (inlier_mask) inlier_mask[i] = best_mask[i]; cnt += best_mask[i]; }
-    if (n_inliers) *n_inliers = cnt;
-    return MS_OK;
+    const int offsets[2] = {0, n};                                         // the batch of one
+    int status = 1;
+    if (int e = ransac_batch("ms_find_homography_ransac", 1, offsets, src_xy, dst_xy, reproj_threshold, max_iters, confidence, H_out, inlier_mask, n_inliers, &status, stream))
+        return e;
+    return status;                                                         // 1: no model (the reference returns an empty Mat)
+}
+
+int ms_find_homography_ransac_batch(int n_problems, const int *offsets, const float *src_xy, const float *dst_xy, double reproj_threshold, int max_iters, double confidence,
+                                    double *H_out, uint8_t *inlier_mask, int *n_inliers, int *status, ms_stream stream)
+{
+    const char *fn = "ms_find_homography_ransac_batch";
+    MS_CHECK(n_problems >= 0, "%s: n_problems = %d must not be negative", fn, n_problems);
+    if (n_problems == 0) return MS_OK;
+    MS_CHECK(offsets, "%s: null offsets", fn);
+    MS_CHECK(H_out, "%s: null H", fn);
+    MS_CHECK(status, "%s: null status", fn);
+    MS_CHECK(offsets[0] == 0, "%s: offsets[0] = %d must be 0", fn, offsets[0]);
+    for (int p = 0; p < n_problems; ++p)
+        MS_CHECK(offsets[p + 1] >= offsets[p], "%s: offsets descend at problem %d (%d after %d)", fn, p, offsets[p + 1], offsets[p]);
+    MS_CHECK(offsets[n_problems] == 0 || src_xy, "%s: null src_xy with %d points", fn, offsets[n_problems]);
+    MS_CHECK(offsets[n_problems] == 0 || dst_xy, "%s: null dst_xy with %d points", fn, offsets[n_problems]);
+    MS_CHECK(std::isfinite(reproj_threshold), "%s: reproj_threshold is not finite", fn);
+    MS_CHECK(std::isfinite(confidence), "%s: confidence is not finite", fn);
+    if (int e = require_device()) return e;
+    return ransac_batch(fn, n_problems, offsets, src_xy, dst_xy, reproj_threshold, max_iters, confidence, H_out, inlier_mask, n_inliers, status, stream);
 }
 
 }  // extern "C"

@@ -308,8 +308,9 @@ int ms_match_pairs(int n_views, const ms_view_features *views, const ms_pair_mat
     MS_CHECK(total <= matches_cap, "%s: matches_cap %d below the %lld matches found (*n_matches holds the number)", fn, matches_cap, total);
 
     int first = 0;
-    std::vector<float> src, dst, src_in, dst_in;
-    std::vector<uint8_t> mask;
+    // BestOf2NearestMatcher::match (matchers.cpp:699-770) over all pairs in two batched rounds; per pair the rule is the reference's, line for line
+    std::vector<int> round1, off1(1, 0);                  // round 1: every pair with count >= num_matches_thresh1, its centred points at off1
+    std::vector<float> src, dst;
     for (int k = 0; k < np; ++k) {
         ms_pair_matches &pm = pairs_out[k];
         pm = ms_pair_matches{};
@@ -323,33 +324,57 @@ int ms_match_pairs(int n_views, const ms_view_features *views, const ms_pair_mat
         for (int i = 0; i < count; ++i) m[i] = ms_feature_match{(int)(sl[i].x & 0xffffu), (int)(sl[i].x >> 16), (int)sl[i].y, 0};
         first += count;
         if (count < prm->num_matches_thresh1) continue;
-        // BestOf2NearestMatcher::match (matchers.cpp:699-770)
         const ms_view_features &fa = views[a], &fb = views[b];
-        src.resize(2 * (size_t)count); dst.resize(2 * (size_t)count); mask.assign((size_t)count + 1, 0);
+        const size_t o = src.size();
+        src.resize(o + 2 * (size_t)count); dst.resize(o + 2 * (size_t)count);
         for (int i = 0; i < count; ++i) {
             const float *pa = fa.keypoints + (size_t)m[i].query * fa.keypoint_stride, *pb = fb.keypoints + (size_t)m[i].train * fb.keypoint_stride;
-            src[2 * i] = pa[0] - fa.width * 0.5f; src[2 * i + 1] = pa[1] - fa.height * 0.5f;
-            dst[2 * i] = pb[0] - fb.width * 0.5f; dst[2 * i + 1] = pb[1] - fb.height * 0.5f;
+            src[o + 2 * i] = pa[0] - fa.width * 0.5f; src[o + 2 * i + 1] = pa[1] - fa.height * 0.5f;
+            dst[o + 2 * i] = pb[0] - fb.width * 0.5f; dst[o + 2 * i + 1] = pb[1] - fb.height * 0.5f;
         }
-        int ninl = 0;
-        int rc = ms_find_homography_ransac(src.data(), dst.data(), count, prm->ransac_reproj_threshold, prm->ransac_max_iters, prm->ransac_confidence, pm.H, mask.data(), &ninl,
-                                           stream);
-        if (rc < 0) return rc;
-        if (rc == 1) continue;                            // no model: have_H = 0
+        round1.push_back(k);
+        off1.push_back(off1.back() + count);
+    }
+    if (round1.empty()) return MS_OK;
+    const int n1 = (int)round1.size();
+    std::vector<double> Hs(9 * (size_t)n1);
+    std::vector<uint8_t> mask((size_t)off1.back() + 1, 0);
+    std::vector<int> st1(n1, 1);
+    if (int rc = ms_find_homography_ransac_batch(n1, off1.data(), src.data(), dst.data(), prm->ransac_reproj_threshold, prm->ransac_max_iters, prm->ransac_confidence, Hs.data(),
+                                                 mask.data(), nullptr, st1.data(), stream))
+        return rc;
+    std::vector<int> round2, off2(1, 0);                  // round 2: the inliers alone of every pair whose model passed the determinant test with num_inliers >= thresh2
+    std::vector<float> src_in, dst_in;
+    for (int r = 0; r < n1; ++r) {
+        ms_pair_matches &pm = pairs_out[round1[r]];
+        if (st1[r] != 0) continue;                        // no model: have_H = 0
+        memcpy(pm.H, &Hs[9 * (size_t)r], sizeof(pm.H));
         pm.have_H = 1;
         if (std::fabs(pm_det3(pm.H)) < DBL_EPSILON) continue;
+        ms_feature_match *m = matches_out + pm.first;
+        const uint8_t *mk = mask.data() + off1[r];
+        const float *s = src.data() + 2 * (size_t)off1[r], *d = dst.data() + 2 * (size_t)off1[r];
         pm.num_inliers = 0;
-        for (int i = 0; i < count; ++i) { m[i].inlier = mask[i] ? 1 : 0; pm.num_inliers += m[i].inlier; }
-        pm.confidence = pm.num_inliers / (8 + 0.3 * count);
+        for (int i = 0; i < pm.count; ++i) { m[i].inlier = mk[i] ? 1 : 0; pm.num_inliers += m[i].inlier; }
+        pm.confidence = pm.num_inliers / (8 + 0.3 * pm.count);
         if (pm.confidence > 3.) pm.confidence = 0.;
         if (pm.num_inliers < prm->num_matches_thresh2) continue;
-        src_in.clear(); dst_in.clear();
-        for (int i = 0; i < count; ++i)
-            if (m[i].inlier) { src_in.push_back(src[2 * i]); src_in.push_back(src[2 * i + 1]); dst_in.push_back(dst[2 * i]); dst_in.push_back(dst[2 * i + 1]); }
-        rc = ms_find_homography_ransac(src_in.data(), dst_in.data(), pm.num_inliers, prm->ransac_reproj_threshold, prm->ransac_max_iters, prm->ransac_confidence, pm.H, nullptr,
-                                       nullptr, stream);
-        if (rc < 0) return rc;
-        if (rc == 1) pm.have_H = 0;
+        for (int i = 0; i < pm.count; ++i)
+            if (m[i].inlier) { src_in.push_back(s[2 * i]); src_in.push_back(s[2 * i + 1]); dst_in.push_back(d[2 * i]); dst_in.push_back(d[2 * i + 1]); }
+        round2.push_back(round1[r]);
+        off2.push_back(off2.back() + pm.num_inliers);
+    }
+    if (round2.empty()) return MS_OK;
+    const int n2 = (int)round2.size();
+    std::vector<int> st2(n2, 1);
+    Hs.assign(9 * (size_t)n2, 0.0);
+    if (int rc = ms_find_homography_ransac_batch(n2, off2.data(), src_in.data(), dst_in.data(), prm->ransac_reproj_threshold, prm->ransac_max_iters, prm->ransac_confidence,
+                                                 Hs.data(), nullptr, nullptr, st2.data(), stream))
+        return rc;
+    for (int r = 0; r < n2; ++r) {
+        ms_pair_matches &pm = pairs_out[round2[r]];
+        memcpy(pm.H, &Hs[9 * (size_t)r], sizeof(pm.H));   // (no model: zeros, as the single call leaves them)
+        if (st2[r] != 0) pm.have_H = 0;
     }
     return MS_OK;
 }

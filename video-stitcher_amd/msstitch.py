@@ -232,6 +232,7 @@ EXPORTS = [
     "ms_dp_seams", "ms_set_seam_finder", "ms_get_seam_finder",
     "ms_focals_from_homography", "ms_estimate_rig", "ms_rig_focal_default_params", "ms_rig_focal_accumulate", "ms_refine_rig_cameras", "ms_refine_rig_focals",
     "ms_pair_match_default_params", "ms_match_pairs", "ms_biggest_component", "ms_wave_correct",
+    "ms_find_homography_ransac_batch",
 ]
 
 _lib = None
@@ -961,6 +962,28 @@ def find_homography_ransac(src, dst, reproj_threshold=3.0, max_iters=2000, confi
     if rc < 0:
         _chk(rc)
     return (None if rc == 1 else H.reshape(3, 3)), m[:n]
+
+
+def find_homography_ransac_batch(problems, reproj_threshold=3.0, max_iters=2000, confidence=0.995):
+    """ms_find_homography_ransac_batch: problems is a list of (src, dst) float32 (n, 2) arrays, every one solved as find_homography_ransac solves it alone, all of
+    them in one device pass.  Returns a list of (H 3x3 float64 or None, inlier mask uint8 (n,))."""
+    import numpy as np
+    srcs = [np.ascontiguousarray(s, np.float32).reshape(-1, 2) for s, _ in problems]
+    dsts = [np.ascontiguousarray(d, np.float32).reshape(-1, 2) for _, d in problems]
+    assert all(len(s) == len(d) for s, d in zip(srcs, dsts)), "a problem's src and dst differ in length"
+    k = len(problems)
+    off = np.zeros(k + 1, np.int32)
+    off[1:] = np.cumsum([len(s) for s in srcs])
+    total = int(off[-1])
+    src = np.concatenate(srcs + [np.zeros((1, 2), np.float32)]); dst = np.concatenate(dsts + [np.zeros((1, 2), np.float32)])
+    H = np.zeros((max(k, 1), 9), np.float64)
+    m = np.zeros(total + 1, np.uint8)
+    cnt = np.zeros(max(k, 1), np.int32); status = np.ones(max(k, 1), np.int32)
+    ip, fp = C.POINTER(C.c_int), C.POINTER(C.c_float)
+    _chk(load().ms_find_homography_ransac_batch(k, off.ctypes.data_as(ip), src.ctypes.data_as(fp), dst.ctypes.data_as(fp), C.c_double(reproj_threshold), int(max_iters),
+                                                C.c_double(confidence), H.ctypes.data_as(C.POINTER(C.c_double)), m.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                cnt.ctypes.data_as(ip), status.ctypes.data_as(ip), _stream() if k else None))      # (an empty batch needs no device)
+    return [(None if status[p] else H[p].reshape(3, 3).copy(), m[off[p]:off[p + 1]].copy()) for p in range(k)]
 
 
 # ------------------------------------------------------------------ compositor context
