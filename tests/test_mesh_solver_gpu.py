@@ -3,7 +3,12 @@
 
 Tolerances: the triangle statistics are exact integers and the salience formula is evaluated in the same order, so saliences must be
 bit-equal; the solve is fp64 CG with a different summation order than the oracle's, vertices must agree to 1e-3 px (the
-observed gap is ~1e-7 px)."""
+observed gap is ~1e-7 px).
+
+The largest system solved here (mesh_40x40 on two views: 6400 unknowns, ~55 000 rows) still gives every thread of the solver one element.  The
+capped grids (more than 8192 unknowns or 131072 rows: 36 x 36 and 40 x 40 on 6 views, 17 x 17 on 16) and the iteration caps at the edges of
+the host's 64-iteration launch blocks, there with the iterate pinned to half a float32 ulp + 16 x the oracle's own sensitivity to summation
+order (<= 3e-11 px), are test_mesh_solver_scale_gpu.py's."""
 import numpy as np
 import pytest
 import torch

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Recalibration-path timing of the descriptor matcher (ms_knn_match_hamming2) and the CPW mesh optimiser (ms_create_mesh) on the config-2/3 rig: 6 warped 1080p views, 100 matches per
 seam (MAX_FEATURES_PER_IMAGE), the reference's default 10 x 10 mesh and BASELINE config 3's 40 x 40 mesh.  Prints one JSON line per mesh
-size; the numpy oracle (oracle/mesh_oracle.py, CPU) is timed beside it on the 10 x 10 case when --cpu is given.
+size; with --cpu the numpy oracle (oracle/mesh_oracle.py, CPU) is timed beside both and compared with them (max_vertex_diff_px, cpu_iterations): the
+40 x 40 case is the one whose solve runs on capped grids (tests/test_mesh_solver_scale_gpu.py); its oracle assembly takes a while.
 
   python tools/bench_mesh_solver.py [--cpu] [--reps 3]"""
 import argparse
@@ -88,7 +89,7 @@ def main():
         line = {"what": "ms_create_mesh", "mesh": "%dx%d" % (M, M), "views": cfg["n"], "matches": sum(map(len, matches)), **info,
                 "ms": round(1e3 * min(ts), 2), "us_per_iteration": round(1e6 * min(ts) / max(1, info["iterations"]), 2),
                 "set_mesh_ms": round(1e3 * t_set, 2), "max_displacement_px": round(max(comp.mesh_displacement(i) for i in range(cfg["n"])), 2)}
-        if a.cpu and M == 10:
+        if a.cpu:
             import mesh_oracle as mo
             imgs = [w.cpu().numpy() for w in warped]
             t0 = time.perf_counter()
