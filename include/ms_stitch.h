@@ -796,6 +796,31 @@ typedef struct ms_orb_params {
 MS_API int ms_orb_default_params(ms_orb_params *prm);
 MS_API int ms_orb_detect_and_compute(const ms_image *gray, const ms_image *mask, const ms_orb_params *prm, float *keypoints_host, int max_keypoints,
                                      ms_image *descriptors, int *n_keypoints, ms_stream stream);
+/* The same for every view of a rig in one device pass: what featurefinder::findFeatures (360_stitcher/featurefinder.cpp:13-46) asks of
+ * cuda::ORB::detectAndCompute (cudafeatures2d/src/orb.cpp:430-865) view after view.  gray: n_views DEVICE 8UC1 images, which may differ in size; masks: NULL, or
+ * n_views entries (data == NULL: no mask for that view); keypoints_host: n_views x max_keypoints x 6 floats; descriptors: n_views DEVICE 8UC1 matrices of
+ * max_keypoints x 32, none overlapping another.  View v gets exactly what ms_orb_detect_and_compute(gray + v, its mask or NULL, prm, keypoints_host +
+ * 6 * max_keypoints * v, max_keypoints, descriptors + v, n_keypoints + v) returns, bit for bit and in the same order: n_keypoints[v] keypoint rows and the first
+ * n_keypoints[v] descriptor rows; descriptor rows from n_keypoints[v] on are not written.  The output is the input ms_match_pairs takes.
+ * A segment is one pyramid level of one view.  Sizes, budgets (orb.cpp:501-512), the detector's buffer (0.05 * area, :753) and every buffer offset follow from
+ * the shapes and prm, so they go up once as a table and no count comes back before the end.  On the device, each step one launch over all segments: the pyramid
+ * level by level (resize from the level below, :686; masks with it and through THRESH_TOZERO 254, :690-693); FAST scores (fast.cu:224-344); raw corners per row,
+ * scan, survivors per row, scan, write -- raster order, and where a level has more raw corners than the detector's buffer the first max_npoints of them in raster
+ * order are the candidates, each suppressed against the whole score map, as in the single call; the cull to 2n by FAST response (:772: a 256-bin histogram, then
+ * one ordered pass; no change and raster order where the level holds no more); Harris (orb.cu:93-138); the cull to n (:778) as a stable rank sort, keys through
+ * LDS in tiles of 1024; angles (orb.cu:160-211) and the six floats of mergeKeyPoints (:823-865) at the view's row offset; descriptors (orb.cu:222-367) straight
+ * into the caller's matrices.  No atomic decides an order: two calls return the same bytes.  Per call, whatever n_views is: nlevels + 10 launches at most,
+ * 1 upload, 1 clear, 1 copy back, 1 synchronisation, over the calling thread's grow-only staging blocks (no allocation once they have grown).  Device scratch in
+ * bytes, with A_v the sum of w * h over the levels of view v (about 3.3 times its area at 1.2 / 8 levels): 48 KiB of tables + 24 * n_views * max_keypoints
+ * + sum over v of [A_v (scores) + (A_v - area_v) (pyramid; twice with a mask) + 0.25 * A_v (candidates: 5 bytes for each of 0.05 * w * h) + 8 rows(A_v)]
+ * -- some 4.5 times the views' area without masks, 5.5 with; MS_ERR_NOMEM before anything is launched where it cannot be had.
+ * MS_ERR_INVALID, before the device is touched and naming the view: n_views outside [1, MS_MAX_VIEWS]; a null array; the single call's parameter limits; a view
+ * that is not 8UC1, has no data or is larger than 32767 in a dimension; a mask of another type or size; a descriptor matrix of another shape than max_keypoints
+ * (>= nfeatures) x 32, or whose byte range (steps included) overlaps another view's.  After the pass: a view with more than max_keypoints keypoints (see the
+ * single call: max_keypoints >= nfeatures + nlevels / 2 always holds them); the device clamps, so nothing past row max_keypoints - 1 of any view is written.
+ * Limits: one parameter set for the batch (no per-view nfeatures).  Synchronises. */
+MS_API int ms_orb_detect_and_compute_batch(int n_views, const ms_image *gray, const ms_image *masks, const ms_orb_params *prm, float *keypoints_host,
+                                           int max_keypoints, ms_image *descriptors, int *n_keypoints, ms_stream stream);
 /* The feature mask createMesh builds for findFeatures (360_stitcher/meshwarper.cpp:82-115): 255 inside the two column bands where neighbouring
  * views overlap (rect_a / rect_b: x0, width -- cv::rectangle clips them to the image) AND where the warped view is not black (inRange(0, 0) negated:
  * the pixels the projection did not fill).  warped_view: DEVICE 8UC3; mask: DEVICE 8UC1 of the same size. */

@@ -13,6 +13,8 @@
 // reads them back too: fast.cu:338-341, :379-382), the two culls (tiny stable sorts; the reference sorts on the device with an unstable
 // thrust sort, so its keypoint order is not defined -- ours is: raster order, stable culls), RANSAC's sequential subset draw and best-model
 // scan, and the final N-point fit + Levenberg-Marquardt polish of ONE model.
+// ms_orb_detect_and_compute_batch (the k_ob_* kernels below) runs the same ORB for every view of a rig with NOTHING on the host between the stages: counts, both culls
+// and the over-cap rule on the device, one synchronisation; it is held to the single call byte for byte (tests/test_orb_batch_gpu.py).
 // Conventions where CUDA leaves freedom (same as oracle/orb_oracle.py): float expressions without fma contraction; atan2f / sincosf as the
 // correctly rounded float of the double function.
 #include <algorithm>
@@ -20,6 +22,7 @@
 #include <climits>
 #include <cmath>
 #include <cstring>
+#include <new>
 #include <numeric>
 #include <vector>
 #include "common.hpp"
@@ -51,11 +54,9 @@ __global__ void __launch_bounds__(256) k_tozero254(uint8_t *m, size_t step, int 
 // (the c_table lookup of fast.cu:201-206 encodes exactly "the 16-bit mask holds 9 contiguous ones": tests/test_orb_oracle.py::test_arc9_equals_the_references_table
 // holds the rule to that table, tests/test_features_edges_gpu.py::test_every_16_bit_arc_mask holds this kernel to the rule over all 65 536 masks);
 // cornerScore's binary search (fast.cu:208-222) finds the largest threshold that still passes = (best arc's smallest difference) - 1.
-__global__ void __launch_bounds__(256) k_fast_score(const uint8_t *__restrict__ img, size_t step, int rows, int cols, const uint8_t *__restrict__ mask, size_t mstep,
-                                                    int edge, int th, uint8_t *__restrict__ score, size_t sstep)
+__device__ __forceinline__ int fast_score_at(const uint8_t *__restrict__ img, size_t step, int rows, int cols, const uint8_t *__restrict__ mask, size_t mstep, int edge, int th,
+                                             int i, int j)
 {
-    const int j = blockIdx.x * 64 + threadIdx.x, i = blockIdx.y * 4 + threadIdx.y;
-    if (j >= cols || i >= rows) return;
     int s = 0;
     const bool inner = i >= edge && j >= edge && i < rows - edge && j < cols - edge && cols > 2 * edge && rows > 2 * edge;
     if (i >= 3 && j >= 3 && i < rows - 3 && j < cols - 3 && inner && (!mask || mask[(size_t)i * mstep + j])) {
@@ -81,7 +82,14 @@ __global__ void __launch_bounds__(256) k_fast_score(const uint8_t *__restrict__ 
             s = min(max(a, b), 256) - 1;
         }
     }
-    score[(size_t)i * sstep + j] = (uint8_t)s;
+    return s;
+}
+__global__ void __launch_bounds__(256) k_fast_score(const uint8_t *__restrict__ img, size_t step, int rows, int cols, const uint8_t *__restrict__ mask, size_t mstep,
+                                                    int edge, int th, uint8_t *__restrict__ score, size_t sstep)
+{
+    const int j = blockIdx.x * 64 + threadIdx.x, i = blockIdx.y * 4 + threadIdx.y;
+    if (j >= cols || i >= rows) return;
+    score[(size_t)i * sstep + j] = (uint8_t)fast_score_at(img, step, rows, cols, mask, mstep, edge, th, i, j);
 }
 
 __device__ __forceinline__ bool is_local_max(const uint8_t *__restrict__ score, size_t sstep, int i, int j)
@@ -152,11 +160,9 @@ __global__ void __launch_bounds__(256) k_feature_mask(const uint8_t *__restrict_
 }
 
 // HarrisResponses (orb.cu:93-138): 7 x 7 block, integer gradient sums, float formula evaluated operation by operation
-__global__ void __launch_bounds__(64) k_harris(const uint8_t *__restrict__ img, size_t step, const short2 *__restrict__ loc, float *__restrict__ resp, int n, int block, float k)
+__device__ __forceinline__ float harris_at(const uint8_t *__restrict__ img, size_t step, int x, int y, int block, float k)
 {
-    const int p = blockIdx.x * 64 + threadIdx.x;
-    if (p >= n) return;
-    const int r = block / 2, x0 = loc[p].x - r, y0 = loc[p].y - r;
+    const int r = block / 2, x0 = x - r, y0 = y - r;
     int a = 0, b = 0, c = 0;
     for (int i = 0; i < block; ++i)
         for (int j = 0; j < block; ++j) {
@@ -169,19 +175,23 @@ __global__ void __launch_bounds__(64) k_harris(const uint8_t *__restrict__ img, 
     scale = 1.0f / scale;
     const float s4 = ((scale * scale) * scale) * scale;
     const float fa = (float)a, fb = (float)b, fc = (float)c, s = fa + fb;
-    resp[p] = ((fa * fb - fc * fc) - (k * s) * s) * s4;
+    return ((fa * fb - fc * fc) - (k * s) * s) * s4;
 }
-
-// IC_Angle (orb.cu:160-211)
-__global__ void __launch_bounds__(64) k_ic_angle(const uint8_t *__restrict__ img, size_t step, const short2 *__restrict__ loc, float *__restrict__ angle, int n, int half)
+__global__ void __launch_bounds__(64) k_harris(const uint8_t *__restrict__ img, size_t step, const short2 *__restrict__ loc, float *__restrict__ resp, int n, int block, float k)
 {
     const int p = blockIdx.x * 64 + threadIdx.x;
     if (p >= n) return;
-    const uint8_t *c = img + (size_t)loc[p].y * step + loc[p].x;
+    resp[p] = harris_at(img, step, loc[p].x, loc[p].y, block, k);
+}
+
+// IC_Angle (orb.cu:160-211)
+__device__ __forceinline__ float ic_angle_at(const uint8_t *__restrict__ img, size_t step, int x, int y, int half, const int *__restrict__ umax)
+{
+    const uint8_t *c = img + (size_t)y * step + x;
     int m01 = 0, m10 = 0;
     for (int u = -half; u <= half; ++u) m10 += u * (int)c[u];
     for (int v = 1; v <= half; ++v) {
-        const int d = c_umax[v];
+        const int d = umax[v];
         int vs = 0, msum = 0;
         for (int u = -d; u <= d; ++u) {
             const int pl = c[(ptrdiff_t)v * (ptrdiff_t)step + u], mi = c[-(ptrdiff_t)v * (ptrdiff_t)step + u];
@@ -192,19 +202,21 @@ __global__ void __launch_bounds__(64) k_ic_angle(const uint8_t *__restrict__ img
     const float PI_F = 3.14159265f;
     float a = (float)atan2((double)(float)m01, (double)(float)m10);
     if (a < 0) a += 2.0f * PI_F;
-    angle[p] = a * (180.0f / PI_F);
+    return a * (180.0f / PI_F);
+}
+__global__ void __launch_bounds__(64) k_ic_angle(const uint8_t *__restrict__ img, size_t step, const short2 *__restrict__ loc, float *__restrict__ angle, int n, int half)
+{
+    const int p = blockIdx.x * 64 + threadIdx.x;
+    if (p >= n) return;
+    angle[p] = ic_angle_at(img, step, loc[p].x, loc[p].y, half, c_umax);
 }
 
 // computeOrbDescriptor<2> (orb.cu:222-246, :352-367): byte b of keypoint p = 8 tests on the pattern rotated by the keypoint angle
-__global__ void __launch_bounds__(256) k_orb_desc(const uint8_t *__restrict__ img, size_t step, const short2 *__restrict__ loc, const float *__restrict__ angle, int n,
-                                                  uint8_t *__restrict__ desc, size_t dstep)
+__device__ __forceinline__ int orb_desc_byte(const uint8_t *__restrict__ img, size_t step, int x, int y, float angle, int b)
 {
-    const int b = threadIdx.x & 31, p = blockIdx.x * 8 + (threadIdx.x >> 5);
-    if (p >= n) return;
     const float PI_F = 3.14159265f;
-    const float a = angle[p] * (float)(PI_F / 180.f);
+    const float a = angle * (float)(PI_F / 180.f);
     const float sina = (float)sin((double)a), cosa = (float)cos((double)a);
-    const int x = loc[p].x, y = loc[p].y;
     auto val = [&](int idx) {
         const float px = (float)c_pattern[16 * b + idx].x, py = (float)c_pattern[16 * b + idx].y;
         const int yy = y + (int)__builtin_rintf(px * sina + py * cosa), xx = x + (int)__builtin_rintf(px * cosa - py * sina);
@@ -213,7 +225,14 @@ __global__ void __launch_bounds__(256) k_orb_desc(const uint8_t *__restrict__ im
     int v = 0;
 #pragma unroll
     for (int t = 0; t < 8; ++t) v |= (val(2 * t) < val(2 * t + 1)) << t;
-    desc[(size_t)p * dstep + b] = (uint8_t)v;
+    return v;
+}
+__global__ void __launch_bounds__(256) k_orb_desc(const uint8_t *__restrict__ img, size_t step, const short2 *__restrict__ loc, const float *__restrict__ angle, int n,
+                                                  uint8_t *__restrict__ desc, size_t dstep)
+{
+    const int b = threadIdx.x & 31, p = blockIdx.x * 8 + (threadIdx.x >> 5);
+    if (p >= n) return;
+    desc[(size_t)p * dstep + b] = (uint8_t)orb_desc_byte(img, step, loc[p].x, loc[p].y, angle[p], b);
 }
 
 // ---- RANSAC: per 4-point hypothesis HomographyEstimatorCallback::runKernel (fundam.cpp:80-142, k_ransac_fit: one lane a hypothesis), then the inlier count
@@ -714,6 +733,439 @@ int ransac_batch(const char *fn, int n_problems, const int *offsets, const float
     return MS_OK;
 }
 
+// ---- batched ORB: ms_orb_detect_and_compute for every view of a rig in one device pass, no host in the loop.
+// A SEGMENT is one pyramid level of one view.  Everything the host decides per segment in the single call -- sizes, budgets, the detector's buffer, where the level's
+// image, mask and score map live -- follows from the shapes and the parameters alone and goes up once, as a table; what depends on the pixels (the counts between the
+// stages) stays on the device.  Every kernel is launched once for all segments: a workgroup finds its segment in a list of (first work item, segment) by bisection.
+constexpr int OB_MAX_SEG = MS_MAX_VIEWS * 16;
+constexpr int OB_SORT_TILE = 1024;                              // Harris keys staged in LDS at a time (4 KiB)
+struct ObSeg {
+    const uint8_t *img, *mask;                                  // level 0: the caller's image and mask as they are; above: in the arena.  mask null: none
+    uint8_t *score;                                             // FAST score map of the level (step w); null where the budget is <= 0
+    uint8_t *desc;                                              // the view's descriptor matrix
+    size_t step, mstep, dstep;
+    int w, h, view, level, first;                               // first: the view's level-0 segment (its segments follow one another)
+    int n, max_npoints;                                         // the level's budget (orb.cpp:501-512) and the detector's buffer (orb.cpp:753)
+    int cap_b, cap_c;                                           // rows the level can hold after the first and the second cull: min(max_npoints, 2n), min(max_npoints, n)
+    int row_off, a_off, b_off, c_off;                           // its slices of the row arrays and of the three candidate arrays
+    float ifx, ify;                                             // resize from the level below: static_cast<float>(1.0 / fx) of launch_resize_linear
+    float loc_scale, size;                                      // mergeKeyPoints' factors (orb.cpp:823-865)
+};
+template <int N> struct ObList { int n, total; int start[N + 1], seg[N]; };         // segment seg[k] owns the work items start[k] .. start[k + 1] - 1
+struct ObTable {
+    int umax[32];
+    ObSeg segs[OB_MAX_SEG];
+    ObList<MS_MAX_VIEWS> pyr[16];                               // the 64 x 4 tiles of level l >= 1 of every view that has one
+    ObList<OB_MAX_SEG> tiles, rows, active, harris, sort, finish, desc; // tiles and rows of the scored segments; those segments; blocks of 64 / 256 / 64 / 8 keypoints
+};
+struct ObBufs {
+    int *rowraw, *rowcnt;                                       // per row of every scored segment: raw corners, survivors (counts, then exclusive offsets inside the segment)
+    int *cnt_a, *cnt_b, *cnt_c;                                 // per segment: candidates after suppression, after the first cull, after the second
+    short2 *loc_a, *loc_b, *loc_c;
+    uint8_t *score_a;                                           // FAST response of the candidates (1..255)
+    float *resp_b, *resp_c;                                     // Harris responses
+    float *kp;                                                  // n_views x max_keypoints x 6
+    int max_keypoints, half;                                    // half: patch_size / 2
+};
+
+template <int N> __device__ __forceinline__ int ob_find(const ObList<N> &L, int item, int &local)
+{
+    int lo = 0, hi = L.n;
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (L.start[mid] <= item) lo = mid; else hi = mid; }
+    local = item - L.start[lo];
+    return L.seg[lo];
+}
+
+// k_resize_linear<1> (prims.hip; resize.cu:71-106) at one pixel: the same float operations in the same order
+__device__ __forceinline__ uint8_t ob_resize_at(const uint8_t *__restrict__ src, size_t sstep, int srows, int scols, float ify, float ifx, int x, int y)
+{
+    const float sx = (float)x * ifx, sy = (float)y * ify;
+    const int x1 = f2i_rd(sx), y1 = f2i_rd(sy);
+    const int x2 = x1 + 1, y2 = y1 + 1;
+    const int x2r = min(x2, scols - 1), y2r = min(y2, srows - 1);
+    const float w11 = ((float)x2 - sx) * ((float)y2 - sy), w12 = (sx - (float)x1) * ((float)y2 - sy);
+    const float w21 = ((float)x2 - sx) * (sy - (float)y1), w22 = (sx - (float)x1) * (sy - (float)y1);
+    const uint8_t *r1 = row_ptr<uint8_t>(src, sstep, y1), *r2 = row_ptr<uint8_t>(src, sstep, y2r);
+    float out = 0.f;
+    out = __builtin_fmaf((float)r1[x1], w11, out);
+    out = __builtin_fmaf((float)r1[x2r], w12, out);
+    out = __builtin_fmaf((float)r2[x1], w21, out);
+    out = __builtin_fmaf((float)r2[x2r], w22, out);
+    return sat_u8(out);
+}
+// a. level l of every view from its level l - 1 (orb.cpp:686), the mask with it and through THRESH_TOZERO 254 (:690-693).  Equal sizes: the weights are 1, 0, 0, 0 -- a copy
+__global__ void __launch_bounds__(256) k_ob_pyramid(const ObTable *__restrict__ T, int level)
+{
+    int tile;
+    const ObSeg &s = T->segs[ob_find(T->pyr[level], blockIdx.x, tile)], &below = (&s)[-1];
+    const int tiles_x = (s.w + 63) / 64, x = (tile % tiles_x) * 64 + threadIdx.x, y = (tile / tiles_x) * 4 + threadIdx.y;
+    if (x >= s.w || y >= s.h) return;
+    const_cast<uint8_t *>(s.img)[(size_t)y * s.step + x] = ob_resize_at(below.img, below.step, below.h, below.w, s.ify, s.ifx, x, y);
+    if (s.mask) {
+        const uint8_t m = ob_resize_at(below.mask, below.mstep, below.h, below.w, s.ify, s.ifx, x, y);
+        const_cast<uint8_t *>(s.mask)[(size_t)y * s.mstep + x] = m <= 254 ? 0 : m;
+    }
+}
+// b. k_fast_score over the tiles of every scored segment
+__global__ void __launch_bounds__(256) k_ob_fast(const ObTable *__restrict__ T, int edge, int th)
+{
+    int tile;
+    const ObSeg &s = T->segs[ob_find(T->tiles, blockIdx.x, tile)];
+    const int tiles_x = (s.w + 63) / 64, j = (tile % tiles_x) * 64 + threadIdx.x, i = (tile / tiles_x) * 4 + threadIdx.y;
+    if (j >= s.w || i >= s.h) return;
+    s.score[(size_t)i * s.w + j] = (uint8_t)fast_score_at(s.img, s.step, s.h, s.w, s.mask, s.mstep, edge, th, i, j);
+}
+// c. suppression and raster-ordered compaction, one wave a row (4 rows a workgroup); the rule of the single call's over-cap branch for every segment: the raw corners
+// (score != 0, rows 3 .. h - 4, columns 3 .. w - 4) are numbered in raster order, those numbered below max_npoints are candidates, and a candidate survives when it
+// is a strict maximum of its 8 neighbours in the WHOLE score map.  Within the cap every raw corner is a candidate: k_row_counts / k_row_write.
+// PASS 0: raw corners of the row.  (scan.)  PASS 1: survivors of the row, from the raw offsets.  (scan.)  PASS 2: write them at the survivor offsets.
+template <int PASS>
+__global__ void __launch_bounds__(256) k_ob_rows(const ObTable *__restrict__ T, ObBufs B)
+{
+    const int item = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (item >= T->rows.total) return;
+    int i;
+    const ObSeg &s = T->segs[ob_find(T->rows, item, i)];
+    const int row = s.row_off + i;
+    const bool inner = i >= 3 && i < s.h - 3;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int raw = PASS == 0 ? 0 : B.rowraw[row], cnt = PASS == 2 ? B.rowcnt[row] : 0;
+    if (inner)
+        for (int j0 = 3; j0 < s.w - 3 && (PASS == 0 || raw < s.max_npoints); j0 += 64) {
+            const int j = j0 + lane;
+            const bool nz = j < s.w - 3 && s.score[(size_t)i * s.w + j] != 0;
+            const unsigned long long mnz = __ballot(nz);
+            if (PASS != 0) {
+                const bool keep = nz && raw + __popcll(mnz & below) < s.max_npoints && is_local_max(s.score, (size_t)s.w, i, j);
+                const unsigned long long mk = __ballot(keep);
+                const int k = cnt + __popcll(mk & below);
+                if (PASS == 2 && keep && k < s.max_npoints) { B.loc_a[s.a_off + k] = make_short2((short)j, (short)i); B.score_a[s.a_off + k] = s.score[(size_t)i * s.w + j]; }
+                cnt += __popcll(mk);
+            }
+            raw += __popcll(mnz);
+        }
+    if (lane == 0) { if (PASS == 0) B.rowraw[row] = raw; if (PASS == 1) B.rowcnt[row] = cnt; }
+}
+// k_row_scan for one segment a workgroup: exclusive scan of its rows in place, the total to total[segment] when asked for
+__global__ void __launch_bounds__(256) k_ob_scan(const ObTable *__restrict__ T, int *__restrict__ rows, int *__restrict__ total)
+{
+    __shared__ int s_part[256];
+    const int sg = T->active.seg[blockIdx.x];
+    const ObSeg &s = T->segs[sg];
+    int *r = rows + s.row_off;
+    const int per = (s.h + 255) / 256, a = threadIdx.x * per, b = min(a + per, s.h);
+    int sum = 0;
+    for (int i = a; i < b; ++i) sum += r[i];
+    s_part[threadIdx.x] = sum;
+    __syncthreads();
+    int off = 0;
+    for (int t = 0; t < (int)threadIdx.x; ++t) off += s_part[t];
+    for (int i = a; i < b; ++i) { const int c = r[i]; r[i] = off; off += c; }
+    if (threadIdx.x == 255 && total) total[sg] = off;
+}
+// d. cull to 2n by FAST response (orb.cpp:772): untouched, in raster order, when the level holds no more; else the first 2n of the stable descending order, in that
+// order.  The keys are 1..255.  One workgroup of 16 waves a segment; wave w owns the w-th sixteenth of the candidates (a stretch of the raster order).  A histogram
+// per wave gives, summed, the threshold score t, the number q still wanted AT t and every score's first output row, and, scanned over the waves, how many of each
+// score lie before a wave's stretch.  Then every wave walks its stretch 64 at a time: an element's place among its score is the count before the stretch + the
+// count the wave has seen (a running count per score, score v in lane v % 64's register v / 64) + its rank among the equal lanes of the 64 (ballots, one score at
+// a time); its row is its score's first row + that place; elements at t from place q on are dropped.  Counts come from atomics, the order never does.
+constexpr int OB_CULL_WAVES = 16;
+__global__ void __launch_bounds__(64 * OB_CULL_WAVES) k_ob_cull_fast(const ObTable *__restrict__ T, ObBufs B)
+{
+    __shared__ int s_hist[OB_CULL_WAVES][256], s_first[256], s_tq[2];
+    const int sg = T->active.seg[blockIdx.x], tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const ObSeg &s = T->segs[sg];
+    const int c = min(B.cnt_a[sg], s.max_npoints), keep = s.cap_b;
+    const short2 *la = B.loc_a + s.a_off;
+    const uint8_t *sa = B.score_a + s.a_off;
+    short2 *lb = B.loc_b + s.b_off;
+    if (c <= keep) {
+        for (int i = tid; i < c; i += 64 * OB_CULL_WAVES) lb[i] = la[i];
+        if (tid == 0) B.cnt_b[sg] = c;
+        return;
+    }
+    const int per = (c + OB_CULL_WAVES - 1) / OB_CULL_WAVES, a = wave * per, b = min(a + per, c);
+    for (int k = tid; k < OB_CULL_WAVES * 256; k += 64 * OB_CULL_WAVES) (&s_hist[0][0])[k] = 0;
+    __syncthreads();
+    for (int i = a + lane; i < b; i += 64) atomicAdd(&s_hist[wave][sa[i]], 1);
+    __syncthreads();
+    if (tid < 256) {                                            // per score: the counts before each wave's stretch, and the total
+        int run = 0;
+        for (int w = 0; w < OB_CULL_WAVES; ++w) { const int h = s_hist[w][tid]; s_hist[w][tid] = run; run += h; }
+        s_first[tid] = run;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int acc = 0, t = 0, q = 0;
+        for (int v = 255; v >= 1; --v) {
+            const int total = s_first[v];
+            s_first[v] = acc;
+            if (!t && acc + total >= keep) { t = v; q = keep - acc; }
+            acc += total;
+        }
+        s_tq[0] = t; s_tq[1] = q;
+    }
+    __syncthreads();
+    const int t = s_tq[0], q = s_tq[1];
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int seen[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) seen[k] = s_hist[wave][64 * k + lane];
+    for (int base = a; base < b; base += 64) {
+        const int i = base + lane, v = i < b ? (int)sa[i] : 0;
+        const bool in = v >= t;
+        unsigned long long todo = __ballot(in);
+        int r = 0;
+        while (todo) {                                          // the lanes of one score at a time
+            const int lv = __builtin_amdgcn_readfirstlane(__shfl(v, __ffsll((long long)todo) - 1));
+            const unsigned long long m = __ballot(in && v == lv);
+            const int held = (lv >> 6) == 0 ? seen[0] : (lv >> 6) == 1 ? seen[1] : (lv >> 6) == 2 ? seen[2] : seen[3];
+            const int before = __shfl(held, lv & 63);
+            if (in && v == lv) r = before + __popcll(m & below);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) seen[k] += (lane == (lv & 63) && k == (lv >> 6)) ? __popcll(m) : 0;
+            todo &= ~m;
+        }
+        if (in && (v > t || r < q)) { const int d = s_first[v] + r; if (d < keep) lb[d] = la[i]; }
+    }
+    if (tid == 0) B.cnt_b[sg] = keep;
+}
+// e. k_harris over the kept candidates of every segment
+__global__ void __launch_bounds__(64) k_ob_harris(const ObTable *__restrict__ T, ObBufs B)
+{
+    int blk;
+    const int sg = ob_find(T->harris, blockIdx.x, blk), p = blk * 64 + threadIdx.x;
+    const ObSeg &s = T->segs[sg];
+    if (p >= min(B.cnt_b[sg], s.cap_b)) return;
+    const short2 l = B.loc_b[s.b_off + p];
+    B.resp_b[s.b_off + p] = harris_at(s.img, s.step, l.x, l.y, 7, 0.04f);       // orb.cpp:774
+}
+// f. cull to n by Harris response (orb.cpp:778), the same rule with float keys: an element's output row is its rank, the number of elements that are greater, or
+// equal and earlier (std::stable_sort under a > b).  A workgroup ranks 256 elements of a segment, one a lane; every key of the segment passes through LDS in tiles.
+__global__ void __launch_bounds__(256) k_ob_cull_harris(const ObTable *__restrict__ T, ObBufs B)
+{
+    __shared__ float s_key[OB_SORT_TILE];
+    int blk;
+    const int sg = ob_find(T->sort, blockIdx.x, blk), tid = threadIdx.x, idx = blk * 256 + tid;
+    const ObSeg &s = T->segs[sg];
+    const int c = min(B.cnt_b[sg], s.cap_b), keep = s.cap_c;
+    const short2 *lb = B.loc_b + s.b_off;
+    const float *rb = B.resp_b + s.b_off;
+    short2 *lc = B.loc_c + s.c_off;
+    float *rc = B.resp_c + s.c_off;
+    if (idx == 0) B.cnt_c[sg] = min(c, keep);
+    if (c <= keep) {
+        if (idx < c) { lc[idx] = lb[idx]; rc[idx] = rb[idx]; }
+        return;
+    }
+    if (blk * 256 >= c) return;                                 // (the whole workgroup)
+    const float key = idx < c ? rb[idx] : 0.f;
+    int rank = 0;
+    for (int t0 = 0; t0 < c; t0 += OB_SORT_TILE) {
+        const int m = min(OB_SORT_TILE, c - t0);
+        __syncthreads();                                        // the tile before is read
+        for (int j = tid; j < m; j += 256) s_key[j] = rb[t0 + j];
+        __syncthreads();
+        for (int j = 0; j < m; ++j) {
+            const float kj = s_key[j];                          // one address a workgroup: a broadcast
+            rank += (kj > key) || (kj == key && t0 + j < idx);
+        }
+    }
+    if (idx < c && rank < keep) { lc[rank] = lb[idx]; rc[rank] = key; }
+}
+// g. a keypoint's row in its view: the counts of the view's lower levels, then its place in its own
+__device__ __forceinline__ int ob_view_row(const ObTable *__restrict__ T, const int *__restrict__ cnt_c, int sg, int p)
+{
+    int row = p;
+    for (int k = T->segs[sg].first; k < sg; ++k) row += cnt_c[k];
+    return row;
+}
+// k_ic_angle (orb.cpp:780) and mergeKeyPoints' six floats (:823-865)
+__global__ void __launch_bounds__(64) k_ob_finish(const ObTable *__restrict__ T, ObBufs B)
+{
+    int blk;
+    const int sg = ob_find(T->finish, blockIdx.x, blk), p = blk * 64 + threadIdx.x;
+    const ObSeg &s = T->segs[sg];
+    if (p >= min(B.cnt_c[sg], s.cap_c)) return;
+    const int row = ob_view_row(T, B.cnt_c, sg, p);
+    if (row >= B.max_keypoints) return;                         // the host fails the call; nothing is written past the view's rows
+    const short2 l = B.loc_c[s.c_off + p];
+    float *k = B.kp + 6 * ((size_t)s.view * B.max_keypoints + row);
+    k[0] = (float)l.x * s.loc_scale; k[1] = (float)l.y * s.loc_scale; k[2] = B.resp_c[s.c_off + p];
+    k[3] = ic_angle_at(s.img, s.step, l.x, l.y, B.half, T->umax);
+    k[4] = (float)s.level; k[5] = s.size;
+}
+// k_orb_desc (orb.cpp:783-821) straight into the view's descriptor matrix
+__global__ void __launch_bounds__(256) k_ob_desc(const ObTable *__restrict__ T, ObBufs B)
+{
+    int blk;
+    const int sg = ob_find(T->desc, blockIdx.x, blk), b = threadIdx.x & 31, p = blk * 8 + (threadIdx.x >> 5);
+    const ObSeg &s = T->segs[sg];
+    if (p >= min(B.cnt_c[sg], s.cap_c)) return;
+    const int row = ob_view_row(T, B.cnt_c, sg, p);
+    if (row >= B.max_keypoints) return;
+    const short2 l = B.loc_c[s.c_off + p];
+    const float angle = B.kp[6 * ((size_t)s.view * B.max_keypoints + row) + 3];
+    s.desc[(size_t)row * s.dstep + b] = (uint8_t)orb_desc_byte(s.img, s.step, l.x, l.y, angle, b);
+}
+
+static inline size_t ob_align(size_t n) { return (n + 255) & ~(size_t)255; }
+template <int N> static inline void ob_add(ObList<N> &L, int seg, long long items)
+{
+    if (items <= 0) return;
+    L.seg[L.n] = seg; L.start[L.n] = L.total; L.total += (int)items; L.start[++L.n] = L.total;
+}
+
+// the arguments are checked and a device is present
+int orb_batch(const char *fn, int n_views, const ms_image *gray, const ms_image *masks, const ms_orb_params *prm, float *kp_host, int max_keypoints, ms_image *desc,
+              int *n_out, ms_stream stream)
+{
+    hipStream_t st = as_stream(stream);
+    const int half = prm->patch_size / 2;
+    // the table: built in pinned memory with arena offsets in place of pointers, which are added once the arena is there
+    const size_t o_tab = 0, o_cnt_ab = ob_align(sizeof(ObTable)), o_cnt = o_cnt_ab + ob_align(2 * sizeof(int) * OB_MAX_SEG), o_kp = o_cnt + ob_align(sizeof(int) * OB_MAX_SEG),
+                 kp_bytes = sizeof(float) * 6 * (size_t)n_views * max_keypoints, back_bytes = ob_align(sizeof(int) * OB_MAX_SEG) + kp_bytes;
+    char *pin = (char *)pinned_scratch().get(o_kp + kp_bytes);
+    if (!pin) return fail(MS_ERR_NOMEM, "%s: cannot allocate pinned staging memory", fn);
+    ObTable &T = *new (pin + o_tab) ObTable();
+    {   // u_max of the circular patch (orb.cpp:514-529)
+        std::vector<int> u(half + 2, 0);
+        const float r2 = std::sqrt(2.f);
+        for (int v = 0; v <= half * r2 / 2 + 1; ++v) u[v] = (int)std::nearbyint(std::sqrt((float)(half * half - v * v)));
+        for (int v = half, v0 = 0; v >= half * r2 / 2; --v) { while (u[v0] == u[v0 + 1]) ++v0; u[v] = v0; ++v0; }
+        for (size_t i = 0; i < u.size() && i < 32; ++i) T.umax[i] = u[i];
+    }
+    // per-level budgets (orb.cpp:501-512)
+    std::vector<int> nper(prm->nlevels);
+    {
+        const float factor = 1.0f / prm->scale_factor;
+        float nd = (float)((double)(prm->nfeatures * (1.0f - factor)) / (1.0 - std::pow((double)factor, prm->nlevels)));
+        int sum = 0;
+        for (int l = 0; l < prm->nlevels - 1; ++l) { nper[l] = (int)std::nearbyint(nd); sum += nper[l]; nd *= factor; }
+        nper[prm->nlevels - 1] = prm->nfeatures - sum;
+    }
+    auto level_scale = [&](int l) { return (float)std::pow((double)prm->scale_factor, l - prm->first_level); };
+    int n_seg = 0;
+    long long rows = 0, na = 0, nb = 0, nc = 0;
+    size_t arena = 0;                                          // pyramid levels >= 1, their masks, the score maps
+    std::vector<size_t> o_img(OB_MAX_SEG, 0), o_msk(OB_MAX_SEG, 0), o_score(OB_MAX_SEG, 0);
+    for (int v = 0; v < n_views; ++v) {
+        const bool have_mask = masks && masks[v].data;
+        const int first = n_seg;
+        for (int level = 0; level < prm->nlevels; ++level) {
+            const float sc = 1.0f / level_scale(level);
+            const int w = (int)std::nearbyint((float)gray[v].cols * sc), h = (int)std::nearbyint((float)gray[v].rows * sc);      // orb.cpp:668
+            if (w < 8 || h < 8) break;
+            const int sg = n_seg++;
+            ObSeg &s = T.segs[sg];
+            s.w = w; s.h = h; s.view = v; s.level = level; s.first = first;
+            s.desc = (uint8_t *)desc[v].data; s.dstep = desc[v].step;
+            if (level == 0) {
+                s.img = (const uint8_t *)gray[v].data; s.step = gray[v].step;
+                if (have_mask) { s.mask = (const uint8_t *)masks[v].data; s.mstep = masks[v].step; }
+            } else {
+                const ObSeg &below = T.segs[sg - 1];
+                s.ifx = (float)(1.0 / ((double)w / below.w)); s.ify = (float)(1.0 / ((double)h / below.h));      // launch_resize_linear with fx = fy = 0
+                o_img[sg] = arena; arena += ob_align((size_t)w * h); s.step = (size_t)w;
+                if (have_mask) { o_msk[sg] = arena; arena += ob_align((size_t)w * h); s.mstep = (size_t)w; }
+                ob_add(T.pyr[level], sg, (long long)div_up(w, 64) * div_up(h, 4));
+            }
+            const float sf = level_scale(level);
+            s.loc_scale = level != prm->first_level ? sf : 1.0f; s.size = (float)prm->patch_size * sf;
+            s.n = nper[level];
+            s.max_npoints = (int)(0.05 * ((double)w * h));                  // orb.cpp:753
+            if (s.n <= 0) continue;                                         // the level contributes its pyramid image only
+            s.cap_b = (int)std::min<long long>(s.max_npoints, 2ll * s.n); s.cap_c = std::min(s.max_npoints, s.n);
+            o_score[sg] = arena; arena += ob_align((size_t)w * h);
+            s.row_off = (int)rows; s.a_off = (int)na; s.b_off = (int)nb; s.c_off = (int)nc;
+            rows += h; na += s.max_npoints; nb += s.cap_b; nc += s.cap_c;
+            ob_add(T.active, sg, 1);
+            ob_add(T.tiles, sg, (long long)div_up(w, 64) * div_up(h, 4));
+            ob_add(T.rows, sg, h);
+            ob_add(T.harris, sg, div_up(s.cap_b, 64));
+            ob_add(T.sort, sg, div_up(s.cap_b, 256));
+            ob_add(T.finish, sg, div_up(s.cap_c, 64));
+            ob_add(T.desc, sg, div_up(s.cap_c, 8));
+            if (na > INT_MAX / 16 || T.tiles.total > INT_MAX / 16) return fail(MS_ERR_INVALID, "%s: view %d: the views are more than one batch holds", fn, v);
+        }
+    }
+    const size_t o_rowraw = o_kp + ob_align(kp_bytes), o_rowcnt = o_rowraw + ob_align(sizeof(int) * (size_t)rows),
+                 o_loc_a = o_rowcnt + ob_align(sizeof(int) * (size_t)rows), o_score_a = o_loc_a + ob_align(sizeof(short2) * (size_t)na), o_loc_b = o_score_a + ob_align((size_t)na),
+                 o_resp_b = o_loc_b + ob_align(sizeof(short2) * (size_t)nb), o_loc_c = o_resp_b + ob_align(sizeof(float) * (size_t)nb),
+                 o_resp_c = o_loc_c + ob_align(sizeof(short2) * (size_t)nc), o_arena = o_resp_c + ob_align(sizeof(float) * (size_t)nc), dev_bytes = o_arena + arena;
+    char *dev = (char *)device_scratch().get(dev_bytes);
+    if (!dev) return fail(MS_ERR_NOMEM, "%s: cannot allocate %zu bytes of device scratch", fn, dev_bytes);
+    for (int sg = 0; sg < n_seg; ++sg) {
+        ObSeg &s = T.segs[sg];
+        if (s.level > 0) { s.img = (const uint8_t *)(dev + o_arena + o_img[sg]); if (s.mstep) s.mask = (const uint8_t *)(dev + o_arena + o_msk[sg]); }
+        if (s.n > 0) s.score = (uint8_t *)(dev + o_arena + o_score[sg]);
+    }
+    ObBufs B{};
+    B.rowraw = (int *)(dev + o_rowraw); B.rowcnt = (int *)(dev + o_rowcnt);
+    B.cnt_a = (int *)(dev + o_cnt_ab); B.cnt_b = B.cnt_a + OB_MAX_SEG; B.cnt_c = (int *)(dev + o_cnt);
+    B.loc_a = (short2 *)(dev + o_loc_a); B.score_a = (uint8_t *)(dev + o_score_a);
+    B.loc_b = (short2 *)(dev + o_loc_b); B.resp_b = (float *)(dev + o_resp_b);
+    B.loc_c = (short2 *)(dev + o_loc_c); B.resp_c = (float *)(dev + o_resp_c);
+    B.kp = (float *)(dev + o_kp); B.max_keypoints = max_keypoints; B.half = half;
+    const ObTable *dT = (const ObTable *)(dev + o_tab);
+    const int n_active = T.active.n;
+
+    // the pass: 1 upload, 1 clear (the block is reused: every count of this call starts at 0), nlevels + 10 launches at most, 1 copy back, 1 synchronise
+    auto enqueue = [&]() -> hipError_t {
+        hipError_t e = hipMemcpyAsync(dev + o_tab, pin + o_tab, sizeof(ObTable), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemsetAsync(dev + o_cnt_ab, 0, o_kp - o_cnt_ab, st);      // the three count arrays lie together
+        for (int level = 1; level < prm->nlevels && e == hipSuccess; ++level) {
+            if (!T.pyr[level].total) break;
+            k_ob_pyramid<<<T.pyr[level].total, dim3(64, 4), 0, st>>>(dT, level);
+            e = hipGetLastError();
+        }
+        if (!n_active || e != hipSuccess) return e;             // (never a launch with an empty grid)
+        k_ob_fast<<<T.tiles.total, dim3(64, 4), 0, st>>>(dT, prm->edge_threshold, prm->fast_threshold);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        const int row_blocks = div_up(T.rows.total, 4);
+        k_ob_rows<0><<<row_blocks, 256, 0, st>>>(dT, B);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        k_ob_scan<<<n_active, 256, 0, st>>>(dT, B.rowraw, nullptr);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        k_ob_rows<1><<<row_blocks, 256, 0, st>>>(dT, B);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        k_ob_scan<<<n_active, 256, 0, st>>>(dT, B.rowcnt, B.cnt_a);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        k_ob_rows<2><<<row_blocks, 256, 0, st>>>(dT, B);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        k_ob_cull_fast<<<n_active, 64 * OB_CULL_WAVES, 0, st>>>(dT, B);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        k_ob_harris<<<T.harris.total, 64, 0, st>>>(dT, B);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        k_ob_cull_harris<<<T.sort.total, 256, 0, st>>>(dT, B);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        k_ob_finish<<<T.finish.total, 64, 0, st>>>(dT, B);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        k_ob_desc<<<T.desc.total, 256, 0, st>>>(dT, B);
+        return hipGetLastError();
+    };
+    hipError_t e = enqueue();
+    if (e == hipSuccess) e = hipMemcpyAsync(pin + o_cnt, dev + o_cnt, back_bytes, hipMemcpyDeviceToHost, st);
+    const hipError_t se = hipStreamSynchronize(st);            // also after a failed enqueue: nothing of this call stays in flight over the scratch blocks
+    MS_HIP(e);
+    MS_HIP(se);
+    const int *cnt_c = (const int *)(pin + o_cnt);
+    std::vector<int> total(n_views, 0);
+    for (int sg = 0; sg < n_seg; ++sg) {
+        const ObSeg &s = T.segs[sg];
+        if (s.n <= 0) continue;
+        if (cnt_c[sg] < 0 || cnt_c[sg] > s.cap_c) return fail(MS_ERR_HIP, "%s: view %d: the device returned an impossible keypoint count (%d of %d)", fn, s.view, cnt_c[sg], s.cap_c);
+        total[s.view] += cnt_c[sg];
+    }
+    for (int v = 0; v < n_views; ++v)
+        if (total[v] > max_keypoints) return fail(MS_ERR_INVALID, "%s: view %d: more than max_keypoints (%d) keypoints", fn, v, max_keypoints);
+    for (int v = 0; v < n_views; ++v) {
+        memcpy(kp_host + 6 * (size_t)max_keypoints * v, pin + o_kp + sizeof(float) * 6 * (size_t)max_keypoints * v, sizeof(float) * 6 * (size_t)total[v]);
+        n_out[v] = total[v];
+    }
+    return MS_OK;
+}
+
 }  // namespace
 }  // namespace ms
 
@@ -896,6 +1348,39 @@ int ms_orb_detect_and_compute(const ms_image *gray, const ms_image *mask, const 
     MS_HIP(hipStreamSynchronize(st));
     *n_out = total;
     return MS_OK;
+}
+
+int ms_orb_detect_and_compute_batch(int n_views, const ms_image *gray, const ms_image *masks, const ms_orb_params *prm, float *kp_host, int max_keypoints,
+                                    ms_image *desc, int *n_out, ms_stream stream)
+{
+    const char *fn = "ms_orb_detect_and_compute_batch";
+    MS_CHECK(n_views >= 1 && n_views <= MS_MAX_VIEWS, "%s: n_views = %d must be in [1, %d]", fn, n_views, MS_MAX_VIEWS);
+    MS_CHECK(gray, "%s: null gray", fn);
+    MS_CHECK(prm, "%s: null prm", fn);
+    MS_CHECK(kp_host, "%s: null keypoints_host", fn);
+    MS_CHECK(desc, "%s: null descriptors", fn);
+    MS_CHECK(n_out, "%s: null n_keypoints", fn);
+    MS_CHECK(prm->nlevels >= 1 && prm->nlevels <= 16 && prm->first_level == 0 && prm->patch_size == 31 && prm->nfeatures >= 1 && prm->scale_factor > 1.f,
+             "%s: supports first_level 0, patch_size 31 (the learned pattern), 1..16 levels", fn);
+    MS_CHECK(prm->edge_threshold >= 19 && prm->edge_threshold >= prm->patch_size / 2 + 1 && prm->fast_threshold >= 1 && prm->fast_threshold <= 254,
+             "%s: edge_threshold %d must be >= 19 and fast_threshold %d in [1, 254]", fn, prm->edge_threshold, prm->fast_threshold);      // (see ms_orb_detect_and_compute)
+    MS_CHECK(max_keypoints >= prm->nfeatures, "%s: max_keypoints %d must be >= nfeatures %d", fn, max_keypoints, prm->nfeatures);
+    for (int v = 0; v < n_views; ++v) {
+        MS_CHECK(gray[v].data && gray[v].type == MS_8UC1, "%s: view %d: gray must be a device 8UC1 image", fn, v);
+        MS_CHECK(gray[v].rows >= 0 && gray[v].cols >= 0 && gray[v].rows <= 32767 && gray[v].cols <= 32767, "%s: view %d: %d x %d is no image size", fn, v, gray[v].cols, gray[v].rows);
+        MS_CHECK(!masks || !masks[v].data || (masks[v].type == MS_8UC1 && masks[v].rows == gray[v].rows && masks[v].cols == gray[v].cols),
+                 "%s: view %d: mask must be 8UC1 of the image size", fn, v);
+        MS_CHECK(desc[v].data && desc[v].type == MS_8UC1 && desc[v].cols == 32 && desc[v].rows >= max_keypoints && desc[v].step >= 32,
+                 "%s: view %d: descriptors must be 8UC1 max_keypoints x 32", fn, v);
+    }
+    for (int v = 0; v < n_views; ++v)                                       // the byte ranges of the descriptor matrices, steps included
+        for (int u = 0; u < v; ++u) {
+            const char *a0 = (const char *)desc[u].data, *a1 = a0 + (size_t)(max_keypoints - 1) * desc[u].step + 32;
+            const char *b0 = (const char *)desc[v].data, *b1 = b0 + (size_t)(max_keypoints - 1) * desc[v].step + 32;
+            MS_CHECK(a1 <= b0 || b1 <= a0, "%s: view %d: its descriptors overlap those of view %d", fn, v, u);
+        }
+    if (int e = require_device()) return e;
+    return orb_batch(fn, n_views, gray, masks, prm, kp_host, max_keypoints, desc, n_out, stream);
 }
 
 int ms_feature_mask(const ms_image *img, int a_x0, int a_w, int b_x0, int b_w, ms_image *mask, ms_stream stream)

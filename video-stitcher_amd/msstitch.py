@@ -233,6 +233,7 @@ EXPORTS = [
     "ms_focals_from_homography", "ms_estimate_rig", "ms_rig_focal_default_params", "ms_rig_focal_accumulate", "ms_refine_rig_cameras", "ms_refine_rig_focals",
     "ms_pair_match_default_params", "ms_match_pairs", "ms_biggest_component", "ms_wave_correct",
     "ms_find_homography_ransac_batch",
+    "ms_orb_detect_and_compute_batch",
 ]
 
 _lib = None
@@ -946,6 +947,39 @@ def orb_detect_and_compute(gray, mask=None, nfeatures=2500, scale_factor=1.2, nl
     _chk(load().ms_orb_detect_and_compute(C.byref(img(gray)), None if mask is None else C.byref(img(mask)), C.byref(prm),
                                           kp.ctypes.data_as(C.POINTER(C.c_float)), cap, C.byref(di), C.byref(n), _stream()))
     return kp[:n.value].copy(), desc[:n.value]
+
+
+def orb_params(nfeatures=2500, scale_factor=1.2, nlevels=8, fast_threshold=20, edge_threshold=None):
+    """ms_orb_default_params with orb_detect_and_compute's keyword arguments applied"""
+    prm = OrbParams()
+    _chk(load().ms_orb_default_params(C.byref(prm)))
+    prm.nfeatures, prm.scale_factor, prm.nlevels, prm.fast_threshold = nfeatures, scale_factor, nlevels, fast_threshold
+    if edge_threshold is not None:
+        prm.edge_threshold = edge_threshold
+    return prm
+
+
+def orb_detect_and_compute_batch(grays, masks=None, **orb_kw):
+    """ms_orb_detect_and_compute_batch: orb_detect_and_compute for every view in one device pass.  grays: torch uint8 (H, W) tensors on the device, of any sizes;
+    masks: None, or one entry per view (a tensor or None); keyword arguments as orb_detect_and_compute takes them, one set for the batch.
+    Returns [(keypoints (n, 6) float32 numpy, descriptors (n, 32) uint8 torch tensor on the device, (width, height)), ...]: per view what orb_detect_and_compute
+    returns, bit for bit and in its order, and the view's size behind it -- the list is what match_pairs / view_features take as it is."""
+    import numpy as np
+    import torch
+    prm = orb_params(**orb_kw)
+    n = len(grays)
+    cap = prm.nfeatures + prm.nlevels // 2      # (see orb_detect_and_compute)
+    kp = np.zeros((max(n, 1), cap, 6), np.float32)
+    descs = [torch.zeros((cap, 32), dtype=torch.uint8, device=g.device) for g in grays]
+    gi = (Image * max(n, 1))(*[img(g) for g in grays])
+    di = (Image * max(n, 1))(*[img(d) for d in descs])
+    mi = None
+    if masks is not None:
+        assert len(masks) == n
+        mi = (Image * max(n, 1))(*[Image() if m is None else img(m) for m in masks])
+    cnt = (C.c_int * max(n, 1))()
+    _chk(load().ms_orb_detect_and_compute_batch(n, gi, mi, C.byref(prm), kp.ctypes.data_as(C.POINTER(C.c_float)), cap, di, cnt, _stream()))
+    return [(kp[v, :cnt[v]].copy(), descs[v][:cnt[v]], (int(grays[v].shape[1]), int(grays[v].shape[0]))) for v in range(n)]
 
 
 def find_homography_ransac(src, dst, reproj_threshold=3.0, max_iters=2000, confidence=0.995):

@@ -347,25 +347,34 @@ template <class Mat> void findFeatures(const std::vector<Mat> &images, const std
     ms_orb_params prm;
     check(ms_orb_default_params(&prm));
     prm.nfeatures = nfeatures; prm.scale_factor = scale_factor; prm.nlevels = nlevels;
-    Mat gray;
     const int cap = nfeatures + nlevels / 2;        // the rounded per-level budgets can add up to (nlevels - 1) / 2 more than nfeatures (ms_stitch.h)
-    std::vector<float> kp((size_t)6 * cap);
-    for (size_t i = 0; i < images.size(); ++i) {
-        gray.create(images[i].rows, images[i].cols, MS_8UC1);
-        ms_image im = wrap(images[i]), g = wrap(gray);
-        check(ms_bgr_to_gray(&im, &g, s));                                             // cuda::cvtColor(gpu_img, gpu_img, CV_BGR2GRAY)
-        features[i].descriptors.create(cap, 32, MS_8UC1);
-        ms_image d = wrap(features[i].descriptors), mk{};
-        const bool have_mask = i < masks.size() && masks[i].data;
-        if (have_mask) mk = wrap(masks[i]);
-        int n = 0;
-        check(ms_orb_detect_and_compute(&g, have_mask ? &mk : nullptr, &prm, kp.data(), cap, &d, &n, s));
-        features[i].img_idx = (int)i;
-        features[i].img_size = Size{images[i].cols, images[i].rows};
-        features[i].keypoints.resize(n);
-        for (int k = 0; k < n; ++k) {
-            const float *r = &kp[6 * (size_t)k];
-            features[i].keypoints[k] = KeyPoint{{r[0], r[1]}, r[5], r[3], r[2], (int)r[4]};
+    // grey per view as the reference converts it, then every view's detectAndCompute in ONE ms_orb_detect_and_compute_batch call, MS_MAX_VIEWS views at a time
+    for (size_t i0 = 0; i0 < images.size(); i0 += MS_MAX_VIEWS) {
+        const size_t m = std::min(images.size() - i0, (size_t)MS_MAX_VIEWS);
+        std::vector<Mat> gray(m);
+        std::vector<ms_image> g(m), mk(m), d(m);
+        std::vector<float> kp((size_t)6 * cap * m);
+        std::vector<int> n(m, 0);
+        for (size_t j = 0; j < m; ++j) {
+            const size_t i = i0 + j;
+            gray[j].create(images[i].rows, images[i].cols, MS_8UC1);
+            ms_image im = wrap(images[i]);
+            g[j] = wrap(gray[j]);
+            check(ms_bgr_to_gray(&im, &g[j], s));                                      // cuda::cvtColor(gpu_img, gpu_img, CV_BGR2GRAY)
+            features[i].descriptors.create(cap, 32, MS_8UC1);
+            d[j] = wrap(features[i].descriptors);
+            mk[j] = (i < masks.size() && masks[i].data) ? wrap(masks[i]) : ms_image{};
+        }
+        check(ms_orb_detect_and_compute_batch((int)m, g.data(), mk.data(), &prm, kp.data(), cap, d.data(), n.data(), s));
+        for (size_t j = 0; j < m; ++j) {
+            const size_t i = i0 + j;
+            features[i].img_idx = (int)i;
+            features[i].img_size = Size{images[i].cols, images[i].rows};
+            features[i].keypoints.resize(n[j]);
+            for (int k = 0; k < n[j]; ++k) {
+                const float *r = &kp[6 * ((size_t)cap * j + k)];
+                features[i].keypoints[k] = KeyPoint{{r[0], r[1]}, r[5], r[3], r[2], (int)r[4]};
+            }
         }
     }
 }
