@@ -781,14 +781,28 @@ MS_API int ms_knn_match_hamming2(const ms_image *query, const ms_image *train, i
  * score and 3 x 3 non-max suppression, per-level budgets, Harris responses, intensity-centroid angles, rBRIEF descriptors (WTA_K = 2, HARRIS_SCORE,
  * no blur: the creator's defaults).  gray: DEVICE 8UC1 (ms_bgr_to_gray); mask: DEVICE 8UC1 of the same size or NULL.
  * keypoints_host: max_keypoints x 6 floats (x, y, response, angle in degrees, octave, size), the rows of cuda::ORB's keypoint matrix;
- * descriptors: DEVICE 8UC1 max_keypoints x 32 (row i belongs to keypoint i).  Keypoint order: levels in turn, inside a level by descending Harris
- * response where the level was culled, raster order otherwise (the reference's order is left to atomics and an unstable sort).  Synchronises.
- * Per-level budgets follow orb.cpp:501-512 (a geometric series rounded per level, the last level takes nfeatures minus the others), which gives
- * some levels 0 at small nfeatures (nfeatures 1: only the last level has a budget) and the last level a negative number at a few (nfeatures 7 at
- * the defaults: -1), where the reference is undefined.  Here a level whose budget is <= 0 contributes no keypoints and the call succeeds.  The
- * other levels keep their budgets, so with a negative last budget up to (nlevels - 1) / 2 more than nfeatures keypoints come back (each rounding adds
- * at most one half): max_keypoints >= nfeatures + nlevels / 2 holds them at any parameters; a smaller buffer that overflows is MS_ERR_INVALID.  The
- * pyramid ends before the first level narrower or lower than 8 pixels; a level not larger than 2 * edge_threshold in both dimensions has no keypoints. */
+ * descriptors: DEVICE 8UC1 max_keypoints x 32 (row i belongs to keypoint i; rows from *n_keypoints on are not written).  Synchronises once.
+ * The result, defined here (the reference leaves the order to atomics and an unstable sort); oracle/orb_oracle.py states it in numpy and the tests hold the
+ * library to it byte for byte:
+ *   order    levels in turn (mergeKeyPoints, orb.cpp:823-865).  Inside a level: raster order after FAST; each cull (to 2n by FAST response, :772, then to n by
+ *            Harris response, :778; cull: :719-733) is a stable descending sort of that order where the level holds more than it keeps, and no change otherwise.
+ *   budgets  orb.cpp:501-512 (a geometric series rounded per level, the last level takes nfeatures minus the others), which gives some levels 0 at small
+ *            nfeatures (nfeatures 1: only the last level has a budget) and the last level a negative number at a few (nfeatures 7 at the defaults: -1), where
+ *            the reference is undefined.  Here a level whose budget is <= 0 contributes no keypoints and the call succeeds.  The other levels keep their
+ *            budgets, so with a negative last budget up to (nlevels - 1) / 2 more than nfeatures keypoints come back (each rounding adds at most one half):
+ *            max_keypoints >= nfeatures + nlevels / 2 holds them at any parameters; a smaller buffer that overflows is MS_ERR_INVALID, and nothing past row
+ *            max_keypoints - 1 is written.
+ *   over-cap where a level has more raw FAST corners than the detector's buffer (max_npoints = 0.05 * its area, orb.cpp:753), the reference keeps whichever win
+ *            its atomic counter (fast.cu:338-341); here the candidates are the first max_npoints raw corners in raster order, each suppressed against the
+ *            whole score map.
+ *   limits   first_level 0, patch_size 31 (the learned pattern), 1..16 levels, nfeatures >= 1, scale_factor > 1; edge_threshold >= 19 (the reach of the
+ *            rotated pattern: the kernels read around a keypoint without bounds checks) and fast_threshold in [1, 254]; an image of at most 32767 x 32767
+ *            (keypoint coordinates are 16-bit on the device); a mask, where given, with data, 8UC1 and of the image size; descriptors 8UC1, 32 columns, at
+ *            least max_keypoints (>= nfeatures) rows and a step of at least 32 bytes.  Anything else is MS_ERR_INVALID before anything is launched.  The
+ *            pyramid ends before the first level narrower or lower than 8 pixels; a level not larger than 2 * edge_threshold in both dimensions has no
+ *            keypoints.
+ * The call is ms_orb_detect_and_compute_batch with n_views = 1 (see there for the mechanism): it works over the calling thread's grow-only staging blocks -- no
+ * allocation once they have grown -- with nlevels + 10 launches at most and ONE synchronisation. */
 typedef struct ms_orb_params {
     int nfeatures; float scale_factor; int nlevels;      /* ORB::create(2500, 1.2f, 8)  featurefinder.cpp:15 */
     int edge_threshold, first_level, patch_size, fast_threshold;     /* 31, 0, 31, 20 (cuda::ORB::create defaults) */
@@ -799,14 +813,14 @@ MS_API int ms_orb_detect_and_compute(const ms_image *gray, const ms_image *mask,
 /* The same for every view of a rig in one device pass: what featurefinder::findFeatures (360_stitcher/featurefinder.cpp:13-46) asks of
  * cuda::ORB::detectAndCompute (cudafeatures2d/src/orb.cpp:430-865) view after view.  gray: n_views DEVICE 8UC1 images, which may differ in size; masks: NULL, or
  * n_views entries (data == NULL: no mask for that view); keypoints_host: n_views x max_keypoints x 6 floats; descriptors: n_views DEVICE 8UC1 matrices of
- * max_keypoints x 32, none overlapping another.  View v gets exactly what ms_orb_detect_and_compute(gray + v, its mask or NULL, prm, keypoints_host +
- * 6 * max_keypoints * v, max_keypoints, descriptors + v, n_keypoints + v) returns, bit for bit and in the same order: n_keypoints[v] keypoint rows and the first
- * n_keypoints[v] descriptor rows; descriptor rows from n_keypoints[v] on are not written.  The output is the input ms_match_pairs takes.
+ * max_keypoints x 32, none overlapping another.  View v gets the result ms_orb_detect_and_compute defines for (gray + v, its mask or NULL, prm), bit for bit and in
+ * that order, at keypoints_host + 6 * max_keypoints * v, descriptors + v and n_keypoints + v: n_keypoints[v] keypoint rows and the first n_keypoints[v]
+ * descriptor rows; descriptor rows from n_keypoints[v] on are not written.  The single call is this with n_views = 1.  The output is the input ms_match_pairs takes.
  * A segment is one pyramid level of one view.  Sizes, budgets (orb.cpp:501-512), the detector's buffer (0.05 * area, :753) and every buffer offset follow from
  * the shapes and prm, so they go up once as a table and no count comes back before the end.  On the device, each step one launch over all segments: the pyramid
  * level by level (resize from the level below, :686; masks with it and through THRESH_TOZERO 254, :690-693); FAST scores (fast.cu:224-344); raw corners per row,
- * scan, survivors per row, scan, write -- raster order, and where a level has more raw corners than the detector's buffer the first max_npoints of them in raster
- * order are the candidates, each suppressed against the whole score map, as in the single call; the cull to 2n by FAST response (:772: a 256-bin histogram, then
+ * scan, survivors per row, scan, write -- raster order, with the over-cap rule of the single call's comment applied in every segment (a level within the buffer has
+ * every raw corner as a candidate); the cull to 2n by FAST response (:772: a 256-bin histogram, then
  * one ordered pass; no change and raster order where the level holds no more); Harris (orb.cu:93-138); the cull to n (:778) as a stable rank sort, keys through
  * LDS in tiles of 1024; angles (orb.cu:160-211) and the six floats of mergeKeyPoints (:823-865) at the view's row offset; descriptors (orb.cu:222-367) straight
  * into the caller's matrices.  No atomic decides an order: two calls return the same bytes.  Per call, whatever n_views is: nlevels + 10 launches at most,
@@ -814,9 +828,9 @@ MS_API int ms_orb_detect_and_compute(const ms_image *gray, const ms_image *mask,
  * bytes, with A_v the sum of w * h over the levels of view v (about 3.3 times its area at 1.2 / 8 levels): 48 KiB of tables + 24 * n_views * max_keypoints
  * + sum over v of [A_v (scores) + (A_v - area_v) (pyramid; twice with a mask) + 0.25 * A_v (candidates: 5 bytes for each of 0.05 * w * h) + 8 rows(A_v)]
  * -- some 4.5 times the views' area without masks, 5.5 with; MS_ERR_NOMEM before anything is launched where it cannot be had.
- * MS_ERR_INVALID, before the device is touched and naming the view: n_views outside [1, MS_MAX_VIEWS]; a null array; the single call's parameter limits; a view
+ * MS_ERR_INVALID, before the device is touched and naming the view: n_views outside [1, MS_MAX_VIEWS]; a null array; the limits of the single call's comment; a view
  * that is not 8UC1, has no data or is larger than 32767 in a dimension; a mask of another type or size; a descriptor matrix of another shape than max_keypoints
- * (>= nfeatures) x 32, or whose byte range (steps included) overlaps another view's.  After the pass: a view with more than max_keypoints keypoints (see the
+ * (>= nfeatures) x 32 with a step of at least 32, or whose byte range (steps included) overlaps another view's.  After the pass: a view with more than max_keypoints keypoints (see the
  * single call: max_keypoints >= nfeatures + nlevels / 2 always holds them); the device clamps, so nothing past row max_keypoints - 1 of any view is written.
  * Limits: one parameter set for the batch (no per-view nfeatures).  Synchronises. */
 MS_API int ms_orb_detect_and_compute_batch(int n_views, const ms_image *gray, const ms_image *masks, const ms_orb_params *prm, float *keypoints_host,

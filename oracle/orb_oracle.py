@@ -6,7 +6,8 @@ Restates, stage by stage, sources/modules/cudafeatures2d/src/orb.cpp:430-865 (ho
   HarrisResponses orb.cu:93-138, cull to n orb.cpp:719-781 | IC_Angle orb.cu:160-211 | computeOrbDescriptor<2> orb.cu:222-246,352-367 |
   mergeKeyPoints orb.cpp:823-865.
 Where the reference leaves the ORDER of keypoints to atomic counters (fast.cu:294, :333) and an unstable device sort (orb.cu:61-88), this
-oracle fixes it: raster order after FAST, stable descending sort in the culls -- tests compare keypoints as sets.  Transcendentals (atan2f, sincosf of
+oracle fixes it: raster order after FAST, stable descending sort in the culls, levels concatenated -- the order include/ms_stitch.h defines; the tests compare the device's keypoint and
+descriptor rows with this oracle's byte for byte and in that order.  Transcendentals (atan2f, sincosf of
 the CUDA fast-math build) are taken as correctly rounded floats of the double functions; float expressions are evaluated without contraction.
 Parity with the reference is unpinned by execution (no CUDA here; opencv_extra's ORB fixtures are absent); every stage function is held to an
 independent statement of its definition (tests/np_ref.py) by tests/test_orb_oracle.py."""

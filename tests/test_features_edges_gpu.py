@@ -10,7 +10,7 @@ import torch
 
 import np_ref as R
 import orb_oracle as oo
-from test_features_gpu import as_set, textured
+from test_features_gpu import textured
 
 pytestmark = pytest.mark.gpu
 
@@ -24,13 +24,17 @@ def oracle_orb(oracle, g, mask=None, edge_threshold=31, **kw):
     return oo.orb_detect_and_compute(g, mask, edge=edge_threshold, resize=lambda im, sz: oracle.resize_linear_8u(im, dsize=sz), **kw)
 
 
-def same(got, want):
-    """the set comparison of test_orb_matches_oracle: keys (x, y, octave), then bit-equal response / angle / size / descriptor"""
-    a, b = as_set(*got), as_set(*want)
-    assert len(got[0]) == len(a) and len(want[0]) == len(b)
-    assert a.keys() == b.keys(), (len(a), len(b), len(a.keys() & b.keys()), sorted(a.keys() ^ b.keys())[:4])
-    bad = [k for k in a if a[k] != b[k]]
-    assert not bad, (len(bad), bad[:3], [a[k][:3] for k in bad[:3]], [b[k][:3] for k in bad[:3]])
+def same(got, want, what=""):
+    """THE comparison of (keypoints, descriptors) pairs: equal lengths, equal keypoint bytes, equal descriptor bytes -- rows in the same order (the oracle's: raster
+    order after FAST, stable descending culls, levels concatenated).  On failure the first differing rows."""
+    (kp, d), (kr, dr) = [(np.ascontiguousarray(k, np.float32), np.ascontiguousarray(x, np.uint8)) for k, x in (got, want)]
+    assert len(kp) == len(kr) == len(d) == len(dr), (what, len(kp), len(kr), len(d), len(dr))
+    if kp.tobytes() != kr.tobytes():
+        rows = np.nonzero((kp.view(np.uint32) != kr.view(np.uint32)).any(axis=1))[0]
+        raise AssertionError((what, "keypoints", len(rows), "rows differ, the first:", rows[:3].tolist(), kp[rows[:3]].tolist(), kr[rows[:3]].tolist()))
+    if d.tobytes() != dr.tobytes():
+        rows = np.nonzero((d != dr).any(axis=1))[0]
+        raise AssertionError((what, "descriptors", len(rows), "rows differ, the first:", rows[:3].tolist(), d[rows[:3]].tolist(), dr[rows[:3]].tolist()))
 
 
 def check(ms, cuda, oracle, g, mask=None, **kw):
@@ -142,7 +146,7 @@ def arc_image(masks, sign, base=100, threshold=20):
 @pytest.mark.parametrize("sign", [1, -1], ids=["brighter", "darker"])
 @pytest.mark.parametrize("part", range(65536 // (ARC_COLS * ARC_ROWS)))
 def test_every_16_bit_arc_mask(ms, cuda, oracle, part, sign):
-    """k_fast_score's rotate-and-AND against the literal rule, over all 65 536 masks (8 192 per call) for brighter and for darker arcs: the grid centres
+    """fast_score_at's rotate-and-AND against the literal rule, over all 65 536 masks (8 192 per call) for brighter and for darker arcs: the grid centres
     reported are exactly the masks that hold a 9-arc, each with score `threshold`.  The admitted pixels off the grid centres (many of them corners:
     raised circle pixels) are compared with the oracle like everything else."""
     masks = np.arange(part * ARC_COLS * ARC_ROWS, (part + 1) * ARC_COLS * ARC_ROWS)
@@ -236,6 +240,28 @@ def test_pitched_image_mask_and_descriptors_equal_the_contiguous_call(ms, cuda, 
     out = desc_wide.cpu().numpy()
     assert out[:n2, 8:40].tobytes() == d0.tobytes()
     assert (out[:, :8] == 0xAB).all() and (out[:, 40:] == 0xAB).all() and (out[n2:] == 0xAB).all(), "bytes outside the descriptor columns / rows were written"
+
+
+def test_the_single_call_is_the_batch_of_one(ms, cuda):
+    """The marshalling of the batch of one -- the mask pointer, the descriptor step, the n_out slot: ms_orb_detect_and_compute through the raw C ABI returns the bytes
+    of the same view inside a two-view batch (view 0 pitched, under a grey blob mask; view 1 contiguous, without a mask) and leaves every descriptor byte outside
+    its rows and columns as it was."""
+    w, h, nf = 301, 233, 500
+    grays, mask = [textured(w, h, 7), textured(w, h, 8)], blob_mask(w, h, 35)
+    dev = [torch.from_numpy(g).to(cuda) for g in grays]
+    want = [(kp, d.cpu().numpy()) for kp, d, _ in ms.orb_detect_and_compute_batch(dev, [torch.from_numpy(mask).to(cuda), None], nfeatures=nf)]
+    assert all(len(kp) > 100 for kp, _ in want)
+    assert want[0][0].tobytes() != ms.orb_detect_and_compute_batch(dev[:1], nfeatures=nf)[0][0].tobytes(), "the mask must matter"
+    wide = torch.from_numpy(noise(w + 90, h, 36)).to(cuda)
+    wide[:, 37:37 + w] = dev[0]
+    wide_m = torch.full((h, w + 13), 255, dtype=torch.uint8, device=cuda)
+    wide_m[:, 5:5 + w] = torch.from_numpy(mask).to(cuda)
+    for v, (g, m) in enumerate([(wide[:, 37:37 + w], wide_m[:, 5:5 + w]), (dev[1], None)]):
+        wide_d = torch.full((nf + 4, 48 + 16 * v), 0xAB, dtype=torch.uint8, device=cuda)
+        kp, n = raw_orb(ms, g, m, wide_d[:, 8:40], nf, max_keypoints=nf + 4)
+        out = wide_d.cpu().numpy()
+        same((kp, out[:n, 8:40]), want[v], "view %d" % v)
+        assert (out[:, :8] == 0xAB).all() and (out[:, 40:] == 0xAB).all() and (out[n:] == 0xAB).all(), "view %d: bytes outside the descriptor columns / rows were written" % v
 
 
 @pytest.mark.parametrize("size", [(62, 62), (63, 63), (64, 64), (70, 70), (64, 70), (9, 500), (500, 9), (7, 90), (300, 26), (90, 75)])

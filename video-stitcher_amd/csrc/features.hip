@@ -6,15 +6,15 @@
 //   featurefinder::matchFeatures' findHomography(src, dst, mask, RANSAC)  (featurefinder.cpp:68-90)
 //       calib3d/src/fundam.cpp:46-260, 319-402; ptsetreg.cpp:53-290; levmarq.cpp:76-214
 //
-// What is on the device: every per-pixel and per-keypoint stage of ORB (image / mask pyramids, FAST scores, non-max suppression and
-// ordered compaction, Harris responses, angles, descriptors) and RANSAC's hypothesis fitting and scoring (all `maxIters` 4-point models of
-// every problem of a batch at once: one lane per model fits it, one workgroup per 64 models counts their inliers; ms_find_homography_ransac
-// is the batch of one).  What stays on the host, as in the reference: the keypoint COUNTS between stages (the reference
-// reads them back too: fast.cu:338-341, :379-382), the two culls (tiny stable sorts; the reference sorts on the device with an unstable
-// thrust sort, so its keypoint order is not defined -- ours is: raster order, stable culls), RANSAC's sequential subset draw and best-model
-// scan, and the final N-point fit + Levenberg-Marquardt polish of ONE model.
-// ms_orb_detect_and_compute_batch (the k_ob_* kernels below) runs the same ORB for every view of a rig with NOTHING on the host between the stages: counts, both culls
-// and the over-cap rule on the device, one synchronisation; it is held to the single call byte for byte (tests/test_orb_batch_gpu.py).
+// ORB is one device pass for every view of a rig (orb_batch and the k_ob_* kernels; ms_orb_detect_and_compute is the batch of one): image / mask pyramids,
+// FAST scores, non-max suppression and ordered compaction, both culls, Harris responses, angles, descriptors.  The host builds a table from the shapes and the
+// parameters (level sizes, per-level budgets, the detector's buffer, every buffer offset), uploads it, and reads the counts and keypoint rows back after ONE
+// synchronisation; no count comes back between the stages (the reference reads them back per level: fast.cu:338-341, :379-382) and no cull runs on the host.
+// The reference sorts with an unstable thrust sort and compacts through atomics, so its keypoint order is not defined.  Ours is: raster order after FAST, a
+// stable descending sort in both culls, levels concatenated -- the order of oracle/orb_oracle.py, which the tests hold every result to byte for byte.
+// RANSAC's hypothesis fitting and scoring are on the device too (all `maxIters` 4-point models of every problem of a batch at once: one lane per model fits it,
+// one workgroup per 64 models counts their inliers; ms_find_homography_ransac is the batch of one).  What stays on the host there, as in the reference: the
+// sequential subset draw and best-model scan, and the final N-point fit + Levenberg-Marquardt polish of ONE model.
 // Conventions where CUDA leaves freedom (same as oracle/orb_oracle.py): float expressions without fma contraction; atan2f / sincosf as the
 // correctly rounded float of the double function.
 #include <algorithm>
@@ -23,10 +23,8 @@
 #include <cmath>
 #include <cstring>
 #include <new>
-#include <numeric>
 #include <vector>
 #include "common.hpp"
-#include "launchers.hpp"
 
 namespace ms {
 namespace {
@@ -35,24 +33,14 @@ struct P2 { signed char x, y; };
 __constant__ P2 c_pattern[512] = {
 #include "orb_pattern.inc"
 };
-__constant__ int c_umax[32];
 
 // FAST circle in the bit order of fast.cu's masks (bit k = C[k / 4] byte k % 4): (dy, dx)
 __constant__ signed char c_circ[16][2] = {{3, 0}, {3, 1}, {2, 2}, {1, 3}, {0, 3}, {-1, 3}, {-2, 2}, {-3, 1}, {-3, 0}, {-3, -1}, {-2, -2}, {-1, -3}, {0, -3}, {1, -3}, {2, -2}, {3, -1}};
 
-// cuda::threshold(m, m, 254, 0, THRESH_TOZERO) of the mask pyramid (orb.cpp:693)
-__global__ void __launch_bounds__(256) k_tozero254(uint8_t *m, size_t step, int rows, int cols)
-{
-    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
-    if (x >= cols || y >= rows) return;
-    uint8_t *p = m + (size_t)y * step + x;
-    if (*p <= 254) *p = 0;
-}
-
 // calcKeypoints<true> (fast.cu:264-307): score map, 0 = no corner.  The mask of the level = user mask AND the inner rectangle left by edgeThreshold
 // (orb.cpp:707-712), applied analytically.  A pixel is a corner when 9 contiguous circle pixels are all darker than v - th or all brighter than v + th
 // (the c_table lookup of fast.cu:201-206 encodes exactly "the 16-bit mask holds 9 contiguous ones": tests/test_orb_oracle.py::test_arc9_equals_the_references_table
-// holds the rule to that table, tests/test_features_edges_gpu.py::test_every_16_bit_arc_mask holds this kernel to the rule over all 65 536 masks);
+// holds the rule to that table, tests/test_features_edges_gpu.py::test_every_16_bit_arc_mask holds this function to the rule over all 65 536 masks);
 // cornerScore's binary search (fast.cu:208-222) finds the largest threshold that still passes = (best arc's smallest difference) - 1.
 __device__ __forceinline__ int fast_score_at(const uint8_t *__restrict__ img, size_t step, int rows, int cols, const uint8_t *__restrict__ mask, size_t mstep, int edge, int th,
                                              int i, int j)
@@ -84,68 +72,14 @@ __device__ __forceinline__ int fast_score_at(const uint8_t *__restrict__ img, si
     }
     return s;
 }
-__global__ void __launch_bounds__(256) k_fast_score(const uint8_t *__restrict__ img, size_t step, int rows, int cols, const uint8_t *__restrict__ mask, size_t mstep,
-                                                    int edge, int th, uint8_t *__restrict__ score, size_t sstep)
-{
-    const int j = blockIdx.x * 64 + threadIdx.x, i = blockIdx.y * 4 + threadIdx.y;
-    if (j >= cols || i >= rows) return;
-    score[(size_t)i * sstep + j] = (uint8_t)fast_score_at(img, step, rows, cols, mask, mstep, edge, th, i, j);
-}
 
+// nonmaxSuppression's test (fast.cu:346-371): a corner survives when its score is strictly above its 8 neighbours'
 __device__ __forceinline__ bool is_local_max(const uint8_t *__restrict__ score, size_t sstep, int i, int j)
 {
     const int s = score[(size_t)i * sstep + j];
     if (s == 0) return false;
     const uint8_t *r0 = score + (size_t)(i - 1) * sstep + j, *r1 = r0 + sstep, *r2 = r1 + sstep;
     return s > r0[-1] && s > r0[0] && s > r0[1] && s > r1[-1] && s > r1[1] && s > r2[-1] && s > r2[0] && s > r2[1];
-}
-// nonmaxSuppression (fast.cu:346-371) in raster order instead of atomic order: per row, how many corners survive (and how many raw corners there are)
-__global__ void __launch_bounds__(256) k_row_counts(const uint8_t *__restrict__ score, size_t sstep, int rows, int cols, int *__restrict__ rowcnt, unsigned *raw_total)
-{
-    __shared__ int s_cnt[4], s_raw[4];
-    const int i = blockIdx.x;
-    int cnt = 0, raw = 0;
-    if (i >= 3 && i < rows - 3)
-        for (int j = 3 + (int)threadIdx.x; j < cols - 3; j += 256) { raw += score[(size_t)i * sstep + j] != 0; cnt += is_local_max(score, sstep, i, j); }
-    for (int o = 32; o > 0; o >>= 1) { cnt += __shfl_xor(cnt, o); raw += __shfl_xor(raw, o); }
-    if ((threadIdx.x & 63) == 0) { s_cnt[threadIdx.x >> 6] = cnt; s_raw[threadIdx.x >> 6] = raw; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        rowcnt[i] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-        const int r = s_raw[0] + s_raw[1] + s_raw[2] + s_raw[3];
-        if (r) atomicAdd(raw_total, (unsigned)r);
-    }
-}
-__global__ void __launch_bounds__(256) k_row_scan(int *rowcnt, int rows, int *total)           // exclusive scan in place, one workgroup
-{
-    __shared__ int s_part[256];
-    const int per = (rows + 255) / 256, a = threadIdx.x * per, b = min(a + per, rows);
-    int s = 0;
-    for (int i = a; i < b; ++i) s += rowcnt[i];
-    s_part[threadIdx.x] = s;
-    __syncthreads();
-    int off = 0;
-    for (int t = 0; t < (int)threadIdx.x; ++t) off += s_part[t];
-    for (int i = a; i < b; ++i) { const int c = rowcnt[i]; rowcnt[i] = off; off += c; }
-    if (threadIdx.x == 255) *total = off;
-}
-__global__ void __launch_bounds__(64) k_row_write(const uint8_t *__restrict__ score, size_t sstep, int rows, int cols, const int *__restrict__ rowoff,
-                                                  short2 *__restrict__ loc, float *__restrict__ resp)
-{
-    const int i = blockIdx.x;                       // one wave per row: ballot gives the in-row order
-    if (i < 3 || i >= rows - 3) return;
-    int off = rowoff[i];
-    for (int j0 = 3; j0 < cols - 3; j0 += 64) {
-        const int j = j0 + (int)threadIdx.x;
-        const bool keep = j < cols - 3 && is_local_max(score, sstep, i, j);
-        const unsigned long long m = __ballot(keep);
-        if (keep) {
-            const int k = off + __popcll(m & ((1ull << threadIdx.x) - 1ull));
-            loc[k] = make_short2((short)j, (short)i);
-            resp[k] = (float)score[(size_t)i * sstep + j];
-        }
-        off += __popcll(m);
-    }
 }
 
 // createMesh's feature mask (meshwarper.cpp:82-115): overlap bands AND not-black
@@ -177,12 +111,6 @@ __device__ __forceinline__ float harris_at(const uint8_t *__restrict__ img, size
     const float fa = (float)a, fb = (float)b, fc = (float)c, s = fa + fb;
     return ((fa * fb - fc * fc) - (k * s) * s) * s4;
 }
-__global__ void __launch_bounds__(64) k_harris(const uint8_t *__restrict__ img, size_t step, const short2 *__restrict__ loc, float *__restrict__ resp, int n, int block, float k)
-{
-    const int p = blockIdx.x * 64 + threadIdx.x;
-    if (p >= n) return;
-    resp[p] = harris_at(img, step, loc[p].x, loc[p].y, block, k);
-}
 
 // IC_Angle (orb.cu:160-211)
 __device__ __forceinline__ float ic_angle_at(const uint8_t *__restrict__ img, size_t step, int x, int y, int half, const int *__restrict__ umax)
@@ -204,12 +132,6 @@ __device__ __forceinline__ float ic_angle_at(const uint8_t *__restrict__ img, si
     if (a < 0) a += 2.0f * PI_F;
     return a * (180.0f / PI_F);
 }
-__global__ void __launch_bounds__(64) k_ic_angle(const uint8_t *__restrict__ img, size_t step, const short2 *__restrict__ loc, float *__restrict__ angle, int n, int half)
-{
-    const int p = blockIdx.x * 64 + threadIdx.x;
-    if (p >= n) return;
-    angle[p] = ic_angle_at(img, step, loc[p].x, loc[p].y, half, c_umax);
-}
 
 // computeOrbDescriptor<2> (orb.cu:222-246, :352-367): byte b of keypoint p = 8 tests on the pattern rotated by the keypoint angle
 __device__ __forceinline__ int orb_desc_byte(const uint8_t *__restrict__ img, size_t step, int x, int y, float angle, int b)
@@ -226,13 +148,6 @@ __device__ __forceinline__ int orb_desc_byte(const uint8_t *__restrict__ img, si
 #pragma unroll
     for (int t = 0; t < 8; ++t) v |= (val(2 * t) < val(2 * t + 1)) << t;
     return v;
-}
-__global__ void __launch_bounds__(256) k_orb_desc(const uint8_t *__restrict__ img, size_t step, const short2 *__restrict__ loc, const float *__restrict__ angle, int n,
-                                                  uint8_t *__restrict__ desc, size_t dstep)
-{
-    const int b = threadIdx.x & 31, p = blockIdx.x * 8 + (threadIdx.x >> 5);
-    if (p >= n) return;
-    desc[(size_t)p * dstep + b] = (uint8_t)orb_desc_byte(img, step, loc[p].x, loc[p].y, angle[p], b);
 }
 
 // ---- RANSAC: per 4-point hypothesis HomographyEstimatorCallback::runKernel (fundam.cpp:80-142, k_ransac_fit: one lane a hypothesis), then the inlier count
@@ -733,10 +648,11 @@ int ransac_batch(const char *fn, int n_problems, const int *offsets, const float
     return MS_OK;
 }
 
-// ---- batched ORB: ms_orb_detect_and_compute for every view of a rig in one device pass, no host in the loop.
-// A SEGMENT is one pyramid level of one view.  Everything the host decides per segment in the single call -- sizes, budgets, the detector's buffer, where the level's
-// image, mask and score map live -- follows from the shapes and the parameters alone and goes up once, as a table; what depends on the pixels (the counts between the
-// stages) stays on the device.  Every kernel is launched once for all segments: a workgroup finds its segment in a list of (first work item, segment) by bisection.
+// ---- ORB: cuda::ORB::detectAndCompute (orb.cpp:430-865) for every view of a rig in one device pass, no host in the loop.
+// A SEGMENT is one pyramid level of one view.  Everything the reference's host code decides per level -- sizes (orb.cpp:668), budgets (:501-512), the detector's
+// buffer (:753), where the level's image, mask and score map live -- follows from the shapes and the parameters alone and goes up once, as a table; what depends on
+// the pixels (the counts between the stages) stays on the device.  Every kernel is launched once for all segments: a workgroup finds its segment in a list of
+// (first work item, segment) by bisection.
 constexpr int OB_MAX_SEG = MS_MAX_VIEWS * 16;
 constexpr int OB_SORT_TILE = 1024;                              // Harris keys staged in LDS at a time (4 KiB)
 struct ObSeg {
@@ -806,7 +722,8 @@ __global__ void __launch_bounds__(256) k_ob_pyramid(const ObTable *__restrict__ 
         const_cast<uint8_t *>(s.mask)[(size_t)y * s.mstep + x] = m <= 254 ? 0 : m;
     }
 }
-// b. k_fast_score over the tiles of every scored segment
+// b. the FAST score map (calcKeypoints<true>, fast.cu:264-307; 0 = no corner) of every scored segment, a 64 x 4 tile a workgroup.  The level's mask is the user's
+// mask AND the inner rectangle left by edgeThreshold (orb.cpp:707-712)
 __global__ void __launch_bounds__(256) k_ob_fast(const ObTable *__restrict__ T, int edge, int th)
 {
     int tile;
@@ -815,9 +732,11 @@ __global__ void __launch_bounds__(256) k_ob_fast(const ObTable *__restrict__ T, 
     if (j >= s.w || i >= s.h) return;
     s.score[(size_t)i * s.w + j] = (uint8_t)fast_score_at(s.img, s.step, s.h, s.w, s.mask, s.mstep, edge, th, i, j);
 }
-// c. suppression and raster-ordered compaction, one wave a row (4 rows a workgroup); the rule of the single call's over-cap branch for every segment: the raw corners
-// (score != 0, rows 3 .. h - 4, columns 3 .. w - 4) are numbered in raster order, those numbered below max_npoints are candidates, and a candidate survives when it
-// is a strict maximum of its 8 neighbours in the WHOLE score map.  Within the cap every raw corner is a candidate: k_row_counts / k_row_write.
+// c. suppression (nonmaxSuppression, fast.cu:346-371) and compaction in raster order instead of the reference's atomic order, one wave a row (4 rows a workgroup);
+// a ballot gives the order inside a row.  One rule for every segment: the raw corners (score != 0, rows 3 .. h - 4, columns 3 .. w - 4) are numbered in raster
+// order, those numbered below max_npoints (the detector's buffer, orb.cpp:753) are candidates, and a candidate survives when it is a strict maximum of its 8
+// neighbours in the WHOLE score map.  Within the buffer every raw corner is a candidate.  Past it the reference keeps whichever max_npoints win its atomic
+// counter (fast.cu:338-341); here the first ones in raster order do.
 // PASS 0: raw corners of the row.  (scan.)  PASS 1: survivors of the row, from the raw offsets.  (scan.)  PASS 2: write them at the survivor offsets.
 template <int PASS>
 __global__ void __launch_bounds__(256) k_ob_rows(const ObTable *__restrict__ T, ObBufs B)
@@ -846,7 +765,7 @@ __global__ void __launch_bounds__(256) k_ob_rows(const ObTable *__restrict__ T, 
         }
     if (lane == 0) { if (PASS == 0) B.rowraw[row] = raw; if (PASS == 1) B.rowcnt[row] = cnt; }
 }
-// k_row_scan for one segment a workgroup: exclusive scan of its rows in place, the total to total[segment] when asked for
+// one segment a workgroup: exclusive scan of its rows in place (a lane sums a stretch of rows, then offsets them), the total to total[segment] when asked for
 __global__ void __launch_bounds__(256) k_ob_scan(const ObTable *__restrict__ T, int *__restrict__ rows, int *__restrict__ total)
 {
     __shared__ int s_part[256];
@@ -863,7 +782,7 @@ __global__ void __launch_bounds__(256) k_ob_scan(const ObTable *__restrict__ T, 
     for (int i = a; i < b; ++i) { const int c = r[i]; r[i] = off; off += c; }
     if (threadIdx.x == 255 && total) total[sg] = off;
 }
-// d. cull to 2n by FAST response (orb.cpp:772): untouched, in raster order, when the level holds no more; else the first 2n of the stable descending order, in that
+// d. cull to 2n by FAST response (orb.cpp:772; cull: :719-733, stable where thrust's device sort is not): untouched, in raster order, when the level holds no more; else the first 2n of the stable descending order, in that
 // order.  The keys are 1..255.  One workgroup of 16 waves a segment; wave w owns the w-th sixteenth of the candidates (a stretch of the raster order).  A histogram
 // per wave gives, summed, the threshold score t, the number q still wanted AT t and every score's first output row, and, scanned over the waves, how many of each
 // score lie before a wave's stretch.  Then every wave walks its stretch 64 at a time: an element's place among its score is the count before the stretch + the
@@ -930,7 +849,7 @@ __global__ void __launch_bounds__(64 * OB_CULL_WAVES) k_ob_cull_fast(const ObTab
     }
     if (tid == 0) B.cnt_b[sg] = keep;
 }
-// e. k_harris over the kept candidates of every segment
+// e. the Harris response (orb.cu:93-138) of the kept candidates of every segment, one a lane
 __global__ void __launch_bounds__(64) k_ob_harris(const ObTable *__restrict__ T, ObBufs B)
 {
     int blk;
@@ -980,7 +899,7 @@ __device__ __forceinline__ int ob_view_row(const ObTable *__restrict__ T, const 
     for (int k = T->segs[sg].first; k < sg; ++k) row += cnt_c[k];
     return row;
 }
-// k_ic_angle (orb.cpp:780) and mergeKeyPoints' six floats (:823-865)
+// the intensity-centroid angle (orb.cpp:780; orb.cu:160-211) and mergeKeyPoints' six floats (:823-865): x, y, response, angle, octave, size
 __global__ void __launch_bounds__(64) k_ob_finish(const ObTable *__restrict__ T, ObBufs B)
 {
     int blk;
@@ -995,7 +914,7 @@ __global__ void __launch_bounds__(64) k_ob_finish(const ObTable *__restrict__ T,
     k[3] = ic_angle_at(s.img, s.step, l.x, l.y, B.half, T->umax);
     k[4] = (float)s.level; k[5] = s.size;
 }
-// k_orb_desc (orb.cpp:783-821) straight into the view's descriptor matrix
+// the descriptors (orb.cpp:783-821): byte b of keypoint p a lane, 8 keypoints a workgroup, straight into the view's descriptor matrix
 __global__ void __launch_bounds__(256) k_ob_desc(const ObTable *__restrict__ T, ObBufs B)
 {
     int blk;
@@ -1016,7 +935,35 @@ template <int N> static inline void ob_add(ObList<N> &L, int seg, long long item
     L.seg[L.n] = seg; L.start[L.n] = L.total; L.total += (int)items; L.start[++L.n] = L.total;
 }
 
-// the arguments are checked and a device is present
+// The parameter and per-view checks of both ORB entry points (the arrays are not null); MS_ERR_INVALID names the call and, where a view is at fault, the view.
+int orb_check(const char *fn, int n_views, const ms_image *gray, const ms_image *masks, const ms_orb_params *prm, int max_keypoints, const ms_image *desc)
+{
+    MS_CHECK(prm->nlevels >= 1 && prm->nlevels <= 16 && prm->first_level == 0 && prm->patch_size == 31 && prm->nfeatures >= 1 && prm->scale_factor > 1.f,
+             "%s: supports first_level 0, patch_size 31 (the learned pattern), 1..16 levels", fn);
+    // the device kernels read a (rotated) 31-px patch, the 15-px intensity-centroid disc and the 7 x 7 Harris block + Sobel halo around every keypoint WITHOUT bounds
+    // checks: keypoints must keep the creator's border (orb.cpp:686-689, edgeThreshold 31 by default; 19 = ceil(18.4) is the reach of the rotated pattern);
+    // a FAST threshold of 0 would make score 0 -- "no corner" in the score map -- a valid corner (fast.cu:224-282 has the same encoding), 255 can never fire
+    MS_CHECK(prm->edge_threshold >= 19 && prm->edge_threshold >= prm->patch_size / 2 + 1 && prm->fast_threshold >= 1 && prm->fast_threshold <= 254,
+             "%s: edge_threshold %d must be >= 19 and fast_threshold %d in [1, 254]", fn, prm->edge_threshold, prm->fast_threshold);
+    MS_CHECK(max_keypoints >= prm->nfeatures, "%s: max_keypoints %d must be >= nfeatures %d", fn, max_keypoints, prm->nfeatures);
+    for (int v = 0; v < n_views; ++v) {
+        MS_CHECK(gray[v].data && gray[v].type == MS_8UC1, "%s: view %d: gray must be a device 8UC1 image", fn, v);
+        MS_CHECK(gray[v].rows >= 0 && gray[v].cols >= 0 && gray[v].rows <= 32767 && gray[v].cols <= 32767, "%s: view %d: %d x %d is no image size", fn, v, gray[v].cols, gray[v].rows);      // (short2 coordinates)
+        MS_CHECK(!masks || !masks[v].data || (masks[v].type == MS_8UC1 && masks[v].rows == gray[v].rows && masks[v].cols == gray[v].cols),
+                 "%s: view %d: mask must be 8UC1 of the image size", fn, v);
+        MS_CHECK(desc[v].data && desc[v].type == MS_8UC1 && desc[v].cols == 32 && desc[v].rows >= max_keypoints && desc[v].step >= 32,
+                 "%s: view %d: descriptors must be 8UC1 max_keypoints x 32", fn, v);
+    }
+    for (int v = 0; v < n_views; ++v)                                       // the byte ranges of the descriptor matrices, steps included
+        for (int u = 0; u < v; ++u) {
+            const char *a0 = (const char *)desc[u].data, *a1 = a0 + (size_t)(max_keypoints - 1) * desc[u].step + 32;
+            const char *b0 = (const char *)desc[v].data, *b1 = b0 + (size_t)(max_keypoints - 1) * desc[v].step + 32;
+            MS_CHECK(a1 <= b0 || b1 <= a0, "%s: view %d: its descriptors overlap those of view %d", fn, v, u);
+        }
+    return MS_OK;
+}
+
+// the arguments are checked (orb_check) and a device is present
 int orb_batch(const char *fn, int n_views, const ms_image *gray, const ms_image *masks, const ms_orb_params *prm, float *kp_host, int max_keypoints, ms_image *desc,
               int *n_out, ms_stream stream)
 {
@@ -1042,9 +989,9 @@ int orb_batch(const char *fn, int n_views, const ms_image *gray, const ms_image 
         float nd = (float)((double)(prm->nfeatures * (1.0f - factor)) / (1.0 - std::pow((double)factor, prm->nlevels)));
         int sum = 0;
         for (int l = 0; l < prm->nlevels - 1; ++l) { nper[l] = (int)std::nearbyint(nd); sum += nper[l]; nd *= factor; }
-        nper[prm->nlevels - 1] = prm->nfeatures - sum;
+        nper[prm->nlevels - 1] = prm->nfeatures - sum;        // may be 0 or negative (the rounding of the other levels): such a level is skipped below
     }
-    auto level_scale = [&](int l) { return (float)std::pow((double)prm->scale_factor, l - prm->first_level); };
+    auto level_scale = [&](int l) { return (float)std::pow((double)prm->scale_factor, l - prm->first_level); };     // getScale: pow(float, int) -> double -> float
     int n_seg = 0;
     long long rows = 0, na = 0, nb = 0, nc = 0;
     size_t arena = 0;                                          // pyramid levels >= 1, their masks, the score maps
@@ -1054,7 +1001,7 @@ int orb_batch(const char *fn, int n_views, const ms_image *gray, const ms_image 
         const int first = n_seg;
         for (int level = 0; level < prm->nlevels; ++level) {
             const float sc = 1.0f / level_scale(level);
-            const int w = (int)std::nearbyint((float)gray[v].cols * sc), h = (int)std::nearbyint((float)gray[v].rows * sc);      // orb.cpp:668
+            const int w = (int)std::nearbyint((float)gray[v].cols * sc), h = (int)std::nearbyint((float)gray[v].rows * sc);      // cvRound(image.cols * scale)  orb.cpp:668
             if (w < 8 || h < 8) break;
             const int sg = n_seg++;
             ObSeg &s = T.segs[sg];
@@ -1073,8 +1020,10 @@ int orb_batch(const char *fn, int n_views, const ms_image *gray, const ms_image 
             const float sf = level_scale(level);
             s.loc_scale = level != prm->first_level ? sf : 1.0f; s.size = (float)prm->patch_size * sf;
             s.n = nper[level];
-            s.max_npoints = (int)(0.05 * ((double)w * h));                  // orb.cpp:753
-            if (s.n <= 0) continue;                                         // the level contributes its pyramid image only
+            s.max_npoints = (int)(0.05 * ((double)w * h));                  // fastDetector_->setMaxNumPoints(0.05 * area)  orb.cpp:753
+            // A budget <= 0 (nfeatures 7 at the defaults gives the last level -1; the reference is undefined there: its cull() releases the buffer and keeps
+            // the count): the level contributes no keypoints, and nothing but its pyramid image, which the next level is resized from, is computed.
+            if (s.n <= 0) continue;
             s.cap_b = (int)std::min<long long>(s.max_npoints, 2ll * s.n); s.cap_c = std::min(s.max_npoints, s.n);
             o_score[sg] = arena; arena += ob_align((size_t)w * h);
             s.row_off = (int)rows; s.a_off = (int)na; s.b_off = (int)nb; s.c_off = (int)nc;
@@ -1184,170 +1133,12 @@ int ms_orb_default_params(ms_orb_params *p)
 int ms_orb_detect_and_compute(const ms_image *gray, const ms_image *mask, const ms_orb_params *prm, float *kp_host, int max_keypoints,
                               ms_image *desc, int *n_out, ms_stream stream)
 {
+    const char *fn = "ms_orb_detect_and_compute";
     if (int e = require_device()) return e;
-    MS_CHECK(gray && gray->data && gray->type == MS_8UC1 && prm && kp_host && desc && desc->data && n_out, "ms_orb_detect_and_compute: bad argument");
-    MS_CHECK(!mask || (mask->data && mask->type == MS_8UC1 && mask->rows == gray->rows && mask->cols == gray->cols), "ms_orb_detect_and_compute: mask must be 8UC1 of the image size");
-    MS_CHECK(prm->nlevels >= 1 && prm->nlevels <= 16 && prm->first_level == 0 && prm->patch_size == 31 && prm->nfeatures >= 1 && prm->scale_factor > 1.f,
-             "ms_orb_detect_and_compute: supports first_level 0, patch_size 31 (the learned pattern), 1..16 levels");
-    // the device kernels read a (rotated) 31-px patch, the 15-px intensity-centroid disc and the 7 x 7 Harris block + Sobel halo around every keypoint WITHOUT bounds
-    // checks: keypoints must keep the creator's border (orb.cpp:686-689, edgeThreshold 31 by default; 19 = ceil(18.4) is the reach of the rotated pattern);
-    // a FAST threshold of 0 would make score 0 -- "no corner" in the score map -- a valid corner (fast.cu:224-282 has the same encoding), 255 can never fire
-    MS_CHECK(prm->edge_threshold >= 19 && prm->edge_threshold >= prm->patch_size / 2 + 1 && prm->fast_threshold >= 1 && prm->fast_threshold <= 254,
-             "ms_orb_detect_and_compute: edge_threshold %d must be >= 19 and fast_threshold %d in [1, 254]", prm->edge_threshold, prm->fast_threshold);
-    MS_CHECK(desc->type == MS_8UC1 && desc->cols == 32 && desc->rows >= max_keypoints && max_keypoints >= prm->nfeatures, "ms_orb_detect_and_compute: descriptors must be 8UC1 max_keypoints x 32, max_keypoints >= nfeatures");
-    hipStream_t st = as_stream(stream);
-    const int half = prm->patch_size / 2;
-    {   // u_max of the circular patch (orb.cpp:514-529)
-        std::vector<int> u(half + 2, 0);
-        const float r2 = std::sqrt(2.f);
-        for (int v = 0; v <= half * r2 / 2 + 1; ++v) u[v] = (int)std::nearbyint(std::sqrt((float)(half * half - v * v)));
-        for (int v = half, v0 = 0; v >= half * r2 / 2; --v) { while (u[v0] == u[v0 + 1]) ++v0; u[v] = v0; ++v0; }
-        int tab[32] = {0};
-        for (size_t i = 0; i < u.size() && i < 32; ++i) tab[i] = u[i];
-        MS_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_umax), tab, sizeof(tab), 0, hipMemcpyHostToDevice, st));
-    }
-    // per-level budgets (orb.cpp:501-512)
-    std::vector<int> nper(prm->nlevels);
-    {
-        const float factor = 1.0f / prm->scale_factor;
-        float nd = (float)((double)(prm->nfeatures * (1.0f - factor)) / (1.0 - std::pow((double)factor, prm->nlevels)));
-        int sum = 0;
-        for (int l = 0; l < prm->nlevels - 1; ++l) { nper[l] = (int)std::nearbyint(nd); sum += nper[l]; nd *= factor; }
-        nper[prm->nlevels - 1] = prm->nfeatures - sum;        // may be 0 or negative (the rounding of the other levels): such a level is skipped below
-    }
-    auto level_scale = [&](int l) { return (float)std::pow((double)prm->scale_factor, l - prm->first_level); };     // getScale: pow(float, int) -> double -> float
-    struct Dev { void *p = nullptr; ~Dev() { if (p) (void)hipFree(p); } int alloc(size_t n) { if (p) (void)hipFree(p); p = nullptr; MS_HIP(hipMalloc(&p, n ? n : 16)); return MS_OK; } };
-    Dev img_a, img_b, msk_a, msk_b, score, rowcnt, counters, loc, resp, ang;
-    const size_t full = (size_t)gray->rows * gray->cols;
-    if (int e = img_a.alloc(full)) return e;
-    if (int e = img_b.alloc(full)) return e;
-    if (mask) { if (int e = msk_a.alloc(full)) return e; if (int e = msk_b.alloc(full)) return e; }
-    if (int e = score.alloc(full)) return e;
-    if (int e = rowcnt.alloc(sizeof(int) * (size_t)gray->rows)) return e;
-    if (int e = counters.alloc(16)) return e;
-    ms_image prev_img{}, prev_msk{};
-    int total = 0;
-    for (int level = 0; level < prm->nlevels; ++level) {
-        const float sc = 1.0f / level_scale(level);
-        const int w = (int)std::nearbyint((float)gray->cols * sc), h = (int)std::nearbyint((float)gray->rows * sc);      // cvRound(image.cols * scale)  orb.cpp:668
-        if (w < 8 || h < 8) break;
-        ms_image cur{(level & 1) ? img_b.p : img_a.p, (size_t)w, w, h, MS_8UC1}, curm{};
-        if (level == prm->first_level) {
-            MS_HIP(hipMemcpy2DAsync(cur.data, cur.step, gray->data, gray->step, (size_t)w, h, hipMemcpyDeviceToDevice, st));
-            if (mask) { curm = ms_image{msk_a.p, (size_t)w, w, h, MS_8UC1}; MS_HIP(hipMemcpy2DAsync(curm.data, curm.step, mask->data, mask->step, (size_t)w, h, hipMemcpyDeviceToDevice, st)); }
-        } else {
-            if (int e = launch_resize_linear(prev_img, cur, 0, 0, st)) return e;                                            // orb.cpp:686
-            if (mask) {
-                curm = ms_image{(level & 1) ? msk_b.p : msk_a.p, (size_t)w, w, h, MS_8UC1};
-                if (int e = launch_resize_linear(prev_msk, curm, 0, 0, st)) return e;                                     // :690
-                k_tozero254<<<dim3(div_up(w, 64), div_up(h, 4)), dim3(64, 4), 0, st>>>((uint8_t *)curm.data, curm.step, h, w);   // :693
-                MS_LAUNCH_CHECK();
-            }
-        }
-        prev_img = cur; prev_msk = curm;
-        // A budget <= 0 (nfeatures 7 at the defaults gives the last level -1; the reference is undefined there: its cull() releases the buffer and keeps
-        // the count): the level contributes no keypoints, and nothing but its pyramid image, which the next level is resized from, is computed.
-        if (nper[level] <= 0) continue;
-        // FAST 9-16, threshold, score, non-max suppression, raster-ordered compaction
-        MS_HIP(hipMemsetAsync(counters.p, 0, 16, st));
-        k_fast_score<<<dim3(div_up(w, 64), div_up(h, 4)), dim3(64, 4), 0, st>>>((const uint8_t *)cur.data, cur.step, h, w, mask ? (const uint8_t *)curm.data : nullptr, curm.step,
-                                                                                  prm->edge_threshold, prm->fast_threshold, (uint8_t *)score.p, (size_t)w);
-        MS_LAUNCH_CHECK();
-        k_row_counts<<<h, 256, 0, st>>>((const uint8_t *)score.p, (size_t)w, h, w, (int *)rowcnt.p, (unsigned *)counters.p);
-        MS_LAUNCH_CHECK();
-        k_row_scan<<<1, 256, 0, st>>>((int *)rowcnt.p, h, (int *)counters.p + 1);
-        MS_LAUNCH_CHECK();
-        unsigned hc[2] = {0, 0};
-        MS_HIP(hipMemcpyAsync(hc, counters.p, sizeof(hc), hipMemcpyDeviceToHost, st));
-        MS_HIP(hipStreamSynchronize(st));                                   // (the reference synchronises here as well: fast.cu:340-341, :381-382)
-        const unsigned raw = hc[0];
-        int count = (int)hc[1];
-        const int max_npoints = (int)(0.05 * ((double)w * h));              // fastDetector_->setMaxNumPoints(0.05 * area)  orb.cpp:753
-        std::vector<short2> hloc;
-        std::vector<float> hresp;
-        if (count == 0) continue;
-        if ((int)raw > max_npoints) {
-            // more raw corners than the detector's buffer: the reference keeps whichever max_npoints win its atomic counter; here the first ones in
-            // raster order do.  Rare (5 % of the pixels are corners): done on the host from the score map.
-            std::vector<uint8_t> hs((size_t)w * h);
-            MS_HIP(hipMemcpy(hs.data(), score.p, hs.size(), hipMemcpyDeviceToHost));
-            int seen = 0;
-            for (int i = 3; i < h - 3 && seen < max_npoints; ++i)
-                for (int j = 3; j < w - 3 && seen < max_npoints; ++j) {
-                    const int s = hs[(size_t)i * w + j];
-                    if (!s) continue;
-                    ++seen;
-                    bool mx = true;
-                    for (int dy = -1; dy <= 1 && mx; ++dy) for (int dx = -1; dx <= 1; ++dx) if ((dy || dx) && s <= hs[(size_t)(i + dy) * w + j + dx]) { mx = false; break; }
-                    if (mx) { hloc.push_back(make_short2((short)j, (short)i)); hresp.push_back((float)s); }
-                }
-            count = (int)hloc.size();
-            if (count == 0) continue;
-        }
-        if (int e = loc.alloc(sizeof(short2) * (size_t)count)) return e;
-        if (int e = resp.alloc(sizeof(float) * (size_t)count)) return e;
-        const int n = nper[level];
-        auto cull = [&](int keep) -> int {                                  // orb.cpp:719-733; stable instead of thrust's unstable device sort
-            if (count <= keep) return MS_OK;
-            if (keep <= 0) { count = 0; return MS_OK; }
-            if (hloc.empty()) {
-                hloc.resize(count); hresp.resize(count);
-                MS_HIP(hipMemcpyAsync(hloc.data(), loc.p, sizeof(short2) * (size_t)count, hipMemcpyDeviceToHost, st));
-                MS_HIP(hipMemcpyAsync(hresp.data(), resp.p, sizeof(float) * (size_t)count, hipMemcpyDeviceToHost, st));
-                MS_HIP(hipStreamSynchronize(st));
-            }
-            std::vector<int> order(count);
-            std::iota(order.begin(), order.end(), 0);
-            std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return hresp[a] > hresp[b]; });
-            std::vector<short2> l2(keep);
-            std::vector<float> r2(keep);
-            for (int i = 0; i < keep; ++i) { l2[i] = hloc[order[i]]; r2[i] = hresp[order[i]]; }
-            hloc.swap(l2); hresp.swap(r2);
-            count = keep;
-            MS_HIP(hipMemcpyAsync(loc.p, hloc.data(), sizeof(short2) * (size_t)count, hipMemcpyHostToDevice, st));
-            MS_HIP(hipMemcpyAsync(resp.p, hresp.data(), sizeof(float) * (size_t)count, hipMemcpyHostToDevice, st));
-            MS_HIP(hipStreamSynchronize(st));          // (the host vectors are reused)
-            return MS_OK;
-        };
-        if (hloc.empty()) {
-            k_row_write<<<h, 64, 0, st>>>((const uint8_t *)score.p, (size_t)w, h, w, (const int *)rowcnt.p, (short2 *)loc.p, (float *)resp.p);
-            MS_LAUNCH_CHECK();
-        } else {
-            MS_HIP(hipMemcpyAsync(loc.p, hloc.data(), sizeof(short2) * (size_t)count, hipMemcpyHostToDevice, st));
-            MS_HIP(hipMemcpyAsync(resp.p, hresp.data(), sizeof(float) * (size_t)count, hipMemcpyHostToDevice, st));
-            MS_HIP(hipStreamSynchronize(st));
-        }
-        if (int e = cull(2 * n)) return e;                                                                                  // orb.cpp:772
-        if (count == 0) continue;                                           // (never a launch with an empty grid)
-        k_harris<<<div_up(count, 64), 64, 0, st>>>((const uint8_t *)cur.data, cur.step, (const short2 *)loc.p, (float *)resp.p, count, 7, 0.04f);   // :774
-        MS_LAUNCH_CHECK();
-        hloc.clear(); hresp.clear();
-        if (int e = cull(n)) return e;                                                                                      // :778
-        if (count == 0) continue;
-        if (int e = ang.alloc(sizeof(float) * (size_t)count)) return e;
-        k_ic_angle<<<div_up(count, 64), 64, 0, st>>>((const uint8_t *)cur.data, cur.step, (const short2 *)loc.p, (float *)ang.p, count, half);          // :780
-        MS_LAUNCH_CHECK();
-        if (total + count > max_keypoints) return fail(MS_ERR_INVALID, "ms_orb_detect_and_compute: more than max_keypoints (%d) keypoints", max_keypoints);
-        k_orb_desc<<<div_up(count, 8), 256, 0, st>>>((const uint8_t *)cur.data, cur.step, (const short2 *)loc.p, (const float *)ang.p, count,
-                                                     (uint8_t *)desc->data + (size_t)total * desc->step, desc->step);                                  // :783-821
-        MS_LAUNCH_CHECK();
-        // mergeKeyPoints (orb.cpp:823-865): x, y, response, angle, octave, size
-        if (hloc.empty()) { hloc.resize(count); MS_HIP(hipMemcpyAsync(hloc.data(), loc.p, sizeof(short2) * (size_t)count, hipMemcpyDeviceToHost, st)); }
-        hresp.resize(count);
-        std::vector<float> hang(count);
-        MS_HIP(hipMemcpyAsync(hresp.data(), resp.p, sizeof(float) * (size_t)count, hipMemcpyDeviceToHost, st));
-        MS_HIP(hipMemcpyAsync(hang.data(), ang.p, sizeof(float) * (size_t)count, hipMemcpyDeviceToHost, st));
-        MS_HIP(hipStreamSynchronize(st));
-        const float sf = level_scale(level), loc_scale = level != prm->first_level ? sf : 1.0f;
-        for (int i = 0; i < count; ++i) {
-            float *k = kp_host + 6 * (size_t)(total + i);
-            k[0] = (float)hloc[i].x * loc_scale; k[1] = (float)hloc[i].y * loc_scale; k[2] = hresp[i]; k[3] = hang[i]; k[4] = (float)level; k[5] = (float)prm->patch_size * sf;
-        }
-        total += count;
-    }
-    MS_HIP(hipStreamSynchronize(st));
-    *n_out = total;
-    return MS_OK;
+    MS_CHECK(gray && prm && kp_host && desc && n_out, "%s: bad argument", fn);
+    MS_CHECK(!mask || mask->data, "%s: mask must be 8UC1 of the image size", fn);      // (in a batch a mask without data means "none"; here NULL does)
+    if (int e = orb_check(fn, 1, gray, mask, prm, max_keypoints, desc)) return e;
+    return orb_batch(fn, 1, gray, mask, prm, kp_host, max_keypoints, desc, n_out, stream);      // the batch of one
 }
 
 int ms_orb_detect_and_compute_batch(int n_views, const ms_image *gray, const ms_image *masks, const ms_orb_params *prm, float *kp_host, int max_keypoints,
@@ -1360,25 +1151,7 @@ int ms_orb_detect_and_compute_batch(int n_views, const ms_image *gray, const ms_
     MS_CHECK(kp_host, "%s: null keypoints_host", fn);
     MS_CHECK(desc, "%s: null descriptors", fn);
     MS_CHECK(n_out, "%s: null n_keypoints", fn);
-    MS_CHECK(prm->nlevels >= 1 && prm->nlevels <= 16 && prm->first_level == 0 && prm->patch_size == 31 && prm->nfeatures >= 1 && prm->scale_factor > 1.f,
-             "%s: supports first_level 0, patch_size 31 (the learned pattern), 1..16 levels", fn);
-    MS_CHECK(prm->edge_threshold >= 19 && prm->edge_threshold >= prm->patch_size / 2 + 1 && prm->fast_threshold >= 1 && prm->fast_threshold <= 254,
-             "%s: edge_threshold %d must be >= 19 and fast_threshold %d in [1, 254]", fn, prm->edge_threshold, prm->fast_threshold);      // (see ms_orb_detect_and_compute)
-    MS_CHECK(max_keypoints >= prm->nfeatures, "%s: max_keypoints %d must be >= nfeatures %d", fn, max_keypoints, prm->nfeatures);
-    for (int v = 0; v < n_views; ++v) {
-        MS_CHECK(gray[v].data && gray[v].type == MS_8UC1, "%s: view %d: gray must be a device 8UC1 image", fn, v);
-        MS_CHECK(gray[v].rows >= 0 && gray[v].cols >= 0 && gray[v].rows <= 32767 && gray[v].cols <= 32767, "%s: view %d: %d x %d is no image size", fn, v, gray[v].cols, gray[v].rows);
-        MS_CHECK(!masks || !masks[v].data || (masks[v].type == MS_8UC1 && masks[v].rows == gray[v].rows && masks[v].cols == gray[v].cols),
-                 "%s: view %d: mask must be 8UC1 of the image size", fn, v);
-        MS_CHECK(desc[v].data && desc[v].type == MS_8UC1 && desc[v].cols == 32 && desc[v].rows >= max_keypoints && desc[v].step >= 32,
-                 "%s: view %d: descriptors must be 8UC1 max_keypoints x 32", fn, v);
-    }
-    for (int v = 0; v < n_views; ++v)                                       // the byte ranges of the descriptor matrices, steps included
-        for (int u = 0; u < v; ++u) {
-            const char *a0 = (const char *)desc[u].data, *a1 = a0 + (size_t)(max_keypoints - 1) * desc[u].step + 32;
-            const char *b0 = (const char *)desc[v].data, *b1 = b0 + (size_t)(max_keypoints - 1) * desc[v].step + 32;
-            MS_CHECK(a1 <= b0 || b1 <= a0, "%s: view %d: its descriptors overlap those of view %d", fn, v, u);
-        }
+    if (int e = orb_check(fn, n_views, gray, masks, prm, max_keypoints, desc)) return e;
     if (int e = require_device()) return e;
     return orb_batch(fn, n_views, gray, masks, prm, kp_host, max_keypoints, desc, n_out, stream);
 }

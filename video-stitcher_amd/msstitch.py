@@ -931,7 +931,8 @@ class OrbParams(C.Structure):
 
 def orb_detect_and_compute(gray, mask=None, nfeatures=2500, scale_factor=1.2, nlevels=8, fast_threshold=20, edge_threshold=None):
     """cuda::ORB::create(nfeatures, scaleFactor, nlevels)->detectAndCompute (featurefinder.cpp:15-40): gray / mask torch uint8 (H, W) on the device.
-    Returns (keypoints (n, 6) float32 numpy: x, y, response, angle, octave, size; descriptors (n, 32) uint8 torch tensor on the device)."""
+    Returns (keypoints (n, 6) float32 numpy: x, y, response, angle, octave, size; descriptors (n, 32) uint8 torch tensor on the device), in the order
+    ms_stitch.h defines (levels in turn; raster order, then the stable culls).  The batch of one: orb_detect_and_compute_batch([gray], [mask])[0]."""
     import numpy as np
     import torch
     prm = OrbParams()
@@ -960,7 +961,7 @@ def orb_params(nfeatures=2500, scale_factor=1.2, nlevels=8, fast_threshold=20, e
 
 
 def orb_detect_and_compute_batch(grays, masks=None, **orb_kw):
-    """ms_orb_detect_and_compute_batch: orb_detect_and_compute for every view in one device pass.  grays: torch uint8 (H, W) tensors on the device, of any sizes;
+    """ms_orb_detect_and_compute_batch: ORB for every view in one device pass (orb_detect_and_compute is this with one view).  grays: torch uint8 (H, W) tensors on the device, of any sizes;
     masks: None, or one entry per view (a tensor or None); keyword arguments as orb_detect_and_compute takes them, one set for the batch.
     Returns [(keypoints (n, 6) float32 numpy, descriptors (n, 32) uint8 torch tensor on the device, (width, height)), ...]: per view what orb_detect_and_compute
     returns, bit for bit and in its order, and the view's size behind it -- the list is what match_pairs / view_features take as it is."""
