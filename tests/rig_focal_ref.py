@@ -133,6 +133,16 @@ def apply_step(f, R, full):
     return np.array([f[v] * math.exp(full[4 * v + 3]) for v in range(n)]), Rn
 
 
+def step(f, R, matches, anchor, shared_focal, lam, huber_px=0.0):
+    """one proposal of refine() at the cameras (f, R) over ALL matches -> (A, delta): the solved matrix P^T H P + lam diag of it, and the step numpy.linalg.solve
+    returns for it (the columns of selection()); the same operations as refine()'s, so the same bits"""
+    P = selection(len(R), anchor, shared_focal)
+    _, H, g = accumulate(f, R, matches, huber_px)
+    Hr = P.T @ H @ P
+    A = Hr + lam * np.diag(np.diag(Hr))
+    return A, np.linalg.solve(A, -(P.T @ g))
+
+
 def refine(f_in, R_in, matches, anchor=0, shared_focal=False, huber_px=0.0, max_iters=50, step_tol=1e-10, min_pair_matches=4):
     """the Levenberg-Marquardt loop of the contract -> (f, R, info dict)"""
     f = np.array(f_in, np.float64); R = np.array(R_in, np.float64)

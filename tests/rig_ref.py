@@ -90,6 +90,17 @@ def angle(A, B):
     return math.atan2(0.5 * math.sqrt(float(v @ v)), 0.5 * (np.trace(M) - 1.0))
 
 
+def step(R, matches, anchor, lam, huber_rad=0.0):
+    """one proposal of refine() at the cameras R over ALL matches -> (A, delta): the solved matrix H + lam diag H without the anchor's rows, and the step
+    numpy.linalg.solve returns for it (view after view, the anchor left out); the same operations as refine()'s, so the same bits"""
+    R = np.asarray(R, np.float64)
+    keep = np.array([v for v in range(3 * len(R)) if v // 3 != anchor])
+    _, H, g = accumulate(R, matches, huber_rad)
+    Hr = H[np.ix_(keep, keep)]
+    A = Hr + lam * np.diag(np.diag(Hr))
+    return A, np.linalg.solve(A, -g[keep])
+
+
 def refine(R_in, matches, anchor=0, huber_rad=0.0, max_iters=50, step_tol=1e-10, min_pair_matches=4):
     """the Levenberg-Marquardt loop of the contract -> (R, info dict)"""
     R = np.array(R_in, np.float64)

@@ -17,6 +17,7 @@ import torch
 
 import lens_ref as L
 import rig_focal_ref as fr
+import rig_lm_cases as lm_cases
 import rig_ref as rr
 import synth
 from helpers import to_dev
@@ -71,6 +72,32 @@ def test_accumulate_per_op(ms, cuda, m):
         assert np.array_equal(H, H.T) and not H[0:4, 8:12].any() and H[4:8, 4:8].all() and H[0:4, 4:8].all()
 
 
+@pytest.mark.parametrize("graph", ["complete", "ring"])
+def test_accumulate_per_op_16_views(ms, cuda, graph):
+    """16 views with 16 focals (rows up to 64 of the full matrix): the complete graph, 120 pairs of 3 matches, and the ring, 16 pairs of 6, shuffled with a third listed
+    as (j, i) (tests/rig_lm_cases.py).  The bound of test_accumulate_per_op per entry: the cost sums every match, an entry of H or g at most the matches of one view.
+    H is symmetric bit for bit, and a block is zero exactly where its pair has no match: none of the complete graph's, 104 of the ring's 120."""
+    f, R, M, pairs = lm_cases.accumulate_case("focal", graph)
+    n_cost, n_entry = lm_cases.accumulate_terms(M)
+    for h in (0.0, lm_cases.accumulate_huber("focal", f, R, M)):
+        cost, H, g = ms.rig_focal_accumulate(f, R, M, h)
+        rc, rH, rg, sc, sH, sg = fr.accumulate(f, R, M, h, with_abs=True)
+        tol_c, tol = (n_cost + 8) * 2.0 ** -52, (n_entry + 8) * 2.0 ** -52
+        print("%s h=%g: cost %.3e of %.3e, H %.3e, g %.3e of %.3e (max |diff| / S)" % (graph, h, abs(cost - rc) / sc, tol_c, np.max(np.abs(H - rH) / np.maximum(sH, 1e-300)),
+                                                                                     np.max(np.abs(g - rg) / np.maximum(sg, 1e-300)), tol))
+        assert abs(cost - rc) <= tol_c * sc
+        assert np.all(np.abs(H - rH) <= tol * sH) and np.all(np.abs(g - rg) <= tol * sg)
+        assert np.array_equal(H, H.T)
+        used = {(min(p), max(p)) for p in pairs}
+        zero = 0
+        for i in range(15):
+            for j in range(i + 1, 16):
+                blk = H[4 * i:4 * i + 4, 4 * j:4 * j + 4]
+                assert blk.any() == ((i, j) in used), (i, j)
+                zero += not blk.any()
+        assert zero == (0 if graph == "complete" else 104) and all(H[4 * v:4 * v + 4, 4 * v:4 * v + 4].all() for v in range(16))
+
+
 # ---- 2. exact recovery ------------------------------------------------------------------------------------------
 def recovery_case(name):
     """-> f0, R0 (the start), ft, Rt (the truth), pairs, matches.  The start: the ideal layout, focals 15 % low and 20 % high in turn (shared: 30 % low)."""
@@ -90,7 +117,7 @@ def test_exact_recovery(ms, cuda, name):
     6e-16 of the true focal ratio and 3e-16 rad; 1e-12 leaves the conditioning of the largest system three orders."""
     f0, R0, ft, Rt, pairs, M = recovery_case(name)
     n, shared = len(f0), name.endswith("shared")
-    for anchor in (0, n - 1):
+    for anchor in sorted({0, n // 2, n - 1}) if n >= 3 else (0, n - 1):
         f, R, info = device_refine(ms, f0, R0, M, anchor=anchor, shared_focal=shared, step_tol=1e-13)
         err_R = max_angle(R, rr.expected(R0, Rt, anchor)); err_f = float(np.max(np.abs(f / ft - 1.0)))
         print("%s anchor=%d: focal ratio off 1 by %.3e, %.3e rad to the truth, %d iterations, stop %d, cost %.3e -> %.3e" % (name, anchor, err_f, err_R, info["iterations"],

@@ -1,7 +1,7 @@
 """Rig rotation refinement on the GPU (csrc/rig.hip) against the numpy reference of tests/rig_ref.py.
 
 1. ms_rig_accumulate per op: every entry of cost, H and g within the worst-case bound for two summation orders of the same rounded terms
-2. exact recovery from noise-free matches, either end of the rig as the anchor
+2. exact recovery from noise-free matches, either end of the rig and its middle as the anchor
 3. noisy matches and outliers (Huber) against the reference on the same inputs
 4. determinism: two calls return the same bits
 5. degenerate but legal inputs
@@ -16,6 +16,7 @@ import pytest
 import torch
 
 import lens_ref as L
+import rig_lm_cases as lm_cases
 import rig_ref as rr
 import synth
 from helpers import to_dev
@@ -67,6 +68,32 @@ def test_accumulate_per_op(ms, cuda, m):
         assert np.array_equal(H, H.T) and not H[0:3, 6:9].any() and H[3:6, 3:6].any()
 
 
+@pytest.mark.parametrize("graph", ["complete", "ring"])
+def test_accumulate_per_op_16_views(ms, cuda, graph):
+    """16 views (rows up to 48 of the full matrix): the complete graph, 120 pairs of 3 matches, and the ring, 16 pairs of 6, shuffled with a third listed as (j, i)
+    (tests/rig_lm_cases.py).  The bound of test_accumulate_per_op per entry: the cost sums every match, an entry of H or g at most the matches of one view.  H is
+    symmetric bit for bit, and a block is zero exactly where its pair has no match: none of the complete graph's, 104 of the ring's 120."""
+    _, R, M, pairs = lm_cases.accumulate_case("rot", graph)
+    n_cost, n_entry = lm_cases.accumulate_terms(M)
+    for h in (0.0, lm_cases.accumulate_huber("rot", None, R, M)):
+        cost, H, g = ms.rig_accumulate(R, M, h)
+        rc, rH, rg, sc, sH, sg = rr.accumulate(R, M, h, with_abs=True)
+        tol_c, tol = (n_cost + 8) * 2.0 ** -52, (n_entry + 8) * 2.0 ** -52
+        print("%s h=%g: cost %.3e of %.3e, H %.3e, g %.3e of %.3e (max |diff| / S)" % (graph, h, abs(cost - rc) / sc, tol_c, np.max(np.abs(H - rH) / np.maximum(sH, 1e-300)),
+                                                                                     np.max(np.abs(g - rg) / np.maximum(sg, 1e-300)), tol))
+        assert abs(cost - rc) <= tol_c * sc
+        assert np.all(np.abs(H - rH) <= tol * sH) and np.all(np.abs(g - rg) <= tol * sg)
+        assert np.array_equal(H, H.T)
+        used = {(min(p), max(p)) for p in pairs}
+        zero = 0
+        for i in range(15):
+            for j in range(i + 1, 16):
+                blk = H[3 * i:3 * i + 3, 3 * j:3 * j + 3]
+                assert blk.any() == ((i, j) in used), (i, j)
+                zero += not blk.any()
+        assert zero == (0 if graph == "complete" else 104) and all(H[3 * v:3 * v + 3, 3 * v:3 * v + 3].any() for v in range(16))
+
+
 # ---- 2. exact recovery ------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n, per_pair", [(2, 3), (3, 8), (6, 24), (16, 16)])
 def test_exact_recovery(ms, cuda, n, per_pair):
@@ -75,7 +102,7 @@ def test_exact_recovery(ms, cuda, n, per_pair):
     Rt = rr.perturbed(R0, rng, 5.0)
     pairs = [(0, 1), (1, 2), (0, 2)] if n == 3 else rr.ring_pairs(n)
     M = rr.make_matches(Rt, pairs, per_pair, rng)
-    for anchor in (0, n - 1):
+    for anchor in sorted({0, n // 2, n - 1}) if n >= 3 else (0, n - 1):
         R, info = device_refine(ms, R0, M, anchor=anchor, step_tol=1e-13, min_pair_matches=min(4, per_pair))
         err = max_angle(R, rr.expected(R0, Rt, anchor))
         print("n=%d anchor=%d: %.3e rad to the truth, %d iterations, stop %d, cost %.3e -> %.3e" % (n, anchor, err, info["iterations"], info["stop_reason"],
