@@ -220,7 +220,7 @@ MS_API int ms_build_warp_maps(int projection, int tl_u, int tl_v, ms_image *map_
  *       (xd, yd) = (X, Y) theta_d / rho, (0, 0) at rho = 0.  The atan2 form equals OpenCV's atan(r) for Z > 0 and goes on past 90 degrees;
  *   MS_LENS_NONE: xd = X / Z, yd = Y / Z, seen iff Z > 0;
  * and the pixel is (K[0] xd + K[1] yd + K[2], K[4] yd + K[5]).  Everything is evaluated in double -- from (double)u / (double)(float)scale with double sin / cos -- and
- * rounded to float once, at the store: calibration-time work, no fp32 evaluation order is part of the contract.  The library holds no inverse of the distortion. */
+ * rounded to float once, at the store: calibration-time work, no fp32 evaluation order is part of the contract.  The inverse, pixel to ray, is ms_lens_unproject below. */
 enum { MS_LENS_NONE = 0, MS_LENS_BROWN = 1, MS_LENS_FISHEYE = 2 };
 typedef struct ms_lens {
     unsigned struct_size;   /* as ms_config: mismatch = MS_ERR_INVALID */
@@ -236,6 +236,26 @@ MS_API int ms_lens_check(const ms_lens *lens);
 /* The model above on the host, for callers and tests: K 9 floats, ray = (X, Y, Z) in camera coordinates, px = the pixel, or (-1, -1) with *seen = 0.
  * lens == NULL is MS_LENS_NONE; a lens ms_lens_check refuses is refused here. */
 MS_API int ms_lens_project(const float *K, const ms_lens *lens, const double ray[3], double px[2], int *seen);
+/* The inverse of the model: the source pixel -> the UNIT camera ray (cv::undistortPoints / cv::fisheye::undistortPoints, normalised), in double, one copy of the
+ * arithmetic for this host call, ms_lens_unproject_points and the lens form of the rig refinement.  yd = (py - K[5]) / K[4], xd = (px - K[2] - K[1] yd) / K[0]; then
+ *   MS_LENS_NONE: the ray is (xd, yd, 1) normalised; every finite pixel is seen;
+ *   MS_LENS_FISHEYE: theta_d = hypot(xd, yd); not seen when theta_d > theta_d(max_theta).  theta solves theta_d(theta) = theta_d on [0, max_theta], where
+ *       ms_lens_check found the profile increasing: a Newton iteration with the analytic slope from min(theta_d, max_theta), kept inside a bracket [lo, hi] (the
+ *       bracket's midpoint where a step leaves it or the slope is not positive), until theta no longer changes, 60 rounds at most.  The ray is
+ *       (sin theta xd / theta_d, sin theta yd / theta_d, cos theta), (0, 0, 1) at theta_d = 0; past 90 degrees it has Z < 0;
+ *   MS_LENS_BROWN: (x, y) solves the full forward model, tangential terms included: a 2-D Newton iteration from (xd, yd) with the analytic 2 x 2 Jacobian, settled
+ *       when max |step| <= 2^-50 max(1, |x|, |y|), 50 rounds at most (OpenCV's five fixed-point rounds are not accurate enough for a
+ *       bundle adjustment; a zero step is not asked for, the last bit may alternate).  Not seen: the iteration does not settle, a Jacobian is singular, anything is
+ *       not finite, hypot(x, y) > tan(max_theta).  The ray is (x, y, 1) normalised.
+ * A pixel that is not finite is not seen.  Not seen: *seen = 0 and ray = (0, 0, 0).  The round trips ray -> ms_lens_project -> ms_lens_unproject and pixel ->
+ * unproject -> project return to 1e-11 rad and 1e-9 pixels (tests/test_rig_lens_abi.py).  Host only, no device needed.  lens == NULL is MS_LENS_NONE.
+ * MS_ERR_INVALID: a null pointer, a lens ms_lens_check refuses, a K entry that is not finite, K[0] or K[4] zero. */
+MS_API int ms_lens_unproject(const float *K, const ms_lens *lens, const double px[2], double ray[3], int *seen);
+/* ms_lens_unproject for n pixels on the device, one lane a point: a rig's keypoints (float pixel pairs, ORB's keypoint rows) become the unit rays
+ * ms_refine_rig_rotations takes.  px_host: n x 2 floats, rays_host: n x 3 doubles, seen_host: n bytes, all HOST; a point the lens does not see gets the ray
+ * (0, 0, 0) and the flag 0.  One upload, one launch, one copy back, one synchronise.  Host and device run the same code: rays differ by libm's sin / cos / hypot
+ * and the last Newton round only (1e-12).  MS_ERR_INVALID as above, and for n outside [1, 2^20]. */
+MS_API int ms_lens_unproject_points(const float *K, const ms_lens *lens, int n, const float *px_host, double *rays_host, unsigned char *seen_host, ms_stream stream);
 /* ms_build_warp_maps for a camera with a lens (buildWarp{Spherical,Cylindrical}Maps, stitching/src/cuda/build_warp_maps.cu:155-216, with the distortion between
  * R^-1 and K, which is why K and R -- 9 floats each, HOST -- are passed separately).  map_x / map_y: 32FC1 of one size, any row step (pitched images, ROIs of
  * larger ones).  lens == NULL is MS_LENS_NONE.  MS_PROJ_PLANE is MS_ERR_UNSUPPORTED. */
@@ -1033,10 +1053,39 @@ MS_API int ms_refine_rig_cameras(int n_views, const double *f_in, const double *
  * doubles; R_out: num_views x 9 floats.  Nothing is applied: the caller sets K[0] = f and K[4] = f (old K[4] / K[0]) and runs the usual chain (ms_set_camera,
  * ms_build_maps, masks, ms_init_blender).  MS_ERR_STATE before ms_build_maps; MS_ERR_UNSUPPORTED for MS_MAPS_CUSTOM contexts (no cameras) and for lens contexts: a
  * warped pixel of a lens context carries the camera ray but not the source pixel, and the ray's pixel at ANOTHER focal lies at another distorted radius -- refining
- * a focal under a lens needs the inverse distortion, which the library does not have.  MS_ERR_INVALID as above, for a list that names its own view or a view out of
+ * a focal under a lens needs the inverse distortion, which this pinhole form does not apply: ms_refine_rig_focals_lens below does.  MS_ERR_INVALID as above, for a list that names its own view or a view out of
  * range, and for a ray with z <= 0 (behind the camera: it has no pixel), naming the match. */
 MS_API int ms_refine_rig_focals(ms_ctx *ctx, const ms_mesh_match *matches, const int *match_count, const ms_rig_focal_params *prm, double *focal_out, float *R_out,
                                 ms_rig_focal_info *info, ms_stream stream);
+/* The lens form: the contract above with every view behind a FIXED lens (lenses: n_views ms_lens, HOST; per view, not unknowns; MS_LENS_NONE where a view has none).
+ * detail::BundleAdjusterRay again; OpenCV has no counterpart that keeps distortion between the pixel and its ray.  Matches are ms_rig_px_match as above: pixels
+ * centred on the principal point, y divided by the aspect ratio, so a view's distorted normalised coordinates are (xa / f, ya / f).  The 46 sums, Huber,
+ * m = sqrt(f_i f_j), r = m (p - q), the Levenberg-Marquardt rule and the stop rules stay; two things generalise, with s = ln f:
+ *   a      the unit ray of ms_lens_unproject at (xa / f_i, ya / f_i) through view i's lens, b the same for view j; p = R_i a, q = R_j b
+ *   ci_k = 0.5 r_k + m (R_i da/ds_i)_k, cj_k = 0.5 r_k - m (R_j db/ds_j)_k, (R d)_k = R[3k] d0 + R[3k+1] d1 + R[3k+2] d2, where da/ds is
+ *     NONE     a2 (e_z - a2 a): the view takes the pinhole contract's expressions for a and ci to the letter (ma = m a2, ci_k = 0.5 r_k + ma (R_i[3k+2] - a2 p_k)), so
+ *              a call whose lenses are all NONE returns the bits of ms_rig_focal_accumulate / ms_refine_rig_cameras
+ *     FISHEYE  e = (xd, yd) / theta_d, theta' = -theta_d / (d theta_d / d theta)(theta): da/ds = (theta' (cos theta e0), theta' (cos theta e1), -(theta' sin theta));
+ *              0 at the centre
+ *     BROWN    J the forward model's Jacobian at (x, y), (x', y') = -J^-1 (xd, yd) by Cramer's rule, n = sqrt(x^2 + y^2 + 1), t = a0 x' + a1 y':
+ *              da/ds = ((x' - a0 t) / n, (y' - a1 t) / n, -(a2 t) / n)
+ *   sin, cos, hypot and the last Newton round are not fixed to the bit: two implementations differ by the order of the sums and by those.
+ * A match with a pixel its lens does not see at the TRIAL cameras adds +infinity to the cost and nothing to any other sum: the trial is rejected by the accept rule
+ * (cost_trial <= cost fails), so every returned camera sees every match.  At the INPUT cameras such a pixel is MS_ERR_INVALID naming the match, found on the host
+ * before the device is touched.  Both calls refuse what their pinhole forms refuse, and a lens ms_lens_check refuses; no floating-point atomics, two calls return
+ * the same bits.  Stated limits: distortion coefficients and principal points are not unknowns; ms_estimate_rig stays pinhole, a lens rig starts from a nominal focal. */
+MS_API int ms_rig_lens_accumulate(int n_views, const double *f, const double *R, const ms_lens *lenses, const ms_rig_px_match *matches, int n, double huber_px,
+                                  double *cost, double *H, double *g, ms_stream stream);
+MS_API int ms_refine_rig_cameras_lens(int n_views, const double *f_in, const double *R_in, const ms_lens *lenses, const ms_rig_px_match *matches, int n,
+                                      const ms_rig_focal_params *prm, double *f_out, double *R_out, ms_rig_focal_info *info, ms_stream stream);
+/* The context form for lens AND analytic contexts, what ms_refine_rig_focals is to pinhole ones: the same per-view lists of projection-warped view pixels become
+ * camera rays by ms_warper_rays' arithmetic; a ray becomes its source pixel by the forward model (ms_lens_project's arithmetic, no inverse needed) with the view's
+ * current camera and lens, centred: (px - K[2], (py - K[5]) K[0] / K[4]), evaluated as the model's pixel for the camera (K[0], 0, 0; K[0], 0) so that nothing is
+ * rounded against the principal point; then ms_refine_rig_cameras_lens runs.  On an analytic context the result is ms_refine_rig_focals' bit for bit.  Nothing is
+ * applied.  MS_ERR_STATE before ms_build_maps; MS_ERR_UNSUPPORTED for MS_MAPS_CUSTOM contexts and for a view with K[1] != 0; MS_ERR_INVALID as above and for a ray
+ * its view's lens does not see, naming the match. */
+MS_API int ms_refine_rig_focals_lens(ms_ctx *ctx, const ms_mesh_match *matches, const int *match_count, const ms_rig_focal_params *prm, double *focal_out, float *R_out,
+                                     ms_rig_focal_info *info, ms_stream stream);
 
 /* ---- Pairwise matching: every view pair of a rig in one call ---------------------------------------------------------------------------------------
  * detail::BestOf2NearestMatcher / BestOf2NearestRangeMatcher (OCV/stitching/src/matchers.cpp:248-297 the two-direction 2-NN match with ratio test and

@@ -354,6 +354,35 @@ int ms_lens_project(const float *K, const ms_lens *lens, const double *ray, doub
     return MS_OK;
 }
 
+// what the two inverse entry points ask of K: the pixel is divided by K[0] and K[4]
+static int lens_unproject_check_k(const char *fn, const float *K)
+{
+    for (int i : {0, 1, 2, 4, 5}) MS_CHECK(std::isfinite(K[i]), "%s: K[%d] is not finite", fn, i);
+    MS_CHECK(K[0] != 0.f && K[4] != 0.f, "%s: K[0] = %g and K[4] = %g must not be zero", fn, (double)K[0], (double)K[4]);
+    return MS_OK;
+}
+
+int ms_lens_unproject(const float *K, const ms_lens *lens, const double *px, double *ray, int *seen)
+{
+    MS_CHECK(K && px && ray && seen, "ms_lens_unproject: null argument");
+    if (lens) if (int e = lens_check("ms_lens_unproject", lens)) return e;
+    if (int e = lens_unproject_check_k("ms_lens_unproject", K)) return e;
+    double r[3] = {0.0, 0.0, 0.0};
+    *seen = lens_unproject(lens_cam(K, nullptr, lens), lens_dist(lens), px[0], px[1], r) ? 1 : 0;
+    for (int k = 0; k < 3; ++k) ray[k] = *seen ? r[k] : 0.0;
+    return MS_OK;
+}
+
+int ms_lens_unproject_points(const float *K, const ms_lens *lens, int n, const float *px_host, double *rays_host, unsigned char *seen_host, ms_stream s)
+{
+    MS_CHECK(K && px_host && rays_host && seen_host, "ms_lens_unproject_points: null argument");
+    MS_CHECK(n >= 1 && n <= (1 << 20), "ms_lens_unproject_points: %d points outside [1, %d]", n, 1 << 20);
+    if (lens) if (int e = lens_check("ms_lens_unproject_points", lens)) return e;
+    if (int e = lens_unproject_check_k("ms_lens_unproject_points", K)) return e;
+    PRE()
+    return lens_unproject_device(K, lens, n, px_host, rays_host, seen_host, as_stream(s));
+}
+
 int ms_build_warp_maps_lens(int projection, int tl_u, int tl_v, ms_image *mx, ms_image *my, const float *K, const float *R, const ms_lens *lens, float scale, ms_stream s)
 {
     MS_CHECK(K && R && scale > 0.f, "ms_build_warp_maps_lens: K, R and a positive scale required");

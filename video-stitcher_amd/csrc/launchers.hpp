@@ -33,6 +33,8 @@ int launch_build_warp_maps(int proj, int tl_u, int tl_v, ms_image &mx, ms_image 
 // *seen_any = false (roi untouched) when no candidate of the window hits the source.  `lens` has passed lens_check.
 int launch_lens_maps(int proj, int tl_u, int tl_v, ms_image &mx, ms_image &my, const float *K, const float *R, const ms_lens *lens, float scale, hipStream_t st);
 int lens_roi_device(int proj, const float *K, const float *R, const ms_lens *lens, float scale, int src_w, int src_h, ms_rect *roi, bool *seen_any, hipStream_t st);
+// n float pixel pairs (HOST) -> n unit rays and flags (HOST): one upload, one launch, one copy back, one synchronise.  The caller has checked its arguments.
+int lens_unproject_device(const float *K, const ms_lens *lens, int n, const float *px_host, double *rays_host, unsigned char *seen_host, hipStream_t st);
 int launch_nv12_to_bgr(const ms_image &src, ms_image &dst, hipStream_t st);
 int launch_nv12_to_bgr_batch(const ms_image *src, ms_image *dst, int n, hipStream_t st);
 int launch_bgr_to_i420(const ms_image &src, ms_image &dst, hipStream_t st);

@@ -2,8 +2,9 @@
 // ms_warp_roi_lens, and through them ms_build_maps / ms_calibrate_seam of a context with a lens.  The per-frame path never runs anything of this unit: it reads
 // the dense maps these kernels store (PROJ_MAPS, tile_kernels.hpp).
 //   The maps are the backward maps of detail::{Spherical,Cylindrical}WarperGpu::buildMaps (stitching/src/cuda/build_warp_maps.cu:67-152) with the distortion
-// between R^-1 and K.  The ROI is found by forward evaluation only -- the library holds no inverse of the distortion: every integer warper coordinate of a
-// fixed candidate window is mapped, and the ROI is the bounding box of those whose truncated map coordinates hit the source (k_valid_mask's rule).
+// between R^-1 and K.  The ROI is found by forward evaluation only: every integer warper coordinate of a fixed candidate window is mapped, and the ROI is the
+// bounding box of those whose truncated map coordinates hit the source (k_valid_mask's rule).
+//   k_lens_unproject, behind ms_lens_unproject_points, is the inverse (lens.hpp, lens_unproject): source pixels, a rig's keypoints, to unit camera rays.
 #include <algorithm>
 #include <climits>
 #include <type_traits>
@@ -127,6 +128,35 @@ int lens_roi_device(int proj, const float *K, const float *R, const ms_lens *len
     MS_HIP(hipStreamSynchronize(st));
     *seen_any = h[0] != INT_MAX;
     if (*seen_any) *roi = ms_rect{h[0], h[1], h[2] - h[0] + 1, h[3] - h[1] + 1};
+    return MS_OK;
+}
+
+// one lane per point: the float pixel widened to double, lens_unproject, the ray and the flag stored; a point the lens does not see gets the ray (0, 0, 0)
+__global__ void __launch_bounds__(256) k_lens_unproject(int n, const float2 *__restrict__ px, LensCam cam, LensDist lens, double *__restrict__ rays, unsigned char *__restrict__ seen)
+{
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= n) return;
+    const float2 p = px[k];
+    double ray[3] = {0.0, 0.0, 0.0};
+    const bool ok = lens_unproject(cam, lens, (double)p.x, (double)p.y, ray);
+    rays[3 * (size_t)k] = ok ? ray[0] : 0.0; rays[3 * (size_t)k + 1] = ok ? ray[1] : 0.0; rays[3 * (size_t)k + 2] = ok ? ray[2] : 0.0;
+    seen[k] = ok ? 1 : 0;
+}
+
+// One device block, pixels | rays | flags: the pixels go up in one copy, rays and flags (adjacent) come back in one.
+int lens_unproject_device(const float *K, const ms_lens *lens, int n, const float *px_host, double *rays_host, unsigned char *seen_host, hipStream_t st)
+{
+    const size_t o_rays = (size_t)n * sizeof(float2), o_seen = o_rays + (size_t)n * 3 * sizeof(double), total = o_seen + (size_t)n;
+    char *base = (char *)device_scratch().get(total), *host = (char *)pinned_scratch().get(total);
+    if (!base || !host) return fail(MS_ERR_NOMEM, "ms_lens_unproject_points: no memory for %zu bytes", total);
+    memcpy(host, px_host, o_rays);
+    MS_HIP(hipMemcpyAsync(base, host, o_rays, hipMemcpyHostToDevice, st));
+    k_lens_unproject<<<div_up(n, 256), 256, 0, st>>>(n, (const float2 *)base, lens_cam(K, nullptr, lens), lens_dist(lens), (double *)(base + o_rays), (unsigned char *)(base + o_seen));
+    MS_LAUNCH_CHECK();
+    MS_HIP(hipMemcpyAsync(host + o_rays, base + o_rays, total - o_rays, hipMemcpyDeviceToHost, st));
+    MS_HIP(hipStreamSynchronize(st));
+    memcpy(rays_host, host + o_rays, (size_t)n * 3 * sizeof(double));
+    memcpy(seen_host, host + o_seen, (size_t)n);
     return MS_OK;
 }
 

@@ -13,8 +13,9 @@ struct RigRay { double a[3], b[3]; };         // a seen by view i, b by view j
 struct RigRays {
     using Match = RigRay;
     static constexpr int B = 3;
+    using Aux = char;                         // no per-view data beside the state
     struct Cams {};                           // a pair needs nothing beside its two rotations
-    static __device__ __forceinline__ Cams load(const RigState<3> *, const RigPair &) { return Cams{}; }
+    static __device__ __forceinline__ Cams load(const RigState<3> *, const RigPair &, const Aux *) { return Cams{}; }
     // The terms of one match, added into acc in the header's order.  h == 0: plain least squares.
     static __device__ __forceinline__ void terms(const double *Ri, const double *Rj, const Cams &, const RigRay &m, double h, double acc[RigSums<3>::SUMS])
     {

@@ -4,23 +4,22 @@
 // -ffp-contract=off keeps every product, sum, division and sqrt of the per-match terms a separate IEEE operation, in the order the header states.
 // This unit holds what is the focal problem's own: the per-match terms (the policy RigPixels, 4 unknowns a view), the homography estimator, the checks of cameras and
 // pixel matches and the entry points.  The kernels k_rig_accum<RigPixels> and k_rig_step<4>, the Levenberg-Marquardt rule and the host side around them are
-// rig_lm.hpp's, shared with rig.hip.
-#include "rig_lm.hpp"
+// rig_lm.hpp's, shared with rig.hip; what a pixel match shares with the lens form (rig_lens.hip) -- the residual, the 46 sums, the checks -- is rig_px.hpp's.
+#include "rig_px.hpp"
 
 namespace ms {
 
-struct RigfPx { double a[2], b[2]; };             // centred pixels: a in view i, b in view j
-
 struct RigPixels {
     using Match = RigfPx;
+    using Aux = char;                             // no per-view data beside the state
     static constexpr int B = 4;
     struct Cams { double fi, fj, m; };            // the pair's two focals and their geometric mean
-    static __device__ __forceinline__ Cams load(const RigState<4> *st, const RigPair &pr)
+    static __device__ __forceinline__ Cams load(const RigState<4> *st, const RigPair &pr, const Aux *)
     {
         const double fi = st->f_trial[pr.i], fj = st->f_trial[pr.j], m = sqrt(fi * fj);
         return Cams{fi, fj, m};
     }
-    // The terms of one match, added into acc in the header's order.  h == 0: plain least squares.
+    // The terms of one match: the rays, the focal columns; the residual and the sums are rig_px.hpp's.
     static __device__ __forceinline__ void terms(const double *Ri, const double *Rj, const Cams &cams, const RigfPx &px, double h, double acc[RigSums<4>::SUMS])
     {
         const double fi = cams.fi, fj = cams.fj, m = cams.m;
@@ -28,36 +27,11 @@ struct RigPixels {
         const double a0 = px.a[0] / na, a1 = px.a[1] / na, a2 = fi / na, b0 = px.b[0] / nb, b1 = px.b[1] / nb, b2 = fj / nb;
         const double p0 = Ri[0] * a0 + Ri[1] * a1 + Ri[2] * a2, p1 = Ri[3] * a0 + Ri[4] * a1 + Ri[5] * a2, p2 = Ri[6] * a0 + Ri[7] * a1 + Ri[8] * a2;
         const double q0 = Rj[0] * b0 + Rj[1] * b1 + Rj[2] * b2, q1 = Rj[3] * b0 + Rj[4] * b1 + Rj[5] * b2, q2 = Rj[6] * b0 + Rj[7] * b1 + Rj[8] * b2;
-        const double u0 = m * p0, u1 = m * p1, u2 = m * p2, v0 = m * q0, v1 = m * q1, v2 = m * q2;
-        const double r0 = m * (p0 - q0), r1 = m * (p1 - q1), r2 = m * (p2 - q2);
-        const double s2 = r0 * r0 + r1 * r1 + r2 * r2;
-        double w = 1.0, rho = s2, out = 0.0;
-        if (h > 0.0) {
-            const double s = sqrt(s2);
-            if (s > h) { w = h / s; rho = (2.0 * h) * s - h * h; out = 1.0; }
-        }
+        const RigPxResidual e = rig_px_residual(m, p0, p1, p2, q0, q1, q2, h);
         const double ma = m * a2, mb = m * b2;
-        const double ci0 = 0.5 * r0 + ma * (Ri[2] - a2 * p0), ci1 = 0.5 * r1 + ma * (Ri[5] - a2 * p1), ci2 = 0.5 * r2 + ma * (Ri[8] - a2 * p2);
-        const double cj0 = 0.5 * r0 - mb * (Rj[2] - b2 * q0), cj1 = 0.5 * r1 - mb * (Rj[5] - b2 * q1), cj2 = 0.5 * r2 - mb * (Rj[8] - b2 * q2);
-        acc[0] += rho;
-        acc[1] += w * (u1 * r2 - u2 * r1); acc[2] += w * (u2 * r0 - u0 * r2); acc[3] += w * (u0 * r1 - u1 * r0);                // g_i: w u x r, then w ci . r
-        acc[4] += w * (ci0 * r0 + ci1 * r1 + ci2 * r2);
-        acc[5] += -(w * (v1 * r2 - v2 * r1)); acc[6] += -(w * (v2 * r0 - v0 * r2)); acc[7] += -(w * (v0 * r1 - v1 * r0));       // g_j: -w v x r, then w cj . r
-        acc[8] += w * (cj0 * r0 + cj1 * r1 + cj2 * r2);
-        acc[9] += w * (u1 * u1 + u2 * u2); acc[10] += -(w * (u0 * u1)); acc[11] += -(w * (u0 * u2)); acc[12] += w * (u1 * ci2 - u2 * ci1);      // H_ii
-        acc[13] += w * (u0 * u0 + u2 * u2); acc[14] += -(w * (u1 * u2)); acc[15] += w * (u2 * ci0 - u0 * ci2);
-        acc[16] += w * (u0 * u0 + u1 * u1); acc[17] += w * (u0 * ci1 - u1 * ci0);
-        acc[18] += w * (ci0 * ci0 + ci1 * ci1 + ci2 * ci2);
-        acc[19] += w * (v1 * v1 + v2 * v2); acc[20] += -(w * (v0 * v1)); acc[21] += -(w * (v0 * v2)); acc[22] += -(w * (v1 * cj2 - v2 * cj1));  // H_jj
-        acc[23] += w * (v0 * v0 + v2 * v2); acc[24] += -(w * (v1 * v2)); acc[25] += -(w * (v2 * cj0 - v0 * cj2));
-        acc[26] += w * (v0 * v0 + v1 * v1); acc[27] += -(w * (v0 * cj1 - v1 * cj0));
-        acc[28] += w * (cj0 * cj0 + cj1 * cj1 + cj2 * cj2);
-        acc[29] += -(w * (u1 * v1 + u2 * v2)); acc[30] += w * (v0 * u1); acc[31] += w * (v0 * u2); acc[32] += w * (u1 * cj2 - u2 * cj1);        // H_ij, row by row
-        acc[33] += w * (v1 * u0); acc[34] += -(w * (u0 * v0 + u2 * v2)); acc[35] += w * (v1 * u2); acc[36] += w * (u2 * cj0 - u0 * cj2);
-        acc[37] += w * (v2 * u0); acc[38] += w * (v2 * u1); acc[39] += -(w * (u0 * v0 + u1 * v1)); acc[40] += w * (u0 * cj1 - u1 * cj0);
-        acc[41] += -(w * (v1 * ci2 - v2 * ci1)); acc[42] += -(w * (v2 * ci0 - v0 * ci2)); acc[43] += -(w * (v0 * ci1 - v1 * ci0));
-        acc[44] += w * (ci0 * cj0 + ci1 * cj1 + ci2 * cj2);
-        acc[45] += out;
+        const double ci0 = 0.5 * e.r0 + ma * (Ri[2] - a2 * p0), ci1 = 0.5 * e.r1 + ma * (Ri[5] - a2 * p1), ci2 = 0.5 * e.r2 + ma * (Ri[8] - a2 * p2);
+        const double cj0 = 0.5 * e.r0 - mb * (Rj[2] - b2 * q0), cj1 = 0.5 * e.r1 - mb * (Rj[5] - b2 * q1), cj2 = 0.5 * e.r2 - mb * (Rj[8] - b2 * q2);
+        rig_px_sums(e, ci0, ci1, ci2, cj0, cj1, cj2, acc);
     }
 };
 
@@ -136,60 +110,6 @@ static bool rigf_nearest_rotation(const double *M, double *R)
         uvt();
     }
     return true;
-}
-
-// ---- host side: the bundle adjustment -----------------------------------------------------------------------------------------------------------
-static int rigf_check_cameras(const char *fn, int n_views, const double *f, const double *R)
-{
-    MS_CHECK(n_views >= 2 && n_views <= MS_MAX_VIEWS, "%s: n_views = %d outside [2, %d]", fn, n_views, MS_MAX_VIEWS);
-    MS_CHECK(f && R, "%s: null argument", fn);
-    for (int v = 0; v < n_views; ++v) {
-        MS_CHECK(std::isfinite(f[v]) && f[v] > 0.0, "%s: focal of view %d (%g) is not finite and positive", fn, v, f[v]);
-        const double *Rv = R + 9 * v;
-        for (int k = 0; k < 9; ++k) MS_CHECK(std::isfinite(Rv[k]), "%s: rotation of view %d is not finite", fn, v);
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 3; ++c) {
-                const double e = Rv[r * 3] * Rv[c * 3] + Rv[r * 3 + 1] * Rv[c * 3 + 1] + Rv[r * 3 + 2] * Rv[c * 3 + 2] - (r == c ? 1.0 : 0.0);
-                MS_CHECK(std::fabs(e) <= 1e-6, "%s: rotation of view %d is not orthonormal: R R^T is off the identity by %g", fn, v, std::fabs(e));
-            }
-    }
-    return MS_OK;
-}
-
-static int rigf_check_matches(const char *fn, int n_views, const ms_rig_px_match *matches, int n)
-{
-    MS_CHECK(matches, "%s: null argument", fn);
-    MS_CHECK(n >= 1 && n <= RIG_MAX_MATCHES, "%s: %d matches outside [1, %d]", fn, n, RIG_MAX_MATCHES);
-    for (int k = 0; k < n; ++k) {
-        const ms_rig_px_match &m = matches[k];
-        MS_CHECK(m.view_a >= 0 && m.view_a < n_views && m.view_b >= 0 && m.view_b < n_views, "%s: match %d names views %d, %d outside [0, %d)", fn, k, m.view_a, m.view_b, n_views);
-        MS_CHECK(m.view_a != m.view_b, "%s: match %d pairs view %d with itself", fn, k, m.view_a);
-        MS_CHECK(std::isfinite(m.a[0]) && std::isfinite(m.a[1]) && std::isfinite(m.b[0]) && std::isfinite(m.b[1]), "%s: match %d: a pixel is not finite", fn, k);
-    }
-    return MS_OK;
-}
-
-// everything ms_refine_rig_cameras does; fn names the entry point in messages
-static int rigf_refine(const char *fn, int n_views, const double *f_in, const double *R_in, const ms_rig_px_match *matches, int n, const ms_rig_focal_params *prm,
-                       double *f_out, double *R_out, ms_rig_focal_info *info, hipStream_t s)
-{
-    if (int e = rigf_check_cameras(fn, n_views, f_in, R_in)) return e;
-    if (int e = rigf_check_matches(fn, n_views, matches, n)) return e;
-    MS_CHECK(f_out && R_out, "%s: null output", fn);
-    MS_CHECK(prm, "%s: null params", fn);
-    MS_CHECK(prm->struct_size == sizeof(ms_rig_focal_params), "%s: params.struct_size %u, this library's ms_rig_focal_params has %zu bytes", fn, prm->struct_size,
-             sizeof(ms_rig_focal_params));
-    const RigLmParams p{prm->anchor_view, prm->shared_focal ? 1 : 0, prm->max_iters, prm->min_pair_matches, prm->huber_px, prm->step_tol};
-    if (int e = rig_check_params(fn, n_views, p, "huber_px")) return e;
-    if (prm->shared_focal)
-        for (int v = 1; v < n_views; ++v)
-            MS_CHECK(f_in[v] == f_in[0], "%s: shared_focal asks for equal input focals; view %d has %.17g, view 0 has %.17g", fn, v, f_in[v], f_in[0]);
-    if (int e = rig_lm_refine<RigPixels>(fn, n_views, f_in, R_in, matches, n, p, f_out, R_out, info, s)) return e;
-    if (info) {
-        info->max_focal_ratio = 1.0;
-        for (int v = 0; v < n_views; ++v) info->max_focal_ratio = std::max(info->max_focal_ratio, std::max(f_out[v] / f_in[v], f_in[v] / f_out[v]));
-    }
-    return MS_OK;
 }
 
 }  // namespace ms
@@ -300,7 +220,7 @@ int ms_rig_focal_accumulate(int n_views, const double *f, const double *R, const
 int ms_refine_rig_cameras(int n_views, const double *f_in, const double *R_in, const ms_rig_px_match *matches, int n, const ms_rig_focal_params *prm, double *f_out,
                           double *R_out, ms_rig_focal_info *info, ms_stream stream)
 {
-    return rigf_refine("ms_refine_rig_cameras", n_views, f_in, R_in, matches, n, prm, f_out, R_out, info, as_stream(stream));
+    return rigf_refine<RigPixels>("ms_refine_rig_cameras", n_views, f_in, R_in, matches, n, prm, f_out, R_out, info, as_stream(stream), [] { return (int)MS_OK; });
 }
 
 int ms_refine_rig_focals(ms_ctx *c, const ms_mesh_match *matches, const int *match_count, const ms_rig_focal_params *prm, double *focal_out, float *R_out,
@@ -310,7 +230,7 @@ int ms_refine_rig_focals(ms_ctx *c, const ms_mesh_match *matches, const int *mat
     MS_CHECK(c && matches && match_count && prm && focal_out && R_out, "%s: null argument", fn);
     if (int e = rig_ctx_check(fn, c)) return e;
     if (c->lens_maps)
-        return fail(MS_ERR_UNSUPPORTED, "%s: the context has a lens (ms_set_lens): a focal under a lens needs the inverse distortion, which the library does not have", fn);
+        return fail(MS_ERR_UNSUPPORTED, "%s: the context has a lens (ms_set_lens): a focal under a lens needs the inverse distortion: ms_refine_rig_focals_lens has it", fn);
     const int N = c->N;
     std::vector<double> R, Rr(9 * N), f(N);
     for (int v = 0; v < N; ++v) f[v] = (double)c->K[v][0];
@@ -325,7 +245,7 @@ int ms_refine_rig_focals(ms_ctx *c, const ms_mesh_match *matches, const int *mat
     };
     if (int e = rig_ctx_matches(fn, c, matches, match_count, R, pm, pixels)) return e;
     // single-precision rotations are orthonormal to about 1e-7 only: what the context holds is used as it is, as ms_refine_rig does
-    if (int e = rigf_refine(fn, N, f.data(), R.data(), pm.data(), (int)pm.size(), prm, focal_out, Rr.data(), info, as_stream(stream))) return e;
+    if (int e = rigf_refine<RigPixels>(fn, N, f.data(), R.data(), pm.data(), (int)pm.size(), prm, focal_out, Rr.data(), info, as_stream(stream), [] { return (int)MS_OK; })) return e;
     for (int q = 0; q < 9 * N; ++q) R_out[q] = (float)Rr[q];
     return MS_OK;
 }

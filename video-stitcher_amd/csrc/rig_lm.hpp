@@ -1,6 +1,7 @@
-// rig_lm.hpp -- the Levenberg-Marquardt core the two rig refinements share: rig.hip (rotations from unit rays, B = 3 unknowns a view) and rig_focal.hip (rotations
-// and focals from centred pixels, B = 4).  Internal; those two units include it and nothing else does.  A unit supplies a policy -- its match record, B, what a
-// workgroup loads per pair beside the two rotations, and the per-match terms of include/ms_stitch.h -- and gets from here, each once:
+// rig_lm.hpp -- the Levenberg-Marquardt core the rig refinements share: rig.hip (rotations from unit rays, B = 3 unknowns a view), rig_focal.hip (rotations and
+// focals from centred pixels, B = 4) and rig_lens.hip (the same through fixed lenses, B = 4).  Internal; those three units include it and nothing else does.  A unit
+// supplies a policy -- its match record, B, what a workgroup loads per pair beside the two rotations (from the state, and from an array Aux of fixed per-view data
+// that goes up next to the state: the lenses; char and empty where a policy has none), and the per-match terms of include/ms_stitch.h -- and gets from here, each once:
 //   k_rig_accum<P>   one workgroup per view pair: the sums of the pair (RigSums<B>) in one fixed order
 //   k_rig_step<B>    one workgroup: assembles the system in pair order, accepts or rejects the trial, moves lambda, folds the focal columns where the focal is shared
 //                    (B = 4), Cholesky in LDS, writes the next trial
@@ -55,7 +56,8 @@ struct RigStepPrm { int n_views, anchor, shared, max_iters, assemble_only; doubl
 // One 256-thread workgroup per used pair.  A thread sums the matches t, t + 256, ... in index order into registers; the 64 lanes of a wave are folded by a
 // butterfly of fixed shape (lane ^ 32, ^ 16, ... ^ 1: every lane ends with the same bits), the four waves through LDS in wave order; SUMS lanes store.
 template <class P> __global__ void __launch_bounds__(256) k_rig_accum(const RigState<P::B> *__restrict__ st, const RigPair *__restrict__ pairs,
-                                                                      const typename P::Match *__restrict__ items, double h, double *__restrict__ part)
+                                                                      const typename P::Match *__restrict__ items, const typename P::Aux *__restrict__ aux, double h,
+                                                                      double *__restrict__ part)
 {
     using S = RigSums<P::B>;
     __shared__ double s_sum[4][S::PART];
@@ -64,7 +66,7 @@ template <class P> __global__ void __launch_bounds__(256) k_rig_accum(const RigS
     double Ri[9], Rj[9], acc[S::SUMS];
 #pragma unroll
     for (int k = 0; k < 9; ++k) { Ri[k] = st->R_trial[pr.i * 9 + k]; Rj[k] = st->R_trial[pr.j * 9 + k]; }
-    const typename P::Cams cams = P::load(st, pr);
+    const typename P::Cams cams = P::load(st, pr, aux);
 #pragma unroll
     for (int e = 0; e < S::SUMS; ++e) acc[e] = 0.0;
     for (int k = threadIdx.x; k < pr.cnt; k += 256) P::terms(Ri, Rj, cams, items[pr.off + k], h, acc);
@@ -333,17 +335,20 @@ template <class Item, class In> static RigGroups<Item> rig_group(int n_views, co
     return G;
 }
 
-// One device block, state | pairs | items | partials (all 8-byte aligned): the first three are laid out in pinned memory and go up in ONE copy.  f: null for B = 3.
-template <class P> struct RigDevice { RigState<P::B> *st; RigPair *pairs; typename P::Match *items; double *part; };
-template <class P> static int rig_upload(const char *fn, const RigGroups<typename P::Match> &G, int n_views, const double *f, const double *R, RigDevice<P> &D, hipStream_t s)
+// One device block, state | pairs | items | aux | partials (all 8-byte aligned): the first four are laid out in pinned memory and go up in ONE copy.  f: null for
+// B = 3; aux: n_aux records of the policy's per-view data, null and 0 where it has none.
+template <class P> struct RigDevice { RigState<P::B> *st; RigPair *pairs; typename P::Match *items; typename P::Aux *aux; double *part; };
+template <class P> static int rig_upload(const char *fn, const RigGroups<typename P::Match> &G, int n_views, const double *f, const double *R, const typename P::Aux *aux,
+                                         int n_aux, RigDevice<P> &D, hipStream_t s)
 {
     using State = RigState<P::B>;
     using Item = typename P::Match;
-    const size_t np = G.pairs.size(), o_pairs = sizeof(State), o_items = o_pairs + np * sizeof(RigPair), o_part = o_items + G.items.size() * sizeof(Item),
-                 total = o_part + np * RigSums<P::B>::PART * sizeof(double);
+    static_assert(sizeof(Item) % 8 == 0 && (sizeof(typename P::Aux) % 8 == 0 || sizeof(typename P::Aux) == 1), "the block's parts stay 8-byte aligned");
+    const size_t np = G.pairs.size(), o_pairs = sizeof(State), o_items = o_pairs + np * sizeof(RigPair), o_aux = o_items + G.items.size() * sizeof(Item),
+                 o_part = o_aux + (size_t)n_aux * sizeof(typename P::Aux), total = o_part + np * RigSums<P::B>::PART * sizeof(double);
     char *base = (char *)device_scratch().get(total), *host = (char *)pinned_scratch().get(o_part);
     if (!base || !host) return fail(MS_ERR_NOMEM, "%s: no memory for %zu bytes", fn, total);
-    D.st = (State *)base; D.pairs = (RigPair *)(base + o_pairs); D.items = (Item *)(base + o_items); D.part = (double *)(base + o_part);
+    D.st = (State *)base; D.pairs = (RigPair *)(base + o_pairs); D.items = (Item *)(base + o_items); D.aux = (typename P::Aux *)(base + o_aux); D.part = (double *)(base + o_part);
     State *st = (State *)host;
     memset(st, 0, sizeof(State));
     memcpy(st->R_cur, R, sizeof(double) * 9 * n_views); memcpy(st->R_trial, R, sizeof(double) * 9 * n_views);
@@ -351,6 +356,7 @@ template <class P> static int rig_upload(const char *fn, const RigGroups<typenam
     st->t.lam = 1e-3;
     memcpy(host + o_pairs, G.pairs.data(), np * sizeof(RigPair));
     memcpy(host + o_items, G.items.data(), G.items.size() * sizeof(Item));
+    if (n_aux) memcpy(host + o_aux, aux, (size_t)n_aux * sizeof(typename P::Aux));
     MS_HIP(hipMemcpyAsync(base, host, o_part, hipMemcpyHostToDevice, s));
     return MS_OK;
 }
@@ -369,17 +375,17 @@ static int rig_check_params(const char *fn, int n_views, const RigLmParams &p, c
 
 // The normal equations at the given cameras, every pair used: one round with assemble_only, the whole state copied back.  The caller has checked its arguments.
 template <class P, class In> static int rig_lm_accumulate(const char *fn, int n_views, const double *f, const double *R, const In *matches, int n, double huber, double *cost,
-                                                          double *H, double *g, hipStream_t s)
+                                                          double *H, double *g, hipStream_t s, const typename P::Aux *aux = nullptr, int n_aux = 0)
 {
     constexpr int B = P::B;
     if (int e = require_device()) return e;
     const RigGroups<typename P::Match> G = rig_group<typename P::Match>(n_views, matches, n, 1);
     RigDevice<P> D;
-    if (int e = rig_upload(fn, G, n_views, f, R, D, s)) return e;
+    if (int e = rig_upload(fn, G, n_views, f, R, aux, n_aux, D, s)) return e;
     std::vector<RigState<B>> host(1);
     RigState<B> &h = host[0];
     const int np = (int)G.pairs.size();
-    k_rig_accum<P><<<np, 256, 0, s>>>(D.st, D.pairs, D.items, huber, D.part);
+    k_rig_accum<P><<<np, 256, 0, s>>>(D.st, D.pairs, D.items, D.aux, huber, D.part);
     k_rig_step<B><<<1, RIG_STEP_THREADS, 0, s>>>(D.st, D.pairs, np, D.part, RigStepPrm{n_views, 0, 0, 1, 1, 0.0});
     MS_LAUNCH_CHECK();
     MS_HIP(hipMemcpyAsync(&h, D.st, sizeof(RigState<B>), hipMemcpyDeviceToHost, s));
@@ -397,7 +403,8 @@ template <class P, class In> static int rig_lm_accumulate(const char *fn, int n_
 // at once (both return at their first instruction once the stop flag is set), one copy back of the cameras and one of the tail, and what the two public info structs
 // share.  f_in / f_out: null for B = 3.
 template <class P, class In, class Info> static int rig_lm_refine(const char *fn, int n_views, const double *f_in, const double *R_in, const In *matches, int n,
-                                                                  const RigLmParams &p, double *f_out, double *R_out, Info *info, hipStream_t s)
+                                                                  const RigLmParams &p, double *f_out, double *R_out, Info *info, hipStream_t s,
+                                                                  const typename P::Aux *aux = nullptr, int n_aux = 0)
 {
     constexpr int B = P::B;
     const RigGroups<typename P::Match> G = rig_group<typename P::Match>(n_views, matches, n, p.min_pair);
@@ -417,11 +424,11 @@ template <class P, class In, class Info> static int rig_lm_refine(const char *fn
     if (int e = require_device()) return e;
 
     RigDevice<P> D;
-    if (int e = rig_upload(fn, G, n_views, f_in, R_in, D, s)) return e;
+    if (int e = rig_upload(fn, G, n_views, f_in, R_in, aux, n_aux, D, s)) return e;
     const RigStepPrm sp{n_views, p.anchor, p.shared, p.max_iters, 0, p.step_tol};
     const int np = (int)G.pairs.size();
     for (int round = 0; round <= p.max_iters; ++round) {
-        k_rig_accum<P><<<np, 256, 0, s>>>(D.st, D.pairs, D.items, p.huber, D.part);
+        k_rig_accum<P><<<np, 256, 0, s>>>(D.st, D.pairs, D.items, D.aux, p.huber, D.part);
         k_rig_step<B><<<1, RIG_STEP_THREADS, 0, s>>>(D.st, D.pairs, np, D.part, sp);
     }
     MS_LAUNCH_CHECK();

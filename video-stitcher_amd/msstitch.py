@@ -234,6 +234,7 @@ EXPORTS = [
     "ms_pair_match_default_params", "ms_match_pairs", "ms_biggest_component", "ms_wave_correct",
     "ms_find_homography_ransac_batch",
     "ms_orb_detect_and_compute_batch",
+    "ms_lens_unproject", "ms_lens_unproject_points", "ms_rig_lens_accumulate", "ms_refine_rig_cameras_lens", "ms_refine_rig_focals_lens",
 ]
 
 _lib = None
@@ -550,6 +551,29 @@ def lens_project(K, lens, ray):
     return (px[0], px[1]), bool(seen.value)
 
 
+def lens_unproject(K, lens, px):
+    """ms_lens_unproject (host only): the source pixel (px, py) -> (the unit camera ray (3,) float64, seen); the ray is (0, 0, 0) when the lens does not see it"""
+    import numpy as np
+    ka, kp = _fa(K, 9)
+    p = (C.c_double * 2)(float(px[0]), float(px[1]))
+    ray = (C.c_double * 3)()
+    seen = C.c_int(-1)
+    _chk(load().ms_lens_unproject(kp, _lens_ptr(lens), p, ray, C.byref(seen)))
+    return np.array(ray[:], np.float64), bool(seen.value)
+
+
+def lens_unproject_points(K, lens, px):
+    """ms_lens_unproject_points (device): px (n, 2) float32 source pixels -> (unit rays (n, 3) float64, seen (n,) bool); unseen points have the ray (0, 0, 0)"""
+    import numpy as np
+    ka, kp = _fa(K, 9)
+    pa = np.ascontiguousarray(px, np.float32).reshape(-1, 2)
+    n = len(pa)
+    rays = np.empty((max(n, 1), 3), np.float64); seen = np.empty(max(n, 1), np.uint8)
+    _chk(load().ms_lens_unproject_points(kp, _lens_ptr(lens), n, pa.ctypes.data_as(C.POINTER(C.c_float)), rays.ctypes.data_as(C.POINTER(C.c_double)),
+                                         seen.ctypes.data_as(C.POINTER(C.c_ubyte)), _stream()))
+    return rays[:n], seen[:n].astype(bool)
+
+
 def build_warp_maps_lens(projection, tl_u, tl_v, rows, cols, K, R, lens, scale, out=None):
     """ms_build_warp_maps_lens; out: (map_x, map_y) float32 cuda tensors to fill (views of larger tensors are fine) instead of new ones"""
     torch = _torch()
@@ -703,6 +727,43 @@ def refine_rig_cameras(f, R, matches, params=None):
     dp = C.POINTER(C.c_double)
     _chk(load().ms_refine_rig_cameras(n, fa.ctypes.data_as(dp), Ra.ctypes.data_as(dp), rig_px_matches(matches), len(matches), C.byref(prm), fo.ctypes.data_as(dp),
                                       out.ctypes.data_as(dp), C.byref(info), _stream()))
+    return fo, out, _rig_focal_info(info)
+
+
+def lens_array(lenses):
+    """[Lens or None, ...] -> a Lens array, one a view; None is MS_LENS_NONE"""
+    arr = (Lens * max(1, len(lenses)))()
+    for v, l in enumerate(lenses):
+        arr[v] = l if l is not None else Lens.make(LENS_NONE, (), 0.0)
+    return arr
+
+
+def rig_lens_accumulate(f, R, lenses, matches, huber_px=0.0):
+    """ms_rig_lens_accumulate: rig_focal_accumulate with the views behind `lenses` (one Lens or None a view) -> (cost, H (4n, 4n), g (4n,)) at these cameras"""
+    import numpy as np
+    fa = np.ascontiguousarray(f, np.float64); Ra = np.ascontiguousarray(R, np.float64)
+    n = len(Ra)
+    assert len(lenses) == n
+    H = np.empty((4 * n, 4 * n), np.float64); g = np.empty(4 * n, np.float64)
+    cost = C.c_double(0)
+    dp = C.POINTER(C.c_double)
+    _chk(load().ms_rig_lens_accumulate(n, fa.ctypes.data_as(dp), Ra.ctypes.data_as(dp), lens_array(lenses), rig_px_matches(matches), len(matches), C.c_double(huber_px),
+                                       C.byref(cost), H.ctypes.data_as(dp), g.ctypes.data_as(dp), _stream()))
+    return cost.value, H, g
+
+
+def refine_rig_cameras_lens(f, R, lenses, matches, params=None):
+    """ms_refine_rig_cameras_lens: refine_rig_cameras with the views behind `lenses` (one Lens or None a view) -> (refined f (n,), refined R (n, 3, 3), info dict)"""
+    import numpy as np
+    fa = np.ascontiguousarray(f, np.float64); Ra = np.ascontiguousarray(R, np.float64)
+    n = len(Ra)
+    assert len(lenses) == n
+    fo = np.empty(n, np.float64); out = np.empty((n, 3, 3), np.float64)
+    prm = params if params is not None else rig_focal_default_params()
+    info = RigFocalInfo()
+    dp = C.POINTER(C.c_double)
+    _chk(load().ms_refine_rig_cameras_lens(n, fa.ctypes.data_as(dp), Ra.ctypes.data_as(dp), lens_array(lenses), rig_px_matches(matches), len(matches), C.byref(prm),
+                                           fo.ctypes.data_as(dp), out.ctypes.data_as(dp), C.byref(info), _stream()))
     return fo, out, _rig_focal_info(info)
 
 
@@ -1198,6 +1259,18 @@ class Compositor:
         info = RigFocalInfo()
         _chk(load().ms_refine_rig_focals(self._ctx, marr, mcnt, C.byref(prm), f.ctypes.data_as(C.POINTER(C.c_double)), out.ctypes.data_as(C.POINTER(C.c_float)),
                                          C.byref(info), _stream()))
+        return f, out, _rig_focal_info(info)
+
+    def refine_rig_focals_lens(self, matches, params=None):
+        """ms_refine_rig_focals_lens: refine_rig_focals for lens contexts (and analytic ones, with the same bits) -> (focals (n,) float64, R (n, 3, 3) float32, info
+        dict).  Nothing is applied to the context."""
+        import numpy as np
+        marr, mcnt = _match_array(matches)
+        prm = params if params is not None else rig_focal_default_params()
+        f = np.empty(self.n, np.float64); out = np.empty((self.n, 3, 3), np.float32)
+        info = RigFocalInfo()
+        _chk(load().ms_refine_rig_focals_lens(self._ctx, marr, mcnt, C.byref(prm), f.ctypes.data_as(C.POINTER(C.c_double)), out.ctypes.data_as(C.POINTER(C.c_float)),
+                                              C.byref(info), _stream()))
         return f, out, _rig_focal_info(info)
 
     def build_maps(self):
