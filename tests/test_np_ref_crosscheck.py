@@ -198,7 +198,7 @@ def _config_rois(oracle):
 
 
 def test_resize_axis_exact_float_quotient_is_the_integer_quotient(oracle):
-    """compositor.hip resize_axis_exact: while t * (n - 1) < 2^23, (int)((float)x * (float)(n - 1) / (float)t) == x * (n - 1) / t for every
+    """mesh_maps.hip resize_axis_exact: while t * (n - 1) < 2^23, (int)((float)x * (float)(n - 1) / (float)t) == x * (n - 1) / t for every
     0 <= x < t.  numpy's fp32 division is correctly rounded, as the build's is (-fhip-fp32-correctly-rounded-divide-sqrt).  Exhaustive over x for
     every (n, t) of the shipped configurations (10 x 10 and 40 x 40 meshes to every ROI size, then the half-resolution cell means back to it),
     then random pairs up to the boundary."""

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import np_ref
 import synth
 from helpers import host, make_rig, to_dev
 
@@ -224,6 +225,110 @@ def test_set_meshes_all_views_in_two_launches(ms, cuda, oracle, rig, nm):
         plain, _, _ = make_rig(ms, "mini4")
         plain.set_meshes([synth.mesh(50, 40, 5, 5)] * 4)          # a context without enable_cpw
     comp.close(); ref.close()
+
+
+def _cpw_rig(ms, name):
+    """(compositor, view count, view ROIs) with enable_cpw: a synth rig, or "tiny" -- four 40 x 30 sources on a 64 x 32 panorama, whose views are smaller than one
+    64 x 16 block of the mesh kernels."""
+    if name != "tiny":
+        comp, cfg, _ = make_rig(ms, name, enable_cpw=True)
+        n = cfg["n"]
+    else:
+        n, w, h, out = 4, 40, 30, (64, 32)
+        comp = ms.Compositor(n, (w, h), ms.PROJ_SPHERICAL, synth.warp_scale(out[0]), num_bands=3, enable_cpw=True, out_size=out)
+        for i in range(n):
+            comp.set_camera(i, *synth.camera(n, w, h, 110.0, i))
+        comp.build_maps(); comp.build_masks(1); comp.init_blender()
+    return comp, n, [comp.view_geom(i).roi for i in range(n)]
+
+
+def _assert_mesh_maps(comp, rois, current, tag):
+    """the maps of every view in `current` ({view: (mesh_x, mesh_y)}) against numpy's convertMeshesToMap, bit for bit, holes included"""
+    for i, (mx, my) in current.items():
+        got = [host(t) for t in comp.mesh_maps(i)]
+        want = np_ref.convert_mesh_to_map(mx, my, rois[i].width, rois[i].height)
+        assert np.array_equal(got[0], want[0], equal_nan=True) and np.array_equal(got[1], want[1], equal_nan=True), (tag, i)
+
+
+def test_mesh_updates_ping_pong_per_view(ms, cuda):
+    """The accumulators an update adds into are zero on entry whatever came before: the same view three times running, two views of different size in turn, and
+    batched calls with a per-view call of a third view between them.  After every call every view updated so far equals numpy."""
+    comp, n, rois = _cpw_rig(ms, "mini6")
+    size = lambda i: (rois[i].width, rois[i].height)
+    a = 0
+    b = next(i for i in range(n) if size(i) != size(a))
+    c = next(i for i in range(n) if i not in (a, b))
+    current, step = {}, [0]
+    amps = (6.0, 25.0, 3.0, 11.0, 25.0, 4.0, 9.0, 25.0, 5.0, 13.0)      # 25: pixels land outside the scatter kernel's LDS window
+
+    def mesh_of(i):
+        k = step[0]; step[0] += 1
+        return synth.mesh(rois[i].width, rois[i].height, 9, 11, phase=0.3 * i + 0.7 * k, amp=amps[k % len(amps)])
+
+    def single(i):
+        current[i] = mesh_of(i)
+        comp.set_mesh(i, *current[i])
+        _assert_mesh_maps(comp, rois, current, ("set_mesh", i, step[0]))
+
+    def batched():
+        k = step[0]; step[0] += 1
+        meshes = [synth.mesh(rois[i].width, rois[i].height, 9, 11, phase=0.3 * i + 0.7 * k, amp=amps[k % len(amps)]) for i in range(n)]
+        comp.set_meshes(meshes)
+        current.update(enumerate(meshes))
+        _assert_mesh_maps(comp, rois, current, ("set_meshes", step[0]))
+    for i in (a, a, a, a, b, a, b):
+        single(i)
+    batched(); single(c); batched()
+    comp.close()
+
+
+@pytest.mark.parametrize("rig", ["tiny", "mini4"])
+@pytest.mark.parametrize("route", ["set_mesh", "set_meshes", "alternating"])
+def test_mesh_size_changes(ms, cuda, rig, route):
+    """A larger vertex mesh regrows the updater's scratch and staging, a smaller one reuses them: 5x5 -> 12x9 -> 5x5 -> 40x40 -> 7x13 through either call and
+    through both in turn, every result equal to numpy."""
+    comp, n, rois = _cpw_rig(ms, rig)
+    for k, nm in enumerate([(5, 5), (12, 9), (5, 5), (40, 40), (7, 13)]):
+        meshes = [synth.mesh(rois[i].width, rois[i].height, nm[0], nm[1], phase=0.4 * i + 1.1 * k, amp=2.0 + 3.0 * k) for i in range(n)]
+        if route == "set_meshes" or (route == "alternating" and k % 2 == 1):
+            comp.set_meshes(meshes)
+        else:
+            for i in range(n):
+                comp.set_mesh(i, *meshes[i])
+        _assert_mesh_maps(comp, rois, dict(enumerate(meshes)), (k, nm))
+    comp.close()
+
+
+@pytest.mark.parametrize("rig", ["tiny", "mini4"])
+def test_mesh_displacement_is_the_maximum_of_the_maps(ms, cuda, rig):
+    """ms_get_mesh_displacement after each kind of update: the fp32 maximum of |map - identity| over the non-NaN entries of the maps read back, exactly."""
+    comp, n, rois = _cpw_rig(ms, rig)
+
+    def check(tag):
+        for i in range(n):
+            gx, gy = [host(t) for t in comp.mesh_maps(i)]
+            yy, xx = np.mgrid[0:rois[i].height, 0:rois[i].width].astype(np.float32)
+            d = np.concatenate([np.abs(gx - xx).ravel(), np.abs(gy - yy).ravel()])
+            d = d[~np.isnan(d)]
+            assert d.dtype == np.float32
+            want = d.max() if d.size else np.float32(0)
+            assert np.float32(comp.mesh_displacement(i)) == want, (tag, i)
+    meshes = [synth.mesh(rois[i].width, rois[i].height, 7, 9, phase=0.5 * i, amp=6.0 + i) for i in range(n)]
+    for i in range(n):
+        comp.set_mesh(i, *meshes[i])
+    check("set_mesh")
+    comp.set_meshes([synth.mesh(rois[i].width, rois[i].height, 7, 9, phase=0.5 * i + 1.3, amp=25.0 - 2 * i) for i in range(n)])
+    check("set_meshes")
+    rng = np.random.default_rng(7)
+    for i in range(n):
+        yy, xx = np.mgrid[0:rois[i].height, 0:rois[i].width].astype(np.float32)
+        xm = xx + rng.uniform(-9, 9, xx.shape).astype(np.float32)
+        ym = yy + rng.uniform(-5, 5, yy.shape).astype(np.float32)
+        xm[rng.random(xx.shape) < 0.1] = np.nan                      # holes, as convertMeshesToMap leaves them
+        ym[1::3, ::2] = np.nan
+        comp.set_mesh_maps(i, to_dev(xm), to_dev(ym))
+    check("set_mesh_maps")
+    comp.close()
 
 
 @pytest.mark.parametrize("batched", [True, False])

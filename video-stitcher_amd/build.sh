@@ -8,9 +8,12 @@ mkdir -p ../build
 # a change of flags (e.g. a -DMS_DEV_KNOBS developer build before, the production flags now) rebuilds every object
 if [ "$(cat ../build/flags.txt 2>/dev/null)" != "$FLAGS" ]; then rm -f ../build/*.o; echo "$FLAGS" > ../build/flags.txt; fi
 newest_hdr=$(ls -t *.hpp *.inc ../../include/ms_stitch.h ../../include/ms_dist.h | head -1)
+UNITS="prims.hip compositor.hip mesh_maps.hip mesh_solver.hip matcher.hip features.hip calib.hip lens.hip rig.hip rig_focal.hip rig_lens.hip seam_dp.hip pair_match.hip api.cpp geometry.cpp dist.cpp"
 pids=()
-for f in prims.hip compositor.hip mesh_solver.hip matcher.hip features.hip calib.hip lens.hip rig.hip rig_focal.hip rig_lens.hip seam_dp.hip pair_match.hip api.cpp geometry.cpp dist.cpp; do
+objs=()
+for f in $UNITS; do
   o=../build/${f%.*}.o
+  objs+=("$o")
   if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ "$newest_hdr" -nt "$o" ]; then
     $HIPCC $FLAGS -x hip -c "$f" -o "$o" & pids+=($!)
   fi
@@ -21,7 +24,7 @@ if [ -f /opt/rocm/include/rccl/rccl.h ] && { [ ! -f ../build/rccl_abi.ok ] || [ 
   touch ../build/rccl_abi.ok
 fi
 for p in "${pids[@]:-}"; do [ -n "$p" ] && { wait "$p" || { echo "compile failed" >&2; exit 1; }; }; done
-$HIPCC --offload-arch=gfx950 -shared -fPIC -o ../libmsstitch.so ../build/prims.o ../build/compositor.o ../build/mesh_solver.o ../build/matcher.o ../build/features.o ../build/calib.o ../build/lens.o ../build/rig.o ../build/rig_focal.o ../build/rig_lens.o ../build/seam_dp.o ../build/pair_match.o ../build/api.o ../build/geometry.o ../build/dist.o -ldl -lrt
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o ../libmsstitch.so "${objs[@]}" -ldl -lrt
 # C++ host pipeline over the C-ABI (thread / queue graph of the reference's timed.cpp); host code only, links the library above
 if [ ! -f ../stitch_app ] || [ ../host/stitch_app.cpp -nt ../stitch_app ] || [ ../shim/ms_shim.hpp -nt ../stitch_app ] || [ ../../include/ms_stitch.h -nt ../stitch_app ]; then
   $HIPCC -O2 -std=c++17 -Wall -Wno-unused-result -pthread ../host/stitch_app.cpp -I../../include -L.. -lmsstitch -Wl,-rpath,'$ORIGIN' -o ../stitch_app

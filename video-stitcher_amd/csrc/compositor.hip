@@ -1382,247 +1382,6 @@ __global__ void __launch_bounds__(64) k_subset_views(const ViewDesc *__restrict_
     out[v] = d;
 }
 
-// CPW mesh -> backward map: scatter-average (APP/meshwarper.cpp:859-875)
-__global__ void __launch_bounds__(256) k_mesh_scatter(const float *__restrict__ bx, const float *__restrict__ by, int pitch, int rows, int cols,
-                                                      float *sx, float *sy, float *cnt, int hw, int hh)
-{
-    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
-    if (x >= cols || y >= rows) return;
-    const float fx = bx[(size_t)y * pitch + x], fy = by[(size_t)y * pitch + x];
-    if (!(fx > -2147483648.f && fx < 2147483648.f && fy > -2147483648.f && fy < 2147483648.f)) return;
-    const int x_ = (int)fx / 2, y_ = (int)fy / 2;
-    if (x_ >= 0 && y_ >= 0 && x_ < hw && y_ < hh) {
-        atomicAdd(&sx[(size_t)y_ * hw + x_], (float)x);   // integer-valued partial sums: order-independent while < 2^24
-        atomicAdd(&sy[(size_t)y_ * hw + x_], (float)y);
-        atomicAdd(&cnt[(size_t)y_ * hw + x_], 1.f);
-    }
-}
-__global__ void __launch_bounds__(256) k_mesh_mean(float *sx, float *sy, const float *__restrict__ cnt, int n)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    sx[i] = sx[i] / cnt[i];     // 0/0 -> NaN hole, as the reference (remap then yields 0)
-    sy[i] = sy[i] / cnt[i];
-}
-
-// custom_resize (APP/resize.cu:9-27) of one output element, the taps fetched through `at(row, col)`: the same expression tree as
-// k_custom_resize (prims.hip), so a fused consumer sees the bits the materialised map would hold
-// one axis of custom_resize: cell index i = x * (n - 1) / t (integer division) and fraction ((float)x * (float)(n - 1) / (float)t) - (float)i.
-// While t * (n - 1) < 2^23 the float quotient q is the correctly rounded value of an exact ratio whose distance to the next integer is at
-// least 1/t > ulp(q)/2, so (int)q IS the integer quotient and the ~40-instruction integer division disappears (`exact` says which case).
-__device__ __forceinline__ void resize_axis(int x, int n, int t, bool exact, int &i, float &frac)
-{
-    const float q = ((float)x) * (float)(n - 1) / (float)t;
-    i = exact ? (int)q : x * (n - 1) / t;
-    frac = q - (float)i;
-}
-__device__ __forceinline__ bool resize_axis_exact(int n, int t) { return (long long)t * (n - 1) < (1ll << 23); }
-template <class At>
-__device__ __forceinline__ float custom_resize_at(int tx, int ty, int cols, int rows, int x, int y, At at)
-{
-    int left, top;
-    float uu, vv;
-    resize_axis(x, cols, tx, resize_axis_exact(cols, tx), left, uu);
-    resize_axis(y, rows, ty, resize_axis_exact(rows, ty), top, vv);
-    float r = ((1.f - uu) * (1.f - vv)) * at(top, left);
-    r = __builtin_fmaf(uu * (1.f - vv), at(top, left + 1), r);
-    r = __builtin_fmaf((1.f - uu) * vv, at(top + 1, left), r);
-    r = __builtin_fmaf(uu * vv, at(top + 1, left + 1), r);
-    return r;
-}
-// convertMeshesToMap, first half in one launch (meshwarper.cpp:838-869): vertex mesh -> per-pixel forward position (custom_resize, not
-// materialised) -> scatter into the half-resolution sums.  Also clears what the previous update dirtied in the other accumulator
-// (ping-pong: no memset call between updates) and the displacement word of this update.
-constexpr int MESH_SR = 4;                         // rows per lane: a workgroup scatters a 64 x 16 pixel block
-constexpr int MESH_WW = 48, MESH_WH = 20, MESH_WMX = 6, MESH_WMY = 4;   // LDS window (half-resolution cells) around where the block's first pixel lands
-// one view's update: what both launches of convertMeshesToMap need (ms_set_meshes runs all views of a context in ONE pair of launches, blockIdx.z = view)
-struct MeshJob {
-    const float *smx, *smy;                    // N x M vertex mesh (device)
-    unsigned long long *ax, *ay;               // half-resolution accumulators of this update
-    unsigned long long *clear; size_t n_clear; // what the previous update dirtied in the other accumulator
-    unsigned *disp_word;
-    float *dx, *dy;                            // dense maps being written (the view's inactive buffer)
-    int aw, ah, hw, hh, pitch, tiles_x, n_tiles;
-};
-struct MeshJobs { MeshJob j[MAX_VIEWS]; };
-__device__ __forceinline__ void mesh_expand_scatter_block(const MeshJob &J, int N, int M, int bx, int by, int gx, int gy)
-{
-    const float *__restrict__ smx = J.smx, *__restrict__ smy = J.smy;
-    const int aw = J.aw, ah = J.ah, hw = J.hw, hh = J.hh;
-    unsigned long long *ax = J.ax, *ay = J.ay, *__restrict__ clear = J.clear;
-    const size_t n_clear = J.n_clear;
-    unsigned *disp_word = J.disp_word;
-    // The pixels of a block land in a compact patch of the half-resolution grid (the mesh is a smooth deformation), and four of them share a
-    // cell: accumulate the patch in LDS and send one pair of global atomics per touched cell instead of one per pixel (device-scope atomics
-    // were 60 % of the update's GPU time); pixels landing outside the window go to memory directly.
-    __shared__ unsigned long long wx[MESH_WH * MESH_WW], wy[MESH_WH * MESH_WW];
-    const int lt = threadIdx.y * 64 + threadIdx.x;
-    const size_t tid = ((size_t)by * gx + bx) * 256 + lt, nthreads = (size_t)gx * gy * 256;
-    for (size_t k = tid; k < n_clear; k += nthreads) clear[k] = 0ull;
-    if (tid == 0) *disp_word = 0u;
-    for (int k = lt; k < MESH_WH * MESH_WW; k += 256) { wx[k] = 0ull; wy[k] = 0ull; }
-    const bool ex = resize_axis_exact(M, aw), ey = resize_axis_exact(N, ah);
-    auto forward = [&](int x, int y, float &fx, float &fy) {          // custom_resize of both vertex maps at (x, y): the expression tree of custom_resize_at
-        int left, top;
-        float uu, vv;
-        resize_axis(x, M, aw, ex, left, uu);
-        resize_axis(y, N, ah, ey, top, vv);
-        const float w00 = (1.f - uu) * (1.f - vv), w01 = uu * (1.f - vv), w10 = (1.f - uu) * vv, w11 = uu * vv;
-        const int i0 = top * M + left, i1 = i0 + M;
-        fx = w00 * smx[i0]; fy = w00 * smy[i0];
-        fx = __builtin_fmaf(w01, smx[i0 + 1], fx); fy = __builtin_fmaf(w01, smy[i0 + 1], fy);
-        fx = __builtin_fmaf(w10, smx[i1], fx);     fy = __builtin_fmaf(w10, smy[i1], fy);
-        fx = __builtin_fmaf(w11, smx[i1 + 1], fx); fy = __builtin_fmaf(w11, smy[i1 + 1], fy);
-    };
-    auto finite_i32 = [](float v) { return v > -2147483648.f && v < 2147483648.f; };
-    float ox, oy;
-    forward(bx * 64, by * (4 * MESH_SR), ox, oy);          // the same for every lane: the window's anchor
-    const int wx0 = (finite_i32(ox) ? (int)ox / 2 : 0) - MESH_WMX, wy0 = (finite_i32(oy) ? (int)oy / 2 : 0) - MESH_WMY;
-    __syncthreads();
-    const int x = bx * 64 + threadIdx.x;
-#pragma unroll
-    for (int r = 0; r < MESH_SR; ++r) {
-        const int y = by * (4 * MESH_SR) + r * 4 + threadIdx.y;
-        if (x >= aw || y >= ah) continue;
-        float fx, fy;
-        forward(x, y, fx, fy);
-        if (!(finite_i32(fx) && finite_i32(fy))) continue;
-        const int x_ = (int)fx / 2, y_ = (int)fy / 2;
-        if (x_ >= 0 && y_ >= 0 && x_ < hw && y_ < hh) {
-            // sum_x += x, sum_y += y, set_values++ as two 64-bit integer adds: [count : 24 | sum : 40].  The reference's float sums are integers,
-            // exact (and therefore order-independent) below 2^24, where (float)sum is the very same value
-            const unsigned long long vx = (1ull << 40) | (unsigned long long)x, vy = (unsigned long long)y;
-            const int cx = x_ - wx0, cy = y_ - wy0;
-            if ((unsigned)cx < (unsigned)MESH_WW && (unsigned)cy < (unsigned)MESH_WH) {
-                atomicAdd(&wx[cy * MESH_WW + cx], vx);
-                atomicAdd(&wy[cy * MESH_WW + cx], vy);
-            } else {
-                atomicAdd(&ax[(size_t)y_ * hw + x_], vx);
-                atomicAdd(&ay[(size_t)y_ * hw + x_], vy);
-            }
-        }
-    }
-    __syncthreads();
-    for (int k = lt; k < MESH_WH * MESH_WW; k += 256) {
-        const unsigned long long vx = wx[k];
-        if (vx == 0ull) continue;
-        const int cy = k / MESH_WW, cx = k - cy * MESH_WW;
-        const size_t g = (size_t)(wy0 + cy) * hw + (wx0 + cx);
-        atomicAdd(&ax[g], vx);
-        atomicAdd(&ay[g], wy[k]);
-    }
-}
-__global__ void __launch_bounds__(256) k_mesh_expand_scatter(const float *__restrict__ smx, const float *__restrict__ smy, int N, int M, int aw, int ah,
-                                                             unsigned long long *ax, unsigned long long *ay, int hw, int hh,
-                                                             unsigned long long *__restrict__ clear, size_t n_clear, unsigned *disp_word)
-{
-    MeshJob J{smx, smy, ax, ay, clear, n_clear, disp_word, nullptr, nullptr, aw, ah, hw, hh, 0, 0, 0};
-    mesh_expand_scatter_block(J, N, M, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.x, (int)gridDim.y);
-}
-__global__ void __launch_bounds__(256) k_mesh_expand_scatter_all(MeshJobs T, int N, int M)
-{
-    const MeshJob &J = T.j[blockIdx.z];
-    const int gx = (J.aw + 63) / 64, gy = (J.ah + 4 * MESH_SR - 1) / (4 * MESH_SR);
-    if ((int)blockIdx.x >= gx || (int)blockIdx.y >= gy) return;          // (the grid is sized for the largest view)
-    mesh_expand_scatter_block(J, N, M, (int)blockIdx.x, (int)blockIdx.y, gx, gy);
-}
-// second half (meshwarper.cpp:870-883): mean (0/0 -> NaN hole) + custom_resize back to the view size for both maps, and the largest
-// displacement of the new maps (see k_mesh_disp)
-constexpr int MESH_TR = 4;                      // output rows per lane: a workgroup step is a 64 x 16 pixel tile (64 x 4 until round 5: the straddling view's 9 420 tiles were 18 serial
-                                                // steps -- each a chain of cell loads, two barriers, stores -- for each of its 512 workgroups: 54 us; four times fewer, fatter steps)
-constexpr int MESH_FW = 72, MESH_FH = 4 * MESH_TR / 2 + 4;       // LDS footprint (cells) of a 64 x 16 output block: <= 64 * (hw - 1) / aw + 2 columns, likewise rows
-__device__ __forceinline__ void mesh_mean_resize_blocks(const MeshJob &J, int first_tile, int tile_stride)
-{
-    const unsigned long long *__restrict__ ax = J.ax, *__restrict__ ay = J.ay;
-    const int hw = J.hw, hh = J.hh, pitch = J.pitch, aw = J.aw, ah = J.ah, tiles_x = J.tiles_x, n_tiles = J.n_tiles;
-    float *__restrict__ dx = J.dx, *__restrict__ dy = J.dy;
-    unsigned *disp_word = J.disp_word;
-    __shared__ float mxs[MESH_FH][MESH_FW], mys[MESH_FH][MESH_FW];
-    __shared__ float wmax[4];
-    const bool ex = resize_axis_exact(hw, aw), ey = resize_axis_exact(hh, ah);
-    constexpr unsigned long long SUM = (1ull << 40) - 1;
-    float d = 0.f;
-    // a workgroup walks 64 x 16 output tiles grid-stride: one atomic on the displacement word per workgroup, not per tile (thousands of
-    // same-address atomics serialise: they were most of this kernel's time)
-    for (int tile = first_tile; tile < n_tiles; tile += tile_stride) {
-        const int tyi = tile / tiles_x, txi = tile - tyi * tiles_x;
-        const int x = txi * 64 + threadIdx.x;
-        // footprint of the tile in the half-resolution maps
-        const int bx0 = txi * 64, by0 = tyi * (4 * MESH_TR), bx1 = min(bx0 + 63, aw - 1), by1 = min(by0 + 4 * MESH_TR - 1, ah - 1);
-        int c0, c1, r0, r1;
-        float t;
-        resize_axis(bx0, hw, aw, ex, c0, t); resize_axis(bx1, hw, aw, ex, c1, t);
-        resize_axis(by0, hh, ah, ey, r0, t); resize_axis(by1, hh, ah, ey, r1, t);
-        const int fw = c1 - c0 + 2, fh = r1 - r0 + 2;
-        const bool staged = fw <= MESH_FW && fh <= MESH_FH;             // (always for hw = aw / 2; the direct path keeps odd geometries correct)
-        if (staged) {
-            for (int k = threadIdx.y * 64 + threadIdx.x; k < fw * fh; k += 256) {
-                const int rr = k / fw, cc = k - rr * fw, r = r0 + rr, c = c0 + cc;
-                float vx = 0.f, vy = 0.f;
-                if (r < hh && c < hw) {            // mean = sum / count; 0 / 0 -> NaN hole, as the reference (remap then yields 0)
-                    const unsigned long long a = ax[(size_t)r * hw + c];
-                    const float n = (float)(a >> 40);
-                    vx = (float)(a & SUM) / n;
-                    vy = (float)(ay[(size_t)r * hw + c] & SUM) / n;
-                }
-                mxs[rr][cc] = vx; mys[rr][cc] = vy;
-            }
-            __syncthreads();
-        }
-#pragma unroll
-        for (int tr = 0; tr < MESH_TR; ++tr) {
-        const int y = by0 + 4 * tr + (int)threadIdx.y;
-        if (x < aw && y < ah) {
-            int left, top;
-            float uu, vv;
-            resize_axis(x, hw, aw, ex, left, uu);
-            resize_axis(y, hh, ah, ey, top, vv);
-            const float w00 = (1.f - uu) * (1.f - vv), w01 = uu * (1.f - vv), w10 = (1.f - uu) * vv, w11 = uu * vv;
-            float mx, my;
-            if (staged) {
-                const int cc = left - c0, rr = top - r0;
-                mx = w00 * mxs[rr][cc];                            my = w00 * mys[rr][cc];
-                mx = __builtin_fmaf(w01, mxs[rr][cc + 1], mx);     my = __builtin_fmaf(w01, mys[rr][cc + 1], my);
-                mx = __builtin_fmaf(w10, mxs[rr + 1][cc], mx);     my = __builtin_fmaf(w10, mys[rr + 1][cc], my);
-                mx = __builtin_fmaf(w11, mxs[rr + 1][cc + 1], mx); my = __builtin_fmaf(w11, mys[rr + 1][cc + 1], my);
-            } else {
-                mx = custom_resize_at(aw, ah, hw, hh, x, y, [&](int r, int c) { const unsigned long long v = ax[(size_t)r * hw + c]; return (float)(v & SUM) / (float)(v >> 40); });
-                my = custom_resize_at(aw, ah, hw, hh, x, y, [&](int r, int c) { return (float)(ay[(size_t)r * hw + c] & SUM) / (float)(ax[(size_t)r * hw + c] >> 40); });
-            }
-            dx[(size_t)y * pitch + x] = mx;
-            dy[(size_t)y * pitch + x] = my;
-            const float a = fabsf(mx - (float)x), b = fabsf(my - (float)y);
-            d = fmaxf(d, fmaxf(a == a ? a : 0.f, b == b ? b : 0.f));
-        }
-        }
-        __syncthreads();                                                 // the staging arrays are rewritten by the next tile
-    }
-    for (int o = 32; o > 0; o >>= 1) d = fmaxf(d, __shfl_xor(d, o));
-    if (threadIdx.x == 0) wmax[threadIdx.y] = d;
-    __syncthreads();
-    if (threadIdx.x == 0 && threadIdx.y == 0) {
-        d = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
-        if (d > 0.f) atomicMax(disp_word, __float_as_uint(d));
-    }
-}
-__global__ void __launch_bounds__(256) k_mesh_mean_resize(const unsigned long long *__restrict__ ax, const unsigned long long *__restrict__ ay, int hw, int hh,
-                                                          float *__restrict__ dx, float *__restrict__ dy, int pitch, int aw, int ah, int tiles_x, int n_tiles, unsigned *disp_word)
-{
-    MeshJob J{nullptr, nullptr, const_cast<unsigned long long *>(ax), const_cast<unsigned long long *>(ay), nullptr, 0, disp_word, dx, dy, aw, ah, hw, hh, pitch, tiles_x, n_tiles};
-    mesh_mean_resize_blocks(J, (int)blockIdx.x, (int)gridDim.x);
-}
-__global__ void __launch_bounds__(256) k_mesh_mean_resize_all(MeshJobs T)
-{
-    mesh_mean_resize_blocks(T.j[blockIdx.y], (int)blockIdx.x, (int)gridDim.x);
-}
-
-static int ctx_check_view(const ms_ctx *c, int v)
-{
-    if (!c) return fail(MS_ERR_INVALID, "null context");
-    if (v < 0 || v >= c->N) return fail(MS_ERR_INVALID, "view index %d out of range [0,%d)", v, c->N);
-    return MS_OK;
-}
-
 static ms_image view_map_image(const ms_ctx *c, int v, int which)
 {
     ms_image m;
@@ -2051,8 +1810,8 @@ void ms_destroy(ms_ctx *c)
     if (c->tab_ready) (void)hipEventDestroy(c->tab_ready);
     if (c->subset_built) (void)hipEventDestroy(c->subset_built);
     if (c->gain_ev) (void)hipEventDestroy(c->gain_ev);
-    if (c->mesh_stage) (void)hipHostFree(c->mesh_stage);
-    for (hipEvent_t e : c->mesh_stage_ev) if (e) (void)hipEventDestroy(e);
+    if (c->mesh_upd.stage) (void)hipHostFree(c->mesh_upd.stage);
+    for (hipEvent_t e : c->mesh_upd.stage_ev) if (e) (void)hipEventDestroy(e);
     delete c;
 }
 
@@ -2797,273 +2556,6 @@ int ms_init_feather(ms_ctx *c, float sharpness, ms_stream stream)
     return ms_init_blender(c, stream);
 }
 
-// max over the view of |x_mesh - x|, |y_mesh - y| (NaN = hole of convertMeshesToMap: samples nothing, ignored); non-negative floats
-// order like their bit patterns, so one atomicMax on the bits reduces the launch
-__global__ void __launch_bounds__(256) k_mesh_disp(const float *__restrict__ mx, const float *__restrict__ my, int pitch, int ah, int aw, unsigned *out)
-{
-    float d = 0.f;
-    for (int y = blockIdx.x; y < ah; y += gridDim.x)            // a block walks rows, grid-stride: few atomics on the one result word
-        for (int x = threadIdx.x; x < aw; x += 256) {
-            const float a = fabsf(mx[(size_t)y * pitch + x] - (float)x), b = fabsf(my[(size_t)y * pitch + x] - (float)y);
-            d = fmaxf(d, fmaxf(a == a ? a : 0.f, b == b ? b : 0.f));
-        }
-    for (int o = 32; o > 0; o >>= 1) d = fmaxf(d, __shfl_xor(d, o));
-    if ((threadIdx.x & 63) == 0 && d > 0.f) atomicMax(out, __float_as_uint(d));
-}
-static int measure_mesh_disp(ms_ctx *c, int view, int tgt, hipStream_t st)
-{
-    if (!c->disp_dev.p) {
-        if (int e = c->disp_dev.alloc(2 * MAX_VIEWS * sizeof(unsigned))) return e;
-        MS_HIP(hipMemsetAsync(c->disp_dev.p, 0xff, 2 * MAX_VIEWS * sizeof(unsigned), st));      // "unbounded" until measured
-    }
-    const int aw = c->roi[view].width, ah = c->roi[view].height;
-    const float *base = (const float *)c->mesh[tgt].p + c->mesh_off[view];
-    unsigned *word = (unsigned *)c->disp_dev.p + 2 * view + tgt;
-    MS_HIP(hipMemsetAsync(word, 0, sizeof(unsigned), st));
-    k_mesh_disp<<<std::min(ah, 128), 256, 0, st>>>(base, base + (size_t)ah * c->map_pitch[view], c->map_pitch[view], ah, aw, word);
-    MS_LAUNCH_CHECK();
-    return MS_OK;          // (no host synchronisation: the stage-1 kernel reads the word on the device, ms_get_mesh_displacement waits on mesh_ready)
-}
-
-// ---- CPW mesh maps ------------------------------------------------------------------------------
-static ms_image mesh_image(const ms_ctx *c, int buf, int v, int which)
-{
-    const int ah = c->roi[v].height, aw = c->roi[v].width;
-    float *base = (float *)c->mesh[buf].p + c->mesh_off[v] + (which ? (size_t)ah * c->map_pitch[v] : 0);
-    return ms_image{base, (size_t)c->map_pitch[v] * sizeof(float), aw, ah, MS_32FC1};
-}
-
-// Callers hold mesh_update_mu (one update at a time).  mesh_mu is taken here only around the bookkeeping ms_stitch shares: ms_stitch holds it from
-// picking the active buffers up to recording last_stitch, so `last_stitch` seen here covers every stitch that may still read the inactive buffer.
-static hipEvent_t mesh_ready_event(ms_ctx *c, int view) { return c->mesh_ready_via_chain[view] ? c->mesh_chain : c->mesh_ready[view]; }      // (caller holds mesh_mu or is the only updater)
-static int mesh_begin_update(ms_ctx *c, int view, int *target, hipStream_t st, bool enqueue_waits = true)
-{
-    if (!c->blender_ready || !c->cfg.enable_cpw) return fail(MS_ERR_STATE, "mesh update needs enable_cpw and ms_init_blender");
-    std::lock_guard<std::mutex> lk(c->mesh_mu);
-    *target = c->mesh_set[view] ? 1 - c->mesh_active[view] : c->mesh_active[view];
-    if (!c->mesh_ready[view]) MS_HIP(hipEventCreateWithFlags(&c->mesh_ready[view], hipEventDisableTiming));
-    if (!c->mesh_chain) MS_HIP(hipEventCreateWithFlags(&c->mesh_chain, hipEventDisableTiming));
-    // the inactive buffer may still be read by a stitch enqueued before the previous swap: the update waits for it ON THE GPU
-    // (the reference releases its mutex before the async remap finishes, timed.cpp:98-103); no host synchronisation anywhere
-    if (enqueue_waits) {      // (ms_set_meshes: once for all views of the call)
-        if (c->stitch_pending) MS_HIP(hipStreamWaitEvent(st, c->last_stitch, 0));
-        if (c->mesh_chain_set) MS_HIP(hipStreamWaitEvent(st, c->mesh_chain, 0));
-    }
-    return MS_OK;
-}
-// one view's update: its own event + the chain, both recorded BEFORE the view is published (ms_set_meshes publishes all its views itself, behind one record of the chain)
-static int mesh_end_update(ms_ctx *c, int view, int tgt, hipStream_t st, bool measure = true)
-{
-    if (measure) if (int e = measure_mesh_disp(c, view, tgt, st)) return e;
-    std::lock_guard<std::mutex> lk(c->mesh_mu);
-    MS_HIP(hipEventRecord(c->mesh_ready[view], st));
-    MS_HIP(hipEventRecord(c->mesh_chain, st));
-    c->mesh_ready_via_chain[view] = false;
-    c->mesh_chain_set = true;
-    c->mesh_wait[view] = true;
-    c->mesh_active[view] = tgt;
-    c->mesh_set[view] = true;
-    return MS_OK;
-}
-
-int ms_set_mesh_maps(ms_ctx *c, int view, const ms_image *xm, const ms_image *ym, ms_stream stream)
-{
-    if (int e = ctx_check_view(c, view)) return e;
-    MS_CHECK(xm && ym && xm->data && ym->data, "ms_set_mesh_maps: null image");
-    std::lock_guard<std::mutex> lk(c->mesh_update_mu);
-    int tgt;
-    hipStream_t st = as_stream(stream);
-    const int aw = c->roi[view].width, ah = c->roi[view].height;
-    MS_CHECK(xm->rows == ah && xm->cols == aw && ym->rows == ah && ym->cols == aw && xm->type == MS_32FC1 && ym->type == MS_32FC1,
-             "ms_set_mesh_maps: maps must be 32FC1 %dx%d", aw, ah);
-    if (int e = mesh_begin_update(c, view, &tgt, st)) return e;
-    ms_image dx = mesh_image(c, tgt, view, 0), dy = mesh_image(c, tgt, view, 1);
-    MS_HIP(hipMemcpy2DAsync(dx.data, dx.step, xm->data, xm->step, (size_t)aw * 4, ah, hipMemcpyDeviceToDevice, st));
-    MS_HIP(hipMemcpy2DAsync(dy.data, dy.step, ym->data, ym->step, (size_t)aw * 4, ah, hipMemcpyDeviceToDevice, st));
-    return mesh_end_update(c, view, tgt, st);
-}
-
-int ms_set_mesh(ms_ctx *c, int view, const float *mesh_x, const float *mesh_y, int N, int M, ms_stream stream)
-{
-    if (int e = ctx_check_view(c, view)) return e;
-    MS_CHECK(mesh_x && mesh_y && N >= 2 && M >= 2, "ms_set_mesh: need an N x M (>= 2x2) vertex mesh");
-    std::lock_guard<std::mutex> lk(c->mesh_update_mu);       // (ms_stitch never takes this one: the waits and allocations below cannot stall it)
-    int tgt;
-    hipStream_t st = as_stream(stream);
-    const int aw = c->roi[view].width, ah = c->roi[view].height, hw = aw / 2, hh = ah / 2;
-    MS_CHECK(hw >= 2 && hh >= 2, "ms_set_mesh: view too small");
-    MS_CHECK((long long)aw * ah < (1ll << 24) && aw < 65536 && ah < 65536, "ms_set_mesh: view %dx%d exceeds the scatter accumulators ([count:24 | sum:40])", aw, ah);
-    // scratch: vertex mesh x|y, then two half-resolution accumulators used in turn (the launch that fills one clears the other)
-    const size_t n_small = (size_t)N * M, n_half = (size_t)hw * hh;
-    size_t half_cap = 0;
-    for (int v = 0; v < c->N; ++v) half_cap = std::max(half_cap, (size_t)(c->roi[v].width / 2) * (c->roi[v].height / 2));
-    if (!c->mesh_tmp.p || c->mesh_small_cap < n_small || c->mesh_half_cap < half_cap || c->mesh_stage_floats < 2 * n_small) {   // first call or a larger mesh: drain earlier updates
-        if (c->mesh_chain_set) MS_HIP(hipEventSynchronize(c->mesh_chain));
-        const size_t bytes = 2 * n_small * sizeof(float) + 4 * half_cap * sizeof(unsigned long long) + 16;
-        if (int e = c->mesh_tmp.alloc(bytes)) return e;
-        MS_HIP(hipMemsetAsync(c->mesh_tmp.p, 0, bytes, st));      // on the update's own stream: a plain hipMemset runs on the NULL stream, asynchronously to the host, and non-blocking streams do not wait for it
-        c->mesh_small_cap = n_small; c->mesh_half_cap = half_cap; c->mesh_dirty = 0; c->mesh_parity = 0;
-        if (c->mesh_stage_floats < 2 * n_small) {
-            if (c->mesh_stage) (void)hipHostFree(c->mesh_stage);
-            c->mesh_stage = nullptr; c->mesh_stage_floats = 0;
-            MS_HIP(hipHostMalloc((void **)&c->mesh_stage, (ms_ctx::MESH_STAGE_GENS + 1) * (2 * n_small * sizeof(float) * MAX_VIEWS), hipHostMallocDefault));      // (the ring + ms_set_mesh's own generation behind it)
-            for (bool &b_ : c->mesh_stage_ev_set) b_ = false;
-            c->mesh_stage_gen = 0;
-            c->mesh_stage_floats = 2 * n_small;
-        }
-    }
-    if (!c->disp_dev.p) {
-        if (int e = c->disp_dev.alloc(2 * MAX_VIEWS * sizeof(unsigned))) return e;
-        MS_HIP(hipMemsetAsync(c->disp_dev.p, 0xff, 2 * MAX_VIEWS * sizeof(unsigned), st));      // "unbounded" until measured
-    }
-    if (int e = mesh_begin_update(c, view, &tgt, st)) return e;
-    float *sm_x = (float *)c->mesh_tmp.p, *sm_y = sm_x + n_small;
-    unsigned long long *acc0 = (unsigned long long *)(((uintptr_t)(sm_x + 2 * c->mesh_small_cap) + 7) & ~(uintptr_t)7);
-    unsigned long long *acc = acc0 + (size_t)c->mesh_parity * 2 * c->mesh_half_cap, *other = acc0 + (size_t)(1 - c->mesh_parity) * 2 * c->mesh_half_cap;
-    unsigned long long *ax = acc, *ay = acc + n_half;
-    // the caller's arrays may be freed right after return: stage them in pinned memory (one slot per view; a slot is reused only by
-    // the next update of the same view, whose copy of the previous one finished long before -- checked on its event)
-    bool slot_busy;
-    hipEvent_t busy_ev = nullptr;
-    { std::lock_guard<std::mutex> mk(c->mesh_mu); slot_busy = c->mesh_ready[view] && (c->mesh_wait[view] || c->mesh_set[view]); if (slot_busy) busy_ev = mesh_ready_event(c, view); }
-    if (slot_busy && busy_ev) MS_HIP(hipEventSynchronize(busy_ev));
-    // (generation MESH_STAGE_GENS, outside the ring ms_set_meshes walks: a batched call can never overwrite a slot whose single-view copy has not run yet -- ADVICE r05)
-    float *stg = c->mesh_stage + ((size_t)ms_ctx::MESH_STAGE_GENS * MAX_VIEWS + view) * c->mesh_stage_floats;
-    memcpy(stg, mesh_x, n_small * 4);
-    memcpy(stg + n_small, mesh_y, n_small * 4);
-    MS_HIP(hipMemcpyAsync(sm_x, stg, 2 * n_small * 4, hipMemcpyHostToDevice, st));
-    unsigned *word = (unsigned *)c->disp_dev.p + 2 * view + tgt;
-    const dim3 grid(div_up(aw, 64), div_up(ah, 4)), blk(64, 4);
-    k_mesh_expand_scatter<<<dim3(div_up(aw, 64), div_up(ah, 4 * MESH_SR)), blk, 0, st>>>(sm_x, sm_y, N, M, aw, ah, ax, ay, hw, hh, other, c->mesh_dirty, word);        // meshwarper.cpp:838-869
-    MS_LAUNCH_CHECK();
-    ms_image dx = mesh_image(c, tgt, view, 0), dy = mesh_image(c, tgt, view, 1);
-    const int tiles_x = div_up(aw, 64), n_tiles = tiles_x * div_up(ah, 4 * MESH_TR);
-    k_mesh_mean_resize<<<std::min(n_tiles, 1024), blk, 0, st>>>(ax, ay, hw, hh, (float *)dx.data, (float *)dy.data, c->map_pitch[view], aw, ah, tiles_x, n_tiles, word);   // :870-883
-    MS_LAUNCH_CHECK();
-    c->mesh_dirty = 2 * n_half;
-    c->mesh_parity ^= 1;
-    return mesh_end_update(c, view, tgt, st, false);
-}
-
-// MeshWarper::convertMeshesToMap as the reference calls it -- for ALL views at once (meshwarper.cpp:823-886 loops over the images): the same two kernels
-// with blockIdx.z / .y = view, i.e. two launches per recalibration instead of two per view.  The per-view launches are latency-bound (47 us each for a
-// 960 x 627 view): six views cost 0.3 ms of GPU time one after the other, about a third of that together.  Same arithmetic, bit-identical maps.
-// mesh_x / mesh_y: HOST, num_views meshes of N x M back to back.
-int ms_set_meshes(ms_ctx *c, const float *mesh_x, const float *mesh_y, int N, int M, ms_stream stream)
-{
-    if (!c) return fail(MS_ERR_INVALID, "null context");
-    MS_CHECK(mesh_x && mesh_y && N >= 2 && M >= 2, "ms_set_meshes: need N x M (>= 2x2) vertex meshes");
-    if (!c->blender_ready || !c->cfg.enable_cpw) return fail(MS_ERR_STATE, "ms_set_meshes needs enable_cpw and ms_init_blender");
-    std::lock_guard<std::mutex> lk(c->mesh_update_mu);
-    hipStream_t st = as_stream(stream);
-    const int NV = c->N;
-    const size_t n_small = (size_t)N * M;
-    std::vector<size_t> acc_off(NV + 1, 0);                  // 64-bit words: per view [ax | ay] x two parities
-    int max_aw = 0, max_ah = 0, max_tiles = 0;
-    for (int v = 0; v < NV; ++v) {
-        const int aw = c->roi[v].width, ah = c->roi[v].height, hw = aw / 2, hh = ah / 2;
-        MS_CHECK(hw >= 2 && hh >= 2, "ms_set_meshes: view %d too small", v);
-        MS_CHECK((long long)aw * ah < (1ll << 24) && aw < 65536 && ah < 65536, "ms_set_meshes: view %dx%d exceeds the scatter accumulators ([count:24 | sum:40])", aw, ah);
-        acc_off[v + 1] = acc_off[v] + 4 * (size_t)hw * hh;
-        max_aw = std::max(max_aw, aw); max_ah = std::max(max_ah, ah);
-        max_tiles = std::max(max_tiles, div_up(aw, 64) * div_up(ah, 4 * MESH_TR));
-    }
-    const size_t sm_floats = 2 * n_small * NV, sm_bytes = (sm_floats * sizeof(float) + 15) & ~(size_t)15;
-    if (!c->mesh_all.p || c->mesh_all_small != n_small || c->mesh_stage_floats < 2 * n_small) {      // first call or another mesh size: drain earlier updates, (re)allocate
-        if (c->mesh_chain_set) MS_HIP(hipEventSynchronize(c->mesh_chain));
-        const size_t bytes = sm_bytes + acc_off[NV] * sizeof(unsigned long long);
-        if (int e = c->mesh_all.alloc(bytes)) return e;
-        MS_HIP(hipMemsetAsync(c->mesh_all.p, 0, bytes, st));      // (stream-ordered: see ms_set_mesh)
-        c->mesh_all_small = n_small; c->mesh_all_parity = 0; c->mesh_all_dirty = false;
-        if (c->mesh_stage_floats < 2 * n_small) {
-            if (c->mesh_stage) (void)hipHostFree(c->mesh_stage);
-            c->mesh_stage = nullptr; c->mesh_stage_floats = 0;
-            MS_HIP(hipHostMalloc((void **)&c->mesh_stage, (ms_ctx::MESH_STAGE_GENS + 1) * (2 * n_small * sizeof(float) * MAX_VIEWS), hipHostMallocDefault));      // (the ring + ms_set_mesh's own generation behind it)
-            for (bool &b_ : c->mesh_stage_ev_set) b_ = false;
-            c->mesh_stage_gen = 0;
-            c->mesh_stage_floats = 2 * n_small;
-        }
-    }
-    if (!c->disp_dev.p) {
-        if (int e = c->disp_dev.alloc(2 * MAX_VIEWS * sizeof(unsigned))) return e;
-        MS_HIP(hipMemsetAsync(c->disp_dev.p, 0xff, 2 * MAX_VIEWS * sizeof(unsigned), st));
-    }
-    int tgt[MAX_VIEWS];
-    for (int v = 0; v < NV; ++v) if (int e = mesh_begin_update(c, v, &tgt[v], st, v == 0)) return e;
-    // stage the caller's arrays in pinned memory (the view's slot is free once its previous update's copy has run: checked on its event), one copy for all views
-    float *sm = (float *)c->mesh_all.p;
-    unsigned long long *acc0 = (unsigned long long *)((char *)c->mesh_all.p + sm_bytes);
-    MeshJobs T{};
-    const int p = c->mesh_all_parity;
-    // the staging generation this call fills: free once the copy of the call a ring ago has run (its own event, recorded right behind that copy).  Until round 5 the host waited
-    // here for the PREVIOUS update, twelve events were recorded and as many waits enqueued per call: a recalibration every 60 frames cost config 3 10.5 % of its frame rate with
-    // 4 % of GPU work in it; now 4.5 % (same-box A/B 22.8 k -> 24.3 k frames/s, profiles/r05_experiments.txt)
-    const int gen = c->mesh_stage_gen;
-    if (c->mesh_stage_ev_set[gen]) MS_HIP(hipEventSynchronize(c->mesh_stage_ev[gen]));      // (blocks only when the caller is a whole ring of updates ahead of the GPU)
-    float *stage_gen = c->mesh_stage + (size_t)gen * MAX_VIEWS * c->mesh_stage_floats;
-    for (int v = 0; v < NV; ++v) {
-        float *stg = stage_gen + (size_t)v * c->mesh_stage_floats;
-        memcpy(stg, mesh_x + (size_t)v * n_small, n_small * 4);
-        memcpy(stg + n_small, mesh_y + (size_t)v * n_small, n_small * 4);
-        const int aw = c->roi[v].width, ah = c->roi[v].height, hw = aw / 2, hh = ah / 2;
-        const size_t n_half = (size_t)hw * hh;
-        unsigned long long *mine = acc0 + acc_off[v] + (size_t)p * 2 * n_half, *other = acc0 + acc_off[v] + (size_t)(1 - p) * 2 * n_half;
-        ms_image dx = mesh_image(c, tgt[v], v, 0), dy = mesh_image(c, tgt[v], v, 1);
-        MeshJob &J = T.j[v];
-        J.smx = sm + (size_t)v * 2 * n_small; J.smy = J.smx + n_small;
-        J.ax = mine; J.ay = mine + n_half;
-        J.clear = other; J.n_clear = c->mesh_all_dirty ? 2 * n_half : 0;
-        J.disp_word = (unsigned *)c->disp_dev.p + 2 * v + tgt[v];
-        J.dx = (float *)dx.data; J.dy = (float *)dy.data;
-        J.aw = aw; J.ah = ah; J.hw = hw; J.hh = hh; J.pitch = c->map_pitch[v];
-        J.tiles_x = div_up(aw, 64); J.n_tiles = J.tiles_x * div_up(ah, 4 * MESH_TR);
-    }
-    if (c->mesh_stage_floats == 2 * n_small)
-        MS_HIP(hipMemcpyAsync(sm, stage_gen, sm_floats * sizeof(float), hipMemcpyHostToDevice, st));        // the slots are back to back
-    else
-        for (int v = 0; v < NV; ++v)
-            MS_HIP(hipMemcpyAsync(sm + (size_t)v * 2 * n_small, stage_gen + (size_t)v * c->mesh_stage_floats, 2 * n_small * sizeof(float), hipMemcpyHostToDevice, st));
-    if (!c->mesh_stage_ev[gen]) MS_HIP(hipEventCreateWithFlags(&c->mesh_stage_ev[gen], hipEventDisableTiming));
-    MS_HIP(hipEventRecord(c->mesh_stage_ev[gen], st));
-    c->mesh_stage_ev_set[gen] = true;
-    c->mesh_stage_gen = (gen + 1) % ms_ctx::MESH_STAGE_GENS;
-    const dim3 blk(64, 4);
-    k_mesh_expand_scatter_all<<<dim3(div_up(max_aw, 64), div_up(max_ah, 4 * MESH_SR), NV), blk, 0, st>>>(T, N, M);         // meshwarper.cpp:838-869, every view
-    MS_LAUNCH_CHECK();
-    k_mesh_mean_resize_all<<<dim3(std::min(max_tiles, 512), NV), blk, 0, st>>>(T);                                           // :870-883
-    MS_LAUNCH_CHECK();
-    c->mesh_all_dirty = true;
-    c->mesh_all_parity ^= 1;
-    // Publish every view in ONE mesh_mu critical section, the chain's record FIRST: a stitch on another thread that takes mesh_mu between two views of a
-    // per-view publication saw mesh_wait[v] set while mesh_chain still held the PREVIOUS update's record (or none), waited for that, cleared the flag and read the
-    // buffer k_mesh_mean_resize_all was still writing.  A stitch now sees either none of this call's views or all of them, behind this call's record.
-    {
-        std::lock_guard<std::mutex> mk(c->mesh_mu);
-        MS_HIP(hipEventRecord(c->mesh_chain, st));
-        c->mesh_chain_set = true;
-        for (int v = 0; v < NV; ++v) {
-            c->mesh_ready_via_chain[v] = true;
-            c->mesh_wait[v] = true;
-            c->mesh_active[v] = tgt[v];
-            c->mesh_set[v] = true;
-        }
-    }
-    return MS_OK;
-}
-
-// MeshWarper::interpolateMesh (meshwarper.cpp:337-354) + convertMeshesToMap: the RECALIB_INTERP branch of the recalibration thread
-// (timed.cpp:449-457) re-expands start + (end - start) * progress every 30 ms
-int ms_set_mesh_interp(ms_ctx *c, int view, const float *x0, const float *y0, const float *x1, const float *y1, int N, int M, float progress, ms_stream stream)
-{
-    MS_CHECK(x0 && y0 && x1 && y1 && N >= 2 && M >= 2, "ms_set_mesh_interp: need two N x M (>= 2x2) vertex meshes");
-    std::vector<float> mx((size_t)N * M), my((size_t)N * M);
-    for (size_t i = 0; i < mx.size(); ++i) {
-        mx[i] = x0[i] + (x1[i] - x0[i]) * progress;        // fp32, in this order (-ffp-contract=off)
-        my[i] = y0[i] + (y1[i] - y0[i]) * progress;
-    }
-    return ms_set_mesh(c, view, mx.data(), my.data(), N, M, stream);
-}
-
 // Enqueue-only update_mask (cfg.update_mask_margin > 0; caller holds mesh_update_mu).  Everything that depends on the masks exists twice; the copy
 // ms_stitch does not read is rebuilt on `st` -- behind the stitches enqueued so far, which may still read it from before the previous swap -- and becomes
 // the active one under mesh_mu; ms_stitch makes its stream wait for `tab_ready`.  No host synchronisation, no allocation, no new work lists: those
@@ -3296,20 +2788,6 @@ int ms_get_active_views(const ms_ctx *c, unsigned *mask)
     const unsigned all = all_views(c->N);
     std::lock_guard<std::recursive_mutex> tables_lk(const_cast<ms_ctx *>(c)->tables_mu);
     *mask = c->act ? c->act->views : all;
-    return MS_OK;
-}
-
-int ms_get_mesh_displacement(ms_ctx *c, int view, float *out_px)
-{
-    if (int e = ctx_check_view(c, view)) return e;
-    MS_CHECK(out_px != nullptr, "ms_get_mesh_displacement: null output");
-    std::lock_guard<std::mutex> lk(c->mesh_update_mu);       // no update in flight while we look; ms_stitch is not blocked by this lock
-    if (!c->blender_ready || !c->cfg.enable_cpw || !c->mesh_set[view] || !c->disp_dev.p) return fail(MS_ERR_STATE, "ms_get_mesh_displacement: no mesh set for view %d", view);
-    if (c->mesh_ready[view]) { hipEvent_t rdy_; { std::lock_guard<std::mutex> mk_(c->mesh_mu); rdy_ = mesh_ready_event(c, view); } if (rdy_) MS_HIP(hipEventSynchronize(rdy_)); }
-    float *h = (float *)pinned_scratch().get(sizeof(float));          // pinned landing zone: see PinnedScratch (common.hpp)
-    if (!h) return fail(MS_ERR_NOMEM, "ms_get_mesh_displacement: no pinned staging memory");
-    MS_HIP(hipMemcpy(h, (const unsigned *)c->disp_dev.p + 2 * view + c->mesh_active[view], sizeof(float), hipMemcpyDeviceToHost));
-    *out_px = *h;
     return MS_OK;
 }
 
@@ -3999,16 +3477,6 @@ int ms_get_weight_level(const ms_ctx *c, int view, int level, ms_image *w)
     if (wait) MS_HIP(hipEventSynchronize(c->tab_ready));              // an enqueue-only ms_update_mask may still be filling the active copy
     const LevelDesc &L = (active == 1 ? c->alt.h_views : c->h_views)[view].lv[level];
     *w = ms_image{(void *)L.wgt, (size_t)L.wpitch * sizeof(float), L.w, L.h, MS_32FC1};
-    return MS_OK;
-}
-
-int ms_get_mesh_maps(const ms_ctx *c, int view, ms_image *xm, ms_image *ym)
-{
-    if (int e = ctx_check_view(c, view)) return e;
-    if (!c->blender_ready || !c->cfg.enable_cpw || !c->mesh_set[view]) return fail(MS_ERR_STATE, "ms_get_mesh_maps: no mesh set for view %d", view);
-    if (c->mesh_ready[view]) { ms_ctx *mc_ = const_cast<ms_ctx *>(c); hipEvent_t rdy_; { std::lock_guard<std::mutex> mk_(mc_->mesh_mu); rdy_ = mesh_ready_event(mc_, view); } if (rdy_) MS_HIP(hipEventSynchronize(rdy_)); }       // updates are asynchronous: the maps are final after this
-    if (xm) *xm = mesh_image(c, c->mesh_active[view], view, 0);
-    if (ym) *ym = mesh_image(c, c->mesh_active[view], view, 1);
     return MS_OK;
 }
 

@@ -1,5 +1,6 @@
 // ctx.hpp -- the context type behind the C ABI's opaque ms_ctx, for the units that define its entry points: compositor.hip (life cycle, tables, the per-frame
-// path), calib.hip (exposure tracking), and through rig_lm.hpp rig.hip (ms_refine_rig) and rig_focal.hip (ms_refine_rig_focals).  Internal; nothing else includes it.
+// path), mesh_maps.hip (CPW mesh maps), calib.hip (exposure tracking), and through rig_lm.hpp rig.hip (ms_refine_rig), rig_focal.hip (ms_refine_rig_focals) and
+// rig_lens.hip (ms_refine_rig_lens).  Internal; nothing else includes it.
 #pragma once
 #include <atomic>
 #include <memory>
@@ -121,13 +122,20 @@ struct ms_ctx {
     size_t mesh_off[ms::MAX_VIEWS] = {};
     int mesh_active[ms::MAX_VIEWS] = {};   // which buffer ms_stitch reads for this view
     bool mesh_set[ms::MAX_VIEWS] = {};
-    ms::DevBuf mesh_tmp;                   // scratch for convertMeshesToMap: vertex mesh x|y, two half-resolution accumulators ([count:24|sum_x:40], [sum_y]) used in turn
-    size_t mesh_small_cap = 0, mesh_half_cap = 0, mesh_dirty = 0;   // capacities (floats / cells); 64-bit words the previous update dirtied in its accumulator
-    int mesh_parity = 0;
-    ms::DevBuf mesh_all;                   // scratch of ms_set_meshes (all views in one pair of launches): every view's vertex meshes, then per view two accumulator pairs used in turn
-    size_t mesh_all_small = 0;         // floats per vertex map the block was sized for
-    int mesh_all_parity = 0;
-    bool mesh_all_dirty = false;       // the accumulators of the other parity hold the previous call's sums (cleared by the next scatter launch)
+    // what only the mesh updates touch (mesh_maps.hip; under mesh_update_mu)
+    static constexpr int MESH_STAGE_GENS = 8;
+    struct MeshUpdater {
+        ms::DevBuf scratch;                // convertMeshesToMap's device block: every view's vertex-mesh slot (x | y), then per view two half-resolution accumulator pairs ([count:24|sum_x:40], [sum_y]) used in turn
+        size_t cap = 0;                    // floats per vertex map the block was sized for
+        size_t acc_off[ms::MAX_VIEWS + 1] = {};      // 64-bit words: where view v's two accumulator pairs begin; [N] = all of them
+        int parity[ms::MAX_VIEWS] = {};    // the pair view v's next update adds into
+        bool dirty[ms::MAX_VIEWS] = {};    // view v's other pair holds the sums of its previous update (cleared by its next scatter launch)
+        float *stage = nullptr;            // pinned host staging of the vertex meshes: a ring of MESH_STAGE_GENS generations of MAX_VIEWS slots + one generation of ms_set_mesh's own behind it (
+        size_t stage_floats = 0;           // ms_set_meshes walks the ring: the host waits for the COPY of the update a whole ring back -- `stage_ev` --, never for the update before this one)
+        int stage_gen = 0;
+        hipEvent_t stage_ev[MESH_STAGE_GENS] = {};
+        bool stage_ev_set[MESH_STAGE_GENS] = {};
+    } mesh_upd;
     std::mutex mesh_mu;                // guards the active indices / events shared with ms_stitch: held only across enqueues, never across a host wait
     std::mutex mesh_update_mu;         // serialises mesh updates among themselves (shared scratch, staging slots); taken BEFORE mesh_mu
     // Held by ms_stitch for the length of its enqueue and by everything that REBUILDS the static tables (ms_init_blender, and through it the synchronous
@@ -145,12 +153,6 @@ struct ms_ctx {
     // ms_set_meshes updates every view behind ONE event: a view whose last update was part of such a call is ready when `mesh_chain` is (a later record of mesh_chain is a later
     // point of the same chain of updates).  Twelve event records and as many stream waits per recalibration were 50 us of idle GPU between its kernels and the next stitch.
     bool mesh_ready_via_chain[ms::MAX_VIEWS] = {};
-    float *mesh_stage = nullptr;       // pinned host staging of the vertex meshes: a ring of MESH_STAGE_GENS generations of MAX_VIEWS slots + one generation of ms_set_mesh's own behind it (
-    size_t mesh_stage_floats = 0;      // ms_set_meshes walks the ring: the host waits for the COPY of the update a whole ring back -- `mesh_stage_ev` --, never for the update before this one)
-    static constexpr int MESH_STAGE_GENS = 8;
-    int mesh_stage_gen = 0;
-    hipEvent_t mesh_stage_ev[MESH_STAGE_GENS] = {};
-    bool mesh_stage_ev_set[MESH_STAGE_GENS] = {};
     int canvas_x = 0, canvas_y = 0;
     // view sharding (ms_config.view_shards = shard count S, view_shard_index = this shard's index): contiguous blocks of views per shard
     unsigned own_mask = 0xffffffffu;
@@ -200,4 +202,19 @@ struct ms_ctx {
 
 namespace ms {
 static inline bool sharded_ctx(const ms_ctx *c) { return c->own_mask != all_views(c->N); }
+static inline int ctx_check_view(const ms_ctx *c, int v)
+{
+    if (!c) return fail(MS_ERR_INVALID, "null context");
+    if (v < 0 || v >= c->N) return fail(MS_ERR_INVALID, "view index %d out of range [0,%d)", v, c->N);
+    return MS_OK;
+}
+// one of a view's two CPW mesh maps (which: 0 = x, 1 = y) in mesh buffer `buf`
+static inline ms_image mesh_image(const ms_ctx *c, int buf, int v, int which)
+{
+    const int ah = c->roi[v].height, aw = c->roi[v].width;
+    float *base = (float *)c->mesh[buf].p + c->mesh_off[v] + (which ? (size_t)ah * c->map_pitch[v] : 0);
+    return ms_image{base, (size_t)c->map_pitch[v] * sizeof(float), aw, ah, MS_32FC1};
+}
+// the event behind a view's last mesh update (caller holds mesh_mu or is the only updater)
+static inline hipEvent_t mesh_ready_event(ms_ctx *c, int view) { return c->mesh_ready_via_chain[view] ? c->mesh_chain : c->mesh_ready[view]; }
 }  // namespace ms
