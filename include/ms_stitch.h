@@ -859,6 +859,16 @@ MS_API int ms_orb_detect_and_compute_batch(int n_views, const ms_image *gray, co
  * views overlap (rect_a / rect_b: x0, width -- cv::rectangle clips them to the image) AND where the warped view is not black (inRange(0, 0) negated:
  * the pixels the projection did not fill).  warped_view: DEVICE 8UC3; mask: DEVICE 8UC1 of the same size. */
 MS_API int ms_feature_mask(const ms_image *warped_view, int a_x0, int a_width, int b_x0, int b_width, ms_image *mask, ms_stream stream);
+/* The grey images and the feature masks of every view of a round in ONE launch: cuda::cvtColor(BGR2GRAY) of findFeatures (360_stitcher/featurefinder.cpp:34) and
+ * createMesh's mask loop (meshwarper.cpp:82-115), which the reference and the two single calls above run view after view.  warped_views: n_views DEVICE 8UC3
+ * images, which may differ in size; bands: n_views x {a_x0, a_width, b_x0, b_width} (HOST), needed with masks; gray / masks: n_views DEVICE 8UC1 images of their
+ * view's size, either array may be NULL but not both.  gray[v] is byte-equal to ms_bgr_to_gray(warped_views + v) and masks[v] to ms_feature_mask(warped_views + v,
+ * the bands of v) -- the bands clipped to the image as there --; bytes past a row's width are not written.  The grid is laid over the views' 256 x 4 pixel tiles,
+ * a workgroup finds its (view, tile) from the per-view table that goes up with the launch; a lane takes 4 pixels of a row and reads each BGR pixel once for both
+ * outputs.  Enqueue-only, as the single calls.
+ * MS_ERR_INVALID before the device is touched, naming the view: n_views outside [1, MS_MAX_VIEWS]; null warped_views; gray and masks both NULL; masks without
+ * bands; a view, grey image or mask without data, empty, of another type, with a step below its row; a grey image or mask of another size than its view. */
+MS_API int ms_feature_inputs_batch(int n_views, const ms_image *warped_views, const int *bands, ms_image *gray, ms_image *masks, ms_stream stream);
 /* cv::findHomography(src, dst, mask, RANSAC) of featurefinder::matchFeatures (featurefinder.cpp:68-90 -> calib3d/src/fundam.cpp:319-402,
  * ptsetreg.cpp:53-290, levmarq.cpp:76-214): src_xy / dst_xy HOST, n points (x, y) each.  reproj_threshold <= 0 -> 3, max_iters <= 0 -> 2000,
  * confidence outside (0, 1) -> 0.995 (the reference's defaults).  Same cv::RNG subset sequence, subset checks, acceptance rule and adaptive
@@ -1147,6 +1157,41 @@ MS_API int ms_pair_match_default_params(ms_pair_match_params *prm);
 MS_API int ms_match_pairs(int n_views, const ms_view_features *views, const ms_pair_match_params *prm,
                           ms_pair_matches *pairs_out, int pairs_cap, int *n_pairs,
                           ms_feature_match *matches_out, int matches_cap, int *n_matches, ms_stream stream);
+/* The application's own matcher over an explicit list of directed problems: featurefinder::matchFeatures and matchFeaturesTemporal
+ * (360_stitcher/featurefinder.cpp:48-108, :110-170) -- knnMatch(k = 2) in ONE direction, the 0.7 ratio test (:62-66), no cross-check, findHomography(RANSAC) on
+ * every non-empty list (:68-90), confidence 1 (:106) -- where ms_match_pairs above is BestOf2NearestMatcher's rule.  One call serves the ring of lines 55-59, the
+ * temporal list of lines 117-121, or both.
+ * sets: a table of n_sets feature sets, n_sets in [1, 2 * MS_MAX_VIEWS] (one round's features and the previous round's fit in one table), ms_view_features with
+ * ms_match_pairs' descriptor rules.  problems: n_problems in [0, MS_MATCH_MAX_PROBLEMS] pairs (query_set, train_set) of table indices; a problem may name any
+ * two sets, the same set twice, and a problem may be repeated.  out: n_problems records -- view_a the query set, view_b the train set, first / count the slice of
+ * matches_out in problem order, n_forward = count, confidence 1.0 always.
+ * The result of problem p is what the per-pair route (ms_knn_match_hamming2, the ratio test, ms_find_homography_ransac) computes for that pair alone, bit for bit,
+ * and depends neither on the problem's neighbours nor on its place in the list.  With fewer than 1 query row or fewer than 2 train rows the list is empty.
+ * Otherwise, for every query row q in ascending order, with its two nearest train rows (j0, d0), (j1, d1) in ms_knn_match_hamming2's (distance, index) order: q
+ * passes iff (double)d0 < ratio * (double)d1 (one double multiply, one compare; at 0.7 that is 10 d0 < 7 d1 for all distances up to 512: the boundary pairs
+ * (7, 10), (14, 20), ... do not pass), and the list is the passing rows as (q, j0, d0).  The order is part of the contract (the fixed RANSAC subset sequence indexes
+ * into it).  With find_homography every problem with count >= 1 gets what ms_find_homography_ransac returns on its own for the matches' keypoints as centred
+ * floats (x - width * 0.5f, y - height * 0.5f), the mask zeroed first: H, the inlier flags, num_inliers, have_H = (status == 0).  find_homography 0: lists
+ * only -- have_H 0, num_inliers 0, every flag 0.
+ * Device stage, two launches whatever n_problems is, one upload, one copy back, one synchronise, over the calling thread's grow-only scratch: a problem is a
+ * directed segment of ms_match_pairs' 2-NN kernel; then one workgroup a problem takes 256 queries a round through the ratio test and an ordered ballot /
+ * prefix-scan compaction (no atomics: two calls return the same bytes).  Host stage: one ms_find_homography_ransac_batch round over the non-empty lists.
+ * MS_ERR_INVALID before the device is touched: a null pointer; n_sets or n_problems out of range; a set index out of range; a struct_size mismatch; ratio not
+ * finite or outside (0, 1]; the RANSAC parameter rules and the per-set rules of ms_match_pairs; a negative matches_cap.  After the device stage and before
+ * RANSAC: matches_cap below the total, with the needed total in *n_matches.  n_problems == 0 is MS_OK with *n_matches = 0 and touches nothing. */
+#define MS_MATCH_MAX_PROBLEMS 64
+typedef struct ms_match_problem { int query_set, train_set; } ms_match_problem;
+typedef struct ms_list_match_params {
+    unsigned struct_size;          /* as ms_config: mismatch = MS_ERR_INVALID */
+    double ratio;                  /* 0.7 (featurefinder.cpp:65) */
+    int find_homography;           /* 1; 0 = lists only */
+    double ransac_reproj_threshold; int ransac_max_iters; double ransac_confidence;   /* 0 = ms_find_homography_ransac's defaults */
+} ms_list_match_params;
+/* ratio 0.7, find_homography 1, RANSAC defaults (featurefinder.cpp:65, :90) */
+MS_API int ms_list_match_default_params(ms_list_match_params *prm);
+MS_API int ms_match_lists(int n_sets, const ms_view_features *sets, int n_problems, const ms_match_problem *problems,
+                          const ms_list_match_params *prm, ms_pair_matches *out, ms_feature_match *matches_out,
+                          int matches_cap, int *n_matches, ms_stream stream);
 /* leaveBiggestComponent (motion_estimators.cpp:1041-1097).  Host only, no device.  The views are joined over the pairs with confidence >= conf_threshold;
  * keep receives the views of the largest component in ascending order (room for n_views), *n_keep their number.  Among components of equal size the one
  * that holds the lowest view index wins.  n_views in [1, MS_MAX_VIEWS]; pairs may be NULL where n_pairs is 0 (then keep is view 0 alone).

@@ -93,6 +93,47 @@ __global__ void __launch_bounds__(256) k_feature_mask(const uint8_t *__restrict_
     mask[(size_t)y * mstep + x] = (band && (p[0] | p[1] | p[2])) ? 255 : 0;
 }
 
+// ms_feature_inputs_batch: view v's images and bands (ax0 <= x < ax1 or bx0 <= x < bx1), its first workgroup and the number of 256-pixel tiles across a row.  The table
+// travels as the kernel's argument: no upload, no scratch.
+struct FiView { const uint8_t *src; uint8_t *gray, *mask; size_t sstep, gstep, mstep; int w, h, ax0, ax1, bx0, bx1, block0, tiles_x; };
+struct FiTable { FiView v[MS_MAX_VIEWS]; int n; };
+
+__device__ __forceinline__ void fi_store4(uint8_t *base, size_t step, int x, int y, unsigned q, int n)
+{
+    uint8_t *d = base + (size_t)y * step + x;
+    if (n == 4 && ((step | (size_t)base) & 3) == 0) *reinterpret_cast<unsigned *>(d) = q;
+    else for (int k = 0; k < n; ++k) d[k] = (uint8_t)(q >> (8 * k));
+}
+
+// cvtColor(BGR2GRAY) (featurefinder.cpp:34: CV_DESCALE(b * 1868 + g * 9617 + r * 4899, 14)) and createMesh's feature mask (meshwarper.cpp:82-115) of every view in one
+// launch: a workgroup = one 256 x 4 pixel tile of one view, a lane = 4 pixels of a row, each BGR pixel read once for both outputs
+__global__ void __launch_bounds__(256) k_feature_inputs(const FiTable T)
+{
+    int vi = 0;
+    while (vi + 1 < T.n && (int)blockIdx.x >= T.v[vi + 1].block0) ++vi;
+    const FiView &V = T.v[vi];
+    const int local = (int)blockIdx.x - V.block0, ty = local / V.tiles_x, tx = local - ty * V.tiles_x;
+    const int x = 4 * (tx * 64 + (int)threadIdx.x), y = ty * 4 + (int)threadIdx.y;
+    if (x >= V.w || y >= V.h) return;
+    const uint8_t *p = V.src + (size_t)y * V.sstep + (size_t)x * 3;
+    const int n = min(4, V.w - x);
+    uint8_t px[12];
+    if (n == 4 && ((V.sstep | (size_t)V.src) & 3) == 0) __builtin_memcpy(px, __builtin_assume_aligned(p, 4), 12);
+    else for (int i = 0; i < 3 * n; ++i) px[i] = p[i];
+    unsigned g = 0, m = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (k < n) {
+            const unsigned b = px[3 * k], gr = px[3 * k + 1], r = px[3 * k + 2];
+            g |= ((b * 1868u + gr * 9617u + r * 4899u + (1u << 13)) >> 14) << (8 * k);
+            const int xk = x + k;
+            const bool band = (xk >= V.ax0 && xk < V.ax1) || (xk >= V.bx0 && xk < V.bx1);
+            if (band && (b | gr | r)) m |= 255u << (8 * k);
+        }
+    if (V.gray) fi_store4(V.gray, V.gstep, x, y, g, n);
+    if (V.mask) fi_store4(V.mask, V.mstep, x, y, m, n);
+}
+
 // HarrisResponses (orb.cu:93-138): 7 x 7 block, integer gradient sums, float formula evaluated operation by operation
 __device__ __forceinline__ float harris_at(const uint8_t *__restrict__ img, size_t step, int x, int y, int block, float k)
 {
@@ -1163,6 +1204,52 @@ int ms_feature_mask(const ms_image *img, int a_x0, int a_w, int b_x0, int b_w, m
              "ms_feature_mask: need an 8UC3 image and an 8UC1 mask of the same size");
     k_feature_mask<<<dim3(div_up(img->cols, 64), div_up(img->rows, 4)), dim3(64, 4), 0, as_stream(stream)>>>(
         (const uint8_t *)img->data, img->step, img->rows, img->cols, a_x0, a_x0 + a_w, b_x0, b_x0 + b_w, (uint8_t *)mask->data, mask->step);
+    MS_LAUNCH_CHECK();
+    return MS_OK;
+}
+
+int ms_feature_inputs_batch(int n_views, const ms_image *views, const int *bands, ms_image *gray, ms_image *masks, ms_stream stream)
+{
+    const char *fn = "ms_feature_inputs_batch";
+    MS_CHECK(n_views >= 1 && n_views <= MS_MAX_VIEWS, "%s: n_views = %d must be in [1, %d]", fn, n_views, MS_MAX_VIEWS);
+    MS_CHECK(views, "%s: null warped_views", fn);
+    MS_CHECK(gray || masks, "%s: gray and masks are both null: nothing to write", fn);
+    MS_CHECK(!masks || bands, "%s: masks need bands", fn);
+    FiTable T{};
+    T.n = n_views;
+    long long blocks = 0;
+    for (int v = 0; v < n_views; ++v) {
+        const ms_image &im = views[v];
+        MS_CHECK(im.data, "%s: view %d: null warped view", fn, v);
+        MS_CHECK(im.rows > 0 && im.cols > 0, "%s: view %d: empty warped view %dx%d", fn, v, im.cols, im.rows);
+        MS_CHECK(im.type == MS_8UC3, "%s: view %d: warped view of type %d (need 8UC3)", fn, v, im.type);
+        MS_CHECK(im.step >= (size_t)im.cols * 3, "%s: view %d: warped view step %zu smaller than a row (%zu bytes)", fn, v, im.step, (size_t)im.cols * 3);
+        FiView &V = T.v[v];
+        V.src = (const uint8_t *)im.data; V.sstep = im.step; V.w = im.cols; V.h = im.rows;
+        const ms_image *outs[2] = {gray ? gray + v : nullptr, masks ? masks + v : nullptr};
+        for (int k = 0; k < 2; ++k) {
+            const ms_image *o = outs[k];
+            const char *what = k ? "mask" : "gray";
+            if (!o) continue;
+            MS_CHECK(o->data, "%s: view %d: null %s image", fn, v, what);
+            MS_CHECK(o->type == MS_8UC1, "%s: view %d: %s image of type %d (need 8UC1)", fn, v, what, o->type);
+            MS_CHECK(o->rows == im.rows && o->cols == im.cols, "%s: view %d: %s image %dx%d, its view %dx%d: size mismatch", fn, v, what, o->cols, o->rows, im.cols, im.rows);
+            MS_CHECK(o->step >= (size_t)o->cols, "%s: view %d: %s image step %zu smaller than a row (%d bytes)", fn, v, what, o->step, o->cols);
+            (k ? V.mask : V.gray) = (uint8_t *)o->data;
+            (k ? V.mstep : V.gstep) = o->step;
+        }
+        if (masks) {                                    // x0 + width as ms_feature_mask forms it, held inside the int range
+            const int *b = bands + 4 * v;
+            auto end = [](int x0, int w) { const long long e = (long long)x0 + w; return (int)std::min<long long>(std::max<long long>(e, INT_MIN), INT_MAX); };
+            V.ax0 = b[0]; V.ax1 = end(b[0], b[1]); V.bx0 = b[2]; V.bx1 = end(b[2], b[3]);
+        }
+        V.tiles_x = div_up(im.cols, 256);
+        V.block0 = (int)blocks;
+        blocks += (long long)V.tiles_x * div_up(im.rows, 4);
+        MS_CHECK(blocks <= INT_MAX, "%s: view %d: the views up to this one hold more than 2^31 - 1 tiles of 256 x 4 pixels", fn, v);
+    }
+    if (int e = require_device()) return e;
+    k_feature_inputs<<<(unsigned)blocks, dim3(64, 4), 0, as_stream(stream)>>>(T);
     MS_LAUNCH_CHECK();
     return MS_OK;
 }

@@ -7,6 +7,8 @@
 // every LDS read is a broadcast --, its four waves take a quarter of the tile each and merge their (distance, index)-ordered best pairs at the end.
 // k_pair_select: one workgroup a pair applies the ratio test and the cross-check and compacts with a ballot / prefix scan, so the list order is exact and
 // no atomic assigns a position.  Integer work but for the one float compare of the ratio test (-ffp-contract=off: one multiply, one compare).
+// ms_match_lists is the application's own rule (360_stitcher/featurefinder.cpp:48-170: one direction, the 0.7 ratio test in double, no cross-check) over an explicit
+// list of directed problems: the same k_pair_knn2 over the same tables, then k_list_select, one workgroup a problem.
 #include <cfloat>
 #include <climits>
 #include <cmath>
@@ -140,7 +142,88 @@ __global__ void __launch_bounds__(PM_THREADS) k_pair_select(const PmPair *__rest
     if (threadIdx.x == 0) hdr[blockIdx.x] = make_int2(base, n_forward);
 }
 
+// A problem of ms_match_lists with a query row and two train rows or more: its 2-NN rows at knn_off, room for nq slots at slot_off
+struct PmList { int nq; unsigned knn_off, slot_off, pad; };
+
+// featurefinder::matchFeatures' rule (featurefinder.cpp:62-66) over one directed problem a workgroup: row q passes iff (double)d0 < ratio * (double)d1 -- one double
+// multiply, one compare --, the passing rows compacted in query order through block_rank, slots as k_pair_select writes them; hdr[problem] = count
+__global__ void __launch_bounds__(PM_THREADS) k_list_select(const PmList *__restrict__ lists, const int4 *__restrict__ knn, double ratio, int *__restrict__ hdr,
+                                                            uint2 *__restrict__ slots)
+{
+    __shared__ int wsum[PM_THREADS / 64];
+    const PmList p = lists[blockIdx.x];
+    uint2 *out = slots + p.slot_off;
+    int base = 0, total;
+    for (int q0 = 0; q0 < p.nq; q0 += PM_THREADS) {
+        const int q = q0 + (int)threadIdx.x;
+        int4 e = make_int4(0, 0, 0, 0);
+        bool pass = false;
+        if (q < p.nq) { e = knn[p.knn_off + q]; pass = (double)e.y < ratio * (double)e.w; }
+        const int pos = block_rank(pass, wsum, total);
+        if (pass) out[base + pos] = make_uint2((unsigned)q | ((unsigned)e.x << 16), (unsigned)e.y);
+        base += total;
+    }
+    if (threadIdx.x == 0) hdr[blockIdx.x] = base;
+}
+
 size_t pm_align(size_t n) { return (n + 255) & ~(size_t)255; }
+
+// the rules ms_match_pairs and ms_match_lists share for their feature tables (`what`: "view" / "set") and RANSAC parameters; *bytes: the descriptor length, 0 where no entry has rows
+int pm_check_features(const char *fn, const char *what, int n, const ms_view_features *views, int *bytes_out)
+{
+    int bytes = 0;
+    for (int v = 0; v < n; ++v) {
+        const ms_view_features &f = views[v];
+        MS_CHECK(f.n_keypoints >= 0 && f.n_keypoints <= MS_MATCH_MAX_KEYPOINTS, "%s: %s %d: n_keypoints %d outside [0, %d]", fn, what, v, f.n_keypoints, MS_MATCH_MAX_KEYPOINTS);
+        MS_CHECK(f.n_keypoints <= f.descriptors.rows, "%s: %s %d: n_keypoints %d above descriptors.rows %d", fn, what, v, f.n_keypoints, f.descriptors.rows);
+        MS_CHECK(f.keypoint_stride >= 2, "%s: %s %d: keypoint_stride %d below 2", fn, what, v, f.keypoint_stride);
+        MS_CHECK(f.width >= 1 && f.height >= 1, "%s: %s %d: image size (width, height) %d x %d", fn, what, v, f.width, f.height);
+        if (f.n_keypoints == 0) continue;
+        MS_CHECK(f.keypoints, "%s: %s %d: null keypoints", fn, what, v);
+        MS_CHECK(f.descriptors.data, "%s: %s %d: null descriptors", fn, what, v);
+        MS_CHECK(f.descriptors.type == MS_8UC1, "%s: %s %d: descriptors type %d (need 8UC1)", fn, what, v, f.descriptors.type);
+        MS_CHECK(f.descriptors.cols > 0 && f.descriptors.cols % 4 == 0 && f.descriptors.cols <= 64, "%s: %s %d: descriptor length %d (need a multiple of 4 up to 64 bytes)", fn, what,
+                 v, f.descriptors.cols);
+        MS_CHECK(f.descriptors.step % 4 == 0 && f.descriptors.step >= (size_t)f.descriptors.cols && (uintptr_t)f.descriptors.data % 4 == 0,
+                 "%s: %s %d: descriptors step %zu / data must be 4-byte aligned and the step not below the row", fn, what, v, f.descriptors.step);
+        MS_CHECK(bytes == 0 || bytes == f.descriptors.cols, "%s: %s %d: descriptor length %d differs from %d of an earlier %s", fn, what, v, f.descriptors.cols, bytes, what);
+        bytes = f.descriptors.cols;
+    }
+    *bytes_out = bytes;
+    return MS_OK;
+}
+
+int pm_check_ransac(const char *fn, double reproj_threshold, int max_iters, double confidence)
+{
+    MS_CHECK(std::isfinite(reproj_threshold) && reproj_threshold >= 0.0 && max_iters >= 0 && std::isfinite(confidence) && confidence >= 0.0 && confidence < 1.0,
+             "%s: ransac_reproj_threshold / ransac_max_iters / ransac_confidence = %g / %d / %g (0 = the default; confidence below 1)", fn, reproj_threshold, max_iters, confidence);
+    return MS_OK;
+}
+
+// k_pair_knn2's tables for one more directed segment, the rows of view q against the rows of view t (two of them or more): returns the segment's offset into knn
+unsigned pm_add_segment(const std::vector<PmView> &hv, int q, int t, std::vector<PmSeg> &segs, std::vector<PmBlock> &blocks, size_t &knn_n)
+{
+    const unsigned off = (unsigned)knn_n;
+    for (int q0 = 0; q0 < hv[q].n; q0 += PM_QUERIES) blocks.push_back(PmBlock{(int)segs.size(), q0});
+    segs.push_back(PmSeg{q, t, off, 0u});
+    knn_n += (size_t)hv[q].n;
+    return off;
+}
+
+std::vector<PmView> pm_views(int n, const ms_view_features *views)
+{
+    std::vector<PmView> hv(n);
+    for (int v = 0; v < n; ++v) hv[v] = PmView{(const uint8_t *)views[v].descriptors.data, views[v].descriptors.step, views[v].n_keypoints, 0};
+    return hv;
+}
+
+// the 2-NN launch over those tables (descriptors of `bytes` bytes; 32 is the specialised kernel)
+hipError_t pm_launch_knn2(const PmView *dv, const PmSeg *ds, const PmBlock *db, unsigned n_blocks, int bytes, int4 *knn, hipStream_t st)
+{
+    if (bytes == 32) k_pair_knn2<8><<<n_blocks, PM_THREADS, 0, st>>>(dv, ds, db, 8, knn);
+    else k_pair_knn2<0><<<n_blocks, PM_THREADS, 0, st>>>(dv, ds, db, bytes / 4, knn);
+    return hipGetLastError();
+}
 
 double pm_det3(const double *H)
 {
@@ -201,29 +284,10 @@ int ms_match_pairs(int n_views, const ms_view_features *views, const ms_pair_mat
     MS_CHECK(prm->num_matches_thresh1 >= 0 && prm->num_matches_thresh2 >= 0, "%s: num_matches_thresh1 / num_matches_thresh2 = %d / %d must not be negative", fn,
              prm->num_matches_thresh1, prm->num_matches_thresh2);
     MS_CHECK(prm->range_width >= 0, "%s: range_width %d must not be negative", fn, prm->range_width);
-    MS_CHECK(std::isfinite(prm->ransac_reproj_threshold) && prm->ransac_reproj_threshold >= 0.0 && prm->ransac_max_iters >= 0 && std::isfinite(prm->ransac_confidence) &&
-                 prm->ransac_confidence >= 0.0 && prm->ransac_confidence < 1.0,
-             "%s: ransac_reproj_threshold / ransac_max_iters / ransac_confidence = %g / %d / %g (0 = the default; confidence below 1)", fn, prm->ransac_reproj_threshold,
-             prm->ransac_max_iters, prm->ransac_confidence);
+    if (int e = pm_check_ransac(fn, prm->ransac_reproj_threshold, prm->ransac_max_iters, prm->ransac_confidence)) return e;
     MS_CHECK(pairs_cap >= 0 && matches_cap >= 0, "%s: pairs_cap / matches_cap = %d / %d must not be negative", fn, pairs_cap, matches_cap);
     int bytes = 0;
-    for (int v = 0; v < n_views; ++v) {
-        const ms_view_features &f = views[v];
-        MS_CHECK(f.n_keypoints >= 0 && f.n_keypoints <= MS_MATCH_MAX_KEYPOINTS, "%s: view %d: n_keypoints %d outside [0, %d]", fn, v, f.n_keypoints, MS_MATCH_MAX_KEYPOINTS);
-        MS_CHECK(f.n_keypoints <= f.descriptors.rows, "%s: view %d: n_keypoints %d above descriptors.rows %d", fn, v, f.n_keypoints, f.descriptors.rows);
-        MS_CHECK(f.keypoint_stride >= 2, "%s: view %d: keypoint_stride %d below 2", fn, v, f.keypoint_stride);
-        MS_CHECK(f.width >= 1 && f.height >= 1, "%s: view %d: image size (width, height) %d x %d", fn, v, f.width, f.height);
-        if (f.n_keypoints == 0) continue;
-        MS_CHECK(f.keypoints, "%s: view %d: null keypoints", fn, v);
-        MS_CHECK(f.descriptors.data, "%s: view %d: null descriptors", fn, v);
-        MS_CHECK(f.descriptors.type == MS_8UC1, "%s: view %d: descriptors type %d (need 8UC1)", fn, v, f.descriptors.type);
-        MS_CHECK(f.descriptors.cols > 0 && f.descriptors.cols % 4 == 0 && f.descriptors.cols <= 64, "%s: view %d: descriptor length %d (need a multiple of 4 up to 64 bytes)", fn, v,
-                 f.descriptors.cols);
-        MS_CHECK(f.descriptors.step % 4 == 0 && f.descriptors.step >= (size_t)f.descriptors.cols && (uintptr_t)f.descriptors.data % 4 == 0,
-                 "%s: view %d: descriptors step %zu / data must be 4-byte aligned and the step not below the row", fn, v, f.descriptors.step);
-        MS_CHECK(bytes == 0 || bytes == f.descriptors.cols, "%s: view %d: descriptor length %d differs from %d of an earlier view", fn, v, f.descriptors.cols, bytes);
-        bytes = f.descriptors.cols;
-    }
+    if (int e = pm_check_features(fn, "view", n_views, views, &bytes)) return e;
     // the candidate pairs (matchers.cpp:794-798)
     std::vector<int> cand;
     for (int i = 0; i < n_views - 1; ++i)
@@ -238,8 +302,7 @@ int ms_match_pairs(int n_views, const ms_view_features *views, const ms_pair_mat
     hipStream_t st = as_stream(stream);
 
     // tables: views, directed pairs, (directed pair, first query) blocks, active pairs
-    std::vector<PmView> hv(n_views);
-    for (int v = 0; v < n_views; ++v) hv[v] = PmView{(const uint8_t *)views[v].descriptors.data, views[v].descriptors.step, views[v].n_keypoints, 0};
+    const std::vector<PmView> hv = pm_views(n_views, views);
     std::vector<PmSeg> segs;
     std::vector<PmBlock> blocks;
     std::vector<PmPair> active;
@@ -252,10 +315,7 @@ int ms_match_pairs(int n_views, const ms_view_features *views, const ms_pair_mat
         for (int dir = 0; dir < 2; ++dir) {
             const int qv = dir ? b : a, tv = dir ? a : b;
             if (hv[tv].n < 2) continue;
-            (dir ? p.knn_ba : p.knn_ab) = (unsigned)knn_n;
-            for (int q0 = 0; q0 < hv[qv].n; q0 += PM_QUERIES) blocks.push_back(PmBlock{(int)segs.size(), q0});
-            segs.push_back(PmSeg{qv, tv, (unsigned)knn_n, 0u});
-            knn_n += (size_t)hv[qv].n;
+            (dir ? p.knn_ba : p.knn_ab) = pm_add_segment(hv, qv, tv, segs, blocks, knn_n);
         }
         active_of[k] = (int)active.size();
         active.push_back(p);
@@ -278,12 +338,9 @@ int ms_match_pairs(int n_views, const ms_view_features *views, const ms_pair_mat
         if (!blocks.empty()) memcpy(pin + o_blocks, blocks.data(), blocks.size() * sizeof(PmBlock));
         memcpy(pin + o_pairs, active.data(), active.size() * sizeof(PmPair));
         hipError_t e = hipMemcpyAsync(dev, pin, up_bytes, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && !blocks.empty()) {
-            const PmView *dv = (const PmView *)(dev + o_views); const PmSeg *ds = (const PmSeg *)(dev + o_segs); const PmBlock *db = (const PmBlock *)(dev + o_blocks);
-            if (bytes == 32) k_pair_knn2<8><<<(unsigned)blocks.size(), PM_THREADS, 0, st>>>(dv, ds, db, 8, (int4 *)(dev + o_knn));
-            else k_pair_knn2<0><<<(unsigned)blocks.size(), PM_THREADS, 0, st>>>(dv, ds, db, bytes / 4, (int4 *)(dev + o_knn));
-            e = hipGetLastError();
-        }
+        if (e == hipSuccess && !blocks.empty())
+            e = pm_launch_knn2((const PmView *)(dev + o_views), (const PmSeg *)(dev + o_segs), (const PmBlock *)(dev + o_blocks), (unsigned)blocks.size(), bytes,
+                               (int4 *)(dev + o_knn), st);
         if (e == hipSuccess) {
             k_pair_select<<<n_active, PM_THREADS, 0, st>>>((const PmPair *)(dev + o_pairs), (const int4 *)(dev + o_knn), 1.f - prm->match_conf, (int2 *)(dev + o_out),
                                                            (uint2 *)(dev + o_out + o_slots));
@@ -375,6 +432,139 @@ int ms_match_pairs(int n_views, const ms_view_features *views, const ms_pair_mat
         ms_pair_matches &pm = pairs_out[round2[r]];
         memcpy(pm.H, &Hs[9 * (size_t)r], sizeof(pm.H));   // (no model: zeros, as the single call leaves them)
         if (st2[r] != 0) pm.have_H = 0;
+    }
+    return MS_OK;
+}
+
+int ms_list_match_default_params(ms_list_match_params *prm)
+{
+    MS_CHECK(prm, "ms_list_match_default_params: null params");
+    *prm = ms_list_match_params{};
+    prm->struct_size = (unsigned)sizeof(ms_list_match_params);
+    prm->ratio = 0.7; prm->find_homography = 1;
+    prm->ransac_reproj_threshold = 0.0; prm->ransac_max_iters = 0; prm->ransac_confidence = 0.0;
+    return MS_OK;
+}
+
+int ms_match_lists(int n_sets, const ms_view_features *sets, int n_problems, const ms_match_problem *problems, const ms_list_match_params *prm, ms_pair_matches *out,
+                   ms_feature_match *matches_out, int matches_cap, int *n_matches, ms_stream stream)
+{
+    const char *fn = "ms_match_lists";
+    MS_CHECK(sets && problems && prm && out && matches_out && n_matches, "%s: null argument", fn);
+    MS_CHECK(n_sets >= 1 && n_sets <= 2 * MS_MAX_VIEWS, "%s: n_sets = %d outside [1, %d]", fn, n_sets, 2 * MS_MAX_VIEWS);
+    MS_CHECK(n_problems >= 0 && n_problems <= MS_MATCH_MAX_PROBLEMS, "%s: n_problems = %d outside [0, %d]", fn, n_problems, MS_MATCH_MAX_PROBLEMS);
+    MS_CHECK(prm->struct_size == sizeof(ms_list_match_params), "%s: params struct_size %u, this library's is %zu", fn, prm->struct_size, sizeof(ms_list_match_params));
+    MS_CHECK(std::isfinite(prm->ratio) && prm->ratio > 0.0 && prm->ratio <= 1.0, "%s: ratio %g outside (0, 1]", fn, prm->ratio);
+    if (int e = pm_check_ransac(fn, prm->ransac_reproj_threshold, prm->ransac_max_iters, prm->ransac_confidence)) return e;
+    MS_CHECK(matches_cap >= 0, "%s: matches_cap = %d must not be negative", fn, matches_cap);
+    for (int p = 0; p < n_problems; ++p)
+        MS_CHECK(problems[p].query_set >= 0 && problems[p].query_set < n_sets && problems[p].train_set >= 0 && problems[p].train_set < n_sets,
+                 "%s: problem %d names the sets (query_set, train_set) %d, %d outside [0, %d)", fn, p, problems[p].query_set, problems[p].train_set, n_sets);
+    int bytes = 0;
+    if (int e = pm_check_features(fn, "set", n_sets, sets, &bytes)) return e;
+    *n_matches = 0;
+    if (n_problems == 0) return MS_OK;
+    if (int e = require_device()) return e;
+    hipStream_t st = as_stream(stream);
+
+    // tables: sets, one directed segment and one list for every problem with a query row and two train rows or more, (segment, first query) blocks
+    const std::vector<PmView> hv = pm_views(n_sets, sets);
+    std::vector<PmSeg> segs;
+    std::vector<PmBlock> blocks;
+    std::vector<PmList> active;
+    std::vector<int> active_of(n_problems, -1);
+    size_t knn_n = 0;
+    for (int p = 0; p < n_problems; ++p) {
+        const int q = problems[p].query_set, t = problems[p].train_set;
+        if (hv[q].n < 1 || hv[t].n < 2) continue;
+        active_of[p] = (int)active.size();
+        const unsigned slot_off = (unsigned)knn_n;        // a list has room for one slot a query row: slots and 2-NN rows share their offsets
+        active.push_back(PmList{hv[q].n, pm_add_segment(hv, q, t, segs, blocks, knn_n), slot_off, 0u});
+    }
+    const int n_active = (int)active.size();
+    const size_t slot_n = knn_n;
+    std::vector<int> hdr(n_active);
+    std::vector<uint2> slots;
+    if (n_active) {
+        const size_t o_views = 0, o_segs = o_views + pm_align(hv.size() * sizeof(PmView)), o_blocks = o_segs + pm_align(segs.size() * sizeof(PmSeg)),
+                     o_lists = o_blocks + pm_align(blocks.size() * sizeof(PmBlock)), up_bytes = o_lists + pm_align(active.size() * sizeof(PmList));
+        const size_t o_knn = up_bytes, o_out = o_knn + pm_align(knn_n * sizeof(int4)), o_slots = pm_align((size_t)n_active * sizeof(int)),
+                     out_bytes = o_slots + slot_n * sizeof(uint2);
+        char *dev = (char *)device_scratch().get(o_out + out_bytes);         // per-thread grow-only block: see DeviceScratch (common.hpp)
+        if (!dev) return fail(MS_ERR_NOMEM, "%s: cannot allocate %zu bytes of device scratch", fn, o_out + out_bytes);
+        char *pin = (char *)pinned_scratch().get(up_bytes + out_bytes);
+        if (!pin) return fail(MS_ERR_NOMEM, "%s: cannot allocate pinned staging memory", fn);
+        memcpy(pin + o_views, hv.data(), hv.size() * sizeof(PmView));
+        memcpy(pin + o_segs, segs.data(), segs.size() * sizeof(PmSeg));
+        memcpy(pin + o_blocks, blocks.data(), blocks.size() * sizeof(PmBlock));
+        memcpy(pin + o_lists, active.data(), active.size() * sizeof(PmList));
+        hipError_t e = hipMemcpyAsync(dev, pin, up_bytes, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess)                               // (an active problem has a query row, so a block)
+            e = pm_launch_knn2((const PmView *)(dev + o_views), (const PmSeg *)(dev + o_segs), (const PmBlock *)(dev + o_blocks), (unsigned)blocks.size(), bytes,
+                               (int4 *)(dev + o_knn), st);
+        if (e == hipSuccess) {
+            k_list_select<<<n_active, PM_THREADS, 0, st>>>((const PmList *)(dev + o_lists), (const int4 *)(dev + o_knn), prm->ratio, (int *)(dev + o_out),
+                                                           (uint2 *)(dev + o_out + o_slots));
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(pin + up_bytes, dev + o_out, out_bytes, hipMemcpyDeviceToHost, st);
+        const hipError_t se = hipStreamSynchronize(st);      // also after a failed enqueue: nothing of this call stays in flight over the scratch blocks
+        MS_HIP(e);
+        MS_HIP(se);
+        memcpy(hdr.data(), pin + up_bytes, (size_t)n_active * sizeof(int));
+        slots.resize(slot_n);
+        memcpy(slots.data(), pin + up_bytes + o_slots, slot_n * sizeof(uint2));      // (ms_find_homography_ransac_batch below stages through the same pinned block)
+    }
+    long long total = 0;
+    for (int k = 0; k < n_active; ++k) {
+        if (hdr[k] < 0 || hdr[k] > active[k].nq) return fail(MS_ERR_HIP, "%s: the device returned an impossible match count %d for a problem of %d query rows", fn, hdr[k], active[k].nq);
+        total += hdr[k];
+    }
+    *n_matches = (int)total;
+    MS_CHECK(total <= matches_cap, "%s: matches_cap %d below the %lld matches found (*n_matches holds the number)", fn, matches_cap, total);
+
+    // featurefinder.cpp:68-106 for every non-empty list in one batched round: centred points, findHomography(RANSAC), the inlier count; confidence 1
+    std::vector<int> round, off(1, 0);
+    std::vector<float> src, dst;
+    int first = 0;
+    for (int p = 0; p < n_problems; ++p) {
+        ms_pair_matches &pm = out[p];
+        pm = ms_pair_matches{};
+        pm.view_a = problems[p].query_set; pm.view_b = problems[p].train_set; pm.first = first; pm.confidence = 1.0;
+        if (active_of[p] < 0) continue;
+        const int count = hdr[active_of[p]];
+        pm.count = pm.n_forward = count;
+        const uint2 *sl = slots.data() + active[active_of[p]].slot_off;
+        ms_feature_match *m = matches_out + first;
+        for (int i = 0; i < count; ++i) m[i] = ms_feature_match{(int)(sl[i].x & 0xffffu), (int)(sl[i].x >> 16), (int)sl[i].y, 0};
+        first += count;
+        if (!prm->find_homography || count < 1) continue;
+        const ms_view_features &fa = sets[pm.view_a], &fb = sets[pm.view_b];
+        const size_t o = src.size();
+        src.resize(o + 2 * (size_t)count); dst.resize(o + 2 * (size_t)count);
+        for (int i = 0; i < count; ++i) {
+            const float *pa = fa.keypoints + (size_t)m[i].query * fa.keypoint_stride, *pb = fb.keypoints + (size_t)m[i].train * fb.keypoint_stride;
+            src[o + 2 * i] = pa[0] - fa.width * 0.5f; src[o + 2 * i + 1] = pa[1] - fa.height * 0.5f;
+            dst[o + 2 * i] = pb[0] - fb.width * 0.5f; dst[o + 2 * i + 1] = pb[1] - fb.height * 0.5f;
+        }
+        round.push_back(p);
+        off.push_back(off.back() + count);
+    }
+    if (round.empty()) return MS_OK;
+    const int nr = (int)round.size();
+    std::vector<double> Hs(9 * (size_t)nr);
+    std::vector<uint8_t> mask((size_t)off.back() + 1, 0);
+    std::vector<int> status(nr, 1), inl(nr, 0);
+    if (int rc = ms_find_homography_ransac_batch(nr, off.data(), src.data(), dst.data(), prm->ransac_reproj_threshold, prm->ransac_max_iters, prm->ransac_confidence, Hs.data(),
+                                                 mask.data(), inl.data(), status.data(), stream))
+        return rc;
+    for (int r = 0; r < nr; ++r) {
+        ms_pair_matches &pm = out[round[r]];
+        memcpy(pm.H, &Hs[9 * (size_t)r], sizeof(pm.H));    // (no model: zeros, as the single call leaves them)
+        pm.have_H = status[r] == 0;
+        pm.num_inliers = inl[r];
+        ms_feature_match *m = matches_out + pm.first;
+        for (int i = 0; i < pm.count; ++i) m[i].inlier = mask[(size_t)off[r] + i] ? 1 : 0;
     }
     return MS_OK;
 }

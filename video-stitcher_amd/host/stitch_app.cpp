@@ -16,11 +16,14 @@
 //   recalibrate thread (timed.cpp:414-463)       recalibrate(): ms_set_mesh per view from its own stream
 //
 // Usage: stitch_app [--views 6] [--size 1920x1080] [--out 3840x1920] [--hfov 90] [--bands 5] [--frames 300] [--cpw]
-//                   [--i420] [--nv12 | --nv12-direct] [--dump pano.bin] [--no-upload] [--solve-mesh]
+//                   [--i420] [--nv12 | --nv12-direct] [--dump pano.bin] [--no-upload] [--solve-mesh [--temporal ALPHA]]
 //                   [--reference-calib [--work-megapix 0.6] [--seam-megapix 0.01] [--compose-megapix 1.4] [--seam-finder voronoi|dp]]
 //                   [--drop-view V:F0:F1] [--dump-frames frames.bin] [--track-gains K] [--exposure-ramp V:F] [--dump-i420 planes.bin]
 //                   [--lens-brown k1,k2,p1,p2,k3 | --lens-fisheye k1,k2,k3,k4[,max_theta]]
 //                   [--rig-error V:YAW:PITCH:ROLL] [--refine-rig]
+// --temporal ALPHA (with --solve-mesh) switches the mesh solver's temporal term on with that weight (USE_TEMPORAL, meshwarper.cpp:121-151; ALPHAS[3], defs.h:69): from
+// the second round on every view is also matched against itself one round earlier (matchFeaturesBoth: both rings in one call), the previous round's features stay
+// alive for that one round, and the JSON line's "temporal_matches" sums the temporal matches handed to the solver.
 // --rig-error (degrees) renders camera V's scene frames (synth_scene_frame: --solve-mesh's frames and --refine-rig's) through a rig that is really rotated by
 // R_y(yaw) R_x(pitch) R_z(roll) in the camera's own frame, while calibration assumes the ideal ring.  --refine-rig runs, after the first calibration, the device
 // front end between neighbouring views on the projection-warped scene frames (as --solve-mesh does every round), then ms_refine_rig with a Huber threshold of two
@@ -112,6 +115,7 @@ struct Options {
     ms_lens lens{sizeof(ms_lens), MS_LENS_NONE, {0, 0, 0, 0, 0, 0, 0, 0}, 0.0};      // --lens-brown / --lens-fisheye: every camera's lens
     int rig_err_view = -1; double rig_err_deg[3] = {0, 0, 0};    // --rig-error V:YAW:PITCH:ROLL
     bool refine_rig = false;                    // --refine-rig
+    double temporal = 0.0;                      // --temporal ALPHA: the weight of the mesh solver's temporal term (0 = off, as the reference ships it)
     int seam_finder = MS_SEAM_VORONOI;          // --seam-finder voronoi | dp (with --reference-calib: what the seam-scale calibration cuts with)
 };
 constexpr int CAMERA_TIMEOUT_MS = 100;               // --drop-view: how long the main loop waits for a camera's frame before it stitches without it
@@ -268,6 +272,7 @@ int main(int argc, char **argv)
             o.lens.model = MS_LENS_FISHEYE;
         }
         else if (k == "--refine-rig") o.refine_rig = true;
+        else if (k == "--temporal") o.temporal = atof(next());
         else if (k == "--seam-finder") {
             const std::string v = next();
             if (v == "voronoi") o.seam_finder = MS_SEAM_VORONOI;
@@ -287,6 +292,8 @@ int main(int argc, char **argv)
     if (o.rig_err_view >= o.views) { fprintf(stderr, "--rig-error: view %d of %d\n", o.rig_err_view, o.views); return 2; }
     if (o.refine_rig && (o.reference_calib || o.nv12)) { fprintf(stderr, "stitch_app: --refine-rig is wired up for the BASELINE rig with BGR cameras (no --reference-calib, no --nv12)\n"); return 2; }
     if (o.seam_finder != MS_SEAM_VORONOI && !o.reference_calib) { fprintf(stderr, "stitch_app: --seam-finder dp needs --reference-calib (the seam-scale calibration has the images; ms_build_masks has none)\n"); return 2; }
+    if (o.temporal != 0.0 && !o.solve_mesh) { fprintf(stderr, "--temporal needs --solve-mesh\n"); return 2; }
+    if (!(o.temporal >= 0.0) || !std::isfinite(o.temporal)) { fprintf(stderr, "--temporal wants ALPHA >= 0\n"); return 2; }
     if (o.track_gains < 0) { fprintf(stderr, "--track-gains wants K >= 0\n"); return 2; }
     if (!o.dump_i420.empty() && !o.i420) { fprintf(stderr, "--dump-i420 needs --i420\n"); return 2; }
     if (o.fused_resize && !o.nv12_direct) { fprintf(stderr, "--fused-resize needs --nv12-direct\n"); return 2; }
@@ -559,7 +566,7 @@ int main(int argc, char **argv)
         std::atomic<int> recalibrations{0};
         std::vector<int> view_round(o.views, 0);          // the round whose mesh each view holds (read after the thread is joined)
         std::atomic<int> solver_iterations{0};
-        std::atomic<long long> total_keypoints{0}, total_matches{0}, total_inliers{0};
+        std::atomic<long long> total_keypoints{0}, total_matches{0}, total_inliers{0}, total_temporal{0};
         std::atomic<float> max_disp{0.f};
         std::string recal_failure;
         if (o.solve_mesh)
@@ -572,6 +579,9 @@ int main(int argc, char **argv)
                     msshim::MeshWarper mw(o.views, 10, 10, warp_scale, 1.0, 1.0);
                     mw.params().theta_rule = 1;
                     mw.params().global_dist = std::max(4, std::min(30, o.out_w / 128));    // GLOBAL_DIST = 30 is tuned to 1080p views; scaled for small rigs
+                    const bool temporal = o.temporal > 0.0;
+                    if (temporal) mw.params().alphas[3] = (float)o.temporal;
+                    std::vector<ff::ImageFeatures<DevMat>> prev_feats;                          // --temporal: prev_features (meshwarper.cpp:313), device descriptors included
                     std::vector<DevMat> recal_full(o.views), images(o.views);
                     std::vector<ms_view_geom> g(o.views);
                     for (int i = 0; i < o.views; ++i) {
@@ -602,12 +612,17 @@ int main(int argc, char **argv)
                         std::vector<ff::ImageFeatures<DevMat>> feats;
                         ff::findFeatures(images, fmasks, feats, (ms_stream)recal_stream);
                         std::vector<ff::MatchesInfo> pairwise(o.views);                      // NUM_IMAGES - 1 + wrapAround (calibration.cpp:284)
-                        ff::matchFeatures(feats, pairwise, (ms_stream)recal_stream);
+                        std::vector<ff::MatchesInfo> temporal_matches(temporal ? o.views : 0);
+                        if (temporal && !prev_feats.empty()) ff::matchFeaturesBoth(feats, prev_feats, pairwise, temporal_matches, (ms_stream)recal_stream);
+                        else ff::matchFeatures(feats, pairwise, (ms_stream)recal_stream);
                         for (auto &m : fmasks) if (m.data) HIPCHECK(hipFree(m.data));
-                        for (auto &f : feats) if (f.descriptors.data) HIPCHECK(hipFree(f.descriptors.data));
+                        if (!temporal) for (auto &f : feats) if (f.descriptors.data) HIPCHECK(hipFree(f.descriptors.data));
+                        for (auto &f : prev_feats) if (f.descriptors.data) HIPCHECK(hipFree(f.descriptors.data));      // the round before: matched, not needed again
                         { size_t nk = 0, nm = 0, ni = 0; for (auto &f : feats) nk += f.keypoints.size(); for (auto &pm : pairwise) { nm += pm.matches.size(); ni += pm.num_inliers; }
                           total_keypoints += (long long)nk; total_matches += (long long)nm; total_inliers += (long long)ni; }
-                        const ms_mesh_info info = mw.calibrateMeshWarp(comp, images, feats, pairwise, (ms_stream)recal_stream);
+                        const ms_mesh_info info = temporal ? mw.calibrateMeshWarp(comp, images, feats, pairwise, temporal_matches, prev_feats, (ms_stream)recal_stream)
+                                                           : mw.calibrateMeshWarp(comp, images, feats, pairwise, (ms_stream)recal_stream);
+                        if (temporal) { total_temporal += (long long)mw.temporalSelected(); prev_feats = feats; }      // (DevMat copies are handles: the descriptors stay where they are)
                         solver_iterations += info.iterations;
                         if (getenv("STITCH_APP_TRACE")) {
                             size_t nm = 0; for (auto &pm : pairwise) nm += pm.matches.size();
@@ -620,6 +635,7 @@ int main(int argc, char **argv)
                         }
                         ++round; ++recalibrations;
                     }
+                    for (auto &f : prev_feats) if (f.descriptors.data) HIPCHECK(hipFree(f.descriptors.data));
                 } catch (const std::exception &e) { recal_failure = e.what(); }
             });
         else if (o.cpw)
@@ -778,6 +794,7 @@ int main(int argc, char **argv)
                o.views, o.w, o.h, o.out_w, o.out_h, pg.num_bands, o.cpw ? "true" : "false", o.i420 ? "true" : "false", o.nv12 ? "true" : "false", o.nv12_direct ? "true" : "false", o.upload ? "true" : "false",
                consumed, secs, consumed / secs, recalibrations.load(), solver_iterations.load(), (double)max_disp.load(),
                total_keypoints.load(), total_matches.load(), total_inliers.load(), o.update_mask, selfcheck < 0 ? "null" : (selfcheck ? "true" : "false"), consume_image_height, consume_checksum, checksum, degraded_frames, i420_call, fused_resize ? "true" : "false", comp.mapSource(), comp.seamFinder() == MS_SEAM_DP ? "dp" : "voronoi");
+        if (o.temporal > 0.0) printf(", \"temporal_alpha\": %g, \"temporal_matches\": %lld", o.temporal, total_temporal.load());
         if (o.track_gains > 0) {
             std::vector<double> g((size_t)o.views);
             int ok = 0, singular = 0;

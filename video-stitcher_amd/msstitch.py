@@ -174,6 +174,18 @@ class PairMatches(C.Structure):
                 ("H", C.c_double * 9), ("confidence", C.c_double)]
 
 
+MATCH_MAX_PROBLEMS = 64             # MS_MATCH_MAX_PROBLEMS
+
+
+class MatchProblem(C.Structure):
+    _fields_ = [("query_set", C.c_int), ("train_set", C.c_int)]
+
+
+class ListMatchParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("ratio", C.c_double), ("find_homography", C.c_int), ("ransac_reproj_threshold", C.c_double), ("ransac_max_iters", C.c_int),
+                ("ransac_confidence", C.c_double)]
+
+
 class GainTrackParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint), ("stride", C.c_int), ("smoothing", C.c_double)]
 
@@ -234,6 +246,7 @@ EXPORTS = [
     "ms_pair_match_default_params", "ms_match_pairs", "ms_biggest_component", "ms_wave_correct",
     "ms_find_homography_ransac_batch",
     "ms_orb_detect_and_compute_batch",
+    "ms_list_match_default_params", "ms_match_lists", "ms_feature_inputs_batch",
     "ms_lens_unproject", "ms_lens_unproject_points", "ms_rig_lens_accumulate", "ms_refine_rig_cameras_lens", "ms_refine_rig_focals_lens",
 ]
 
@@ -823,6 +836,39 @@ def match_pairs(features, matches_cap=None, params=None, pair_mask=None, **kw):
     return res
 
 
+def list_match_default_params(**kw):
+    """ms_list_match_default_params; keyword arguments override fields"""
+    p = ListMatchParams()
+    _chk(load().ms_list_match_default_params(C.byref(p)))
+    for k, v in kw.items():
+        assert hasattr(p, k), k
+        setattr(p, k, v)
+    return p
+
+
+def match_lists(sets, problems, matches_cap=None, params=None, **kw):
+    """ms_match_lists (featurefinder::matchFeatures / matchFeaturesTemporal over a list of directed problems): sets as view_features takes them, problems a list of
+    (query_set, train_set); keyword arguments override fields of ms_list_match_params (ratio, find_homography, ransac_*).  Returns one dict per problem, as match_pairs
+    does: view_a (the query set), view_b (the train set), first, count, n_forward, num_inliers, have_H, H (3 x 3 float64, None without a model), confidence, and
+    matches, a (count, 4) int32 array of (query, train, distance, inlier)."""
+    import numpy as np
+    prm = params if params is not None else list_match_default_params(**kw)
+    table, keep = view_features(sets)
+    k = len(problems)
+    probs = (MatchProblem * max(1, k))(*[MatchProblem(int(q), int(t)) for q, t in problems])
+    if matches_cap is None:         # a problem's list never holds more than one match per query row
+        matches_cap = sum(max(table[q].n_keypoints, 0) for q, _ in problems if 0 <= q < len(sets))
+    recs = (PairMatches * max(1, k))()
+    out = np.zeros((max(1, matches_cap), 4), np.int32)
+    n_matches = C.c_int(0)
+    _chk(load().ms_match_lists(len(sets), table, k, probs, C.byref(prm), recs, out.ctypes.data_as(C.POINTER(FeatureMatch)), int(matches_cap), C.byref(n_matches),
+                               _stream() if k else None))      # (an empty list needs no device)
+    del keep
+    return [{"view_a": p.view_a, "view_b": p.view_b, "first": p.first, "count": p.count, "n_forward": p.n_forward, "num_inliers": p.num_inliers, "have_H": p.have_H,
+             "H": np.array(p.H[:], np.float64).reshape(3, 3) if p.have_H else None, "confidence": p.confidence, "matches": out[p.first:p.first + p.count].copy()}
+            for p in recs[:k]]
+
+
 def pair_matches(pairs):
     """match_pairs' records (view_a, view_b, confidence are read) -> a PairMatches array, for biggest_component"""
     arr = (PairMatches * max(1, len(pairs)))()
@@ -905,6 +951,23 @@ def bgr_to_gray(src):
     dst = _new(tuple(src.shape[:2]), _torch().uint8)
     _chk(load().ms_bgr_to_gray(C.byref(img(src)), C.byref(img(dst)), _stream()))
     return dst
+
+
+def feature_inputs_batch(views, bands=None, gray=True, masks=None):
+    """ms_feature_inputs_batch: the grey images (gray=True) and / or the feature masks (masks defaults to `bands is not None`) of every 8UC3 view in one launch; bands:
+    one (a_x0, a_width, b_x0, b_width) per view.  Returns (list of grey tensors or None, list of mask tensors or None)."""
+    import numpy as np
+    n = len(views)
+    if masks is None:
+        masks = bands is not None
+    u8 = _torch().uint8
+    g = [_new(tuple(t.shape[:2]), u8) for t in views] if gray else None
+    m = [_new(tuple(t.shape[:2]), u8) for t in views] if masks else None
+    b = None if bands is None else np.ascontiguousarray(bands, np.int32).reshape(n, 4)
+    arr = lambda ts: (Image * max(n, 1))(*[img(t) for t in ts])
+    _chk(load().ms_feature_inputs_batch(n, arr(views), None if b is None else b.ctypes.data_as(C.POINTER(C.c_int)), arr(g) if gray else None, arr(m) if masks else None,
+                                        _stream()))
+    return g, m
 
 
 def resize_linear_batch_prepared(srcs, dsts, fx=0.0, fy=0.0):

@@ -11,6 +11,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 #include "../../include/ms_stitch.h"
 
@@ -326,16 +327,24 @@ struct MatchesInfo {
 template <class Mat> void featureMasks(const std::vector<Mat> &images, std::vector<Mat> &masks, int overlap = 400, ms_stream s = nullptr)
 {
     masks.resize(images.size());
-    for (size_t idx = 0; idx < images.size(); ++idx) {
-        const int cols = images[idx].cols, rows = images[idx].rows;
-        masks[idx].create(rows, cols, MS_8UC1);
-        int ax0 = 0, bx0 = cols - overlap;
-        if (idx == 3 && images.size() == 6) {        // "Opencv splits the third video (idx == 3) in the middle"
-            const float split_l = images[0].cols * 0.25f * 2.0f, split_r = -images[0].cols * 0.25f * 2.0f;
-            ax0 = (int)split_l - overlap; bx0 = cols + (int)split_r;
+    // every view's mask in ONE ms_feature_inputs_batch launch, MS_MAX_VIEWS views at a time
+    for (size_t i0 = 0; i0 < images.size(); i0 += MS_MAX_VIEWS) {
+        const size_t m = std::min(images.size() - i0, (size_t)MS_MAX_VIEWS);
+        std::vector<ms_image> im(m), mk(m);
+        std::vector<int> bands(4 * m);
+        for (size_t j = 0; j < m; ++j) {
+            const size_t idx = i0 + j;
+            const int cols = images[idx].cols, rows = images[idx].rows;
+            masks[idx].create(rows, cols, MS_8UC1);
+            int ax0 = 0, bx0 = cols - overlap;
+            if (idx == 3 && images.size() == 6) {        // "Opencv splits the third video (idx == 3) in the middle"
+                const float split_l = images[0].cols * 0.25f * 2.0f, split_r = -images[0].cols * 0.25f * 2.0f;
+                ax0 = (int)split_l - overlap; bx0 = cols + (int)split_r;
+            }
+            im[j] = wrap(images[idx]); mk[j] = wrap(masks[idx]);
+            bands[4 * j] = ax0; bands[4 * j + 1] = overlap; bands[4 * j + 2] = bx0; bands[4 * j + 3] = overlap;
         }
-        ms_image im = wrap(images[idx]), mk = wrap(masks[idx]);
-        check(ms_feature_mask(&im, ax0, overlap, bx0, overlap, &mk, s));
+        check(ms_feature_inputs_batch((int)m, im.data(), bands.data(), nullptr, mk.data(), s));
     }
 }
 
@@ -348,23 +357,24 @@ template <class Mat> void findFeatures(const std::vector<Mat> &images, const std
     check(ms_orb_default_params(&prm));
     prm.nfeatures = nfeatures; prm.scale_factor = scale_factor; prm.nlevels = nlevels;
     const int cap = nfeatures + nlevels / 2;        // the rounded per-level budgets can add up to (nlevels - 1) / 2 more than nfeatures (ms_stitch.h)
-    // grey per view as the reference converts it, then every view's detectAndCompute in ONE ms_orb_detect_and_compute_batch call, MS_MAX_VIEWS views at a time
+    // grey as the reference converts it, every view in ONE ms_feature_inputs_batch launch, then every view's detectAndCompute in ONE ms_orb_detect_and_compute_batch
+    // call, MS_MAX_VIEWS views at a time
     for (size_t i0 = 0; i0 < images.size(); i0 += MS_MAX_VIEWS) {
         const size_t m = std::min(images.size() - i0, (size_t)MS_MAX_VIEWS);
         std::vector<Mat> gray(m);
-        std::vector<ms_image> g(m), mk(m), d(m);
+        std::vector<ms_image> im(m), g(m), mk(m), d(m);
         std::vector<float> kp((size_t)6 * cap * m);
         std::vector<int> n(m, 0);
         for (size_t j = 0; j < m; ++j) {
             const size_t i = i0 + j;
             gray[j].create(images[i].rows, images[i].cols, MS_8UC1);
-            ms_image im = wrap(images[i]);
+            im[j] = wrap(images[i]);
             g[j] = wrap(gray[j]);
-            check(ms_bgr_to_gray(&im, &g[j], s));                                      // cuda::cvtColor(gpu_img, gpu_img, CV_BGR2GRAY)
             features[i].descriptors.create(cap, 32, MS_8UC1);
             d[j] = wrap(features[i].descriptors);
             mk[j] = (i < masks.size() && masks[i].data) ? wrap(masks[i]) : ms_image{};
         }
+        check(ms_feature_inputs_batch((int)m, im.data(), nullptr, g.data(), nullptr, s));       // cuda::cvtColor(gpu_img, gpu_img, CV_BGR2GRAY)
         check(ms_orb_detect_and_compute_batch((int)m, g.data(), mk.data(), &prm, kp.data(), cap, d.data(), n.data(), s));
         for (size_t j = 0; j < m; ++j) {
             const size_t i = i0 + j;
@@ -380,49 +390,108 @@ template <class Mat> void findFeatures(const std::vector<Mat> &images, const std
 }
 
 // the body shared by matchFeatures (featurefinder.cpp:48-108) and matchFeaturesTemporal (:110-170): knnMatch(k = 2) + 0.7 ratio, centred points,
-// findHomography(RANSAC), inlier count; confidence ends as 1 in both
+// findHomography(RANSAC), inlier count; confidence ends as 1 in both.  matchLists runs it for a list of (query features, train features) pairs in ONE ms_match_lists
+// call -- MS_MATCH_MAX_PROBLEMS / 4 pairs at a time, so that the sets a call names always fit its table --; info[p] receives pair p's result.
+template <class Mat> void matchLists(const std::vector<std::pair<const ImageFeatures<Mat> *, const ImageFeatures<Mat> *>> &pairs, const std::vector<MatchesInfo *> &info,
+                                     ms_stream s = nullptr)
+{
+    static_assert(sizeof(KeyPoint) == 6 * sizeof(float), "KeyPoint rows are read as 6 floats, x and y first");
+    const size_t chunk = MS_MATCH_MAX_PROBLEMS / 4;          // 16 problems name 32 sets at most: 2 * MS_MAX_VIEWS
+    ms_list_match_params prm;
+    check(ms_list_match_default_params(&prm));
+    for (size_t p0 = 0; p0 < pairs.size(); p0 += chunk) {
+        const size_t m = std::min(pairs.size() - p0, chunk);
+        std::vector<const ImageFeatures<Mat> *> table;
+        std::vector<ms_match_problem> problems(m);
+        size_t cap = 0;
+        for (size_t j = 0; j < m; ++j) {
+            const ImageFeatures<Mat> *f[2] = {pairs[p0 + j].first, pairs[p0 + j].second};
+            int at[2];
+            for (int k = 0; k < 2; ++k) {
+                const size_t i = (size_t)(std::find(table.begin(), table.end(), f[k]) - table.begin());
+                if (i == table.size()) table.push_back(f[k]);
+                at[k] = (int)i;
+            }
+            problems[j] = ms_match_problem{at[0], at[1]};
+            cap += f[0]->keypoints.size();                   // a list holds at most one match per query row
+        }
+        std::vector<ms_view_features> sets(table.size());
+        for (size_t i = 0; i < table.size(); ++i) {          // (a set without keypoints takes no part: its image size may be unset)
+            const ImageFeatures<Mat> &f = *table[i];
+            const bool none = f.keypoints.empty();
+            sets[i] = ms_view_features{wrap(f.descriptors), none ? nullptr : &f.keypoints[0].pt.x, 6, (int)f.keypoints.size(), none ? 1 : f.img_size.width, none ? 1 : f.img_size.height};
+        }
+        std::vector<ms_pair_matches> out(m);
+        std::vector<ms_feature_match> matches(cap + 1);
+        int n_matches = 0;
+        check(ms_match_lists((int)sets.size(), sets.data(), (int)m, problems.data(), &prm, out.data(), matches.data(), (int)cap, &n_matches, s));
+        for (size_t j = 0; j < m; ++j) {
+            MatchesInfo &pm = *info[p0 + j];
+            const ms_pair_matches &r = out[j];
+            pm.matches.clear(); pm.inliers_mask.clear(); pm.num_inliers = 0; pm.have_H = false;
+            for (int i = 0; i < r.count; ++i) {
+                const ms_feature_match &fm = matches[r.first + i];
+                pm.matches.push_back(DMatch{fm.query, fm.train, (float)fm.distance});
+                pm.inliers_mask.push_back((unsigned char)fm.inlier);
+            }
+            if (r.count > 0) {                               // findHomography ran: H (zeros without a model), the inlier count
+                for (int e = 0; e < 9; ++e) pm.H[e] = r.H[e];
+                pm.num_inliers = r.num_inliers; pm.have_H = r.have_H != 0;
+            }
+            pm.confidence = r.confidence;
+        }
+    }
+}
 template <class Mat> void matchPair(const ImageFeatures<Mat> &f1, const ImageFeatures<Mat> &f2, MatchesInfo &pm, ms_stream s = nullptr)
 {
-    pm.matches.clear(); pm.inliers_mask.clear(); pm.num_inliers = 0; pm.have_H = false;
-    const int n1 = (int)f1.keypoints.size(), n2 = (int)f2.keypoints.size();
-    if (n1 > 0 && n2 > 0) {
-        ms_image q = wrap(f1.descriptors), t = wrap(f2.descriptors);
-        q.rows = n1; t.rows = n2;
-        std::vector<int> idx((size_t)2 * n1), dist((size_t)2 * n1);
-        check(ms_knn_match_hamming2(&q, &t, idx.data(), dist.data(), s));
-        for (int j = 0; j < n1; ++j)
-            if (idx[2 * j + 1] >= 0 && (float)dist[2 * j] < 0.7 * (float)dist[2 * j + 1]) pm.matches.push_back(DMatch{j, idx[2 * j], (float)dist[2 * j]});
-    }
-    if (!pm.matches.empty()) {
-        std::vector<float> src(2 * pm.matches.size()), dst(2 * pm.matches.size());
-        for (size_t j = 0; j < pm.matches.size(); ++j) {
-            const DMatch &m = pm.matches[j];
-            src[2 * j] = f1.keypoints[m.queryIdx].pt.x - f1.img_size.width * 0.5f; src[2 * j + 1] = f1.keypoints[m.queryIdx].pt.y - f1.img_size.height * 0.5f;
-            dst[2 * j] = f2.keypoints[m.trainIdx].pt.x - f2.img_size.width * 0.5f; dst[2 * j + 1] = f2.keypoints[m.trainIdx].pt.y - f2.img_size.height * 0.5f;
-        }
-        pm.inliers_mask.assign(pm.matches.size(), 0);
-        const int rc = ms_find_homography_ransac(src.data(), dst.data(), (int)pm.matches.size(), 0, 0, 0, pm.H, pm.inliers_mask.data(), &pm.num_inliers, s);
-        check(rc);
-        pm.have_H = rc == 0;
-    }
-    pm.confidence = 1;
+    matchLists<Mat>({{&f1, &f2}}, {&pm}, s);                 // the batch of one
 }
-template <class Mat> void matchFeatures(const std::vector<ImageFeatures<Mat>> &features, std::vector<MatchesInfo> &pairwise_matches, ms_stream s = nullptr)
+// the ring of featurefinder.cpp:55-59: view i against its left neighbour
+template <class Mat> void ringPairs(const std::vector<ImageFeatures<Mat>> &features, std::vector<MatchesInfo> &pairwise_matches,
+                                    std::vector<std::pair<const ImageFeatures<Mat> *, const ImageFeatures<Mat> *>> &pairs, std::vector<MatchesInfo *> &info)
 {
     const int n = (int)features.size();
     for (size_t i = 0; i < pairwise_matches.size(); ++i) {
         const int idx1 = (int)i, idx2 = i == 0 ? n - 1 : (int)i - 1;
         pairwise_matches[i].src_img_idx = idx1; pairwise_matches[i].dst_img_idx = idx2;
-        matchPair(features[idx1], features[idx2], pairwise_matches[i], s);
+        pairs.push_back({&features[idx1], &features[idx2]});
+        info.push_back(&pairwise_matches[i]);
     }
+}
+// featurefinder.cpp:117-121: view i now against view i of the previous round
+template <class Mat> void temporalPairs(const std::vector<ImageFeatures<Mat>> &features, const std::vector<ImageFeatures<Mat>> &prev_features, std::vector<MatchesInfo> &temporal_matches,
+                                        std::vector<std::pair<const ImageFeatures<Mat> *, const ImageFeatures<Mat> *>> &pairs, std::vector<MatchesInfo *> &info)
+{
+    for (size_t i = 0; i < temporal_matches.size(); ++i) {
+        temporal_matches[i].src_img_idx = temporal_matches[i].dst_img_idx = (int)i;
+        pairs.push_back({&features[i], &prev_features[i]});
+        info.push_back(&temporal_matches[i]);
+    }
+}
+template <class Mat> void matchFeatures(const std::vector<ImageFeatures<Mat>> &features, std::vector<MatchesInfo> &pairwise_matches, ms_stream s = nullptr)
+{
+    std::vector<std::pair<const ImageFeatures<Mat> *, const ImageFeatures<Mat> *>> pairs;
+    std::vector<MatchesInfo *> info;
+    ringPairs(features, pairwise_matches, pairs, info);
+    matchLists<Mat>(pairs, info, s);
 }
 template <class Mat> void matchFeaturesTemporal(const std::vector<ImageFeatures<Mat>> &features, const std::vector<ImageFeatures<Mat>> &prev_features,
                                                 std::vector<MatchesInfo> &pairwise_matches, ms_stream s = nullptr)
 {
-    for (size_t i = 0; i < pairwise_matches.size(); ++i) {
-        pairwise_matches[i].src_img_idx = pairwise_matches[i].dst_img_idx = (int)i;
-        matchPair(features[i], prev_features[i], pairwise_matches[i], s);
-    }
+    std::vector<std::pair<const ImageFeatures<Mat> *, const ImageFeatures<Mat> *>> pairs;
+    std::vector<MatchesInfo *> info;
+    temporalPairs(features, prev_features, pairwise_matches, pairs, info);
+    matchLists<Mat>(pairs, info, s);
+}
+// both of the above in one call (createMesh with USE_TEMPORAL, meshwarper.cpp:119-125): with N views, 2N problems over a table of 2N sets
+template <class Mat> void matchFeaturesBoth(const std::vector<ImageFeatures<Mat>> &features, const std::vector<ImageFeatures<Mat>> &prev_features,
+                                            std::vector<MatchesInfo> &pairwise_matches, std::vector<MatchesInfo> &temporal_matches, ms_stream s = nullptr)
+{
+    std::vector<std::pair<const ImageFeatures<Mat> *, const ImageFeatures<Mat> *>> pairs;
+    std::vector<MatchesInfo *> info;
+    ringPairs(features, pairwise_matches, pairs, info);
+    temporalPairs(features, prev_features, temporal_matches, pairs, info);
+    matchLists<Mat>(pairs, info, s);
 }
 
 // detail::BestOf2NearestMatcher / BestOf2NearestRangeMatcher::operator() (OCV/stitching/src/matchers.cpp:784-808 -> MatchPairsBody, :65-111) over ms_match_pairs:
@@ -483,6 +552,7 @@ class MeshWarper {
 public:
     static const int RECALIB_THRESH = 15;            // defs.h:49
     static const int MAX_FEATURES_PER_IMAGE = 100;   // defs.h:60
+    static const int MAX_TEMPORAL_FEATURES_PER_IMAGE = 100;   // defs.h:61
 
     MeshWarper(int num_images, int mesh_width, int mesh_height, float focal_length, double compose_scale, double work_scale)
         : n_(num_images), old_(num_images), prev_(num_images), prev_avg_(2 * num_images, 0.f), have_old_(num_images, 0)
@@ -564,23 +634,58 @@ public:
         return use;
     }
 
+    // filterTemporalMatches, meshwarper.cpp:948-982: inliers of a view's match against itself one round earlier that moved no more than 30 px along either axis;
+    // (x1, y1) is the point now, (x2, y2) the point in the previous round's keypoints
+    template <class Features, class Matches>
+    void filterTemporalMatches(const std::vector<Matches> &temporal_matches, const std::vector<Features> &features, const std::vector<Features> &prev_features,
+                               std::vector<std::vector<ms_mesh_match>> &filt) const
+    {
+        filt.assign(n_, {});
+        for (const Matches &pw : temporal_matches) {
+            const int src = pw.src_img_idx, dst = pw.dst_img_idx;
+            if (!pw.matches.size() || !pw.num_inliers) continue;
+            for (size_t i = 0; i < pw.inliers_mask.size(); ++i) {
+                if (!pw.inliers_mask[i]) continue;
+                const auto &p1 = features[src].keypoints[pw.matches[i].queryIdx].pt;
+                const auto &p2 = prev_features[dst].keypoints[pw.matches[i].trainIdx].pt;
+                if (std::fabs(p1.y - p2.y) > 30) continue;
+                if (std::fabs(p1.x - p2.x) > 30) continue;
+                filt[src].push_back(ms_mesh_match{p1.x, p1.y, p2.x, p2.y, dst});
+            }
+        }
+    }
+    // the lists createMesh hands to calcTemporalLocalTerm (meshwarper.cpp:139-150): the first MAX_TEMPORAL_FEATURES_PER_IMAGE of every view's filtered matches
+    template <class Features, class Matches>
+    std::vector<std::vector<ms_mesh_match>> selectTemporal(const std::vector<Matches> &temporal_matches, const std::vector<Features> &features,
+                                                           const std::vector<Features> &prev_features) const
+    {
+        std::vector<std::vector<ms_mesh_match>> all;
+        filterTemporalMatches(temporal_matches, features, prev_features, all);
+        for (auto &l : all) l.resize(std::min<size_t>(MAX_TEMPORAL_FEATURES_PER_IMAGE, l.size()));
+        return all;
+    }
+
     // createMesh from the matching step on: warped = images[idx] (the remapped frames, device 8UC3); meshes come back as n x N x M host floats
     template <class Mat, class Features, class Matches>
     ms_mesh_info createMesh(const std::vector<Mat> &warped, const std::vector<Features> &features, const std::vector<Matches> &pairwise_matches,
                             std::vector<float> &mesh_x, std::vector<float> &mesh_y, ms_stream s = nullptr)
     {
-        const std::vector<std::vector<ms_mesh_match>> use = select(features, pairwise_matches);
-        std::vector<ms_image> views;
-        std::vector<ms_mesh_match> flat;
-        std::vector<int> count;
-        for (const Mat &m : warped) views.push_back(wrap(m));
-        for (const auto &l : use) { flat.insert(flat.end(), l.begin(), l.end()); count.push_back((int)l.size()); }
-        mesh_x.assign((size_t)n_ * prm_.mesh_rows * prm_.mesh_cols, 0.f);
-        mesh_y.assign(mesh_x.size(), 0.f);
-        ms_mesh_info info{};
-        check(ms_create_mesh(n_, views.data(), flat.data(), count.data(), nullptr, nullptr, &prm_, mesh_x.data(), mesh_y.data(), &info, s));
-        return info;
+        return solve(warped, select(features, pairwise_matches), nullptr, mesh_x, mesh_y, s);
     }
+    // ... with USE_TEMPORAL (meshwarper.cpp:121-151, :289-291): temporal_matches from matchFeaturesTemporal / matchFeaturesBoth against prev_features, the features of
+    // the round before.  Without previous features (the first round) or with params().alphas[3] == 0 there is no temporal term, as in the overload above.
+    // temporalSelected() tells how many temporal matches the last call handed to the solver.
+    template <class Mat, class Features, class Matches>
+    ms_mesh_info createMesh(const std::vector<Mat> &warped, const std::vector<Features> &features, const std::vector<Matches> &pairwise_matches,
+                            const std::vector<Matches> &temporal_matches, const std::vector<Features> &prev_features, std::vector<float> &mesh_x, std::vector<float> &mesh_y,
+                            ms_stream s = nullptr)
+    {
+        const std::vector<std::vector<ms_mesh_match>> use = select(features, pairwise_matches);
+        if (prev_features.empty() || prm_.alphas[3] == 0) return solve(warped, use, nullptr, mesh_x, mesh_y, s);
+        const std::vector<std::vector<ms_mesh_match>> temporal = selectTemporal(temporal_matches, features, prev_features);
+        return solve(warped, use, &temporal, mesh_x, mesh_y, s);
+    }
+    size_t temporalSelected() const { return temporal_selected_; }
 
     // calibrateMeshWarp (meshwarper.cpp:356-376): createMesh + convertMeshesToMap into the compositor
     template <class Mat, class Features, class Matches>
@@ -593,8 +698,40 @@ public:
         for (int v = 0; v < n_; ++v) comp.convertMeshToMap(v, mx.data() + v * per, my.data() + v * per, prm_.mesh_rows, prm_.mesh_cols, s);
         return info;
     }
+    // ... with the temporal term: createMesh's second overload
+    template <class Mat, class Features, class Matches>
+    ms_mesh_info calibrateMeshWarp(Compositor &comp, const std::vector<Mat> &warped, const std::vector<Features> &features, const std::vector<Matches> &pairwise_matches,
+                                   const std::vector<Matches> &temporal_matches, const std::vector<Features> &prev_features, ms_stream s = nullptr)
+    {
+        std::vector<float> mx, my;
+        const ms_mesh_info info = createMesh(warped, features, pairwise_matches, temporal_matches, prev_features, mx, my, s);
+        const size_t per = (size_t)prm_.mesh_rows * prm_.mesh_cols;
+        for (int v = 0; v < n_; ++v) comp.convertMeshToMap(v, mx.data() + v * per, my.data() + v * per, prm_.mesh_rows, prm_.mesh_cols, s);
+        return info;
+    }
 
 private:
+    // createMesh's loop + solve over the selected lists; temporal: nullptr, or one list per view
+    template <class Mat>
+    ms_mesh_info solve(const std::vector<Mat> &warped, const std::vector<std::vector<ms_mesh_match>> &use, const std::vector<std::vector<ms_mesh_match>> *temporal,
+                       std::vector<float> &mesh_x, std::vector<float> &mesh_y, ms_stream s)
+    {
+        std::vector<ms_image> views;
+        std::vector<ms_mesh_match> flat, tflat;
+        std::vector<int> count, tcount;
+        for (const Mat &m : warped) views.push_back(wrap(m));
+        for (const auto &l : use) { flat.insert(flat.end(), l.begin(), l.end()); count.push_back((int)l.size()); }
+        if (temporal) for (const auto &l : *temporal) { tflat.insert(tflat.end(), l.begin(), l.end()); tcount.push_back((int)l.size()); }
+        temporal_selected_ = tflat.size();
+        mesh_x.assign((size_t)n_ * prm_.mesh_rows * prm_.mesh_cols, 0.f);
+        mesh_y.assign(mesh_x.size(), 0.f);
+        ms_mesh_info info{};
+        check(ms_create_mesh(n_, views.data(), flat.data(), count.data(), temporal ? tflat.data() : nullptr, temporal ? tcount.data() : nullptr, &prm_, mesh_x.data(), mesh_y.data(),
+                             &info, s));
+        return info;
+    }
+
+    size_t temporal_selected_ = 0;
     int n_;
     ms_mesh_params prm_{};
     std::vector<std::vector<ms_mesh_match>> old_, prev_;    // old_matches / prev_matches, resolved to positions

@@ -60,6 +60,18 @@ int shim_compile_check()
         msshim::MeshWarper mw(6, 10, 10, 600.f, 1.0, 0.5);
         mw.calibrateMeshWarp(comp, frames, ffeats, fpair);
         mw.calibrateMeshWarp(comp, frames, feats, pairwise);
+        // USE_TEMPORAL (meshwarper.cpp:121-151): one pair alone, both rings in one call, the ±30 px filter and the mesh with the temporal term
+        msshim::featurefinder::matchPair(ffeats[0], ffeats[1], fpair[0]);
+        std::vector<msshim::featurefinder::MatchesInfo> ftemp(6);
+        msshim::featurefinder::matchFeaturesBoth(ffeats, fprev, fpair, ftemp);
+        mw.params().alphas[3] = 0.01f;
+        std::vector<std::vector<ms_mesh_match>> tfilt;
+        mw.filterTemporalMatches(ftemp, ffeats, fprev, tfilt);
+        mw.calibrateMeshWarp(comp, frames, ffeats, fpair, ftemp, fprev);
+        std::vector<Matches> temporal(6);
+        std::vector<float> mesh_x, mesh_y;
+        mw.createMesh(frames, feats, pairwise, temporal, feats, mesh_x, mesh_y);
+        (void)mw.temporalSelected();
     } catch (const msshim::Error &e) {
         return e.code;
     }
