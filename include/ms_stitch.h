@@ -1271,6 +1271,110 @@ MS_API int ms_selftest_divide_range(float d_lo, float d_hi, unsigned long long *
  * the rint / clamp / NaN->0 definition over ALL 2^32 float bit patterns on the device; *mismatches_out must come back 0. */
 MS_API int ms_selftest_cvt_u8(unsigned long long *mismatches_out, ms_stream stream);
 
+/* =============================================================================================
+ * 5. Virtual cameras: viewports, cube faces and re-levelled panoramas rendered from the panorama
+ * =============================================================================================
+ * The reference stops at the equirect: consume() ships it to a player that "place[s] the image correctly on the sphere" (APP/timed.cpp:296-300) and the
+ * re-projection happens there.  These entry points do the player's step on the device: the direction "virtual camera pixel -> panorama pixel" as dense maps
+ * (ms_build_view_maps: detail::{Spherical,Cylindrical}Projector::mapForward, OCV/stitching/include/opencv2/stitching/detail/warpers_inl.hpp:222-236, :258-273, behind
+ * the inverse lens model of ms_lens_unproject), and a batched cuda::remap that wraps at the +-pi seam (ms_reproject).
+ * Stated limits: 8UC3 panoramas only (no 16S source); INTER_LINEAR only (no nearest, no cubic); no antialiasing -- a view coarser than the panorama point-samples
+ * it, as cuda::remap does; coordinates always come from maps (a pose that changes every frame rebuilds them: ms_build_view_maps is one launch); MS_PROJ_PLANE
+ * panoramas are MS_ERR_UNSUPPORTED; one GPU. */
+
+/* How a panorama image lies on the warper surface: image pixel (x, y) is the warper coordinate (u0 + x, v0 + y) of a warper of `scale`. */
+typedef struct ms_pano_frame {
+    unsigned struct_size;   /* as ms_config: mismatch = MS_ERR_INVALID */
+    int projection;         /* MS_PROJ_SPHERICAL or MS_PROJ_CYLINDRICAL; MS_PROJ_PLANE is MS_ERR_UNSUPPORTED */
+    float scale;            /* the warper scale */
+    int u0, v0;             /* warper coordinates of image pixel (0, 0) */
+    int wrap_cols;          /* 0, or the image's column count where the image spans the full turn (column wrap_cols is column 0 again) */
+    int clamp_rows;         /* 0 or 1: the image's first and last rows are the poles' (samples beyond them repeat the edge row) */
+} ms_pano_frame;
+
+/* A virtual camera.  R: view to rig, row-major, the convention of ms_set_camera (a rig direction is R times the view's ray). */
+enum { MS_VIEW_CAMERA = 0, MS_VIEW_SURFACE = 1 };
+typedef struct ms_view {
+    unsigned struct_size;   /* as ms_config: mismatch = MS_ERR_INVALID */
+    int kind;               /* MS_VIEW_CAMERA: a camera with K and a lens; MS_VIEW_SURFACE: a piece of a warper surface, e.g. the whole equirect under another rotation */
+    int width, height;      /* [1, 32767] each */
+    float R[9];
+    float K[9];             /* CAMERA: intrinsics, as ms_lens_unproject takes them */
+    ms_lens lens;           /* CAMERA: MS_LENS_NONE (also an all-zero struct) = pinhole; BROWN / FISHEYE as ms_lens_unproject: a virtual fisheye */
+    int projection;         /* SURFACE: MS_PROJ_SPHERICAL or MS_PROJ_CYLINDRICAL */
+    float scale;            /* SURFACE: its warper scale */
+    int tl_u, tl_v;         /* SURFACE: warper coordinates of view pixel (0, 0) */
+} ms_view;
+
+/* One view of an ms_reproject call: its maps (DEVICE 32FC1 of one size -- that size is the view's --, data 4-byte aligned, step a multiple of 4) and where the view
+ * goes in every destination frame. */
+typedef struct ms_view_job {
+    ms_image map_x, map_y;
+    int dst_x, dst_y;
+} ms_view_job;
+
+/* A pan / tilt / zoom pinhole (host only, no device).  R = Ry(yaw) Rx(pitch) Rz(roll) with Ry(a) = [c 0 s; 0 1 0; -s 0 c], Rx(a) = [1 0 0; 0 c -s; 0 s c],
+ * Rz(a) = [c -s 0; s c 0; 0 0 1]: yaw a degrees puts the optical axis at u = a scale (radians times scale) of the warper, positive pitch looks up, toward v = 0.
+ * K: f = (width / 2) / tan(hfov / 2) on both axes, centre ((width - 1) / 2, (height - 1) / 2).  Computed in double, stored as float.  *out is filled completely
+ * (struct_size, kind = MS_VIEW_CAMERA, lens MS_LENS_NONE).  MS_ERR_INVALID: a null pointer, an angle that is not finite, hfov_deg outside (0, 179], width or
+ * height outside [1, 32767]. */
+MS_API int ms_look_at_view(double yaw_deg, double pitch_deg, double roll_deg, double hfov_deg, int width, int height, ms_view *out);
+/* Face `face` of a cube map of size x size faces: 0..5 = front, right, back, left, up, down = ms_look_at_view with (yaw, pitch) = (0, 0), (90, 0), (180, 0),
+ * (-90, 0), (0, 90), (0, -90), roll 0, hfov 90: f = size / 2, c = (size - 1) / 2, pixel centres at half-integers of the face.  MS_ERR_INVALID: a null
+ * pointer, face outside [0, 5], size outside [1, 32767]. */
+MS_API int ms_cube_face_view(int face, int size, ms_view *out);
+
+/* Where a context's output images lie on the warper surface (place_panorama's placement, read back).  MS_PANO_CANVAS: the out8u canvas -- u0 = -out_width / 2,
+ * v0 = 0 (spherical) or -out_height / 2 (cylindrical), wrap_cols = out_width where 2 llrint(pi (double)scale) == out_width (else 0), clamp_rows = 1 for a
+ * spherical canvas with out_height == llrint(pi (double)scale) (else 0).  MS_PANO_ROI: the pano ROI (out16s, out8u without a canvas): u0, v0 = dst_roi_final.x, .y,
+ * no wrap, no clamp.  MS_ERR_STATE before ms_build_maps / ms_set_maps; MS_ERR_UNSUPPORTED for MS_PROJ_PLANE contexts and for the canvas of a context with
+ * out_width == 0; MS_ERR_INVALID: a null pointer, another `which`. */
+enum { MS_PANO_CANVAS = 0, MS_PANO_ROI = 1 };
+MS_API int ms_get_pano_frame(const ms_ctx *ctx, int which, ms_pano_frame *out);
+
+/* The backward maps of a view into a panorama image: map (x, y) = the panorama image coordinates view pixel (x, y) samples.  ONE launch, one lane per pixel;
+ * everything in double and rounded to float once, at the store (calibration-time arithmetic, as ms_build_warp_maps_lens: no fp32 evaluation order is part of
+ * the contract; tests/reproject_ref.py is the numpy statement).
+ *   1. the view ray c of the integer pixel (x, y).  CAMERA: ms_lens_unproject's arithmetic on ((double)x, (double)y); not seen = the entry (-1, -1).
+ *      SURFACE: the warper's backward direction (detail::*Projector::mapBackward, warpers_inl.hpp:238-255, :275-290) at U' = (double)(tl_u + x) / (double)scale,
+ *      V' = (double)(tl_v + y) / (double)scale: spherical (sin V' sin U', -cos V', sin V' cos U'), cylindrical (sin U', V', cos U');
+ *   2. the rig direction d_k = R[3k] c0 + R[3k+1] c1 + R[3k+2] c2 with (double)R, summed left to right;
+ *   3. panorama coordinates (mapForward): h = hypot(d0, d2), S = (double)src->scale, U = S atan2(d0, d2); spherical V = S atan2(h, -d1) -- equal to
+ *      SphericalProjector::mapForward's S (pi - acos(d1 / |d|)) and accurate at the poles, where acos is not; cylindrical V = S d1 / h, h == 0 = not seen;
+ *   4. image coordinates X = U - u0, Y = V - v0; with wrap_cols > 0, X -= wrap_cols floor(X / wrap_cols), and a float result equal to wrap_cols is stored as 0.
+ *      Without wrap X is stored as it is: ms_reproject turns what lies outside into black.
+ * map_x / map_y: DEVICE 32FC1 of the view's size, any row step (pitched images, ROIs of larger ones).
+ * Refused before the device is touched -- MS_ERR_INVALID: a null pointer, a struct_size mismatch, an unknown kind, maps that are not 32FC1 or not of the view's
+ * size, a non-finite K (CAMERA), R or scale, a scale outside (0, 8192], a lens ms_lens_check refuses, K[0] or K[4] zero, wrap_cols < 0, clamp_rows other than 0 / 1,
+ * width or height outside [1, 32767]; MS_ERR_UNSUPPORTED: MS_PROJ_PLANE as either projection. */
+MS_API int ms_build_view_maps(const ms_pano_frame *src, const ms_view *view, ms_image *map_x, ms_image *map_y, ms_stream stream);
+
+/* cuda::remap(src, dst, xmap, ymap, INTER_LINEAR, BORDER_CONSTANT, Scalar(0), stream) (OCV/cudawarping/src/remap.cpp:61-102) for n_frames panoramas and n_jobs
+ * views in ONE launch, sampling a panorama that wraps: the job table travels in the kernel argument, nothing is allocated, the host never waits.
+ *   src:  n_frames DEVICE 8UC3 panoramas of one size and one step (step < 2^24, rows * step < 2^32), any base address.
+ *   dst:  n_frames DEVICE images of one geometry.  MS_VIEW_BGR: 8UC3, any step -- a job may write a rectangle of a larger atlas.  MS_VIEW_I420: contiguous 8UC1
+ *         of (rows * 3 / 2) x cols, exactly as ms_bgr_to_i420's.
+ *   jobs: HOST.  Job j writes the rectangle (dst_x, dst_y, map cols, map rows) of every frame; no byte outside the jobs' rectangles (I420: outside the three
+ *         planes' sub-rectangles) is written.
+ * Arithmetic.  The result equals, bit for bit, ms_remap(INTER_LINEAR, BORDER_CONSTANT) on the source extended by one column on either side and one row above and
+ * below, with the maps shifted by (+1, +1) -- one fp32 addition per coordinate, which the kernel performs.  The extra columns hold columns cols - 1 and 0 of the
+ * source when wrap_cols == cols, zeros otherwise; the extra rows then repeat rows 0 and rows - 1 (of the column-extended image) when clamp_rows is set, zeros
+ * otherwise.  In words: taps, weights, the fma chain and the saturation are ms_remap's; a tap at column -1 or cols wraps, a tap at row -1 or rows repeats the
+ * edge row, every other tap outside reads 0.  The maps may hold ANY float -- NaN, +-inf, +-1e30, the (-1, -1) marker (which, by the rule above, samples the
+ * extension's corner pixel) --: the kernel writes what ms_remap writes and never forms an address outside the source.
+ * MS_VIEW_I420 equals ms_bgr_to_i420 of the BGR atlas the call would have written: Y from every pixel, U and V from the top-left pixel of each 2 x 2 block.
+ * Kernel shape (csrc/reproject.hip): a lane owns four pixels -- 4 x 1 of a row for BGR (12-byte stores), one 2 x 2 block for I420 --, builds their tap state
+ * once from the maps and walks MS_VIEW_FRAME_GROUP frames with it; workgroups are tiles of MS_VIEW_TILE_W x MS_VIEW_TILE_H (BGR) / 32 x 32 (I420) pixels.
+ * MS_ERR_INVALID, before a kernel is enqueued: a null pointer; n_frames outside [1, MS_VIEW_MAX_FRAMES] or n_jobs outside [1, MS_VIEW_MAX_JOBS]; an unknown
+ * format; src frames that are not 8UC3, differ in geometry, have step >= 2^24 or rows * step >= 2^32; wrap_cols other than 0 or cols; clamp_rows other than
+ * 0 / 1; a job whose maps differ in size, are not 32FC1 or are misaligned; dst frames of another type or differing in geometry; a rectangle that leaves dst;
+ * two jobs whose rectangles overlap; for I420 an odd dst_x, dst_y, width, height or frame size, or a non-contiguous dst; a dst frame whose byte range
+ * overlaps a src frame's. */
+enum { MS_VIEW_BGR = 0, MS_VIEW_I420 = 1 };
+enum { MS_VIEW_MAX_FRAMES = 64, MS_VIEW_MAX_JOBS = 16, MS_VIEW_FRAME_GROUP = 8, MS_VIEW_TILE_W = 64, MS_VIEW_TILE_H = 16 };
+MS_API int ms_reproject(const ms_image *src, ms_image *dst, int n_frames, const ms_view_job *jobs, int n_jobs, int wrap_cols, int clamp_rows, int format,
+                        ms_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

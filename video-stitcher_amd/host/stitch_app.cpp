@@ -18,6 +18,7 @@
 // Usage: stitch_app [--views 6] [--size 1920x1080] [--out 3840x1920] [--hfov 90] [--bands 5] [--frames 300] [--cpw]
 //                   [--i420] [--nv12 | --nv12-direct] [--dump pano.bin] [--no-upload] [--solve-mesh [--temporal ALPHA]]
 //                   [--reference-calib [--work-megapix 0.6] [--seam-megapix 0.01] [--compose-megapix 1.4] [--seam-finder voronoi|dp]]
+//                   [--viewport YAW,PITCH,ROLL,HFOV,WxH | --cubemap N]
 //                   [--drop-view V:F0:F1] [--dump-frames frames.bin] [--track-gains K] [--exposure-ramp V:F] [--dump-i420 planes.bin]
 //                   [--lens-brown k1,k2,p1,p2,k3 | --lens-fisheye k1,k2,k3,k4[,max_theta]]
 //                   [--rig-error V:YAW:PITCH:ROLL] [--refine-rig]
@@ -111,6 +112,10 @@ struct Options {
     int track_gains = 0;                        // --track-gains K
     int ramp_view = -1; double ramp_factor = 1.0;      // --exposure-ramp V:F
     std::string dump_i420;                      // --dump-i420 FILE
+    bool viewport = false;                      // --viewport YAW,PITCH,ROLL,HFOV,WxH: a virtual pan / tilt / zoom camera rendered from the canvas (ms_reproject) in consume()
+    double vp_yaw = 0, vp_pitch = 0, vp_roll = 0, vp_hfov = 90;
+    int vp_w = 0, vp_h = 0;
+    int cubemap = 0;                            // --cubemap N: a 3N x 2N atlas of six N x N faces (ms_cube_face_view order, left to right, top to bottom)
     bool fused_resize = false;                  // --fused-resize: with --nv12-direct and a compose-scale resize, planes -> small_imgs in one pass
     ms_lens lens{sizeof(ms_lens), MS_LENS_NONE, {0, 0, 0, 0, 0, 0, 0, 0}, 0.0};      // --lens-brown / --lens-fisheye: every camera's lens
     int rig_err_view = -1; double rig_err_deg[3] = {0, 0, 0};    // --rig-error V:YAW:PITCH:ROLL
@@ -261,6 +266,11 @@ int main(int argc, char **argv)
         else if (k == "--dump-frames") o.dump_frames = next();
         else if (k == "--track-gains") o.track_gains = atoi(next());
         else if (k == "--dump-i420") o.dump_i420 = next();
+        else if (k == "--viewport") {
+            if (sscanf(next(), "%lf,%lf,%lf,%lf,%dx%d", &o.vp_yaw, &o.vp_pitch, &o.vp_roll, &o.vp_hfov, &o.vp_w, &o.vp_h) != 6) { fprintf(stderr, "--viewport wants YAW,PITCH,ROLL,HFOV,WxH\n"); return 2; }
+            o.viewport = true;
+        }
+        else if (k == "--cubemap") o.cubemap = atoi(next());
         else if (k == "--fused-resize") o.fused_resize = true;
         else if (k == "--lens-brown") {      // k1,k2,p1,p2,k3 in distCoeffs order: k3 is k[4]
             double *c = o.lens.k;
@@ -296,6 +306,9 @@ int main(int argc, char **argv)
     if (!(o.temporal >= 0.0) || !std::isfinite(o.temporal)) { fprintf(stderr, "--temporal wants ALPHA >= 0\n"); return 2; }
     if (o.track_gains < 0) { fprintf(stderr, "--track-gains wants K >= 0\n"); return 2; }
     if (!o.dump_i420.empty() && !o.i420) { fprintf(stderr, "--dump-i420 needs --i420\n"); return 2; }
+    if (o.viewport && o.cubemap) { fprintf(stderr, "--viewport and --cubemap exclude each other\n"); return 2; }
+    if (o.cubemap < 0 || (o.cubemap && o.i420 && o.cubemap % 2)) { fprintf(stderr, "--cubemap wants N >= 1 (even with --i420)\n"); return 2; }
+    if (o.viewport && o.i420 && (o.vp_w % 2 || o.vp_h % 2)) { fprintf(stderr, "--viewport with --i420 wants an even size\n"); return 2; }
     if (o.fused_resize && !o.nv12_direct) { fprintf(stderr, "--fused-resize needs --nv12-direct\n"); return 2; }
     if (ms_lens_check(&o.lens) != MS_OK) { fprintf(stderr, "stitch_app: %s\n", ms_last_error()); return 2; }
     FILE *frames_file = nullptr;       // --dump-frames (opened before any thread starts)
@@ -350,7 +363,8 @@ int main(int argc, char **argv)
         const bool resize_in = o.reference_calib && cal.rig.resize_input;
         const int cw = o.reference_calib ? cal.rig.compose_width : o.w, ch = o.reference_calib ? cal.rig.compose_height : o.h;
         // --nv12-direct --i420 in one call, where no 8U canvas is needed otherwise (the canvas is what --dump, --dump-frames and --consume read)
-        const bool nv12_i420 = o.nv12_direct && o.i420 && !resize_in && o.dump.empty() && o.dump_frames.empty() && o.consume_w <= 0;
+        const bool view_on = o.viewport || o.cubemap > 0;      // (the virtual cameras sample the canvas too)
+        const bool nv12_i420 = o.nv12_direct && o.i420 && !resize_in && o.dump.empty() && o.dump_frames.empty() && o.consume_w <= 0 && !view_on;
         const bool fused_resize = o.fused_resize && resize_in;
         const char *i420_call = !o.i420 ? "none" : (nv12_i420 ? "ms_stitch_nv12_i420" : "ms_bgr_to_i420");
         hipStream_t stitch_stream, recal_stream;
@@ -537,11 +551,49 @@ int main(int argc, char **argv)
             encoder_host.resize((size_t)o.consume_w * o.consume_h * 3 / 2);
             HIPCHECK(hipStreamCreateWithFlags(&consume_stream, hipStreamNonBlocking));
         }
+        // --viewport / --cubemap: the player's step (timed.cpp:296-300) on the device.  The maps are built once, from where the canvas lies on the sphere
+        // (ms_get_pano_frame); consume() then renders every view of a frame in one ms_reproject call, as BGR or (--i420) as the encoder's planes.
+        std::vector<DevMat> view_mx, view_my;
+        std::vector<ms_view_job> view_jobs;
+        DevMat view_frame;
+        std::vector<unsigned char> view_host;
+        hipStream_t view_stream = nullptr;
+        int view_w = 0, view_h = 0, view_wrap = 0, view_clamp = 0;
+        unsigned long long view_checksum = 0;
+        if (view_on) {
+            ms_pano_frame pf;
+            msshim::check(ms_get_pano_frame(comp.raw(), MS_PANO_CANVAS, &pf));
+            view_wrap = pf.wrap_cols; view_clamp = pf.clamp_rows;
+            const int n_views = o.cubemap ? 6 : 1;
+            view_w = o.cubemap ? 3 * o.cubemap : o.vp_w; view_h = o.cubemap ? 2 * o.cubemap : o.vp_h;
+            view_mx.resize(n_views); view_my.resize(n_views); view_jobs.resize(n_views);
+            HIPCHECK(hipStreamCreateWithFlags(&view_stream, hipStreamNonBlocking));
+            for (int i = 0; i < n_views; ++i) {
+                ms_view v;
+                if (o.cubemap) msshim::check(ms_cube_face_view(i, o.cubemap, &v));
+                else msshim::check(ms_look_at_view(o.vp_yaw, o.vp_pitch, o.vp_roll, o.vp_hfov, o.vp_w, o.vp_h, &v));
+                view_mx[i].create(v.height, v.width, MS_32FC1); view_my[i].create(v.height, v.width, MS_32FC1);
+                ms_image mx = msshim::wrap(view_mx[i]), my = msshim::wrap(view_my[i]);
+                msshim::check(ms_build_view_maps(&pf, &v, &mx, &my, (ms_stream)view_stream));
+                view_jobs[i] = ms_view_job{mx, my, o.cubemap ? (i % 3) * o.cubemap : 0, o.cubemap ? (i / 3) * o.cubemap : 0};
+            }
+            HIPCHECK(hipStreamSynchronize(view_stream));
+            if (o.i420) view_frame.create(view_h * 3 / 2, view_w, MS_8UC1, 1, true);
+            else view_frame.create(view_h, view_w, MS_8UC3, 3, true);
+            view_host.resize((size_t)view_w * view_h * (o.i420 ? 3 : 6) / 2);
+        }
         std::thread consumer([&] {                      // consume(): wait for the frame, (I420,) bring it to the host side
             for (;;) {
                 Slot *s = results.pop();
                 if (!s) break;
                 HIPCHECK(hipEventSynchronize(s->done));
+                if (view_on) {                          // the virtual cameras' frame instead of (beside) the equirect: one launch, then the encoder's copy
+                    ms_image src = msshim::wrap(s->pano8u), dst = msshim::wrap(view_frame);
+                    msshim::check(ms_reproject(&src, &dst, 1, view_jobs.data(), (int)view_jobs.size(), view_wrap, view_clamp, o.i420 ? MS_VIEW_I420 : MS_VIEW_BGR, (ms_stream)view_stream));
+                    HIPCHECK(hipMemcpyAsync(view_host.data(), view_frame.data, view_host.size(), hipMemcpyDeviceToHost, view_stream));
+                    HIPCHECK(hipStreamSynchronize(view_stream));
+                    if (s->seq == o.frames - 1) for (unsigned char b : view_host) view_checksum = (view_checksum ^ b) * 1099511628211ull;
+                }
                 if (o.consume_w > 0) {                  // timed.cpp:251-316 without the download / CPU resize / CPU cvtColor: one kernel, then the encoder's copy
                     consume_image_height = msshim::consume_i420(s->pano8u, encoder_frame, o.consume_w, o.consume_h, true, (ms_stream)consume_stream);
                     HIPCHECK(hipMemcpyAsync(encoder_host.data(), encoder_frame.data, encoder_host.size(), hipMemcpyDeviceToHost, consume_stream));
@@ -794,6 +846,7 @@ int main(int argc, char **argv)
                o.views, o.w, o.h, o.out_w, o.out_h, pg.num_bands, o.cpw ? "true" : "false", o.i420 ? "true" : "false", o.nv12 ? "true" : "false", o.nv12_direct ? "true" : "false", o.upload ? "true" : "false",
                consumed, secs, consumed / secs, recalibrations.load(), solver_iterations.load(), (double)max_disp.load(),
                total_keypoints.load(), total_matches.load(), total_inliers.load(), o.update_mask, selfcheck < 0 ? "null" : (selfcheck ? "true" : "false"), consume_image_height, consume_checksum, checksum, degraded_frames, i420_call, fused_resize ? "true" : "false", comp.mapSource(), comp.seamFinder() == MS_SEAM_DP ? "dp" : "voronoi");
+        if (view_on) printf(", \"view_out\": \"%dx%d\", \"view_checksum\": \"%016llx\"", view_w, view_h, view_checksum);
         if (o.temporal > 0.0) printf(", \"temporal_alpha\": %g, \"temporal_matches\": %lld", o.temporal, total_temporal.load());
         if (o.track_gains > 0) {
             std::vector<double> g((size_t)o.views);

@@ -68,6 +68,49 @@ class Lens(C.Structure):
         return cls.make(LENS_FISHEYE, k, max_theta_deg)
 
 
+class PanoFrame(C.Structure):
+    """ms_pano_frame: how a panorama image lies on the warper surface (Compositor.pano_frame, or PanoFrame.make for an image of one's own)"""
+    _fields_ = [("struct_size", C.c_uint), ("projection", C.c_int), ("scale", C.c_float), ("u0", C.c_int), ("v0", C.c_int), ("wrap_cols", C.c_int),
+                ("clamp_rows", C.c_int)]
+
+    @classmethod
+    def make(cls, projection, scale, u0, v0, wrap_cols=0, clamp_rows=0):
+        return cls(C.sizeof(cls), projection, scale, u0, v0, wrap_cols, clamp_rows)
+
+
+VIEW_CAMERA, VIEW_SURFACE = 0, 1
+VIEW_BGR, VIEW_I420 = 0, 1
+PANO_CANVAS, PANO_ROI = 0, 1
+VIEW_MAX_FRAMES, VIEW_MAX_JOBS, VIEW_FRAME_GROUP, VIEW_TILE_W, VIEW_TILE_H = 64, 16, 8, 64, 16
+VIEW_TILE_I420 = 32      # the I420 form's tiles are 32 x 32 pixels
+
+
+class View(C.Structure):
+    """ms_view: a virtual camera.  look_at_view / cube_face_view fill pinholes; View.camera / View.surface the general forms"""
+    _fields_ = [("struct_size", C.c_uint), ("kind", C.c_int), ("width", C.c_int), ("height", C.c_int), ("R", C.c_float * 9), ("K", C.c_float * 9), ("lens", Lens),
+                ("projection", C.c_int), ("scale", C.c_float), ("tl_u", C.c_int), ("tl_v", C.c_int)]
+
+    @classmethod
+    def camera(cls, width, height, K, R, lens=None):
+        v = cls(C.sizeof(cls), VIEW_CAMERA, width, height)
+        v.R[:] = [float(x) for x in list(R)]; v.K[:] = [float(x) for x in list(K)]
+        v.lens = lens if lens is not None else Lens.make(LENS_NONE)
+        v.projection = PROJ_SPHERICAL
+        return v
+
+    @classmethod
+    def surface(cls, width, height, R, projection, scale, tl_u, tl_v):
+        v = cls(C.sizeof(cls), VIEW_SURFACE, width, height)
+        v.R[:] = [float(x) for x in list(R)]
+        v.lens = Lens.make(LENS_NONE)
+        v.projection = projection; v.scale = scale; v.tl_u = tl_u; v.tl_v = tl_v
+        return v
+
+
+class ViewJob(C.Structure):
+    _fields_ = [("map_x", Image), ("map_y", Image), ("dst_x", C.c_int), ("dst_y", C.c_int)]
+
+
 class SeamParams(C.Structure):
     _fields_ = [("seam_scale", C.c_double), ("seam_warp_scale", C.c_float), ("dilate", C.c_int), ("estimate_gains", C.c_int)]
 
@@ -248,6 +291,7 @@ EXPORTS = [
     "ms_orb_detect_and_compute_batch",
     "ms_list_match_default_params", "ms_match_lists", "ms_feature_inputs_batch",
     "ms_lens_unproject", "ms_lens_unproject_points", "ms_rig_lens_accumulate", "ms_refine_rig_cameras_lens", "ms_refine_rig_focals_lens",
+    "ms_look_at_view", "ms_cube_face_view", "ms_get_pano_frame", "ms_build_view_maps", "ms_reproject",
 ]
 
 _lib = None
@@ -594,6 +638,48 @@ def build_warp_maps_lens(projection, tl_u, tl_v, rows, cols, K, R, lens, scale, 
     ka, kp = _fa(K, 9); ra, rp = _fa(R, 9)
     _chk(load().ms_build_warp_maps_lens(projection, tl_u, tl_v, C.byref(img(mx)), C.byref(img(my)), kp, rp, _lens_ptr(lens), C.c_float(scale), _stream()))
     return mx, my
+
+
+def look_at_view(yaw_deg, pitch_deg, roll_deg, hfov_deg, width, height):
+    """ms_look_at_view (host only): a pan / tilt / zoom pinhole as a View"""
+    v = View()
+    _chk(load().ms_look_at_view(C.c_double(yaw_deg), C.c_double(pitch_deg), C.c_double(roll_deg), C.c_double(hfov_deg), width, height, C.byref(v)))
+    return v
+
+
+def cube_face_view(face, size):
+    """ms_cube_face_view (host only): face 0..5 = front, right, back, left, up, down"""
+    v = View()
+    _chk(load().ms_cube_face_view(face, size, C.byref(v)))
+    return v
+
+
+def build_view_maps(pano_frame, view, out=None):
+    """ms_build_view_maps: the (map_x, map_y) float32 cuda tensors of a View into the panorama image pano_frame describes; out: tensors to fill (views of larger ones are fine)"""
+    torch = _torch()
+    mx, my = out if out is not None else (_new((view.height, view.width), torch.float32), _new((view.height, view.width), torch.float32))
+    _chk(load().ms_build_view_maps(C.byref(pano_frame), C.byref(view), C.byref(img(mx)), C.byref(img(my)), _stream()))
+    return mx, my
+
+
+def reproject_prepared(srcs, dsts, jobs, wrap_cols=0, clamp_rows=0, fmt=VIEW_BGR):
+    """ms_reproject with the descriptors marshalled once: srcs / dsts lists of cuda tensors (one per frame), jobs a list of (map_x, map_y, dst_x, dst_y);
+    returns a callable(stream_handle=None)"""
+    n, m = len(srcs), len(jobs)
+    a = (Image * n)(*[img(t) for t in srcs]); b = (Image * n)(*[img(t) for t in dsts])
+    jt = (ViewJob * m)(*[ViewJob(img(mx), img(my), dx, dy) for mx, my, dx, dy in jobs])
+    fn = load().ms_reproject
+
+    def run(stream=None):
+        _chk(fn(a, b, n, jt, m, wrap_cols, clamp_rows, fmt, stream if stream is not None else _stream()))
+    run.keep = (srcs, dsts, jobs)
+    return run
+
+
+def reproject(srcs, dsts, jobs, wrap_cols=0, clamp_rows=0, fmt=VIEW_BGR):
+    """ms_reproject: every job's view of every source panorama into its rectangle of the matching destination frame, in one launch"""
+    reproject_prepared(srcs, dsts, jobs, wrap_cols, clamp_rows, fmt)()
+    return dsts
 
 
 def warp_roi_lens(projection, K, R, lens, scale, src_w, src_h):
@@ -1437,6 +1523,12 @@ class Compositor:
         g = PanoGeom()
         _chk(load().ms_get_pano_geom(self._ctx, C.byref(g)))
         return g
+
+    def pano_frame(self, which=PANO_CANVAS):
+        """ms_get_pano_frame: how the canvas (PANO_CANVAS) or the pano ROI (PANO_ROI) lies on the warper surface, for build_view_maps"""
+        p = PanoFrame()
+        _chk(load().ms_get_pano_frame(self._ctx, which, C.byref(p)))
+        return p
 
     def maps(self, view):
         xm, ym = Image(), Image()
