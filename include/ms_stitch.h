@@ -1083,7 +1083,8 @@ MS_API int ms_refine_rig_focals(ms_ctx *ctx, const ms_mesh_match *matches, const
  * A match with a pixel its lens does not see at the TRIAL cameras adds +infinity to the cost and nothing to any other sum: the trial is rejected by the accept rule
  * (cost_trial <= cost fails), so every returned camera sees every match.  At the INPUT cameras such a pixel is MS_ERR_INVALID naming the match, found on the host
  * before the device is touched.  Both calls refuse what their pinhole forms refuse, and a lens ms_lens_check refuses; no floating-point atomics, two calls return
- * the same bits.  Stated limits: distortion coefficients and principal points are not unknowns; ms_estimate_rig stays pinhole, a lens rig starts from a nominal focal. */
+ * the same bits.  Stated limits: principal points are not unknowns, and the lenses are fixed in these two calls (ms_refine_rig_coeffs below frees the coefficients of
+ * a lens the whole rig shares); ms_estimate_rig stays pinhole, a lens rig starts from a nominal focal. */
 MS_API int ms_rig_lens_accumulate(int n_views, const double *f, const double *R, const ms_lens *lenses, const ms_rig_px_match *matches, int n, double huber_px,
                                   double *cost, double *H, double *g, ms_stream stream);
 MS_API int ms_refine_rig_cameras_lens(int n_views, const double *f_in, const double *R_in, const ms_lens *lenses, const ms_rig_px_match *matches, int n,
@@ -1096,6 +1097,67 @@ MS_API int ms_refine_rig_cameras_lens(int n_views, const double *f_in, const dou
  * its view's lens does not see, naming the match. */
 MS_API int ms_refine_rig_focals_lens(ms_ctx *ctx, const ms_mesh_match *matches, const int *match_count, const ms_rig_focal_params *prm, double *focal_out, float *R_out,
                                      ms_rig_focal_info *info, ms_stream stream);
+/* The coefficient form: the lens form above with ONE lens shared by all views (lens: one ms_lens of model BROWN or FISHEYE, HOST) and G of its k[] entries free,
+ * 1 <= G <= 4, named by the bit mask free_coeffs (bit b frees k[b]).  FISHEYE: bits 0..3 (k1..k4).  BROWN: bits 0, 1, 4 (k1, k2, k3) and 2, 3 (p1, p2); bits 5..7, the
+ * rational denominator, stay fixed (non-zero values are fine): a free one is MS_ERR_UNSUPPORTED.  It generalises ms_rig_lens_accumulate / ms_refine_rig_cameras_lens:
+ * the residual, m = sqrt(f_i f_j), Huber, the 46 sums, the Levenberg-Marquardt rule and the stop rules are theirs, and the 46 sums of a pair are their bits.
+ * Per match there are G more columns of the residual's Jacobian, one per free coefficient in ascending bit order, from the implicit-function theorem on the forward
+ * model with the pixel and the focal held; with theta, e, (x, y), J, n, a as in the lens form and the trial lens's coefficients:
+ *   FISHEYE  q_0 = theta (theta theta), q_n = q_(n-1) (theta theta) (= theta^(2n+3)), theta'_n = -q_n / (d theta_d / d theta)(theta):
+ *            da/dk_n = (theta'_n (cos theta e0), theta'_n (cos theta e1), -(theta'_n sin theta)); 0 at the centre
+ *   BROWN    r2 = x x + y y, D = 1 + ((k6 r2 + k5) r2 + k4) r2 (the fixed denominator), s = r2 / D for k1, (r2 r2) / D for k2, ((r2 r2) r2) / D for k3:
+ *            dF = (x s, y s);  p1: dF = ((2 x) y, r2 + (2 y) y);  p2: dF = (r2 + (2 x) x, (2 x) y);
+ *            (x', y') = -J^-1 dF by Cramer's rule: x' = -((J3 dF0 - J1 dF1) / det), y' = -((J0 dF1 - J2 dF0) / det), t = a0 x' + a1 y':
+ *            da/dk_n = ((x' - a0 t) / n, (y' - a1 t) / n, -(a2 t) / n), the projection onto the sphere da/ds uses
+ *   e_n,k = m (R_i da/dk_n)_k - m (R_j db/dk_n)_k, (R d)_k as above.
+ * The border sums of a pair follow its 46, G + G (G + 1) / 2 + 8 G of them (46 for G = 4), in this order:
+ *     g_n      sum w (e_n0 r0 + e_n1 r1 + e_n2 r2), n = 0 .. G - 1
+ *     H_nn'    upper triangle row-major (00 01 .. 0(G-1) 11 ..): sum w (e_n0 e_n'0 + e_n1 e_n'1 + e_n2 e_n'2)
+ *     then for n = 0 .. G - 1 eight sums: H(rot_i, n) = w (u x e_n)_k, k = 0 1 2;  H(f_i, n) = w (ci0 e_n0 + ci1 e_n1 + ci2 e_n2);
+ *                                         H(rot_j, n) = -(w (v x e_n)_k);           H(f_j, n) = w (cj0 e_n0 + cj1 e_n1 + cj2 e_n2)
+ * with the cross products written out as in g_i.  The solved system gets G rows after the existing ones (after the one focal where the focal is shared): 65 unknowns at
+ * most.  The step is additive, k <- k + d; lambda diag(H) makes the scale of a coefficient irrelevant; step_tol is tested on max |.| over ALL components of the step.
+ * A trial lens must stay a lens: ms_lens_check's profile rule (4096 samples on [0, max_theta]) is evaluated on the device for the trial coefficients, and a trial
+ * that fails it is treated as a non-positive pivot is: lambda <- 10 lambda, one iteration, solve again.  The fisheye limit theta_d(max_theta) is the TRIAL lens's; a
+ * pixel the trial lens no longer sees adds +infinity to the cost as above.  So every returned lens passes ms_lens_check and sees every match.
+ * Stated limits: one lens a rig, at most 4 free coefficients, no denominators, no principal points, no prior on the coefficients (a coefficient the matches do not
+ * constrain -- rays near the axis only -- is held by the damping alone). */
+typedef struct ms_rig_coeff_params {
+    unsigned struct_size;          /* as ms_config: mismatch = MS_ERR_INVALID */
+    int anchor_view;               /* the fields of ms_rig_focal_params, with its defaults ... */
+    int shared_focal;
+    int max_iters;
+    double huber_px;
+    double step_tol;
+    int min_pair_matches;
+    unsigned free_coeffs;          /* ... and the free entries of lens.k[], bit b for k[b]; default 1 (k1) */
+} ms_rig_coeff_params;
+typedef struct ms_rig_coeff_info {
+    int iterations, stop_reason;   /* the fields of ms_rig_focal_info ... */
+    double cost_initial, cost_final;
+    int matches_used, pairs_used, pairs_ignored;
+    int outliers;
+    double max_rotation_rad;
+    double max_focal_ratio;
+    double max_coeff_change;       /* ... and the largest |k_out - k_in| over the free coefficients */
+} ms_rig_coeff_info;
+MS_API int ms_rig_coeff_default_params(ms_rig_coeff_params *prm);
+/* The normal equations per op, ms_rig_lens_accumulate's with the coefficient rows last: H is (4 n_views + G)^2 row-major, g has 4 n_views + G entries.  The cost,
+ * the leading 4 n_views x 4 n_views block and the first 4 n_views entries of g are the bits of ms_rig_lens_accumulate with `lens` on every view; free_coeffs == 0
+ * (G = 0) is allowed here and returns exactly those.  Synchronises. */
+MS_API int ms_rig_coeff_accumulate(int n_views, const double *f, const double *R, const ms_lens *lens, unsigned free_coeffs, const ms_rig_px_match *matches, int n,
+                                   double huber_px, double *cost, double *H, double *g, ms_stream stream);
+/* ms_refine_rig_cameras_lens with the shared lens's free coefficients among the unknowns: one pinned upload, max_iters + 1 rounds of two kernels, one copy back, one
+ * synchronise; no floating-point atomics, two calls return the same bits.  lens_out is lens_in with the free entries replaced.  Refused before the device is touched:
+ * everything ms_refine_rig_cameras_lens refuses (MS_ERR_INVALID), and a null lens, MS_LENS_NONE as the lens, free_coeffs empty or with more than 4 bits, a bit outside
+ * the model's set (MS_ERR_INVALID; a BROWN denominator bit: MS_ERR_UNSUPPORTED), a pixel the input lens does not see (naming the match). */
+MS_API int ms_refine_rig_coeffs(int n_views, const double *f_in, const double *R_in, const ms_lens *lens_in, const ms_rig_px_match *matches, int n,
+                                const ms_rig_coeff_params *prm, double *f_out, double *R_out, ms_lens *lens_out, ms_rig_coeff_info *info, ms_stream stream);
+/* The context form, built like ms_refine_rig_focals_lens: the lists become centred source pixels through the context's cameras and lens, then ms_refine_rig_coeffs
+ * runs.  It needs a lens context whose views all hold the same model, coefficients and max_theta_deg: otherwise MS_ERR_UNSUPPORTED naming the first view that
+ * differs (view 0 where it has no lens).  Nothing is applied: the caller runs ms_set_lens and the usual chain.  State errors and refusals as ms_refine_rig_focals_lens. */
+MS_API int ms_refine_rig_coeffs_ctx(ms_ctx *ctx, const ms_mesh_match *matches, const int *match_count, const ms_rig_coeff_params *prm, double *focal_out, float *R_out,
+                                    ms_lens *lens_out, ms_rig_coeff_info *info, ms_stream stream);
 
 /* ---- Pairwise matching: every view pair of a rig in one call ---------------------------------------------------------------------------------------
  * detail::BestOf2NearestMatcher / BestOf2NearestRangeMatcher (OCV/stitching/src/matchers.cpp:248-297 the two-direction 2-NN match with ratio test and

@@ -31,31 +31,9 @@ struct RigLensPixels {
             t[0] = ma * (R[2] - a2 * p[0]); t[1] = ma * (R[5] - a2 * p[1]); t[2] = ma * (R[8] - a2 * p[2]);
             return true;
         }
-        const double xd = px[0] / f, yd = px[1] / f;
-        double a0, a1, a2, d0, d1, d2;
-        if (l.model == MS_LENS_FISHEYE) {
-            const double td = hypot(xd, yd);
-            double theta;
-            if (!lens_fisheye_solve(l, td, theta)) return false;
-            if (td > 0.0) {
-                const double st = sin(theta), ct = cos(theta), tp = -td / lens_fisheye_slope(l.k, theta), e0 = xd / td, e1 = yd / td;
-                a0 = st * xd / td; a1 = st * yd / td; a2 = ct;
-                d0 = tp * (ct * e0); d1 = tp * (ct * e1); d2 = -(tp * st);
-            } else { a0 = 0.0; a1 = 0.0; a2 = 1.0; d0 = 0.0; d1 = 0.0; d2 = 0.0; }
-        } else {
-            double x, y, fx, fy, J[4];
-            if (!lens_brown_solve(l, xd, yd, x, y)) return false;
-            lens_brown_forward(l.k, x, y, fx, fy, J);
-            const double det = J[0] * J[3] - J[1] * J[2];
-            if (!(fabs(det) > 0.0)) return false;
-            const double xs = -((J[3] * xd - J[1] * yd) / det), ys = -((J[0] * yd - J[2] * xd) / det);      // (x', y') = -J^-1 (xd, yd)
-            const double n = sqrt(x * x + y * y + 1.0);
-            a0 = x / n; a1 = y / n; a2 = 1.0 / n;
-            const double dot = a0 * xs + a1 * ys;
-            d0 = (xs - a0 * dot) / n; d1 = (ys - a1 * dot) / n; d2 = -(a2 * dot) / n;
-        }
-        p[0] = R[0] * a0 + R[1] * a1 + R[2] * a2; p[1] = R[3] * a0 + R[4] * a1 + R[5] * a2; p[2] = R[6] * a0 + R[7] * a1 + R[8] * a2;
-        t[0] = m * (R[0] * d0 + R[1] * d1 + R[2] * d2); t[1] = m * (R[3] * d0 + R[4] * d1 + R[5] * d2); t[2] = m * (R[6] * d0 + R[7] * d1 + R[8] * d2);
+        RigLensRay ray;                               // (rig_px.hpp: the coefficient refinement runs the same code)
+        if (!rig_lens_ray(l, f, px, ray)) return false;
+        rig_lens_rotate(m, R, ray, p, t);
         return true;
     }
     // The terms of one match.  A pixel its lens does not see at the trial cameras: +infinity to the cost and nothing to any other sum, so k_rig_step refuses the trial.

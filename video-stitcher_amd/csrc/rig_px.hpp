@@ -1,5 +1,5 @@
 // rig_px.hpp -- what the two pixel policies of the rig refinement share (include/ms_stitch.h, "Self-calibrating rigs"): RigPixels (rig_focal.hip, pinhole views) and
-// RigLensPixels (rig_lens.hip, views behind fixed lenses).  Internal; those two units include it.  Both have 4 unknowns a view and the match record of centred pixels;
+// RigLensPixels (rig_lens.hip, views behind fixed lenses); rig_coeffs.hip (one shared lens with free coefficients) builds on both.  Internal; those three units include it.  Both have 4 unknowns a view and the match record of centred pixels;
 // they differ in how a pixel becomes its unit ray a and the ray's derivative by the log focal, i.e. in the focal columns ci, cj.  From the rotated rays on, the
 // residual, the Huber weight and the 46 sums are one copy, here, and so are the checks of cameras and pixel matches and the frame of the refinement's entry points.
 #pragma once
@@ -48,6 +48,52 @@ static __device__ __forceinline__ void rig_px_sums(const RigPxResidual &e, doubl
     acc[41] += -(w * (v1 * ci2 - v2 * ci1)); acc[42] += -(w * (v2 * ci0 - v0 * ci2)); acc[43] += -(w * (v0 * ci1 - v1 * ci0));
     acc[44] += w * (ci0 * cj0 + ci1 * cj1 + ci2 * cj2);
     acc[45] += e.out;
+}
+
+// One view's side of a match behind a BROWN or FISHEYE lens, shared by RigLensPixels (rig_lens.hip) and the coefficient refinement (rig_coeffs.hip): the unit ray a of
+// the centred pixel px at the focal f, da/ds (s = ln f), and the quantities both are made of, which the coefficient columns need again.  false: the lens does not see
+// the pixel at this focal.
+struct RigLensRay {
+    double a0, a1, a2, d0, d1, d2;
+    double theta, st, ct, e0, e1, slope;          // FISHEYE (td > 0; at the centre a = e_z, d = 0 and centre is set)
+    double x, y, J[4], det, n;                    // BROWN
+    bool centre;
+};
+static __device__ __forceinline__ bool rig_lens_ray(const LensDist &l, double f, const double *px, RigLensRay &o)
+{
+    const double xd = px[0] / f, yd = px[1] / f;
+    o.centre = false;
+    if (l.model == MS_LENS_FISHEYE) {
+        const double td = hypot(xd, yd);
+        if (!lens_fisheye_solve(l, td, o.theta)) return false;
+        if (td > 0.0) {
+            o.st = sin(o.theta); o.ct = cos(o.theta); o.slope = lens_fisheye_slope(l.k, o.theta); o.e0 = xd / td; o.e1 = yd / td;
+            const double st = o.st, ct = o.ct, tp = -td / o.slope, e0 = o.e0, e1 = o.e1;
+            o.a0 = st * xd / td; o.a1 = st * yd / td; o.a2 = ct;
+            o.d0 = tp * (ct * e0); o.d1 = tp * (ct * e1); o.d2 = -(tp * st);
+        } else { o.centre = true; o.a0 = 0.0; o.a1 = 0.0; o.a2 = 1.0; o.d0 = 0.0; o.d1 = 0.0; o.d2 = 0.0; }
+    } else {
+        double fx, fy;
+        if (!lens_brown_solve(l, xd, yd, o.x, o.y)) return false;
+        lens_brown_forward(l.k, o.x, o.y, fx, fy, o.J);
+        const double x = o.x, y = o.y, *J = o.J;
+        o.det = J[0] * J[3] - J[1] * J[2];
+        const double det = o.det;
+        if (!(fabs(det) > 0.0)) return false;
+        const double xs = -((J[3] * xd - J[1] * yd) / det), ys = -((J[0] * yd - J[2] * xd) / det);      // (x', y') = -J^-1 (xd, yd)
+        o.n = sqrt(x * x + y * y + 1.0);
+        const double n = o.n;
+        o.a0 = x / n; o.a1 = y / n; o.a2 = 1.0 / n;
+        const double dot = o.a0 * xs + o.a1 * ys;
+        o.d0 = (xs - o.a0 * dot) / n; o.d1 = (ys - o.a1 * dot) / n; o.d2 = -(o.a2 * dot) / n;
+    }
+    return true;
+}
+// p = R a and t = m R da/ds of that ray
+static __device__ __forceinline__ void rig_lens_rotate(double m, const double *R, const RigLensRay &o, double *p, double *t)
+{
+    p[0] = R[0] * o.a0 + R[1] * o.a1 + R[2] * o.a2; p[1] = R[3] * o.a0 + R[4] * o.a1 + R[5] * o.a2; p[2] = R[6] * o.a0 + R[7] * o.a1 + R[8] * o.a2;
+    t[0] = m * (R[0] * o.d0 + R[1] * o.d1 + R[2] * o.d2); t[1] = m * (R[3] * o.d0 + R[4] * o.d1 + R[5] * o.d2); t[2] = m * (R[6] * o.d0 + R[7] * o.d1 + R[8] * o.d2);
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------------------

@@ -194,7 +194,15 @@ class RigFocalInfo(C.Structure):
                 ("pairs_used", C.c_int), ("pairs_ignored", C.c_int), ("outliers", C.c_int), ("max_rotation_rad", C.c_double), ("max_focal_ratio", C.c_double)]
 
 
-MATCH_MAX_KEYPOINTS = 32768         # MS_MATCH_MAX_KEYPOINTS
+class RigCoeffParams(C.Structure):
+    _fields_ = RigFocalParams._fields_ + [("free_coeffs", C.c_uint)]
+
+
+class RigCoeffInfo(C.Structure):
+    _fields_ = RigFocalInfo._fields_ + [("max_coeff_change", C.c_double)]
+
+
+MATCH_MAX_KEYPOINTS = 32768        # MS_MATCH_MAX_KEYPOINTS
 WAVE_HORIZ, WAVE_VERT = 0, 1        # ms_wave_correct
 
 
@@ -291,6 +299,7 @@ EXPORTS = [
     "ms_orb_detect_and_compute_batch",
     "ms_list_match_default_params", "ms_match_lists", "ms_feature_inputs_batch",
     "ms_lens_unproject", "ms_lens_unproject_points", "ms_rig_lens_accumulate", "ms_refine_rig_cameras_lens", "ms_refine_rig_focals_lens",
+    "ms_rig_coeff_default_params", "ms_rig_coeff_accumulate", "ms_refine_rig_coeffs", "ms_refine_rig_coeffs_ctx",
     "ms_look_at_view", "ms_cube_face_view", "ms_get_pano_frame", "ms_build_view_maps", "ms_reproject",
 ]
 
@@ -866,6 +875,51 @@ def refine_rig_cameras_lens(f, R, lenses, matches, params=None):
     return fo, out, _rig_focal_info(info)
 
 
+def rig_coeff_default_params(**kw):
+    """ms_rig_coeff_default_params; keyword arguments override fields (free_coeffs: bit b frees lens.k[b])"""
+    p = RigCoeffParams()
+    _chk(load().ms_rig_coeff_default_params(C.byref(p)))
+    for k, v in kw.items():
+        assert hasattr(p, k), k
+        setattr(p, k, v)
+    return p
+
+
+def _rig_coeff_info(info):
+    return {k: getattr(info, k) for k, _ in RigCoeffInfo._fields_}
+
+
+def rig_coeff_accumulate(f, R, lens, free_coeffs, matches, huber_px=0.0):
+    """ms_rig_coeff_accumulate: rig_lens_accumulate with the one Lens on every view and the coefficient rows of the free_coeffs mask last ->
+    (cost, H (4n + G, 4n + G), g (4n + G,)) at these cameras and this lens"""
+    import numpy as np
+    fa = np.ascontiguousarray(f, np.float64); Ra = np.ascontiguousarray(R, np.float64)
+    n = len(Ra)
+    d = 4 * n + bin(int(free_coeffs) & 0xffffffff).count("1")
+    H = np.empty((d, d), np.float64); g = np.empty(d, np.float64)
+    cost = C.c_double(0)
+    dp = C.POINTER(C.c_double)
+    _chk(load().ms_rig_coeff_accumulate(n, fa.ctypes.data_as(dp), Ra.ctypes.data_as(dp), C.byref(lens) if lens is not None else None, C.c_uint(free_coeffs),
+                                        rig_px_matches(matches), len(matches), C.c_double(huber_px), C.byref(cost), H.ctypes.data_as(dp), g.ctypes.data_as(dp), _stream()))
+    return cost.value, H, g
+
+
+def refine_rig_coeffs(f, R, lens, matches, params=None):
+    """ms_refine_rig_coeffs: refine_rig_cameras_lens with one Lens shared by all views and params.free_coeffs of its coefficients free ->
+    (refined f (n,), refined R (n, 3, 3), refined Lens, info dict)"""
+    import numpy as np
+    fa = np.ascontiguousarray(f, np.float64); Ra = np.ascontiguousarray(R, np.float64)
+    n = len(Ra)
+    fo = np.empty(n, np.float64); out = np.empty((n, 3, 3), np.float64)
+    prm = params if params is not None else rig_coeff_default_params()
+    info = RigCoeffInfo()
+    lens_out = Lens()
+    dp = C.POINTER(C.c_double)
+    _chk(load().ms_refine_rig_coeffs(n, fa.ctypes.data_as(dp), Ra.ctypes.data_as(dp), C.byref(lens) if lens is not None else None, rig_px_matches(matches), len(matches),
+                                     C.byref(prm), fo.ctypes.data_as(dp), out.ctypes.data_as(dp), C.byref(lens_out), C.byref(info), _stream()))
+    return fo, out, lens_out, _rig_coeff_info(info)
+
+
 def pair_match_default_params(**kw):
     """ms_pair_match_default_params; keyword arguments override fields (pair_mask: see match_pairs)"""
     p = PairMatchParams()
@@ -1421,6 +1475,19 @@ class Compositor:
         _chk(load().ms_refine_rig_focals_lens(self._ctx, marr, mcnt, C.byref(prm), f.ctypes.data_as(C.POINTER(C.c_double)), out.ctypes.data_as(C.POINTER(C.c_float)),
                                               C.byref(info), _stream()))
         return f, out, _rig_focal_info(info)
+
+    def refine_rig_coeffs(self, matches, params=None):
+        """ms_refine_rig_coeffs_ctx: refine_rig_focals_lens with the coefficients params.free_coeffs of the lens all views share free -> (focals (n,) float64,
+        R (n, 3, 3) float32, Lens, info dict).  Nothing is applied to the context."""
+        import numpy as np
+        marr, mcnt = _match_array(matches)
+        prm = params if params is not None else rig_coeff_default_params()
+        f = np.empty(self.n, np.float64); out = np.empty((self.n, 3, 3), np.float32)
+        info = RigCoeffInfo()
+        lens_out = Lens()
+        _chk(load().ms_refine_rig_coeffs_ctx(self._ctx, marr, mcnt, C.byref(prm), f.ctypes.data_as(C.POINTER(C.c_double)), out.ctypes.data_as(C.POINTER(C.c_float)),
+                                             C.byref(lens_out), C.byref(info), _stream()))
+        return f, out, lens_out, _rig_coeff_info(info)
 
     def build_maps(self):
         _chk(load().ms_build_maps(self._ctx, _stream()))
