@@ -1083,7 +1083,7 @@ MS_API int ms_refine_rig_focals(ms_ctx *ctx, const ms_mesh_match *matches, const
  * A match with a pixel its lens does not see at the TRIAL cameras adds +infinity to the cost and nothing to any other sum: the trial is rejected by the accept rule
  * (cost_trial <= cost fails), so every returned camera sees every match.  At the INPUT cameras such a pixel is MS_ERR_INVALID naming the match, found on the host
  * before the device is touched.  Both calls refuse what their pinhole forms refuse, and a lens ms_lens_check refuses; no floating-point atomics, two calls return
- * the same bits.  Stated limits: principal points are not unknowns, and the lenses are fixed in these two calls (ms_refine_rig_coeffs below frees the coefficients of
+ * the same bits.  Stated limits: principal points are held in these two calls (ms_refine_rig_pp below frees them), and so are the lenses (ms_refine_rig_coeffs frees the coefficients of
  * a lens the whole rig shares); ms_estimate_rig stays pinhole, a lens rig starts from a nominal focal. */
 MS_API int ms_rig_lens_accumulate(int n_views, const double *f, const double *R, const ms_lens *lenses, const ms_rig_px_match *matches, int n, double huber_px,
                                   double *cost, double *H, double *g, ms_stream stream);
@@ -1120,7 +1120,7 @@ MS_API int ms_refine_rig_focals_lens(ms_ctx *ctx, const ms_mesh_match *matches, 
  * A trial lens must stay a lens: ms_lens_check's profile rule (4096 samples on [0, max_theta]) is evaluated on the device for the trial coefficients, and a trial
  * that fails it is treated as a non-positive pivot is: lambda <- 10 lambda, one iteration, solve again.  The fisheye limit theta_d(max_theta) is the TRIAL lens's; a
  * pixel the trial lens no longer sees adds +infinity to the cost as above.  So every returned lens passes ms_lens_check and sees every match.
- * Stated limits: one lens a rig, at most 4 free coefficients, no denominators, no principal points, no prior on the coefficients (a coefficient the matches do not
+ * Stated limits: one lens a rig, at most 4 free coefficients, no denominators, no principal points (ms_refine_rig_pp, with the lenses fixed), no prior on the coefficients (a coefficient the matches do not
  * constrain -- rays near the axis only -- is held by the damping alone). */
 typedef struct ms_rig_coeff_params {
     unsigned struct_size;          /* as ms_config: mismatch = MS_ERR_INVALID */
@@ -1158,6 +1158,88 @@ MS_API int ms_refine_rig_coeffs(int n_views, const double *f_in, const double *R
  * differs (view 0 where it has no lens).  Nothing is applied: the caller runs ms_set_lens and the usual chain.  State errors and refusals as ms_refine_rig_focals_lens. */
 MS_API int ms_refine_rig_coeffs_ctx(ms_ctx *ctx, const ms_mesh_match *matches, const int *match_count, const ms_rig_coeff_params *prm, double *focal_out, float *R_out,
                                     ms_lens *lens_out, ms_rig_coeff_info *info, ms_stream stream);
+/* The centre form: the lens form above (every view behind a FIXED lens, one per view, MS_LENS_NONE where it has none) with each view's principal point among the
+ * unknowns -- what detail::BundleAdjusterReproj (OCV/stitching/src/motion_estimators.cpp:329-511) estimates beside the focal (its ppx, ppy under the
+ * refinement mask).  Matches are ms_rig_px_match as before: pixels centred on the NOMINAL principal point, y divided by the aspect ratio.  pp: n_views x 2 doubles (ox, oy), the
+ * offset of the true centre from the point the pixels are centred on, in the same units.  View i's side of a match is the centred pixel (xa - ox_i, ya - oy_i), each
+ * one subtraction; from there on the ray a, p = R_i a, m = sqrt(f_i f_j), r = m (p - q), Huber, the Levenberg-Marquardt rule and the stop rules are the lens form's,
+ * and a pixel the lens does not see at the trial cameras and offsets adds +infinity to the cost and nothing to any other sum.
+ * Six unknowns a view in the order (delta_0, delta_1, delta_2, s, ox, oy); the step of a centre is additive, o <- o + d.  With A = d a / d (xd, yd) at
+ * (xd, yd) = pixel / f, da/dox = -(A[:,0]) / f and da/doy = -(A[:,1]) / f:
+ *   NONE     n = sqrt(x x + y y + f f) (the pinhole contract's na):
+ *            da/dox = (-((1 - a0 a0) / n), (a0 a1) / n, (a0 a2) / n),  da/doy = ((a0 a1) / n, -((1 - a1 a1) / n), (a1 a2) / n)       (= -((e_x - a0 a) / n), -((e_y - a1 a) / n))
+ *   FISHEYE  A v = ((v . e) / slope) (cos theta e0, cos theta e1, -sin theta) + ((v . e^) sin theta / theta_d) (-e1, e0, 0), e^ = (-e1, e0), slope = d theta_d / d theta;
+ *            with g = sin theta / theta_d, c0 = e0 / slope, c1 = e1 / slope, s0 = e1 g, s1 = e0 g:
+ *            A[:,0] = (c0 (cos theta e0) + s0 e1, c0 (cos theta e1) - s0 e0, -(c0 sin theta)),  A[:,1] = (c1 (cos theta e0) - s1 e1, c1 (cos theta e1) + s1 e0, -(c1 sin theta));
+ *            at the centre A is the first two columns of the identity.  da/dox = (-(A00 / f), -(A10 / f), -(A20 / f)), da/doy likewise
+ *   BROWN    (x', y') is column c of J^-1 by Cramer's rule: (J3 / det, -(J2 / det)) for c = 0, (-(J1 / det), J0 / det) for c = 1; t = a0 x' + a1 y';
+ *            A[:,c] = ((x' - a0 t) / n, (y' - a1 t) / n, -(a2 t) / n), the projection onto the sphere da/ds and da/dk use; da/dox, da/doy from A as for FISHEYE
+ *   Residual columns: ex_i,k = m (R_i da/dox_i)_k and ey_i likewise, (R d)_k = R[3k] d0 + R[3k+1] d1 + R[3k+2] d2; for view j the columns are -(m (R_j db/dox_j)_k),
+ *   -(m (R_j db/doy_j)_k).  With c_i = (ci, ex_i, ey_i) and c_j = (cj, -(m R_j db/dox_j), -(m R_j db/doy_j)) the three non-rotation columns of each view:
+ * The 92 sums of a pair (RigSums<6>), x the cross product written out as in g_i, . the dot product x0 y0 + x1 y1 + x2 y2 left to right:
+ *     cost  sum rho
+ *     g_i   sum w (u x r)_k, k = 0 1 2;  then sum w (c_i[n] . r), n = 0 1 2          g_j   sum -(w (v x r)_k);  then sum w (c_j[n] . r)
+ *     H_ii  symmetric, upper triangle row-major (00 01 .. 05 11 .. 15 22 .. 55): the rotation block of the 46 sums; (k, 3 + n): w (u x c_i[n])_k;
+ *           (3 + n, 3 + n'), n <= n': w (c_i[n] . c_i[n'])
+ *     H_jj  the same with v and c_j, its rotation-column entries negated: -(w (v x c_j[n])_k)
+ *     H_ij  6 x 6 row-major (rows: view i): the rotation block of the 46 sums; (r, 3 + n): w (u x c_j[n])_r; (3 + n, c): -(w (v x c_i[n])_c);
+ *           (3 + n, 3 + n'): w (c_i[n] . c_j[n'])
+ *     outliers
+ *   every product, sum, division and sqrt one IEEE operation in the order written.  The 46 sums among the 92 that involve only the rotations and the focals are the
+ *   lens form's expressions in the lens form's summation order: they are THE BITS of ms_rig_lens_accumulate on matches whose pixels had the offsets subtracted in
+ *   double beforehand.
+ * The system: the anchor's rotation is held, its focal and centre are free; with per-view focals at most 6 * 16 - 3 = 93 unknowns; shared_focal folds the focal
+ * rows and columns of all views into one (78 at most); the centres are always per view.  step_tol is tested on max |.| over ALL components of the step, the centre
+ * components divided by the view's current focal first, so the test is in radians like the rest.
+ * Prior: pp_prior is a weight w >= 0, 0 = none.  The refinement's cost is the data cost plus w sum_v ((ox_v - ox_in_v)^2 + (oy_v - oy_in_v)^2); the step kernel adds it
+ * after the assembly, view after view: w onto the two diagonal entries, w (o - o_in) onto the two entries of g; accept and reject use the total cost.  w is
+ * (match noise / centre tolerance)^2: with 0.5 px of match noise, w = 0.0025 holds a centre to about 10 px where the matches say nothing.  A ring of 4 views
+ * constrains its centres weakly (they trade against the rotations); from 6 views on no prior is needed.
+ * A warning the siblings share in principle and this form makes practical: r = m (p - q) with m = sqrt(f_i f_j) has a trivial minimum at f -> 0 (|p - q| <= 2).  From
+ * a start inside the basin of the true cameras the loop never goes there, but free centres widen the ways out of a poor one: on sparse, partly false matches a
+ * shared-focal run without Huber has walked to f ~ 1e-27 at a cost of 0.  The call does not judge its answer: check info.max_focal_ratio and max_pp_shift against
+ * what the rig can be, select pairs by confidence before it as BundleAdjusterBase does, and give pp_prior where matches are few.
+ * Stated limits: the lenses are fixed in this call (alternate it with ms_refine_rig_coeffs for a joint calibration; a joint form would carry about 154 sums a
+ * pair); no aspect ratio or skew among the unknowns; no centre shared between views. */
+typedef struct ms_rig_pp_params {
+    unsigned struct_size;          /* as ms_config: mismatch = MS_ERR_INVALID */
+    int anchor_view;               /* the fields of ms_rig_focal_params, with its defaults ... */
+    int shared_focal;
+    int max_iters;
+    double huber_px;
+    double step_tol;
+    int min_pair_matches;
+    double pp_prior;               /* ... and the weight of the prior on the centres; default 0 (none) */
+} ms_rig_pp_params;
+typedef struct ms_rig_pp_info {
+    int iterations, stop_reason;   /* the fields of ms_rig_focal_info ... */
+    double cost_initial, cost_final;   /* (with the prior's share) */
+    int matches_used, pairs_used, pairs_ignored;
+    int outliers;
+    double max_rotation_rad;
+    double max_focal_ratio;
+    double max_pp_shift;           /* ... and the largest |o_out - o_in| over both components of every view, in pixels */
+} ms_rig_pp_info;
+/* anchor 0, per-view focals, 50 iterations, no Huber, step_tol 1e-10, 4 matches a pair, no prior */
+MS_API int ms_rig_pp_default_params(ms_rig_pp_params *prm);
+/* The normal equations of the centre form, per op (no counterpart in OpenCV, which differentiates calcError numerically: calcJacobian, motion_estimators.cpp:448-511):
+ * cost, H ((6 n_views)^2 row-major, view v at rows 6v .. 6v + 5, no view held) and g (6 n_views) at the focals f, rotations R and offsets pp, every pair used
+ * whatever its size, no prior.  lenses == NULL: every view is MS_LENS_NONE.  H is symmetric bit for bit.  All pointers HOST.  Synchronises. */
+MS_API int ms_rig_pp_accumulate(int n_views, const double *f, const double *R, const double *pp, const ms_lens *lenses, const ms_rig_px_match *matches, int n,
+                                double huber_px, double *cost, double *H, double *g, ms_stream stream);
+/* detail::BundleAdjusterReproj's estimate with the centres free (BundleAdjusterBase::estimate, motion_estimators.cpp:223-326), on the ray residual of the lens form:
+ * one pinned upload, max_iters + 1 rounds of two kernels, one copy back, one synchronise; no floating-point atomics, two calls return the same bits; the anchor's
+ * R_out is its R_in's bits.  pp_in / pp_out: n_views x 2 doubles; lenses may be NULL (all NONE).  Refused before the device is touched: everything
+ * ms_refine_rig_cameras_lens refuses, a non-finite offset, a negative or non-finite pp_prior, and a pixel its lens does not see at the input cameras AND offsets,
+ * naming the match (all MS_ERR_INVALID). */
+MS_API int ms_refine_rig_pp(int n_views, const double *f_in, const double *R_in, const double *pp_in, const ms_lens *lenses, const ms_rig_px_match *matches, int n,
+                            const ms_rig_pp_params *prm, double *f_out, double *R_out, double *pp_out, ms_rig_pp_info *info, ms_stream stream);
+/* The context form (BundleAdjusterReproj on a context's cameras): the lists become centred source pixels exactly as in ms_refine_rig_focals_lens, pp_in = 0, then
+ * ms_refine_rig_pp runs.  pp_out: num_views x 2 doubles, the new K[2] and K[5] of each view: K[2] + ox and K[5] + oy K[4] / K[0].  focal_out: num_views doubles;
+ * R_out: num_views x 9 floats.  Nothing is applied: the caller sets K and runs the usual chain (ms_set_camera, ms_build_maps, masks, ms_init_blender).  State errors
+ * and refusals are ms_refine_rig_focals_lens': MS_ERR_STATE before ms_build_maps, MS_ERR_UNSUPPORTED for MS_MAPS_CUSTOM contexts and for a view with K[1] != 0. */
+MS_API int ms_refine_rig_pp_ctx(ms_ctx *ctx, const ms_mesh_match *matches, const int *match_count, const ms_rig_pp_params *prm, double *focal_out, double *pp_out,
+                                float *R_out, ms_rig_pp_info *info, ms_stream stream);
 
 /* ---- Pairwise matching: every view pair of a rig in one call ---------------------------------------------------------------------------------------
  * detail::BestOf2NearestMatcher / BestOf2NearestRangeMatcher (OCV/stitching/src/matchers.cpp:248-297 the two-direction 2-NN match with ratio test and

@@ -202,6 +202,14 @@ class RigCoeffInfo(C.Structure):
     _fields_ = RigFocalInfo._fields_ + [("max_coeff_change", C.c_double)]
 
 
+class RigPpParams(C.Structure):
+    _fields_ = RigFocalParams._fields_ + [("pp_prior", C.c_double)]
+
+
+class RigPpInfo(C.Structure):
+    _fields_ = RigFocalInfo._fields_ + [("max_pp_shift", C.c_double)]
+
+
 MATCH_MAX_KEYPOINTS = 32768        # MS_MATCH_MAX_KEYPOINTS
 WAVE_HORIZ, WAVE_VERT = 0, 1        # ms_wave_correct
 
@@ -300,6 +308,7 @@ EXPORTS = [
     "ms_list_match_default_params", "ms_match_lists", "ms_feature_inputs_batch",
     "ms_lens_unproject", "ms_lens_unproject_points", "ms_rig_lens_accumulate", "ms_refine_rig_cameras_lens", "ms_refine_rig_focals_lens",
     "ms_rig_coeff_default_params", "ms_rig_coeff_accumulate", "ms_refine_rig_coeffs", "ms_refine_rig_coeffs_ctx",
+    "ms_rig_pp_default_params", "ms_rig_pp_accumulate", "ms_refine_rig_pp", "ms_refine_rig_pp_ctx",
     "ms_look_at_view", "ms_cube_face_view", "ms_get_pano_frame", "ms_build_view_maps", "ms_reproject",
 ]
 
@@ -920,6 +929,52 @@ def refine_rig_coeffs(f, R, lens, matches, params=None):
     return fo, out, lens_out, _rig_coeff_info(info)
 
 
+def rig_pp_default_params(**kw):
+    """ms_rig_pp_default_params; keyword arguments override fields (pp_prior: the weight of the prior on the centres, 0 = none)"""
+    p = RigPpParams()
+    _chk(load().ms_rig_pp_default_params(C.byref(p)))
+    for k, v in kw.items():
+        assert hasattr(p, k), k
+        setattr(p, k, v)
+    return p
+
+
+def _rig_pp_info(info):
+    return {k: getattr(info, k) for k, _ in RigPpInfo._fields_}
+
+
+def rig_pp_accumulate(f, R, pp, lenses, matches, huber_px=0.0):
+    """ms_rig_pp_accumulate: rig_lens_accumulate with the principal-point offsets pp (n, 2) among the unknowns; lenses: one Lens or None a view, or None for a rig
+    without lenses -> (cost, H (6n, 6n), g (6n,)) at these cameras, view v at rows 6v .. 6v + 5 in the order (rotation, log focal, ox, oy)"""
+    import numpy as np
+    fa = np.ascontiguousarray(f, np.float64); Ra = np.ascontiguousarray(R, np.float64); pa = np.ascontiguousarray(pp, np.float64)
+    n = len(Ra)
+    assert pa.shape == (n, 2) and (lenses is None or len(lenses) == n)
+    H = np.empty((6 * n, 6 * n), np.float64); g = np.empty(6 * n, np.float64)
+    cost = C.c_double(0)
+    dp = C.POINTER(C.c_double)
+    _chk(load().ms_rig_pp_accumulate(n, fa.ctypes.data_as(dp), Ra.ctypes.data_as(dp), pa.ctypes.data_as(dp), lens_array(lenses) if lenses is not None else None,
+                                     rig_px_matches(matches), len(matches), C.c_double(huber_px), C.byref(cost), H.ctypes.data_as(dp), g.ctypes.data_as(dp), _stream()))
+    return cost.value, H, g
+
+
+def refine_rig_pp(f, R, pp, lenses, matches, params=None):
+    """ms_refine_rig_pp: refine_rig_cameras_lens with every view's principal-point offset free; pp (n, 2) float64, lenses as rig_pp_accumulate takes them ->
+    (refined f (n,), refined R (n, 3, 3), refined pp (n, 2), info dict)"""
+    import numpy as np
+    fa = np.ascontiguousarray(f, np.float64); Ra = np.ascontiguousarray(R, np.float64); pa = np.ascontiguousarray(pp, np.float64)
+    n = len(Ra)
+    assert pa.shape == (n, 2) and (lenses is None or len(lenses) == n)
+    fo = np.empty(n, np.float64); out = np.empty((n, 3, 3), np.float64); po = np.empty((n, 2), np.float64)
+    prm = params if params is not None else rig_pp_default_params()
+    info = RigPpInfo()
+    dp = C.POINTER(C.c_double)
+    _chk(load().ms_refine_rig_pp(n, fa.ctypes.data_as(dp), Ra.ctypes.data_as(dp), pa.ctypes.data_as(dp), lens_array(lenses) if lenses is not None else None,
+                                 rig_px_matches(matches), len(matches), C.byref(prm), fo.ctypes.data_as(dp), out.ctypes.data_as(dp), po.ctypes.data_as(dp), C.byref(info),
+                                 _stream()))
+    return fo, out, po, _rig_pp_info(info)
+
+
 def pair_match_default_params(**kw):
     """ms_pair_match_default_params; keyword arguments override fields (pair_mask: see match_pairs)"""
     p = PairMatchParams()
@@ -1488,6 +1543,19 @@ class Compositor:
         _chk(load().ms_refine_rig_coeffs_ctx(self._ctx, marr, mcnt, C.byref(prm), f.ctypes.data_as(C.POINTER(C.c_double)), out.ctypes.data_as(C.POINTER(C.c_float)),
                                              C.byref(lens_out), C.byref(info), _stream()))
         return f, out, lens_out, _rig_coeff_info(info)
+
+    def refine_rig_pp(self, matches, params=None):
+        """ms_refine_rig_pp_ctx: refine_rig_focals_lens with every view's principal point free -> (focals (n,) float64, pp (n, 2) float64: the new K[2], K[5] of
+        each view, R (n, 3, 3) float32, info dict).  Nothing is applied to the context."""
+        import numpy as np
+        marr, mcnt = _match_array(matches)
+        prm = params if params is not None else rig_pp_default_params()
+        f = np.empty(self.n, np.float64); pp = np.empty((self.n, 2), np.float64); out = np.empty((self.n, 3, 3), np.float32)
+        info = RigPpInfo()
+        dp = C.POINTER(C.c_double)
+        _chk(load().ms_refine_rig_pp_ctx(self._ctx, marr, mcnt, C.byref(prm), f.ctypes.data_as(dp), pp.ctypes.data_as(dp), out.ctypes.data_as(C.POINTER(C.c_float)),
+                                         C.byref(info), _stream()))
+        return f, pp, out, _rig_pp_info(info)
 
     def build_maps(self):
         _chk(load().ms_build_maps(self._ctx, _stream()))
