@@ -1422,9 +1422,14 @@ MS_API int ms_selftest_cvt_u8(unsigned long long *mismatches_out, ms_stream stre
  * re-projection happens there.  These entry points do the player's step on the device: the direction "virtual camera pixel -> panorama pixel" as dense maps
  * (ms_build_view_maps: detail::{Spherical,Cylindrical}Projector::mapForward, OCV/stitching/include/opencv2/stitching/detail/warpers_inl.hpp:222-236, :258-273, behind
  * the inverse lens model of ms_lens_unproject), and a batched cuda::remap that wraps at the +-pi seam (ms_reproject).
- * Stated limits: 8UC3 panoramas only (no 16S source); INTER_LINEAR only (no nearest, no cubic); no antialiasing -- a view coarser than the panorama point-samples
- * it, as cuda::remap does; coordinates always come from maps (a pose that changes every frame rebuilds them: ms_build_view_maps is one launch); MS_PROJ_PLANE
- * panoramas are MS_ERR_UNSUPPORTED; one GPU. */
+ * Stated limits: 8UC3 panoramas only (no 16S source); INTER_LINEAR only (no nearest, no cubic); coordinates always come from maps (a pose that changes every
+ * frame rebuilds them: ms_build_view_maps is one launch); MS_PROJ_PLANE panoramas are MS_ERR_UNSUPPORTED; one GPU.
+ * Antialiasing: ms_reproject point-samples, as cuda::remap does -- right for a view as fine as the panorama, moire for a coarser one.  ms_reproject_aa is the
+ * player's mip-mapped texture unit: ISOTROPIC trilinear over a per-call mip chain (ms_build_pano_mips), the level chosen per pixel from the view's footprint
+ * (ms_build_view_footprint).  No anisotropic filtering, no cubic or Lanczos taps.  What that buys, measured on the numpy statement (tests/reproject_aa_ref.py, stripes
+ * of period 3 panorama pixels on a 384 x 192 equirect, RMS error against an 8 x 8 supersample, relative to point sampling): 0.14 for a 24 x 14 viewport of 90
+ * degrees (footprint 3.3-5.1 px), and 1.06 -- WORSE than point sampling -- for a 48 x 27 one (footprint 1.6-2.5): isotropic trilinear blurs a signal that lies barely
+ * above the view's Nyquist rate, the known price of mip mapping.  footprint_scale is the caller's knob: below 1 it trades that blur for alias. */
 
 /* How a panorama image lies on the warper surface: image pixel (x, y) is the warper coordinate (u0 + x, v0 + y) of a warper of `scale`. */
 typedef struct ms_pano_frame {
@@ -1518,6 +1523,69 @@ enum { MS_VIEW_BGR = 0, MS_VIEW_I420 = 1 };
 enum { MS_VIEW_MAX_FRAMES = 64, MS_VIEW_MAX_JOBS = 16, MS_VIEW_FRAME_GROUP = 8, MS_VIEW_TILE_W = 64, MS_VIEW_TILE_H = 16 };
 MS_API int ms_reproject(const ms_image *src, ms_image *dst, int n_frames, const ms_view_job *jobs, int n_jobs, int wrap_cols, int clamp_rows, int format,
                         ms_stream stream);
+
+/* The packing of a panorama's mip chain (host only, no device) -- replaces the mip chain the player's GPU builds for the equirect texture it is handed
+ * (APP/timed.cpp:296-300).  out[l - 1] describes level l = 1..levels of a cols x rows 8UC3 image: cols_l = (cols_{l-1} + 1) / 2, rows_l = (rows_{l-1} + 1) / 2,
+ * pixel (x, y) at byte offset + y step + 3 x of the frame's buffer; *bytes is that buffer's size.  The levels do not overlap; every offset is a multiple of 256,
+ * every step a multiple of 16 (>= 3 cols_l), and the buffer itself must be 16-byte aligned: the builder stores whole words, and level 3 is read back with aligned
+ * wide loads when levels 4 and up are made.  Read the levels through this function only.  MS_ERR_INVALID: a null pointer, levels outside
+ * [1, MS_VIEW_MAX_LEVELS], cols or rows outside [1, 32767]. */
+enum { MS_VIEW_MAX_LEVELS = 6 };
+typedef struct ms_mip_level { size_t offset, step; int cols, rows; } ms_mip_level;
+MS_API int ms_pano_mips_layout(int cols, int rows, int levels, ms_mip_level *out, size_t *bytes);
+
+/* The mip chains of n_frames panoramas -- replaces glGenerateMipmap's box filter in the player (APP/timed.cpp:296-300 hands the equirect to it).
+ *   src:  n_frames DEVICE 8UC3 images of one geometry, as ms_reproject's src (any base address, step < 2^24, rows * step < 2^32), sides in [1, 32767].
+ *   mips: HOST array of n_frames DEVICE buffers of ms_pano_mips_layout's *bytes bytes each, 16-byte aligned.
+ * Arithmetic (integers, exact).  Level 0 is the source and is never copied.  Level l is made from the STORED bytes of level l - 1, per channel
+ *   p_l(x, y) = (p(2x, 2y) + p(2x+1, 2y) + p(2x, 2y+1) + p(2x+1, 2y+1) + 2) >> 2,
+ * an index past the last column or row of level l - 1 reading the last one.  No byte outside a level's cols_l x rows_l x 3 pixels is written (row padding and
+ * the bytes between levels keep what they held).
+ * Launches: ceil(levels / 3), whatever n_frames is -- a lane holds an 8 x 8 block of the source and finishes its level-1, -2 and -3 pixels in registers; levels
+ * 4 to 6 are the same kernel on level 3 (csrc/reproject_aa.hip).  Nothing is allocated, the host never waits.
+ * MS_ERR_INVALID, before the device is touched: a null pointer; n_frames outside [1, MS_VIEW_MAX_FRAMES]; levels outside [1, MS_VIEW_MAX_LEVELS]; src frames
+ * that are not 8UC3, differ in geometry or break the limits above; a null or misaligned mips[f]; a mips buffer whose byte range overlaps a src frame's or
+ * another mips buffer's.  No CPU fallback: MS_ERR_NO_DEVICE as elsewhere. */
+MS_API int ms_build_pano_mips(const ms_image *src, void *const *mips, int n_frames, int levels, ms_stream stream);
+
+/* The footprint of a view's pixels in the panorama -- replaces the derivative the player's texture unit takes per fragment to choose a mip level.  rho(x, y) is
+ * the side, in level-0 panorama pixels, of the patch view pixel (x, y) covers.  Calibration-time work like ms_build_view_maps: ONE launch, one lane per pixel,
+ * everything in double and rounded to float once, at the store; tests/reproject_aa_ref.py is the numpy statement.
+ *   An entry is UNSEEN when both maps hold exactly -1 or either value is not finite; rho of an unseen pixel is 0, an unseen neighbour counts as absent.
+ *   a = E(x+1, y) - E(x, y) with E = ((double)map_x, (double)map_y); E(x, y) - E(x-1, y) where the forward neighbour is absent (outside the maps, or unseen);
+ *   (0, 0) where both are.  b likewise along y.
+ *   Wrap: with W = src->wrap_cols > 0 the x component d of each difference becomes d - W floor(d / W + 0.5).
+ *   Spherical weight: for a spherical src the x components are then multiplied by s = sin(min(max((Y + v0) / S, 0), pi)), Y = map_y(x, y), S = (double)src->scale;
+ *   a cylindrical src has s = 1.  An equirect row at polar angle theta holds 1 / sin(theta) columns per unit of angle: a step of many columns near a pole is a
+ *   small step on the sphere, and the panorama there is band-limited in angle, not in columns.  Without the weight every "up" or "down" view would be blurred to
+ *   the coarsest level.
+ *   rho = footprint_scale max(hypot(a), hypot(b)).  footprint_scale in (0, 16]; 1 is neutral, below 1 trades blur for alias (section 5's head).
+ * map_x / map_y / rho: DEVICE 32FC1 of one size, any row step, data and step 4-byte aligned.
+ * MS_ERR_INVALID, before the device is touched: a null pointer; ms_build_view_maps' checks on src (struct_size, projection, scale, wrap_cols, clamp_rows); maps
+ * or rho that are not 32FC1, not of one size or misaligned; a footprint_scale that is not finite or lies outside (0, 16].  MS_ERR_UNSUPPORTED: MS_PROJ_PLANE. */
+MS_API int ms_build_view_footprint(const ms_pano_frame *src, const ms_image *map_x, const ms_image *map_y, double footprint_scale, ms_image *rho, ms_stream stream);
+
+/* ms_reproject with the player's trilinear, mip-mapped texture lookup (APP/timed.cpp:296-300: the equirect goes to a player whose GPU samples it so) in place of
+ * the point sample: n_frames panoramas and n_jobs views in ONE launch, the job table in the kernel argument, exactly like ms_reproject.
+ *   src, dst, wrap_cols, clamp_rows, format: as ms_reproject's.  mips: HOST array of n_frames DEVICE buffers, ms_build_pano_mips' of the same src and levels.
+ *   jobs: HOST; job, as ms_reproject's, and rho: DEVICE 32FC1 of the maps' size (ms_build_view_footprint's, or any float -- see below).
+ * Arithmetic per pixel, all fp32.  (X, Y) the map entry, r = rho, L = levels.
+ *   Level: !(r > 1) (NaN, zero and negatives included): l = 0, t = 0.  Else r >= 2^L: l = L, t = 0.  Else l = floor(log2 r), read from the float's exponent
+ *   field, and t = fmaf(r, 2^-l, -1.0f) -- exact, 0 <= t < 1.
+ *   Coordinates at level k: X_k = fmaf(X, 2^-k, 2^-(k+1) - 0.5f), Y_k likewise (the constants are exact: one rounding each; level 0 keeps X, Y).
+ *   C_k[c] is the UNSATURATED fp32 fma chain of ms_reproject run on image level k (level 0 = src) at (X_k, Y_k): the +1 shift and the extended-source rule with
+ *   that level's cols_k, rows_k; the level wraps iff wrap_cols != 0 and clamps iff clamp_rows is set.
+ *   o[c] = fmaf(t, C_{l+1}[c] - C_l[c], C_l[c]), stored through ms_remap's saturation; where t == 0 level l + 1 is not read and o[c] = C_l[c].
+ * Consequences: a job whose rho is at most 1 everywhere is ms_reproject's output, bit for bit; MS_VIEW_I420 equals ms_bgr_to_i420 of the BGR atlas the call would
+ * have written; the maps and rho may hold ANY float and no address outside the source or a level is ever formed.
+ * Kernel shape (csrc/reproject_aa.hip): ms_reproject's -- a lane owns four pixels, builds their two tap states once and walks MS_VIEW_FRAME_GROUP frames with them;
+ * a wave whose pixels all stay on level 0 takes ms_reproject's one-level loop.
+ * MS_ERR_INVALID, before a kernel is enqueued: everything ms_reproject refuses; a null mips; levels outside [1, MS_VIEW_MAX_LEVELS]; a null or misaligned mips[f];
+ * src sides outside [1, 32767]; wrap_cols != 0 with cols no multiple of 2^levels (the coarse level would not close the turn); a rho that is not 32FC1 of the
+ * maps' size or is misaligned; a dst frame whose byte range overlaps a mips buffer's. */
+typedef struct ms_view_job_aa { ms_view_job job; ms_image rho; } ms_view_job_aa;
+MS_API int ms_reproject_aa(const ms_image *src, void *const *mips, int levels, ms_image *dst, int n_frames, const ms_view_job_aa *jobs, int n_jobs, int wrap_cols,
+                           int clamp_rows, int format, ms_stream stream);
 
 #ifdef __cplusplus
 }

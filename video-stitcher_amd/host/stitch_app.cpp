@@ -18,7 +18,7 @@
 // Usage: stitch_app [--views 6] [--size 1920x1080] [--out 3840x1920] [--hfov 90] [--bands 5] [--frames 300] [--cpw]
 //                   [--i420] [--nv12 | --nv12-direct] [--dump pano.bin] [--no-upload] [--solve-mesh [--temporal ALPHA]]
 //                   [--reference-calib [--work-megapix 0.6] [--seam-megapix 0.01] [--compose-megapix 1.4] [--seam-finder voronoi|dp]]
-//                   [--viewport YAW,PITCH,ROLL,HFOV,WxH | --cubemap N]
+//                   [--viewport YAW,PITCH,ROLL,HFOV,WxH | --cubemap N] [--aa LEVELS]
 //                   [--drop-view V:F0:F1] [--dump-frames frames.bin] [--track-gains K] [--exposure-ramp V:F] [--dump-i420 planes.bin]
 //                   [--lens-brown k1,k2,p1,p2,k3 | --lens-fisheye k1,k2,k3,k4[,max_theta]]
 //                   [--rig-error V:YAW:PITCH:ROLL] [--refine-rig]
@@ -37,6 +37,8 @@
 // ms_stitch_nv12 + ms_bgr_to_i420), --track-gains reads the planes (ms_track_gains_nv12).  With a compose-scale resize (--reference-calib) the frames go
 // through ms_nv12_to_bgr_batch + ms_resize_linear_batch: the one-pass ms_nv12_resize_linear_batch gives the same bytes (--fused-resize selects it) but is
 // measured slower than the two launches (41 against 37 us per six 1080p frames, README).  With --nv12 the exposure ramp scales the Y plane only (the camera's exposure, not its colour).
+// --aa LEVELS (with --viewport or --cubemap) renders the views antialiased: the footprints are built once, beside the maps (ms_build_view_footprint), every canvas
+// gets its mip chain of LEVELS levels (ms_build_pano_mips) and ms_reproject_aa samples it; the JSON line then carries "aa_levels".  Without it nothing changes.
 // --dump-i420 FILE writes the last frame's I420 planes (every --i420 mode); the JSON line's "i420_call" names the call that produced them.
 // --track-gains K: every K-th stitch call is followed by one ms_track_gains on the stitch stream with that call's frames (exposure tracking; 0 = off, the
 // default: nothing changes).  --exposure-ramp V:F multiplies camera V's synthetic frames by F from the middle of the run on, so that the tracker has a drift
@@ -115,6 +117,7 @@ struct Options {
     bool viewport = false;                      // --viewport YAW,PITCH,ROLL,HFOV,WxH: a virtual pan / tilt / zoom camera rendered from the canvas (ms_reproject) in consume()
     double vp_yaw = 0, vp_pitch = 0, vp_roll = 0, vp_hfov = 90;
     int vp_w = 0, vp_h = 0;
+    int aa = 0;                                 // --aa LEVELS: ms_build_pano_mips + ms_reproject_aa instead of ms_reproject
     int cubemap = 0;                            // --cubemap N: a 3N x 2N atlas of six N x N faces (ms_cube_face_view order, left to right, top to bottom)
     bool fused_resize = false;                  // --fused-resize: with --nv12-direct and a compose-scale resize, planes -> small_imgs in one pass
     ms_lens lens{sizeof(ms_lens), MS_LENS_NONE, {0, 0, 0, 0, 0, 0, 0, 0}, 0.0};      // --lens-brown / --lens-fisheye: every camera's lens
@@ -271,6 +274,7 @@ int main(int argc, char **argv)
             o.viewport = true;
         }
         else if (k == "--cubemap") o.cubemap = atoi(next());
+        else if (k == "--aa") o.aa = atoi(next());
         else if (k == "--fused-resize") o.fused_resize = true;
         else if (k == "--lens-brown") {      // k1,k2,p1,p2,k3 in distCoeffs order: k3 is k[4]
             double *c = o.lens.k;
@@ -308,6 +312,8 @@ int main(int argc, char **argv)
     if (!o.dump_i420.empty() && !o.i420) { fprintf(stderr, "--dump-i420 needs --i420\n"); return 2; }
     if (o.viewport && o.cubemap) { fprintf(stderr, "--viewport and --cubemap exclude each other\n"); return 2; }
     if (o.cubemap < 0 || (o.cubemap && o.i420 && o.cubemap % 2)) { fprintf(stderr, "--cubemap wants N >= 1 (even with --i420)\n"); return 2; }
+    if (o.aa && !(o.viewport || o.cubemap)) { fprintf(stderr, "--aa needs --viewport or --cubemap\n"); return 2; }
+    if (o.aa < 0 || o.aa > MS_VIEW_MAX_LEVELS) { fprintf(stderr, "--aa wants 1..%d levels\n", (int)MS_VIEW_MAX_LEVELS); return 2; }
     if (o.viewport && o.i420 && (o.vp_w % 2 || o.vp_h % 2)) { fprintf(stderr, "--viewport with --i420 wants an even size\n"); return 2; }
     if (o.fused_resize && !o.nv12_direct) { fprintf(stderr, "--fused-resize needs --nv12-direct\n"); return 2; }
     if (ms_lens_check(&o.lens) != MS_OK) { fprintf(stderr, "stitch_app: %s\n", ms_last_error()); return 2; }
@@ -555,6 +561,9 @@ int main(int argc, char **argv)
         // (ms_get_pano_frame); consume() then renders every view of a frame in one ms_reproject call, as BGR or (--i420) as the encoder's planes.
         std::vector<DevMat> view_mx, view_my;
         std::vector<ms_view_job> view_jobs;
+        std::vector<DevMat> view_rho;                   // --aa: the footprints, and one mips buffer (the consumer renders one canvas at a time)
+        std::vector<ms_view_job_aa> view_jobs_aa;
+        DevMat view_mips;
         DevMat view_frame;
         std::vector<unsigned char> view_host;
         hipStream_t view_stream = nullptr;
@@ -567,6 +576,7 @@ int main(int argc, char **argv)
             const int n_views = o.cubemap ? 6 : 1;
             view_w = o.cubemap ? 3 * o.cubemap : o.vp_w; view_h = o.cubemap ? 2 * o.cubemap : o.vp_h;
             view_mx.resize(n_views); view_my.resize(n_views); view_jobs.resize(n_views);
+            if (o.aa) { view_rho.resize(n_views); view_jobs_aa.resize(n_views); }
             HIPCHECK(hipStreamCreateWithFlags(&view_stream, hipStreamNonBlocking));
             for (int i = 0; i < n_views; ++i) {
                 ms_view v;
@@ -576,6 +586,18 @@ int main(int argc, char **argv)
                 ms_image mx = msshim::wrap(view_mx[i]), my = msshim::wrap(view_my[i]);
                 msshim::check(ms_build_view_maps(&pf, &v, &mx, &my, (ms_stream)view_stream));
                 view_jobs[i] = ms_view_job{mx, my, o.cubemap ? (i % 3) * o.cubemap : 0, o.cubemap ? (i / 3) * o.cubemap : 0};
+                if (o.aa) {
+                    view_rho[i].create(v.height, v.width, MS_32FC1);
+                    ms_image rho = msshim::wrap(view_rho[i]);
+                    msshim::check(ms_build_view_footprint(&pf, &mx, &my, 1.0, &rho, (ms_stream)view_stream));
+                    view_jobs_aa[i] = ms_view_job_aa{view_jobs[i], rho};
+                }
+            }
+            if (o.aa) {
+                ms_mip_level lv[MS_VIEW_MAX_LEVELS];
+                size_t mip_bytes = 0;
+                msshim::check(ms_pano_mips_layout(o.out_w, o.out_h, o.aa, lv, &mip_bytes));
+                view_mips.create(1, (int)mip_bytes, MS_8UC1, 1, true);
             }
             HIPCHECK(hipStreamSynchronize(view_stream));
             if (o.i420) view_frame.create(view_h * 3 / 2, view_w, MS_8UC1, 1, true);
@@ -589,7 +611,14 @@ int main(int argc, char **argv)
                 HIPCHECK(hipEventSynchronize(s->done));
                 if (view_on) {                          // the virtual cameras' frame instead of (beside) the equirect: one launch, then the encoder's copy
                     ms_image src = msshim::wrap(s->pano8u), dst = msshim::wrap(view_frame);
-                    msshim::check(ms_reproject(&src, &dst, 1, view_jobs.data(), (int)view_jobs.size(), view_wrap, view_clamp, o.i420 ? MS_VIEW_I420 : MS_VIEW_BGR, (ms_stream)view_stream));
+                    if (o.aa) {
+                        void *mips = view_mips.data;
+                        msshim::check(ms_build_pano_mips(&src, &mips, 1, o.aa, (ms_stream)view_stream));
+                        msshim::check(ms_reproject_aa(&src, &mips, o.aa, &dst, 1, view_jobs_aa.data(), (int)view_jobs_aa.size(), view_wrap, view_clamp, o.i420 ? MS_VIEW_I420 : MS_VIEW_BGR,
+                                                      (ms_stream)view_stream));
+                    } else {
+                        msshim::check(ms_reproject(&src, &dst, 1, view_jobs.data(), (int)view_jobs.size(), view_wrap, view_clamp, o.i420 ? MS_VIEW_I420 : MS_VIEW_BGR, (ms_stream)view_stream));
+                    }
                     HIPCHECK(hipMemcpyAsync(view_host.data(), view_frame.data, view_host.size(), hipMemcpyDeviceToHost, view_stream));
                     HIPCHECK(hipStreamSynchronize(view_stream));
                     if (s->seq == o.frames - 1) for (unsigned char b : view_host) view_checksum = (view_checksum ^ b) * 1099511628211ull;
@@ -847,6 +876,7 @@ int main(int argc, char **argv)
                consumed, secs, consumed / secs, recalibrations.load(), solver_iterations.load(), (double)max_disp.load(),
                total_keypoints.load(), total_matches.load(), total_inliers.load(), o.update_mask, selfcheck < 0 ? "null" : (selfcheck ? "true" : "false"), consume_image_height, consume_checksum, checksum, degraded_frames, i420_call, fused_resize ? "true" : "false", comp.mapSource(), comp.seamFinder() == MS_SEAM_DP ? "dp" : "voronoi");
         if (view_on) printf(", \"view_out\": \"%dx%d\", \"view_checksum\": \"%016llx\"", view_w, view_h, view_checksum);
+        if (o.aa) printf(", \"aa_levels\": %d", o.aa);
         if (o.temporal > 0.0) printf(", \"temporal_alpha\": %g, \"temporal_matches\": %lld", o.temporal, total_temporal.load());
         if (o.track_gains > 0) {
             std::vector<double> g((size_t)o.views);

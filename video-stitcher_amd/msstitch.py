@@ -111,6 +111,18 @@ class ViewJob(C.Structure):
     _fields_ = [("map_x", Image), ("map_y", Image), ("dst_x", C.c_int), ("dst_y", C.c_int)]
 
 
+class MipLevel(C.Structure):
+    """ms_mip_level: where one level of a panorama's mip chain lies in the frame's buffer (pano_mips_layout)"""
+    _fields_ = [("offset", C.c_size_t), ("step", C.c_size_t), ("cols", C.c_int), ("rows", C.c_int)]
+
+
+class ViewJobAA(C.Structure):
+    _fields_ = [("job", ViewJob), ("rho", Image)]
+
+
+VIEW_MAX_LEVELS = 6
+
+
 class SeamParams(C.Structure):
     _fields_ = [("seam_scale", C.c_double), ("seam_warp_scale", C.c_float), ("dilate", C.c_int), ("estimate_gains", C.c_int)]
 
@@ -310,6 +322,7 @@ EXPORTS = [
     "ms_rig_coeff_default_params", "ms_rig_coeff_accumulate", "ms_refine_rig_coeffs", "ms_refine_rig_coeffs_ctx",
     "ms_rig_pp_default_params", "ms_rig_pp_accumulate", "ms_refine_rig_pp", "ms_refine_rig_pp_ctx",
     "ms_look_at_view", "ms_cube_face_view", "ms_get_pano_frame", "ms_build_view_maps", "ms_reproject",
+    "ms_pano_mips_layout", "ms_build_pano_mips", "ms_build_view_footprint", "ms_reproject_aa",
 ]
 
 _lib = None
@@ -697,6 +710,61 @@ def reproject_prepared(srcs, dsts, jobs, wrap_cols=0, clamp_rows=0, fmt=VIEW_BGR
 def reproject(srcs, dsts, jobs, wrap_cols=0, clamp_rows=0, fmt=VIEW_BGR):
     """ms_reproject: every job's view of every source panorama into its rectangle of the matching destination frame, in one launch"""
     reproject_prepared(srcs, dsts, jobs, wrap_cols, clamp_rows, fmt)()
+    return dsts
+
+
+def pano_mips_layout(cols, rows, levels):
+    """ms_pano_mips_layout (host only): ([MipLevel] for levels 1..levels of a cols x rows 8UC3 image, bytes of one frame's buffer)"""
+    lv = (MipLevel * VIEW_MAX_LEVELS)(); n = C.c_size_t(0)
+    _chk(load().ms_pano_mips_layout(cols, rows, levels, lv, C.byref(n)))
+    return [lv[i] for i in range(levels)], n.value
+
+
+def mip_level_view(buf, level):
+    """level (a MipLevel) of the chain in buf (a flat uint8 tensor that starts at the mips buffer's first byte), as a (rows, cols, 3) view"""
+    return _torch().as_strided(buf, (level.rows, level.cols, 3), (level.step, 3, 1), buf.storage_offset() + level.offset)
+
+
+def build_pano_mips(srcs, levels, out=None):
+    """ms_build_pano_mips: the mip chains of the panoramas srcs (one launch per three levels, whatever len(srcs) is); out: flat uint8 cuda tensors to fill
+    (pano_mips_layout's bytes each, 16-byte aligned) instead of new ones.  Returns the buffers."""
+    torch = _torch()
+    n = len(srcs)
+    if out is None:
+        _, nbytes = pano_mips_layout(srcs[0].shape[1], srcs[0].shape[0], levels)
+        out = [_new((nbytes,), torch.uint8) for _ in range(n)]
+    a = (Image * n)(*[img(t) for t in srcs])
+    ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in out])
+    _chk(load().ms_build_pano_mips(a, ptrs, n, levels, _stream()))
+    return out
+
+
+def build_view_footprint(pano_frame, map_x, map_y, footprint_scale=1.0, out=None):
+    """ms_build_view_footprint: rho, the side in level-0 panorama pixels of the patch each view pixel covers (float32 cuda tensor of the maps' size)"""
+    torch = _torch()
+    rho = out if out is not None else _new(tuple(map_x.shape), torch.float32)
+    _chk(load().ms_build_view_footprint(C.byref(pano_frame), C.byref(img(map_x)), C.byref(img(map_y)), C.c_double(footprint_scale), C.byref(img(rho)), _stream()))
+    return rho
+
+
+def reproject_aa_prepared(srcs, mips, levels, dsts, jobs, wrap_cols=0, clamp_rows=0, fmt=VIEW_BGR):
+    """ms_reproject_aa with the descriptors marshalled once: mips the buffers of build_pano_mips, jobs a list of (map_x, map_y, rho, dst_x, dst_y);
+    returns a callable(stream_handle=None)"""
+    n, m = len(srcs), len(jobs)
+    a = (Image * n)(*[img(t) for t in srcs]); b = (Image * n)(*[img(t) for t in dsts])
+    ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in mips])
+    jt = (ViewJobAA * m)(*[ViewJobAA(ViewJob(img(mx), img(my), dx, dy), img(rho)) for mx, my, rho, dx, dy in jobs])
+    fn = load().ms_reproject_aa
+
+    def run(stream=None):
+        _chk(fn(a, ptrs, levels, b, n, jt, m, wrap_cols, clamp_rows, fmt, stream if stream is not None else _stream()))
+    run.keep = (srcs, mips, dsts, jobs)
+    return run
+
+
+def reproject_aa(srcs, mips, levels, dsts, jobs, wrap_cols=0, clamp_rows=0, fmt=VIEW_BGR):
+    """ms_reproject_aa: ms_reproject with a trilinear, mip-mapped lookup -- every job's view of every panorama, one launch"""
+    reproject_aa_prepared(srcs, mips, levels, dsts, jobs, wrap_cols, clamp_rows, fmt)()
     return dsts
 
 
