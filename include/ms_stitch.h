@@ -1422,8 +1422,8 @@ MS_API int ms_selftest_cvt_u8(unsigned long long *mismatches_out, ms_stream stre
  * re-projection happens there.  These entry points do the player's step on the device: the direction "virtual camera pixel -> panorama pixel" as dense maps
  * (ms_build_view_maps: detail::{Spherical,Cylindrical}Projector::mapForward, OCV/stitching/include/opencv2/stitching/detail/warpers_inl.hpp:222-236, :258-273, behind
  * the inverse lens model of ms_lens_unproject), and a batched cuda::remap that wraps at the +-pi seam (ms_reproject).
- * Stated limits: 8UC3 panoramas only (no 16S source); INTER_LINEAR only (no nearest, no cubic); coordinates always come from maps (a pose that changes every
- * frame rebuilds them: ms_build_view_maps is one launch); MS_PROJ_PLANE panoramas are MS_ERR_UNSUPPORTED; one GPU.
+ * Stated limits: 8UC3 panoramas only (no 16S source); INTER_LINEAR only (no nearest, no cubic); coordinates come from maps, except under a ROTATION that changes every
+ * frame, which ms_reproject_poses renders without maps (a zoom or a lens that changes per frame still rebuilds them: ms_build_view_maps is one launch); MS_PROJ_PLANE panoramas are MS_ERR_UNSUPPORTED; one GPU.
  * Antialiasing: ms_reproject point-samples, as cuda::remap does -- right for a view as fine as the panorama, moire for a coarser one.  ms_reproject_aa is the
  * player's mip-mapped texture unit: ISOTROPIC trilinear over a per-call mip chain (ms_build_pano_mips), the level chosen per pixel from the view's footprint
  * (ms_build_view_footprint).  No anisotropic filtering, no cubic or Lanczos taps.  What that buys, measured on the numpy statement (tests/reproject_aa_ref.py, stripes
@@ -1586,6 +1586,45 @@ MS_API int ms_build_view_footprint(const ms_pano_frame *src, const ms_image *map
 typedef struct ms_view_job_aa { ms_view_job job; ms_image rho; } ms_view_job_aa;
 MS_API int ms_reproject_aa(const ms_image *src, void *const *mips, int levels, ms_image *dst, int n_frames, const ms_view_job_aa *jobs, int n_jobs, int wrap_cols,
                            int clamp_rows, int format, ms_stream stream);
+
+/* ms_reproject for a camera that MOVES: n_frames panoramas and n_jobs views in ONE launch, every frame under a rotation of its own, the coordinates computed in
+ * the kernel -- no maps are built, stored or read, and the host stays out of the loop.
+ *   frame:     how the src images lie on the warper surface, as ms_build_view_maps takes it; frame->wrap_cols must be 0 or the source's column count.
+ *   src, dst, format: as ms_reproject's.
+ *   jobs:      HOST, n_jobs in [1, MS_VIEW_POSE_MAX_JOBS].  view: as ms_build_view_maps takes it (kind, size, K, lens / projection, scale, tl_u, tl_v) -- view.R is
+ *              read by ms_view_pose_table only; job j writes the rectangle (dst_x, dst_y, view.width, view.height) of every frame.
+ *   poses_dev: DEVICE, 4-byte aligned, n_jobs * n_frames * 9 floats: the rotation (view to rig, row-major, ms_set_camera's convention) of job j in frame f starts
+ *              at poses_dev[(j * n_frames + f) * 9].  On the device because 8 x 64 x 36 bytes do not fit a kernel argument, and because a stabiliser or a
+ *              pose filter may well produce the table there: nothing is allocated or copied by the call, the host never waits.
+ * Contract, bit for bit.  Frame f, job j gets exactly the bytes that ms_build_view_maps(frame, view_j with R = that frame's nine floats) followed by
+ * ms_reproject(&src[f], &dst[f], 1, {those maps, dst_x, dst_y}, 1, frame->wrap_cols, frame->clamp_rows, format) writes: steps 1 to 4 of ms_build_view_maps in
+ * double, rounded to float once, then ms_reproject's taps, weights, fma chain and saturation -- the wrap rule and the == wrap_cols -> 0 rule, the (-1, -1) entry
+ * of an unseen pixel (which samples the extension's corner), I420 as ms_bgr_to_i420 of the BGR atlas.  No byte outside the jobs' rectangles is written.
+ * The host cannot inspect the rotations: ANY nine floats -- NaN, +-inf, zeros, a matrix scaled by 1e30 -- give what the formulas above give for them (the
+ * two-call route where ms_build_view_maps accepts the matrix), and no address outside the source is ever formed: the taps are made from the two floats alone.
+ * Kernel shape (csrc/reproject_poses.hip): ms_reproject's tiles and lanes.  A lane builds the view rays of its four pixels once -- ms_lens_unproject's Newton
+ * solves, the dear part of a lens view -- and walks MS_VIEW_POSE_FRAME_GROUP frames with them; per frame and pixel it rotates the ray and evaluates one hypot
+ * and two atan2 in double.
+ * Stated limits: rotations only (a zoom or a lens that changes per frame still rebuilds maps); point sampling only -- there is no _aa form, the footprint depends
+ * on the pose; MS_VIEW_POSE_MAX_JOBS jobs; 8UC3 sources; one GPU.
+ * Refused before the device is touched -- MS_ERR_INVALID: a null pointer; a struct_size mismatch; everything ms_build_view_maps refuses about frame and about
+ * each view except a non-finite view.R; frame->wrap_cols other than 0 or the source's columns; everything ms_reproject refuses about src, dst, n_frames, format,
+ * rectangles that leave dst or overlap, I420 parity and dst overlapping src; n_jobs outside [1, MS_VIEW_POSE_MAX_JOBS]; a misaligned poses_dev.
+ * MS_ERR_UNSUPPORTED: MS_PROJ_PLANE as either projection. */
+enum { MS_VIEW_POSE_MAX_JOBS = 8, MS_VIEW_POSE_FRAME_GROUP = 8 };   /* a cube map is 6 jobs */
+typedef struct ms_view_pose_job {
+    ms_view view;
+    int dst_x, dst_y;       /* as ms_view_job's */
+} ms_view_pose_job;
+MS_API int ms_reproject_poses(const ms_pano_frame *frame, const ms_image *src, ms_image *dst, int n_frames, const ms_view_pose_job *jobs, int n_jobs,
+                              const float *poses_dev, int format, ms_stream stream);
+
+/* The pose table of "these views, under the rig rotation P_f in frame f" (host only, no device): poses_host[(j * n_frames + f) * 9 + i] =
+ * (float)(P_f (double)jobs[j].view.R)[i], row-major 3 x 3 products, each summed left to right in double.  rig_poses: n_frames x 9 doubles, row-major, or NULL
+ * for the identity: every frame then gets view.R itself.  Upload the result and hand it to ms_reproject_poses.
+ * MS_ERR_INVALID: a null jobs or poses_host; n_jobs outside [1, MS_VIEW_POSE_MAX_JOBS]; n_frames outside [1, MS_VIEW_MAX_FRAMES]; a view's struct_size
+ * mismatch; a view.R or rig_poses entry that is not finite. */
+MS_API int ms_view_pose_table(const ms_view_pose_job *jobs, int n_jobs, const double *rig_poses, int n_frames, float *poses_host);
 
 #ifdef __cplusplus
 }

@@ -8,7 +8,7 @@ mkdir -p ../build
 # a change of flags (e.g. a -DMS_DEV_KNOBS developer build before, the production flags now) rebuilds every object
 if [ "$(cat ../build/flags.txt 2>/dev/null)" != "$FLAGS" ]; then rm -f ../build/*.o; echo "$FLAGS" > ../build/flags.txt; fi
 newest_hdr=$(ls -t *.hpp *.inc ../../include/ms_stitch.h ../../include/ms_dist.h | head -1)
-UNITS="prims.hip compositor.hip mesh_maps.hip mesh_solver.hip matcher.hip features.hip calib.hip lens.hip rig.hip rig_focal.hip rig_lens.hip rig_coeffs.hip rig_pp.hip seam_dp.hip pair_match.hip reproject.hip reproject_aa.hip api.cpp geometry.cpp dist.cpp"
+UNITS="prims.hip compositor.hip mesh_maps.hip mesh_solver.hip matcher.hip features.hip calib.hip lens.hip rig.hip rig_focal.hip rig_lens.hip rig_coeffs.hip rig_pp.hip seam_dp.hip pair_match.hip reproject.hip reproject_aa.hip reproject_poses.hip api.cpp geometry.cpp dist.cpp"
 pids=()
 objs=()
 for f in $UNITS; do

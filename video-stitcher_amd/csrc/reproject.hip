@@ -39,24 +39,8 @@ __global__ void __launch_bounds__(256) k_view_maps(const ViewMapArgs A, int cols
         if (A.view_proj == MS_PROJ_SPHERICAL) { const double sv = sin(v); c[0] = sv * sin(u); c[1] = -cos(v); c[2] = sv * cos(u); }
         else { c[0] = sin(u); c[1] = v; c[2] = cos(u); }
     }
-    float ox = -1.f, oy = -1.f;
-    if (seen) {
-        const double *r = A.cam.r;
-        const double d0 = r[0] * c[0] + r[1] * c[1] + r[2] * c[2], d1 = r[3] * c[0] + r[4] * c[1] + r[5] * c[2], d2 = r[6] * c[0] + r[7] * c[1] + r[8] * c[2];
-        const double h = hypot(d0, d2), S = A.src_scale;
-        const double U = S * atan2(d0, d2);
-        double V = 0.0;
-        if (A.src_proj == MS_PROJ_SPHERICAL) V = S * atan2(h, -d1);
-        else if (h == 0.0) seen = false;
-        else V = S * d1 / h;
-        if (seen) {
-            double X = U - (double)A.u0;
-            const double Y = V - (double)A.v0;
-            if (A.wrap > 0) X -= (double)A.wrap * floor(X / (double)A.wrap);
-            ox = (float)X; oy = (float)Y;
-            if (A.wrap > 0 && ox == (float)A.wrap) ox = 0.f;
-        }
-    }
+    float ox, oy;
+    rp_pano_coords(seen, A.cam.r, c, A.src_scale, A.src_proj, A.u0, A.v0, A.wrap, ox, oy);
     row_ptr<float>(mapx, mxstep, y)[x] = ox;
     row_ptr<float>(mapy, mystep, y)[x] = oy;
 }
@@ -146,17 +130,10 @@ __global__ void __launch_bounds__(256) k_reproject(const ReprojArgs A)
     }
 }
 
+}  // namespace ms
+
 // ------------------------------------------------------------------------------------------------
 // host side
-
-static bool finite9(const float *m) { for (int i = 0; i < 9; ++i) if (!std::isfinite(m[i])) return false; return true; }
-static void rot_mul(const double *a, const double *b, double *o)
-{
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) o[3 * i + j] = a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j] + a[3 * i + 2] * b[6 + j];
-}
-
-}  // namespace ms
 
 using namespace ms;
 
@@ -174,8 +151,8 @@ int ms_look_at_view(double yaw_deg, double pitch_deg, double roll_deg, double hf
     const double Rx[9] = {1, 0, 0, 0, cos(pa), -sin(pa), 0, sin(pa), cos(pa)};
     const double Rz[9] = {cos(ra), -sin(ra), 0, sin(ra), cos(ra), 0, 0, 0, 1};
     double Ryx[9], R[9];
-    rot_mul(Ry, Rx, Ryx);
-    rot_mul(Ryx, Rz, R);
+    rp_rot_mul(Ry, Rx, Ryx);
+    rp_rot_mul(Ryx, Rz, R);
     ms_view v{};
     v.struct_size = sizeof(ms_view);
     v.kind = MS_VIEW_CAMERA;
@@ -233,23 +210,9 @@ int ms_build_view_maps(const ms_pano_frame *src, const ms_view *view, ms_image *
     const char *fn = "ms_build_view_maps";
     MS_CHECK(src && view && map_x && map_y, "%s: null argument (src / view / map_x / map_y)", fn);
     MS_CHECK(src->struct_size == sizeof(ms_pano_frame), "%s: ms_pano_frame.struct_size %u, this library's is %zu", fn, src->struct_size, sizeof(ms_pano_frame));
-    MS_CHECK(view->struct_size == sizeof(ms_view), "%s: ms_view.struct_size %u, this library's is %zu", fn, view->struct_size, sizeof(ms_view));
-    MS_CHECK(view->kind == MS_VIEW_CAMERA || view->kind == MS_VIEW_SURFACE, "%s: view kind %d is neither MS_VIEW_CAMERA nor MS_VIEW_SURFACE", fn, view->kind);
     if (int e = rp_check_pano_frame(fn, src)) return e;
-    if (int e = rp_check_side(fn, "view width x height", view->width, view->height)) return e;
-    MS_CHECK(finite9(view->R), "%s: view R is not finite", fn);
     const ms_lens *lens = nullptr;
-    if (view->kind == MS_VIEW_CAMERA) {
-        MS_CHECK(finite9(view->K), "%s: view K is not finite", fn);
-        MS_CHECK(view->K[0] != 0.f && view->K[4] != 0.f, "%s: view K[0] = %g and K[4] = %g must not be zero", fn, (double)view->K[0], (double)view->K[4]);
-        if (view->lens.model != MS_LENS_NONE) {
-            if (int e = lens_check("ms_build_view_maps: view lens", &view->lens)) return e;
-            lens = &view->lens;
-        }
-    } else {
-        if (int e = rp_check_proj(fn, "view projection", view->projection)) return e;
-        if (int e = rp_check_scale(fn, "view scale", view->scale)) return e;
-    }
+    if (int e = rp_check_view(fn, "view", view, true, &lens)) return e;
     if (int e = rp_check_view_map(fn, "map_x", *map_x)) return e;
     if (int e = rp_check_view_map(fn, "map_y", *map_y)) return e;
     MS_CHECK(map_x->cols == view->width && map_x->rows == view->height && map_y->cols == view->width && map_y->rows == view->height,

@@ -1,6 +1,7 @@
-// reproject.hpp -- what the two samplers of the virtual cameras share (include/ms_stitch.h section 5): ms_reproject (reproject.hip) and ms_reproject_aa
-// (reproject_aa.hip).  The tap state of cuda::remap(INTER_LINEAR, BORDER_CONSTANT) on a source that wraps at the +-pi seam and repeats its pole rows, its
-// row reads and fma chain, the BGR / I420 store of a lane's four pixels, and the host-side argument checks and job table of a call.
+// reproject.hpp -- what the three samplers of the virtual cameras share (include/ms_stitch.h section 5): ms_reproject (reproject.hip), ms_reproject_aa
+// (reproject_aa.hip) and ms_reproject_poses (reproject_poses.hip).  The tap state of cuda::remap(INTER_LINEAR, BORDER_CONSTANT) on a source that wraps at the +-pi
+// seam and repeats its pole rows, its row reads and fma chain, the BGR / I420 store of a lane's four pixels, the coordinates of a view ray in the panorama image
+// (ms_build_view_maps' and ms_reproject_poses'), and the host-side argument checks and job table of a call.
 #pragma once
 #include <cmath>
 #include <cstdio>
@@ -144,8 +145,41 @@ __device__ __forceinline__ void rp_store_i420(const Args &A, int f, int dx, int 
     V[(size_t)(dy / 2) * (W / 2) + dx / 2] = (uint8_t)vq;
 }
 
+// Steps 2 to 4 of ms_build_view_maps (include/ms_stitch.h): the view ray c under the rotation r (view to rig, row-major) -> the rig direction -> panorama
+// coordinates (mapForward) -> image coordinates with the wrap rule, in double, rounded to float once.  ONE copy: k_view_maps (reproject.hip) stores the two floats,
+// k_reproject_poses (reproject_poses.hip) samples at them; the library is built with -ffp-contract=off, so the same source gives the same bits in both.
+// seen: the view sees the pixel (step 1); an unseen pixel, and a direction a cylindrical panorama does not see (h == 0), is the entry (-1, -1).
+__device__ __forceinline__ void rp_pano_coords(bool seen, const double *r, const double *c, double S, int src_proj, int u0, int v0, int wrap, float &out_x, float &out_y)
+{
+    float ox = -1.f, oy = -1.f;
+    if (seen) {
+        const double d0 = r[0] * c[0] + r[1] * c[1] + r[2] * c[2], d1 = r[3] * c[0] + r[4] * c[1] + r[5] * c[2], d2 = r[6] * c[0] + r[7] * c[1] + r[8] * c[2];
+        const double h = hypot(d0, d2);
+        const double U = S * atan2(d0, d2);
+        double V = 0.0;
+        if (src_proj == MS_PROJ_SPHERICAL) V = S * atan2(h, -d1);
+        else if (h == 0.0) seen = false;
+        else V = S * d1 / h;
+        if (seen) {
+            double X = U - (double)u0;
+            const double Y = V - (double)v0;
+            if (wrap > 0) X -= (double)wrap * floor(X / (double)wrap);
+            ox = (float)X; oy = (float)Y;
+            if (wrap > 0 && ox == (float)wrap) ox = 0.f;
+        }
+    }
+    out_x = ox; out_y = oy;
+}
+
 // ------------------------------------------------------------------------------------------------
 // host side: the checks the entry points of section 5 share
+
+// o = a b for row-major 3 x 3 matrices, each product summed left to right (ms_look_at_view's Ry Rx Rz, ms_view_pose_table's P R)
+static inline void rp_rot_mul(const double *a, const double *b, double *o)
+{
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) o[3 * i + j] = a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j] + a[3 * i + 2] * b[6 + j];
+}
 
 static inline int rp_check_proj(const char *fn, const char *what, int proj)
 {
@@ -182,15 +216,46 @@ static inline int rp_check_pano_frame(const char *fn, const ms_pano_frame *src)
     return MS_OK;
 }
 
-// Everything ms_reproject refuses, and what its launch needs: the job table, the tile count and the frame the rectangles lie in.  `jobs` is walked with
-// job_stride bytes between entries (ms_view_job, or the ms_view_job at the head of an ms_view_job_aa).
-struct RpPlan { ReprojJob job[MS_VIEW_MAX_JOBS]; int tiles, fw, fh; };
-static inline int rp_plan(const char *fn, const ms_image *src, ms_image *dst, int n_frames, const void *jobs, size_t job_stride, int n_jobs, int wrap_cols, int clamp_rows,
-                          int format, RpPlan &P)
+// ms_build_view_maps' checks on a view (`what` names it: "view", "jobs[2].view"); *lens is the view's lens, or null for a pinhole / a surface.  check_R: R must be
+// finite (ms_reproject_poses takes its rotations from the pose table and never reads view.R).
+static inline int rp_check_view(const char *fn, const char *what, const ms_view *view, bool check_R, const ms_lens **lens)
 {
-    MS_CHECK(src && dst && jobs, "%s: null argument (src / dst / jobs)", fn);
+    char name[96];
+    MS_CHECK(view->struct_size == sizeof(ms_view), "%s: %s: ms_view.struct_size %u, this library's is %zu", fn, what, view->struct_size, sizeof(ms_view));
+    MS_CHECK(view->kind == MS_VIEW_CAMERA || view->kind == MS_VIEW_SURFACE, "%s: %s kind %d is neither MS_VIEW_CAMERA nor MS_VIEW_SURFACE", fn, what, view->kind);
+    snprintf(name, sizeof(name), "%s width x height", what);
+    if (int e = rp_check_side(fn, name, view->width, view->height)) return e;
+    auto finite9 = [](const float *m) { for (int i = 0; i < 9; ++i) if (!std::isfinite(m[i])) return false; return true; };
+    if (check_R) MS_CHECK(finite9(view->R), "%s: %s R is not finite", fn, what);
+    *lens = nullptr;
+    if (view->kind == MS_VIEW_CAMERA) {
+        MS_CHECK(finite9(view->K), "%s: %s K is not finite", fn, what);
+        MS_CHECK(view->K[0] != 0.f && view->K[4] != 0.f, "%s: %s K[0] = %g and K[4] = %g must not be zero", fn, what, (double)view->K[0], (double)view->K[4]);
+        if (view->lens.model != MS_LENS_NONE) {
+            snprintf(name, sizeof(name), "%s: %s lens", fn, what);
+            if (int e = lens_check(name, &view->lens)) return e;
+            *lens = &view->lens;
+        }
+    } else {
+        snprintf(name, sizeof(name), "%s projection", what);
+        if (int e = rp_check_proj(fn, name, view->projection)) return e;
+        snprintf(name, sizeof(name), "%s scale", what);
+        if (int e = rp_check_scale(fn, name, view->scale)) return e;
+    }
+    return MS_OK;
+}
+
+// What every sampler of section 5 refuses about its frames and rectangles, and the tile layout of its launch: the counts, the format, the source and destination
+// frames, each job's rectangle (inside dst, even for I420, disjoint from the earlier ones) and dst against src in memory.  job_rect(j, rect) checks what is the
+// caller's own about job j -- its maps (ms_reproject, ms_reproject_aa) or its view (ms_reproject_poses) -- and names the rectangle.
+struct RpRect { int w, h, dst_x, dst_y; };
+struct RpLayout { RpRect rect[MS_VIEW_MAX_JOBS]; int tile0[MS_VIEW_MAX_JOBS], tiles_x[MS_VIEW_MAX_JOBS]; int tiles, fw, fh; };
+template <class JobRect>
+static inline int rp_layout(const char *fn, const ms_image *src, ms_image *dst, int n_frames, int n_jobs, int max_jobs, int wrap_cols, int clamp_rows, int format,
+                            JobRect job_rect, RpLayout &L)
+{
     MS_CHECK(n_frames >= 1 && n_frames <= MS_VIEW_MAX_FRAMES, "%s: n_frames = %d outside [1, %d]", fn, n_frames, MS_VIEW_MAX_FRAMES);
-    MS_CHECK(n_jobs >= 1 && n_jobs <= MS_VIEW_MAX_JOBS, "%s: n_jobs = %d outside [1, %d]", fn, n_jobs, MS_VIEW_MAX_JOBS);
+    MS_CHECK(n_jobs >= 1 && n_jobs <= max_jobs, "%s: n_jobs = %d outside [1, %d]", fn, n_jobs, max_jobs);
     MS_CHECK(format == MS_VIEW_BGR || format == MS_VIEW_I420, "%s: format %d is neither MS_VIEW_BGR nor MS_VIEW_I420", fn, format);
     const bool i420 = format == MS_VIEW_I420;
     const ms_image &s0 = src[0], &d0 = dst[0];
@@ -215,31 +280,20 @@ static inline int rp_plan(const char *fn, const ms_image *src, ms_image *dst, in
         fh = d0.rows / 3 * 2;
     }
     int tiles = 0;
-    auto job_at = [&](int j) -> const ms_view_job & { return *(const ms_view_job *)((const char *)jobs + (size_t)j * job_stride); };
     for (int j = 0; j < n_jobs; ++j) {
-        const ms_view_job &J = job_at(j);
-        char name[48];
-        snprintf(name, sizeof(name), "jobs[%d].map_x", j);
-        if (int e = rp_check_view_map(fn, name, J.map_x)) return e;
-        snprintf(name, sizeof(name), "jobs[%d].map_y", j);
-        if (int e = rp_check_view_map(fn, name, J.map_y)) return e;
-        MS_CHECK(J.map_x.cols == J.map_y.cols && J.map_x.rows == J.map_y.rows, "%s: jobs[%d]: map_x is %d x %d, map_y %d x %d", fn, j, J.map_x.cols, J.map_x.rows, J.map_y.cols, J.map_y.rows);
-        if (int e = rp_check_side(fn, "a job's maps", J.map_x.cols, J.map_x.rows)) return e;
-        const int w = J.map_x.cols, h = J.map_x.rows;
-        MS_CHECK(J.dst_x >= 0 && J.dst_y >= 0 && (long long)J.dst_x + w <= fw && (long long)J.dst_y + h <= fh,
-                 "%s: jobs[%d]: the rectangle (%d, %d, %d x %d) leaves the %d x %d dst", fn, j, J.dst_x, J.dst_y, w, h, fw, fh);
-        if (i420) MS_CHECK(J.dst_x % 2 == 0 && J.dst_y % 2 == 0 && w % 2 == 0 && h % 2 == 0, "%s: jobs[%d]: an I420 rectangle (%d, %d, %d x %d) must be even", fn, j, J.dst_x, J.dst_y, w, h);
+        RpRect &J = L.rect[j];
+        if (int e = job_rect(j, J)) return e;
+        MS_CHECK(J.dst_x >= 0 && J.dst_y >= 0 && (long long)J.dst_x + J.w <= fw && (long long)J.dst_y + J.h <= fh,
+                 "%s: jobs[%d]: the rectangle (%d, %d, %d x %d) leaves the %d x %d dst", fn, j, J.dst_x, J.dst_y, J.w, J.h, fw, fh);
+        if (i420) MS_CHECK(J.dst_x % 2 == 0 && J.dst_y % 2 == 0 && J.w % 2 == 0 && J.h % 2 == 0, "%s: jobs[%d]: an I420 rectangle (%d, %d, %d x %d) must be even", fn, j, J.dst_x, J.dst_y, J.w, J.h);
         for (int k = 0; k < j; ++k) {
-            const ms_view_job &Q = job_at(k);
-            MS_CHECK(J.dst_x >= Q.dst_x + Q.map_x.cols || Q.dst_x >= J.dst_x + w || J.dst_y >= Q.dst_y + Q.map_x.rows || Q.dst_y >= J.dst_y + h,
+            const RpRect &Q = L.rect[k];
+            MS_CHECK(J.dst_x >= Q.dst_x + Q.w || Q.dst_x >= J.dst_x + J.w || J.dst_y >= Q.dst_y + Q.h || Q.dst_y >= J.dst_y + J.h,
                      "%s: the rectangles of jobs[%d] and jobs[%d] overlap", fn, k, j);
         }
-        ReprojJob &R = P.job[j];
-        R.mx = (const float *)J.map_x.data; R.my = (const float *)J.map_y.data; R.mxstep = J.map_x.step; R.mystep = J.map_y.step;
-        R.cols = w; R.rows = h; R.dst_x = J.dst_x; R.dst_y = J.dst_y;
-        R.tile0 = tiles;
-        R.tiles_x = i420 ? div_up(w, 32) : div_up(w, MS_VIEW_TILE_W);
-        tiles += R.tiles_x * (i420 ? div_up(h, 32) : div_up(h, MS_VIEW_TILE_H));
+        L.tile0[j] = tiles;
+        L.tiles_x[j] = i420 ? div_up(J.w, 32) : div_up(J.w, MS_VIEW_TILE_W);
+        tiles += L.tiles_x[j] * (i420 ? div_up(J.h, 32) : div_up(J.h, MS_VIEW_TILE_H));
     }
     const size_t s_bytes = (size_t)(s0.rows - 1) * s0.step + (size_t)s0.cols * 3;
     const size_t d_bytes = (size_t)(d0.rows - 1) * d0.step + (size_t)d0.cols * (i420 ? 1 : 3);
@@ -248,7 +302,40 @@ static inline int rp_plan(const char *fn, const ms_image *src, ms_image *dst, in
             const uintptr_t a = (uintptr_t)dst[f].data, b = (uintptr_t)src[g].data;
             MS_CHECK(a + d_bytes <= b || b + s_bytes <= a, "%s: dst frame %d overlaps src frame %d in memory", fn, f, g);
         }
-    P.tiles = tiles; P.fw = fw; P.fh = fh;
+    L.tiles = tiles; L.fw = fw; L.fh = fh;
+    return MS_OK;
+}
+
+// Everything ms_reproject refuses, and what its launch needs: the job table, the tile count and the frame the rectangles lie in.  `jobs` is walked with
+// job_stride bytes between entries (ms_view_job, or the ms_view_job at the head of an ms_view_job_aa).
+struct RpPlan { ReprojJob job[MS_VIEW_MAX_JOBS]; int tiles, fw, fh; };
+static inline int rp_plan(const char *fn, const ms_image *src, ms_image *dst, int n_frames, const void *jobs, size_t job_stride, int n_jobs, int wrap_cols, int clamp_rows,
+                          int format, RpPlan &P)
+{
+    MS_CHECK(src && dst && jobs, "%s: null argument (src / dst / jobs)", fn);
+    auto job_at = [&](int j) -> const ms_view_job & { return *(const ms_view_job *)((const char *)jobs + (size_t)j * job_stride); };
+    RpLayout L;
+    const int e = rp_layout(fn, src, dst, n_frames, n_jobs, MS_VIEW_MAX_JOBS, wrap_cols, clamp_rows, format, [&](int j, RpRect &r) -> int {
+        const ms_view_job &J = job_at(j);
+        char name[48];
+        snprintf(name, sizeof(name), "jobs[%d].map_x", j);
+        if (int e = rp_check_view_map(fn, name, J.map_x)) return e;
+        snprintf(name, sizeof(name), "jobs[%d].map_y", j);
+        if (int e = rp_check_view_map(fn, name, J.map_y)) return e;
+        MS_CHECK(J.map_x.cols == J.map_y.cols && J.map_x.rows == J.map_y.rows, "%s: jobs[%d]: map_x is %d x %d, map_y %d x %d", fn, j, J.map_x.cols, J.map_x.rows, J.map_y.cols, J.map_y.rows);
+        if (int e = rp_check_side(fn, "a job's maps", J.map_x.cols, J.map_x.rows)) return e;
+        r = RpRect{J.map_x.cols, J.map_x.rows, J.dst_x, J.dst_y};
+        return MS_OK;
+    }, L);
+    if (e) return e;
+    for (int j = 0; j < n_jobs; ++j) {
+        const ms_view_job &J = job_at(j);
+        ReprojJob &R = P.job[j];
+        R.mx = (const float *)J.map_x.data; R.my = (const float *)J.map_y.data; R.mxstep = J.map_x.step; R.mystep = J.map_y.step;
+        R.cols = L.rect[j].w; R.rows = L.rect[j].h; R.dst_x = J.dst_x; R.dst_y = J.dst_y;
+        R.tile0 = L.tile0[j]; R.tiles_x = L.tiles_x[j];
+    }
+    P.tiles = L.tiles; P.fw = L.fw; P.fh = L.fh;
     return MS_OK;
 }
 

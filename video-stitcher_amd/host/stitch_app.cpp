@@ -18,7 +18,7 @@
 // Usage: stitch_app [--views 6] [--size 1920x1080] [--out 3840x1920] [--hfov 90] [--bands 5] [--frames 300] [--cpw]
 //                   [--i420] [--nv12 | --nv12-direct] [--dump pano.bin] [--no-upload] [--solve-mesh [--temporal ALPHA]]
 //                   [--reference-calib [--work-megapix 0.6] [--seam-megapix 0.01] [--compose-megapix 1.4] [--seam-finder voronoi|dp]]
-//                   [--viewport YAW,PITCH,ROLL,HFOV,WxH | --cubemap N] [--aa LEVELS]
+//                   [--viewport YAW,PITCH,ROLL,HFOV,WxH | --cubemap N] [--aa LEVELS | --orbit DEG]
 //                   [--drop-view V:F0:F1] [--dump-frames frames.bin] [--track-gains K] [--exposure-ramp V:F] [--dump-i420 planes.bin]
 //                   [--lens-brown k1,k2,p1,p2,k3 | --lens-fisheye k1,k2,k3,k4[,max_theta]]
 //                   [--rig-error V:YAW:PITCH:ROLL] [--refine-rig]
@@ -39,6 +39,9 @@
 // measured slower than the two launches (41 against 37 us per six 1080p frames, README).  With --nv12 the exposure ramp scales the Y plane only (the camera's exposure, not its colour).
 // --aa LEVELS (with --viewport or --cubemap) renders the views antialiased: the footprints are built once, beside the maps (ms_build_view_footprint), every canvas
 // gets its mip chain of LEVELS levels (ms_build_pano_mips) and ms_reproject_aa samples it; the JSON line then carries "aa_levels".  Without it nothing changes.
+// --orbit DEG (with --viewport or --cubemap, not with --aa) moves the virtual cameras: canvas n of the run is rendered under the rig rotation Ry(n DEG)
+// (ms_look_at_view's Ry).  The pose table of the whole run is built once (ms_view_pose_table) and uploaded before the loop, laid out [frame][job][9]; the consumer
+// calls ms_reproject_poses with one frame and that frame's slice.  No maps are built; the JSON line then carries "orbit_deg".
 // --dump-i420 FILE writes the last frame's I420 planes (every --i420 mode); the JSON line's "i420_call" names the call that produced them.
 // --track-gains K: every K-th stitch call is followed by one ms_track_gains on the stitch stream with that call's frames (exposure tracking; 0 = off, the
 // default: nothing changes).  --exposure-ramp V:F multiplies camera V's synthetic frames by F from the middle of the run on, so that the tracker has a drift
@@ -117,6 +120,8 @@ struct Options {
     bool viewport = false;                      // --viewport YAW,PITCH,ROLL,HFOV,WxH: a virtual pan / tilt / zoom camera rendered from the canvas (ms_reproject) in consume()
     double vp_yaw = 0, vp_pitch = 0, vp_roll = 0, vp_hfov = 90;
     int vp_w = 0, vp_h = 0;
+    bool orbit = false;                         // --orbit DEG: ms_reproject_poses under the rig rotation Ry(n DEG) for canvas n, no maps
+    double orbit_deg = 0.0;
     int aa = 0;                                 // --aa LEVELS: ms_build_pano_mips + ms_reproject_aa instead of ms_reproject
     int cubemap = 0;                            // --cubemap N: a 3N x 2N atlas of six N x N faces (ms_cube_face_view order, left to right, top to bottom)
     bool fused_resize = false;                  // --fused-resize: with --nv12-direct and a compose-scale resize, planes -> small_imgs in one pass
@@ -275,6 +280,7 @@ int main(int argc, char **argv)
         }
         else if (k == "--cubemap") o.cubemap = atoi(next());
         else if (k == "--aa") o.aa = atoi(next());
+        else if (k == "--orbit") { o.orbit_deg = atof(next()); o.orbit = true; }
         else if (k == "--fused-resize") o.fused_resize = true;
         else if (k == "--lens-brown") {      // k1,k2,p1,p2,k3 in distCoeffs order: k3 is k[4]
             double *c = o.lens.k;
@@ -313,6 +319,9 @@ int main(int argc, char **argv)
     if (o.viewport && o.cubemap) { fprintf(stderr, "--viewport and --cubemap exclude each other\n"); return 2; }
     if (o.cubemap < 0 || (o.cubemap && o.i420 && o.cubemap % 2)) { fprintf(stderr, "--cubemap wants N >= 1 (even with --i420)\n"); return 2; }
     if (o.aa && !(o.viewport || o.cubemap)) { fprintf(stderr, "--aa needs --viewport or --cubemap\n"); return 2; }
+    if (o.orbit && !(o.viewport || o.cubemap)) { fprintf(stderr, "--orbit needs --viewport or --cubemap\n"); return 2; }
+    if (o.orbit && o.aa) { fprintf(stderr, "--orbit and --aa exclude each other (ms_reproject_poses point-samples)\n"); return 2; }
+    if (o.orbit && !std::isfinite(o.orbit_deg)) { fprintf(stderr, "--orbit wants a finite angle in degrees\n"); return 2; }
     if (o.aa < 0 || o.aa > MS_VIEW_MAX_LEVELS) { fprintf(stderr, "--aa wants 1..%d levels\n", (int)MS_VIEW_MAX_LEVELS); return 2; }
     if (o.viewport && o.i420 && (o.vp_w % 2 || o.vp_h % 2)) { fprintf(stderr, "--viewport with --i420 wants an even size\n"); return 2; }
     if (o.fused_resize && !o.nv12_direct) { fprintf(stderr, "--fused-resize needs --nv12-direct\n"); return 2; }
@@ -564,6 +573,9 @@ int main(int argc, char **argv)
         std::vector<DevMat> view_rho;                   // --aa: the footprints, and one mips buffer (the consumer renders one canvas at a time)
         std::vector<ms_view_job_aa> view_jobs_aa;
         DevMat view_mips;
+        std::vector<ms_view_pose_job> view_pose_jobs;   // --orbit: the views themselves and the run's pose table, [frame][job][9]
+        DevMat view_poses;
+        ms_pano_frame view_pano{};
         DevMat view_frame;
         std::vector<unsigned char> view_host;
         hipStream_t view_stream = nullptr;
@@ -573,6 +585,7 @@ int main(int argc, char **argv)
             ms_pano_frame pf;
             msshim::check(ms_get_pano_frame(comp.raw(), MS_PANO_CANVAS, &pf));
             view_wrap = pf.wrap_cols; view_clamp = pf.clamp_rows;
+            view_pano = pf;
             const int n_views = o.cubemap ? 6 : 1;
             view_w = o.cubemap ? 3 * o.cubemap : o.vp_w; view_h = o.cubemap ? 2 * o.cubemap : o.vp_h;
             view_mx.resize(n_views); view_my.resize(n_views); view_jobs.resize(n_views);
@@ -582,6 +595,7 @@ int main(int argc, char **argv)
                 ms_view v;
                 if (o.cubemap) msshim::check(ms_cube_face_view(i, o.cubemap, &v));
                 else msshim::check(ms_look_at_view(o.vp_yaw, o.vp_pitch, o.vp_roll, o.vp_hfov, o.vp_w, o.vp_h, &v));
+                if (o.orbit) { view_pose_jobs.push_back(ms_view_pose_job{v, o.cubemap ? (i % 3) * o.cubemap : 0, o.cubemap ? (i / 3) * o.cubemap : 0}); continue; }
                 view_mx[i].create(v.height, v.width, MS_32FC1); view_my[i].create(v.height, v.width, MS_32FC1);
                 ms_image mx = msshim::wrap(view_mx[i]), my = msshim::wrap(view_my[i]);
                 msshim::check(ms_build_view_maps(&pf, &v, &mx, &my, (ms_stream)view_stream));
@@ -599,6 +613,16 @@ int main(int argc, char **argv)
                 msshim::check(ms_pano_mips_layout(o.out_w, o.out_h, o.aa, lv, &mip_bytes));
                 view_mips.create(1, (int)mip_bytes, MS_8UC1, 1, true);
             }
+            if (o.orbit) {
+                std::vector<float> table((size_t)o.frames * n_views * 9);
+                for (int n = 0; n < o.frames; ++n) {
+                    const double a = n * o.orbit_deg * (M_PI / 180.0);
+                    const double Ry[9] = {cos(a), 0, sin(a), 0, 1, 0, -sin(a), 0, cos(a)};
+                    msshim::check(ms_view_pose_table(view_pose_jobs.data(), n_views, Ry, 1, table.data() + (size_t)n * n_views * 9));
+                }
+                view_poses.create(1, (int)table.size(), MS_32FC1, 4, true);
+                HIPCHECK(hipMemcpy(view_poses.data, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice));
+            }
             HIPCHECK(hipStreamSynchronize(view_stream));
             if (o.i420) view_frame.create(view_h * 3 / 2, view_w, MS_8UC1, 1, true);
             else view_frame.create(view_h, view_w, MS_8UC3, 3, true);
@@ -611,7 +635,11 @@ int main(int argc, char **argv)
                 HIPCHECK(hipEventSynchronize(s->done));
                 if (view_on) {                          // the virtual cameras' frame instead of (beside) the equirect: one launch, then the encoder's copy
                     ms_image src = msshim::wrap(s->pano8u), dst = msshim::wrap(view_frame);
-                    if (o.aa) {
+                    if (o.orbit) {
+                        const float *poses = (const float *)view_poses.data + (size_t)s->seq * view_pose_jobs.size() * 9;
+                        msshim::check(ms_reproject_poses(&view_pano, &src, &dst, 1, view_pose_jobs.data(), (int)view_pose_jobs.size(), poses, o.i420 ? MS_VIEW_I420 : MS_VIEW_BGR,
+                                                         (ms_stream)view_stream));
+                    } else if (o.aa) {
                         void *mips = view_mips.data;
                         msshim::check(ms_build_pano_mips(&src, &mips, 1, o.aa, (ms_stream)view_stream));
                         msshim::check(ms_reproject_aa(&src, &mips, o.aa, &dst, 1, view_jobs_aa.data(), (int)view_jobs_aa.size(), view_wrap, view_clamp, o.i420 ? MS_VIEW_I420 : MS_VIEW_BGR,
@@ -877,6 +905,7 @@ int main(int argc, char **argv)
                total_keypoints.load(), total_matches.load(), total_inliers.load(), o.update_mask, selfcheck < 0 ? "null" : (selfcheck ? "true" : "false"), consume_image_height, consume_checksum, checksum, degraded_frames, i420_call, fused_resize ? "true" : "false", comp.mapSource(), comp.seamFinder() == MS_SEAM_DP ? "dp" : "voronoi");
         if (view_on) printf(", \"view_out\": \"%dx%d\", \"view_checksum\": \"%016llx\"", view_w, view_h, view_checksum);
         if (o.aa) printf(", \"aa_levels\": %d", o.aa);
+        if (o.orbit) printf(", \"orbit_deg\": %g", o.orbit_deg);
         if (o.temporal > 0.0) printf(", \"temporal_alpha\": %g, \"temporal_matches\": %lld", o.temporal, total_temporal.load());
         if (o.track_gains > 0) {
             std::vector<double> g((size_t)o.views);

@@ -121,6 +121,12 @@ class ViewJobAA(C.Structure):
 
 
 VIEW_MAX_LEVELS = 6
+VIEW_POSE_MAX_JOBS, VIEW_POSE_FRAME_GROUP = 8, 8
+
+
+class ViewPoseJob(C.Structure):
+    """ms_view_pose_job: one view of an ms_reproject_poses call (its R is read by view_pose_table only) and where it goes in every destination frame"""
+    _fields_ = [("view", View), ("dst_x", C.c_int), ("dst_y", C.c_int)]
 
 
 class SeamParams(C.Structure):
@@ -323,6 +329,7 @@ EXPORTS = [
     "ms_rig_pp_default_params", "ms_rig_pp_accumulate", "ms_refine_rig_pp", "ms_refine_rig_pp_ctx",
     "ms_look_at_view", "ms_cube_face_view", "ms_get_pano_frame", "ms_build_view_maps", "ms_reproject",
     "ms_pano_mips_layout", "ms_build_pano_mips", "ms_build_view_footprint", "ms_reproject_aa",
+    "ms_view_pose_table", "ms_reproject_poses",
 ]
 
 _lib = None
@@ -710,6 +717,47 @@ def reproject_prepared(srcs, dsts, jobs, wrap_cols=0, clamp_rows=0, fmt=VIEW_BGR
 def reproject(srcs, dsts, jobs, wrap_cols=0, clamp_rows=0, fmt=VIEW_BGR):
     """ms_reproject: every job's view of every source panorama into its rectangle of the matching destination frame, in one launch"""
     reproject_prepared(srcs, dsts, jobs, wrap_cols, clamp_rows, fmt)()
+    return dsts
+
+
+def _pose_jobs(jobs):
+    """jobs: a list of (View, dst_x, dst_y) or ViewPoseJob"""
+    return (ViewPoseJob * max(1, len(jobs)))(*[j if isinstance(j, ViewPoseJob) else ViewPoseJob(j[0], j[1], j[2]) for j in jobs])
+
+
+def view_pose_table(jobs, rig_poses=None):
+    """ms_view_pose_table (host only): the (n_jobs, n_frames, 9) float32 numpy table of jobs' views under the rig rotations rig_poses ((n_frames, 3, 3) float64;
+    None: one frame, every view's own R)"""
+    import numpy as np
+    P = None if rig_poses is None else np.ascontiguousarray(rig_poses, np.float64).reshape(-1, 9)
+    n_frames = 1 if P is None else len(P)
+    out = np.empty((len(jobs), n_frames, 9), np.float32)
+    _chk(load().ms_view_pose_table(_pose_jobs(jobs), len(jobs), None if P is None else P.ctypes.data_as(C.POINTER(C.c_double)), n_frames,
+                                   out.ctypes.data_as(C.POINTER(C.c_float))))
+    return out
+
+
+def reproject_poses_prepared(pano_frame, srcs, dsts, jobs, poses, fmt=VIEW_BGR):
+    """ms_reproject_poses with the descriptors marshalled once: jobs a list of (View, dst_x, dst_y), poses a cuda float32 tensor of len(jobs) * len(srcs) * 9
+    rotations laid out [job][frame][9]; returns a callable(stream_handle=None)"""
+    torch = _torch()
+    n, m = len(srcs), len(jobs)
+    if not (poses.is_cuda and poses.dtype == torch.float32 and poses.is_contiguous() and poses.numel() == m * n * 9):
+        raise ValueError("poses must be a contiguous cuda float32 tensor of %d x %d x 9 elements" % (m, n))
+    a = (Image * n)(*[img(t) for t in srcs]); b = (Image * n)(*[img(t) for t in dsts])
+    jt = _pose_jobs(jobs)
+    fn = load().ms_reproject_poses
+    pp = C.c_void_p(poses.data_ptr())
+
+    def run(stream=None):
+        _chk(fn(C.byref(pano_frame), a, b, n, jt, m, pp, fmt, stream if stream is not None else _stream()))
+    run.keep = (srcs, dsts, jobs, poses)
+    return run
+
+
+def reproject_poses(pano_frame, srcs, dsts, jobs, poses, fmt=VIEW_BGR):
+    """ms_reproject_poses: every job's view of every source panorama, each frame under its own rotation, in one launch and without maps"""
+    reproject_poses_prepared(pano_frame, srcs, dsts, jobs, poses, fmt)()
     return dsts
 
 
